@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- layers compressed / second (covariance + decomposition + rebuild), Llama-3-8B @ 30 %.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either under torch.distributed.run -- RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment -- or plainly as
      above: with WORLD_SIZE unset the script starts its own N ranks as fresh child processes, one per GPU, BEFORE it touches the
      GPU, waits for them and exits with the worst of their exit codes)
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the roofline of its timed launches and the
+timed layers' selection certificate.  --full adds every measurement and check beside the headline (cpu_baseline,
+full_size_parity_vs_oracle, the MFMA rate probes, f64_route, next_rows, the value_* legs, i8_vs_f64_outputs; --no-cpu-baseline /
+--no-extra-legs leave parts of it out).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs()); the inputs depend on the arguments only, so two builds can be compared output for output.
 
 One STEP = one transformer layer taken through the whole hot path on synthetic Llama-3-8B-shaped inputs
 (BASELINE.json configs[2]): 32 calibration batches of 16 x 2048 tokens (= 512 samples) pushed
@@ -18,14 +24,14 @@ The JSON line carries numbers and short labels only ("The b
   roofline     -- the dominant kernel.  Default covariance route (--cov-mode i8: error-free split into int8 digit planes, truncated
                   plane-pair product): i8_syrk_kernel on sigma_mlp, int8 MFMA bound, priced on the MFMAs it ISSUED, timed alone by
                   HIP events the library records around it on the launch stream; .algorithmic restates it in SURVEY 8(d)'s fp64-SYRK
-                  units; .error_bound is the per-call guaranteed bound the device computed; .f64_route the v_mfma_f64 kernel on the
-                  same batch.  --cov-mode f64: cov_accum_multi_kernel, fp64 MFMA bound
-  cpu_baseline -- this repo's CPU oracle (torch-CPU fp64 restatement of the reference) timed on the host cores on a bounded
+                  units; .error_bound is the per-call guaranteed bound the device computed; .f64_route (--full) the v_mfma_f64
+                  kernel on the same batch.  --cov-mode f64: cov_accum_multi_kernel, fp64 MFMA bound
+  cpu_baseline -- (--full) this repo's CPU oracle (torch-CPU fp64 restatement of the reference) timed on the host cores on a bounded
                   sample of the same workload (N = 1, rank 0 only); full_size_parity_vs_oracle: its outputs against the GPU's
-  value_f64_route / value_gated / value_massive -- the SAME step loop timed again (N = 1 only, after the headline): everything
+  value_f64_route / value_gated / value_massive -- (--full) the SAME step loop timed again (N = 1 only, after the headline): everything
                   on v_mfma_f64; SiLU-gated sigma_mlp activations (what a real Llama MLP feeds the hook: six planes); four
                   massive-activation columns in sigma_mlp and sigma_x (they leave the launch alone, through the fp64 column kernel)
-  i8_vs_f64_outputs -- the headline leg's compressed tensors against the f64 leg's, same layers, full token count
+  i8_vs_f64_outputs -- (--full) the headline leg's compressed tensors against the f64 leg's, same layers, full token count
 """
 from __future__ import annotations
 
@@ -48,6 +54,7 @@ from modegpt_amd import engine, ops, sharding  # noqa: E402  (imports only: noth
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X public fp64-matrix spec; bench also reports the measured issue rate
 INT8_MFMA_PEAK_TOPS = 5000.0  # dense int8 = 2x the bf16 rate per clock (MI355X_MICROARCH.md, matrix cores table)
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_ARRAY_BYTES = 4 << 20    # --dump-outputs, per array: the twelve arrays of a layer stay under 64 MB in all
 
 
 class LaunchTimer:
@@ -318,16 +325,43 @@ def rope_gather_roofline(shape, keep, dev, launches=20):
             "frac": gbs / HBM_PEAK_GBS, "avg_launch_us": us, "workload": f"q [16, 2048, {n_h} x {r}] bf16"}
 
 
+def dump_outputs(path, tensors, mask, covs):
+    """--dump-outputs: what the caller of the last timed step receives -- its compressed tensors (bf16, written as float32, which
+    is exact) and the rotary mask (float64) -- and the layer's four statistics (float64), as path/<name>.npy.  An array larger
+    than DUMP_ARRAY_BYTES is written as a sample of its flattened elements, at positions drawn from a generator seeded with 0 and
+    sorted: the same positions in every run with the same shapes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: tensors[k] for k in sharding.TENSOR_ORDER if tensors.get(k) is not None}
+    if mask is not None:
+        arrays["rotary_mask"] = mask
+    arrays.update({f"sigma_{k}": v for k, v in covs.items()})
+    for name, t in arrays.items():
+        dt = torch.float32 if t.dtype in (torch.bfloat16, torch.float16, torch.float32) else torch.float64
+        limit = DUMP_ARRAY_BYTES // (4 if dt == torch.float32 else 8)
+        if t.numel() > limit:
+            pos = torch.randint(0, t.numel(), (limit,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(dt).cpu().numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every measurement and check beside it: CPU baseline and full-size parity "
+                         "against the oracle, MFMA rate probes, the fp64 route of one batch, the rope roofline, the extra legs and "
+                         "the i8-vs-f64 output comparison (off: the run does only what the headline needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed layer's outputs as DIR/<name>.npy (float32 / float64; "
+                         "arrays above %d MB as a fixed, seeded sample)" % (DUMP_ARRAY_BYTES >> 20))
     ap.add_argument("--model", default="llama-3-8b", choices=sorted(engine.SHAPES))
     ap.add_argument("--batches", type=int, default=32, help="calibration batches per layer (32 x 16 = 512 samples)")
     ap.add_argument("--batch_size", type=int, default=16, help="samples of 2048 tokens per batch")
     ap.add_argument("--keep", type=float, default=0.7)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / full_size_parity_vs_oracle")
     ap.add_argument("--pipeline", dest="pipeline", action="store_true", default=True,
                     help="(default) layer L's decomposition chain runs on a side stream beside layer L + 1's covariance kernels: "
                          "the chain enqueues without a host round trip (deferred status), so its kernels fill what the covariance "
@@ -343,14 +377,17 @@ def parse_args(argv=None):
                     help="layers of the i8-vs-f64 output comparison whose activations are generated per (layer, batch) -- distinct "
                          "sigma per layer (SURVEY 8d: seed (1234, layer, batch)); outside every timed region")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip value_f64_route / value_gated (the same step loop on the fp64 route and on SiLU-gated data)")
+                    help="with --full: skip value_f64_route / value_gated (the same step loop on the fp64 route and on SiLU-gated data)")
     ap.add_argument("--cov-mode", default=None, choices=["f64", "i8"],
                     help="matrix cores for sigma_mlp / sigma_x: i8 (fp64 result emulated by digit planes on v_mfma_i32_i8, <= 1e-12; "
                          "the default, ops.COV_MODE / env MODEGPT_COV_MODE) or f64 (v_mfma_f64, the reference's accumulation)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="no kernels: launcher, rendezvous, record packing and the one all-gather on synthetic records "
                          "(runs on CPU / gloo; prints value null)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def launch_ranks(n: int) -> int:
@@ -493,6 +530,8 @@ def main():
         elapsed = float(tmax.item())
     assert len(gathered) == world * a.steps
     del gathered, records
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, *last[1:])
 
     i8 = ops.COV_MODE == "i8" and shape["arch"] != "opt"
     stats, bounds = {}, []
@@ -580,9 +619,9 @@ def main():
     # i8 against f64 on layers with DISTINCT statistics (seed (1234, layer, batch) and per-layer column scales; generated one batch
     # at a time, outside every timed region): compressed tensors of the two routes, their selection certificates
     distinct, kept = None, None
-    if rank == 0 and world == 1 and i8 and a.distinct_layers > 0 and not (a.no_cpu_baseline and a.no_extra_legs):
+    if rank == 0 and world == 1 and i8 and a.full and a.distinct_layers > 0 and not (a.no_cpu_baseline and a.no_extra_legs):
         distinct, kept = distinct_sigma_parity(shape, adapter, ids[:a.distinct_layers], a, dev, n_texts, tokens)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         li, tensors, mask, covs = last
         gpu_out = dict(tensors)
         gpu_out["mask"] = mask
@@ -638,7 +677,7 @@ def main():
         out["cpu_baseline"] = None
     kept = None
     del last, done
-    if rank == 0 and world == 1 and not a.no_extra_legs and shape["arch"] != "opt":
+    if rank == 0 and world == 1 and a.full and not a.no_extra_legs and shape["arch"] != "opt":
         if i8:
             # (1) the faithful route: the SAME step loop with every covariance on v_mfma_f64 (SURVEY section 7's parity path) --
             #     and its compressed tensors against the headline leg's, layer by layer, at the full token count

@@ -249,3 +249,14 @@ def test_bench_launcher_propagates_a_failing_rank():
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
     assert "no GPU here" in p.stderr
+
+
+def test_bench_arguments():
+    """--full (off by default) and --dump-outputs DIR parse; a run without timed steps is refused before anything starts."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, None)
+    a = bench.parse_args(["--steps", "1", "--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr

@@ -1069,3 +1069,33 @@ def test_bench_line_contract():
     c = d["selection_certificate"]           # the MLP rank selections of the three timed layers: certified (or flagged) against eps
     assert c["layers"] == 3 and 0 <= c["certified"] <= 3 and c["margin_min"] > 0 and 0 < c["eps"] < 2e-11 and c["score_bound_max"] > 0
     assert r["i8_tolerance_factor"] == 1.0
+
+
+def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps, the last timed layer's compressed tensors, rotary mask and four
+    statistics land in DIR as float32 / float64 .npy files, under 64 MB in all; two runs with the same arguments write the same
+    arrays, and --steps sets the number of timed steps the line reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                            "--batches", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["cpu_baseline"] is None and "value_f64_route" not in d
+        names = sorted(os.listdir(out))
+        assert names == sorted(["up.npy", "gate.npy", "down.npy", "q_proj.npy", "k_proj.npy", "v_proj.npy", "o_proj.npy",
+                                "rotary_mask.npy", "sigma_mlp.npy", "sigma_x.npy", "sigma_q.npy", "sigma_k.npy"]), names
+        assert sum(os.path.getsize(out / n) for n in names) <= 64 << 20
+        arrays = {n: np.load(out / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["sigma_mlp.npy"].dtype == np.float64 and arrays["up.npy"].dtype == np.float32
+        dumps.append(arrays)
+    for n, a in dumps[0].items():
+        assert a.shape == dumps[1][n].shape and np.array_equal(a, dumps[1][n]), n
