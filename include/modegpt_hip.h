@@ -208,10 +208,14 @@ int mdg_bi_accum(const void* x_in, const void* x_out, int dtype, int64_t n_token
  * A[i*sa_i + k*sa_k] (or A[a_rows[i]*sa_i + k*sa_k] when a_rows != NULL), element (k,j) of op(B) is
  * B[k*sb_k + j*sb_j]; C is row-major [M, N] with ldc, dtype f64 or bf16 (bf16: beta must be 0, rounding as
  * torch's .to(bfloat16)).  flags: MDG_GEMM_*.  Batched with element strides. */
-#define MDG_GEMM_LOWER_ONLY 1   /* M==N: only tiles with row-block >= col-block are computed (SYRK update) */
-#define MDG_GEMM_A_LOWER_TRI 2  /* op(A)[i,k] = 0 for k > i (k range clipped per row tile) */
-#define MDG_GEMM_B_LOWER_TRI 4  /* op(B)[k,j] = 0 for k < j (k range clipped per col tile) */
-#define MDG_GEMM_A_UPPER_TRI 8  /* op(A)[i,k] = 0 for k < i */
+/* The triangle flags clip the k-range per 128 x 128 tile of C: the entries of the zero triangle that lie inside the tile's diagonal
+ * 128 x 128 block ARE read and must hold zeros; the entries beyond that block are never read (they may hold anything, NaN too).
+ * a_rows may be unsorted and may repeat rows.  beta == 0 never reads C. */
+#define MDG_GEMM_LOWER_ONLY 1   /* M==N: only tiles with row-block >= col-block are computed (SYRK update); a diagonal tile is
+                                   written WHOLE (its part above the diagonal too), tiles above the diagonal are not touched */
+#define MDG_GEMM_A_LOWER_TRI 2  /* op(A)[i,k] = 0 for k > i: k < i0 + 128 for the rows i0 .. i0+127 of a tile (k >= i0 + 128 not read) */
+#define MDG_GEMM_B_LOWER_TRI 4  /* op(B)[k,j] = 0 for k < j: k >= j0 for the columns j0 .. j0+127 of a tile (k < j0 not read) */
+#define MDG_GEMM_A_UPPER_TRI 8  /* op(A)[i,k] = 0 for k < i: k >= i0 for the rows i0 .. i0+127 of a tile (k < i0 not read) */
 int mdg_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const void* A, int a_dtype, int64_t sa_i,
                  int64_t sa_k, const int64_t* a_rows, const void* B, int b_dtype, int64_t sb_k,
                  int64_t sb_j, double beta, void* C, int c_dtype, int64_t ldc, int64_t batch,

@@ -106,14 +106,17 @@ template <bool KC> struct FastPanel<MDG_F64, KC> {
   // xmax: rows / columns of the operand this tile really has (< 128 in the last, ragged tile row or column).  With k contiguous a
   // thread's loads belong to ONE row, so a row beyond the end simply re-reads the last valid one (its products are never stored);
   // with x contiguous a 16-byte load spans two rows' worth of x and the caller keeps ragged tiles off this path.
-  __device__ __forceinline__ void init(int64_t sx, int64_t sk, int64_t x0, const int64_t* rows, int tid, int xmax = 128) {
+  // base: element offset of the stage base from the operand's origin (with a row gather: the tile's smallest gathered row offset,
+  // so that the 32-bit per-lane offsets stay relative to the rows this tile really reads).
+  __device__ __forceinline__ void init(int64_t sx, int64_t sk, int64_t x0, const int64_t* rows, int64_t base, int tid,
+                                       int xmax = 128) {
 #pragma unroll
     for (int p = 0; p < 4; p++) {
       const int e = tid + 256 * p;
       if (KC) {
         const int kp = e & 7, x = min(e >> 3, xmax - 1);
         const int64_t row = rows ? rows[x0 + x] : x0 + x;
-        voff[p] = (unsigned)((row * sx + 2 * kp) * 8);
+        voff[p] = (unsigned)((row * sx - base + 2 * kp) * 8);
         lo[p] = (2 * kp) * PITCH + (e >> 3);
       } else {
         const int xp = e & 63, k = e >> 6;
@@ -144,11 +147,12 @@ template <bool KC> struct FastPanel<MDG_BF16, KC> {
   uint4 r;
   unsigned voff;
   int lo;
-  __device__ __forceinline__ void init(int64_t sx, int64_t sk, int64_t x0, const int64_t* rows, int tid, int xmax = 128) {
+  __device__ __forceinline__ void init(int64_t sx, int64_t sk, int64_t x0, const int64_t* rows, int64_t base, int tid,
+                                       int xmax = 128) {
     if (KC) {
       const int kp = tid & 1, x = min(tid >> 1, xmax - 1);
       const int64_t row = rows ? rows[x0 + x] : x0 + x;
-      voff = (unsigned)((row * sx + 8 * kp) * 2);
+      voff = (unsigned)((row * sx - base + 8 * kp) * 2);
       lo = (8 * kp) * PITCH + (tid >> 1);
     } else {
       const int xp = tid & 15, k = tid >> 4;
@@ -175,16 +179,17 @@ template <bool KC> struct FastPanel<MDG_BF16, KC> {
 
 template <int ADT, int BDT, bool AKC, bool BKC>
 __device__ __forceinline__ void gemm_tile_fast(const GemmArgs& g, double* lds, const char* Ab, const char* Bb, int64_t i0,
-                                               int64_t j0, int64_t k_begin, int64_t n_stage, Acc& acc, int tid, int lane,
-                                               int wr, int wc) {
+                                               int64_t j0, int64_t k_begin, int64_t n_stage, int64_t a_base, Acc& acc, int tid,
+                                               int lane, int wr, int wc) {
   FastPanel<ADT, AKC> fa;
   FastPanel<BDT, BKC> fb;
   // uniform stage bases: tile origin + first k of the range; per-lane offsets cover the row/col and in-stage k
   const int64_t esa = (int64_t)sizeof(typename ElemOf<ADT>::type), esb = (int64_t)sizeof(typename ElemOf<BDT>::type);
   const bool gather = g.a_rows != nullptr;
-  fa.init(g.sa_i, g.sa_k, gather ? i0 : 0, g.a_rows, tid, (int)min((int64_t)TILE, g.M - i0));   // with a gather the row offset is absolute
-  fb.init(g.sb_j, g.sb_k, 0, nullptr, tid, (int)min((int64_t)TILE, g.N - j0));
-  const char* pa = Ab + ((gather || !AKC ? 0 : i0 * g.sa_i) + (AKC ? k_begin : k_begin * g.sa_k + i0)) * esa;
+  // with a gather the stage base sits at the tile's smallest gathered row offset (a_base) and the per-lane offsets are taken from there
+  fa.init(g.sa_i, g.sa_k, gather ? i0 : 0, g.a_rows, a_base, tid, (int)min((int64_t)TILE, g.M - i0));
+  fb.init(g.sb_j, g.sb_k, 0, nullptr, 0, tid, (int)min((int64_t)TILE, g.N - j0));
+  const char* pa = Ab + ((gather ? a_base : AKC ? i0 * g.sa_i : 0) + (AKC ? k_begin : k_begin * g.sa_k + i0)) * esa;
   const char* pb = Bb + ((BKC ? j0 * g.sb_j + k_begin : k_begin * g.sb_k + j0)) * esb;
   const int64_t da = FastPanel<ADT, AKC>::stage_bytes(g.sa_k), db = FastPanel<BDT, BKC>::stage_bytes(g.sb_k);
   fa.load(pa);
@@ -219,7 +224,7 @@ __device__ __forceinline__ void gemm_tile_fast(const GemmArgs& g, double* lds, c
 
 template <int ADT, int BDT, bool AKC, bool BKC>
 __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
-  __shared__ double lds[4 * PANEL + 2 * TILE];
+  __shared__ double lds[4 * PANEL + 2 * TILE + 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   int bi, bj;
@@ -252,9 +257,23 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   // element offsets of the 128 rows of op(A) / columns of op(B) this tile touches (-1 = out of range -> zero fill)
   int64_t* aoff = (int64_t*)(lds + 4 * PANEL);
   int64_t* boff = aoff + TILE;
+  int64_t* aspan = boff + TILE;  // gathered, k-contiguous A: [smallest, largest] row offset of the tile's rows, per wave 0 / 1
   if (tid < TILE) {
     int64_t gi = i0 + tid;
-    aoff[tid] = gi < g.M ? (g.a_rows ? g.a_rows[gi] : gi) * g.sa_i : -1;
+    const int64_t off = gi < g.M ? (g.a_rows ? g.a_rows[gi] : gi) * g.sa_i : -1;
+    aoff[tid] = off;
+    if (AKC && g.a_rows) {
+      long long lo = off >= 0 ? off : INT64_MAX, hi = off;
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) {
+        lo = min(lo, __shfl_xor(lo, m));
+        hi = max(hi, __shfl_xor(hi, m));
+      }
+      if (lane == 0) {
+        aspan[2 * wave] = lo;
+        aspan[2 * wave + 1] = hi;
+      }
+    }
   } else {
     int64_t gj = j0 + (tid - TILE);
     boff[tid - TILE] = gj < g.N ? gj * g.sb_j : -1;
@@ -264,10 +283,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
   const int64_t n_stage = k_end > k_begin ? (k_end - k_begin + BK - 1) / BK : 0;
   // (a ragged last tile row / column stays on the vector path where that operand is k-contiguous: FastPanel::init)
   const bool interior = (AKC || i0 + TILE <= g.M) && (BKC || j0 + TILE <= g.N);
-  if (g.fast_ok && interior && n_stage > 0 && (k_end - k_begin) % BK == 0 && (AKC || !g.a_rows)) {
+  // A gathered tile's per-lane offsets are measured from its smallest row offset: the furthest byte a stage reads must lie < 4 GiB
+  // from there (the rows of a sorted selection span a few hundred rows; unsorted ones far apart go element-wise)
+  int64_t a_base = 0;
+  bool a_fits = true;
+  if (AKC && g.a_rows) {
+    a_base = min(aspan[0], aspan[2]);
+    a_fits = (max(aspan[1], aspan[3]) - a_base + BK) * (int64_t)sizeof(typename ElemOf<ADT>::type) < ((int64_t)1 << 32);
+  }
+  if (g.fast_ok && interior && n_stage > 0 && (k_end - k_begin) % BK == 0 && (AKC || !g.a_rows) && a_fits) {
     Acc facc;  // separate accumulator set: the two paths never share live registers
     acc_zero(facc);
-    gemm_tile_fast<ADT, BDT, AKC, BKC>(g, lds, Ab, Bb, i0, j0, k_begin, n_stage, facc, tid, lane, wr, wc);
+    gemm_tile_fast<ADT, BDT, AKC, BKC>(g, lds, Ab, Bb, i0, j0, k_begin, n_stage, a_base, facc, tid, lane, wr, wc);
     gemm_epilogue(g, facc, batch, i0, j0, wr, wc, lane);
     return;
   }
@@ -341,7 +368,8 @@ int gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const void* A, int a
     bool ok = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && (a_bs % ua == 0) && (b_bs % ub == 0);
     ok = ok && (a_kc ? sa_i % ua == 0 : (sa_i == 1 && sa_k % ua == 0));
     ok = ok && (b_kc ? sb_j % ub == 0 : (sb_j == 1 && sb_k % ub == 0));
-    // per-lane offsets are 32-bit: the furthest element a stage touches must be < 4 GiB from the stage base
+    // per-lane offsets are 32-bit: the furthest element a stage touches must be < 4 GiB from the stage base (a gathered A is
+    // checked per tile on the device, against the rows that tile really reads)
     const int64_t span_a = a_rows ? (int64_t)1 << 62 : (a_kc ? TILE * sa_i : BK * sa_k + TILE) * (int64_t)(16 / ua);
     const int64_t span_b = (b_kc ? TILE * sb_j : BK * sb_k + TILE) * (int64_t)(16 / ub);
     ok = ok && span_b < ((int64_t)1 << 32) && (a_rows || span_a < ((int64_t)1 << 32));
