@@ -38,7 +38,8 @@ extern "C" {
                              9: the int8 route's tolerance factor is an ARGUMENT of mdg_cov_accum_i8 / mdg_cov_accum_i8_multi (the
                                 process-wide setter / getter of ABI 8 are gone: no accuracy state in the library);
                                 mdg_ridge_scores takes `sens`, mdg_select_margin added (certificate of the MLP rank selection);
-                                the exact route of the int8 covariance (`flags`, route_counts[4], mdg_cov_accum_i8_route's `exact`) */
+                                the exact route of the int8 covariance (`flags`, route_counts[4], mdg_cov_accum_i8_route's `exact`);
+                                added under 9: mdg_qk_select_margin, mdg_vo_spectrum */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -303,6 +304,30 @@ int mdg_nystrom_down_overlapped(const double* C, int64_t n, int64_t ldc, const i
 int mdg_qk_select(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q,
                   double ridge_k, int rank, int mode, int64_t* mask, int64_t* q_rows, int64_t* k_rows,
                   void* stream);
+/* The certificate of that selection: can the selected SET (and its ORDER -- the reference does not sort the mask) differ for any
+ * sigma_q / sigma_k within the error bound of the covariance route, or under the rounding of the reference's own route to the same
+ * score?  The reference reaches ||col_j(sqrt(C + rho I))||^2 through eigh -> sqrt -> V diag V^T -> column norm
+ * (compression_utils.py:15-55, compress_qk.py:355-367, 403-419, 452-464); mdg_qk_select uses the identity C_jj + rho.  The two agree
+ * in exact arithmetic only: the eigh route carries rounding of the order u * lambda_max, however small C_jj is.  Model: a diagonal
+ * entry c = C_jj of any head matrix is known to within
+ *     delta_j = eps_rel * |c| + eps_abs * (||C||_inf + rho)
+ * eps_rel: the covariance route's entry-wise bound (relative to c itself on the diagonal); eps_abs: the eigh route's rounding
+ * relative to ||C||_inf (largest absolute row sum, an upper bound on lambda_max that needs no eigensolve; the kernel computes it from
+ * the hd x hd matrices it reads).  Every score of the three modes is monotone non-decreasing in every diagonal entry, so the bound
+ * is INTERVAL ARITHMETIC, not first order: s_lo / s_hi = the score formula with every factor max(c - delta + rho, 0) /
+ * max(c + delta + rho, 0).  Same shapes, modes and argument checks as mdg_qk_select; mask [n_kv, rank] is what that call wrote
+ * (it is read, not recomputed).  out (DEVICE, [n_kv][8] doubles), per kv head:
+ *   [0] smallest selected score             [1] largest unselected score           -> margin = ([0] - [1]) / [0]
+ *   [2] min over selected of s_lo           [3] max over unselected of s_hi        -> the set is certified iff [2] > [3]
+ *   [4] max over units of (s_hi - s_lo) / (2 s): the relative half-width a score can move
+ *   [5] number of units whose interval reaches across the midpoint of [0] and [1]
+ *   [6] number of neighbouring positions in the selected (score-descending) order whose intervals overlap; 0: the order is certified too
+ *   [7] 1.0 if the set is certified else 0.0
+ * rank == number of units: nothing to separate, certified, [1] = -inf.  NaN scores rank as in mdg_qk_select (largest) and make the
+ * head uncertified.  Only enqueues; one workgroup per kv head.  Not in the reference. */
+int mdg_qk_select_margin(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q,
+                         double ridge_k, int rank, int mode, const int64_t* mask, double eps_rel, double eps_abs,
+                         double* out, void* stream);
 
 /* ------------------------------------------------------------------ VO: SVD of sqrt(C) W_v^T
  * v_out [n_kv*rank, d] bf16, o_out [d, n_heads*rank] bf16 (compress_vo.py:89-90).  W_v [n_kv*hd, d],
@@ -315,6 +340,24 @@ int mdg_vo_compress(const double* cov_x, int64_t d, int64_t ldc, const void* Wv,
                     int64_t ld_wo, int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, void* v_out,
                     int64_t ld_v, void* o_out, int64_t ld_o, double* v_f64, double* o_f64, void* ws,
                     size_t ws_bytes, void* stream);
+/* What the truncation at `rank` did to the spectrum (compress_vo.py:130-131,145-146 / :187-223 cut U, S, Vh at `rank` and report
+ * nothing about sigma_r against sigma_r+1; when they nearly coincide the kept subspace is not determined by the data).  Reads the
+ * eigenvalues the LAST mdg_vo_compress call left in workspace `ws` (same shapes): the spectrum that call truncated -- the Gram
+ * matrix's for the grouped variant, the second SVD's for the two-SVD MHA variant (lambda = sigma^2 of the reference's SVD).
+ * out (DEVICE, [n_kv][8] doubles), per kv head:
+ *   [0], [1] lambda_r, lambda_r+1 ([1] = 0 when rank == hd)
+ *   [2] relative gap (sigma_r - sigma_r+1) / sigma_r, sigma = sqrt(max(lambda, 0))
+ *   [3] retained energy sum_{i<r} lambda_i / sum_i lambda_i
+ *   [4] grouped: the Weyl bound b = eps * || |W_v,h| s ||_2^2, s_a = sqrt(c_aa) of sigma_x; NaN for the MHA variant
+ *   [5] 1.0 if lambda_r - lambda_r+1 > 2 b (the kept subspace is separated from the dropped one for every sigma_x within the
+ *       bound), 0.0 if not; NaN for the MHA variant
+ *   [6], [7] lambda_1, lambda_hd
+ * [4]: an entry-wise error |E_ab| <= eps s_a s_b of sigma_x gives ||W E W^T||_2 <= || |W| |E| |W|^T ||_2 <= eps || |W| s ||_2^2, and the
+ * matrix diagonalised is W_v,h (sigma_x + rho I) W_v,h^T, so by Weyl no eigenvalue moves by more than b.  One pass over the head's
+ * hd x d slice of W_v and the diagonal of sigma_x.  The MHA variant's second spectrum also depends on W_o; no bound is given for
+ * it, the gap alone is reported.  Only enqueues; one workgroup per kv head. */
+int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_t d, int64_t ldc, const void* Wv, int64_t ld_wv,
+                    int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, double eps, double* out, void* stream);
 
 /* ------------------------------------------------------------------ sqrt_M (compression_utils.py:15-55)
  * root = V diag(sqrt(max(lambda + ridge*scale, 0))) V^T, inv_root (optional) with the 1e-12 clamp;

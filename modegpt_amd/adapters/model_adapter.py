@@ -108,6 +108,54 @@ class ModelAdapter(ABC):
             store.update({str(k): v for k, v in report.items()})
         return report
 
+    # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
+    def attention_margin(self, layer_idx: int, kind: str, tensor, *eps: float) -> None:
+        """compress_qk (kind "qk": ops.qk_select_margin's [n_kv, 8], eps = (eps_rel, eps_abs)) and compress_vo (kind "vo":
+        ops.vo_compress(want_spectrum=True)'s [n_kv, 8], eps = (eps,)) hand their device tensors over for layer `layer_idx`."""
+        if kind not in ("qk", "vo"):
+            raise ValueError(f"attention_margin: kind must be 'qk' or 'vo', got {kind!r}")
+        self.__dict__.setdefault("_attention_margins", {})[(kind, int(layer_idx))] = (tensor, tuple(float(e) for e in eps))
+
+    def report_attention_margins(self, log=None) -> dict:
+        """Reads the recorded attention certificates (64 bytes per kv head; call it where the host waits for the chains anyway) and
+        returns {"qk": {layer: ops.decode_qk_margin(...)}, "vo": {layer: ops.decode_vo_spectrum(...)}}; the same goes to
+        metrics["qk_selection"] / metrics["vo_spectrum"] under str(layer).  WARNS once per layer whose QK pair selection is not
+        certified -- some head's weakest selected and strongest unselected pair sit closer than the covariance route's error bound
+        and the rounding of the reference's eigh route can move them, so the reference may keep another pair set there
+        (compress_qk.py:366-367) -- and once per grouped VO layer in which some head's sigma_r and sigma_r+1 are not separated
+        (compress_vo.py:130-146: the kept subspace is then not determined by the data)."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_attention_margins", {})
+        report = {"qk": {}, "vo": {}}
+        for kind, layer in sorted(pending):
+            tensor, eps = pending[(kind, layer)]
+            rows = tensor.cpu().tolist()
+            if kind == "qk":
+                m = ops.decode_qk_margin(rows, *eps)
+                if not m["certified"]:
+                    flagged = [i for i, h in enumerate(m["heads"]) if not h["certified"]]
+                    log.warning(f"[QK] Layer {layer}: pair selection NOT certified -- kv head {m['weakest_head']}: threshold margin "
+                                f"{m['margin']:.3e} against a score half-width {m['score_halfwidth']:.3e} (eps_rel = {eps[0]:.2e}, "
+                                f"eps_abs = {eps[1]:.2e}); {m['heads'][m['weakest_head']]['units_at_risk']} pairs within reach of the "
+                                f"threshold; uncertified kv heads: {flagged}")
+            else:
+                m = ops.decode_vo_spectrum(rows, *eps)
+                if m["separated"] is False:
+                    flagged = [i for i, h in enumerate(m["heads"]) if h["separated"] is False]
+                    worst = min(flagged, key=lambda i: m["heads"][i]["gap"])
+                    w = m["heads"][worst]
+                    log.warning(f"[VO] Layer {layer}: kept subspace NOT separated -- kv head {worst}: relative gap "
+                                f"{w['gap']:.3e} between sigma_r and sigma_r+1 (lambda_r - lambda_r+1 = "
+                                f"{w['lambda_r'] - w['lambda_next']:.3e} against twice the bound {w['bound']:.3e}, eps = {eps[0]:.2e})")
+            report[kind][layer] = m
+        if pending:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            for kind, key in (("qk", "qk_selection"), ("vo", "vo_spectrum")):
+                if report[kind]:
+                    self.metrics.setdefault(key, {}).update({str(k): v for k, v in report[kind].items()})
+        return report
+
     # ---- reconstruction: per-(layer, stage) artefacts and the final swap (model_adapter.py:184-237) ----
     def save_layer(self, output_dir: str, suffix: str, weights: dict, layer_idx):
         """torch.save({name: bf16 tensor}) to <output_dir>/layer_<i>_<suffix>; env vars in the path expand.  The file is in

@@ -10,10 +10,38 @@ from torch import Tensor
 from .. import _lib, ops
 from ..adapters.model_adapter import ModelAdapter
 from ..model_utils import dtype_p, local_device
+from .compress_mlp import I8_GUARANTEED_EPS
 
 logger = logging.getLogger("MoDeGPT")
 
 _SQRT_M_DEFAULT_RIDGE = 1e-4  # sqrt_M's default ridge_lambda (compression_utils.py:16)
+
+# What the reference's route to a squared column norm -- eigh -> sqrt -> V diag V^T -> column norm (compression_utils.py:15-55) --
+# can differ by from the identity C_jj + rho this engine scores with, relative to ||C||_inf + rho: the `eps_abs` of the QK
+# certificate (mdg_qk_select_margin).  The one figure of the certificate that is measured, not derived; measured against the CPU
+# oracle's sqrt_M (torch.linalg.eigh on LAPACK), never against this engine:
+#     worst over the family of  | ||col_j(sqrt_M(C, rho))||^2 - (C_jj + rho) | / (||C||_inf + rho)  =  EIGH_ROUTE_MEASURED_ULPS * 2^-53
+# over every sigma_q / sigma_k head of tests/golden/ (rho in {1e-4, 1e-2}) and 96 seeded synthetic matrices (hd in {64, 128},
+# C = X^T X / T with column scales spread over 0, 2, 4, 6 decades and mild mixing, rho in {1e-4, 1e-2}, 6 seeds each;
+# tests/test_attn_certificate_host.py builds the family and re-measures it).  Times EIGH_ROUTE_SAFETY = 4, because the reference
+# runs torch.linalg.eigh on whatever backend its user has -- LAPACK builds, thread counts and the GPU solvers round differently --
+# and a certificate has to cover those too.
+EIGH_ROUTE_MEASURED_ULPS = 41.04     # (at tests/golden tiny_mha sigma_k[2], rho = 1e-4; the synthetic part of the family: 24 .. 39 depending on LAPACK threads)
+EIGH_ROUTE_SAFETY = 4
+EIGH_ROUTE_EPS_ABS = EIGH_ROUTE_SAFETY * EIGH_ROUTE_MEASURED_ULPS * 2.0 ** -53
+
+
+def attention_error_eps(adapter) -> float:
+    """The entry-wise relative error bound eps of the sigma_q / sigma_k / sigma_x this run accumulated, |sigma_ij - exact| <= eps
+    sqrt(sigma_ii sigma_jj), for the attention certificates.  `adapter.cov_error_eps` when the caller states it.  Otherwise: which
+    route each of these statistics took is not recorded separately, so the larger of the int8 route's guarantee (1.1e-11 x the
+    tolerance factor + one fp64 rounding per fold) and the worst case of fp64 accumulation over the calibration tokens,
+    (tokens / 4 + 4) 2^-53 -- whatever the model's dtype or width."""
+    stated = getattr(adapter, "cov_error_eps", None)
+    if stated is not None:
+        return float(stated)
+    tokens = int(getattr(adapter, "calib_tokens", 0) or getattr(adapter.config, "calib_size", 32) * 2048)
+    return max(I8_GUARANTEED_EPS * ops.i8_tolerance() + 64 * 2.0 ** -53, (tokens / 4 + 4) * 2.0 ** -53)
 
 
 def qk_rank_rule(head_dim: int, keep_ratio: float, arch: str, rank: Optional[int] = None) -> int:
@@ -49,6 +77,12 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     cq = cov_q_list.to(device=local_device(), dtype=dtype_p)
     ck = cov_k_list.to(device=local_device(), dtype=dtype_p)
     mask, q_rows, k_rows = ops.qk_select(cq, ck, rank, mode, ridge_q, ridge_k)
+    record = getattr(adapter, "attention_margin", None)           # (a duck-typed adapter without it: no certificate)
+    if record is not None:
+        # the selection's certificate stays on the device until the adapter next waits for the stream (report_attention_margins)
+        eps_rel = attention_error_eps(adapter)
+        record(layer_idx, "qk", ops.qk_select_margin(cq, ck, rank, mode, ridge_q, ridge_k, mask, eps_rel, EIGH_ROUTE_EPS_ABS),
+               eps_rel, EIGH_ROUTE_EPS_ABS)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

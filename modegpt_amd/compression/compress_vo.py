@@ -11,6 +11,7 @@ from .. import ops
 from ..adapters.model_adapter import ModelAdapter
 from ..model_utils import dtype_p, local_device
 from ._window import over_layers
+from .compress_qk import attention_error_eps
 
 logger = logging.getLogger("MoDeGPT")
 
@@ -107,8 +108,17 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
             logger.warning(f"[VO] Layer {layer}: cannot access v_proj/o_proj: {e}")
             return None
         # (the eigensolver's convergence flag is read once per layer, by the adapter: over_layers)
-        return ops.vo_compress(C, W_v.detach().to(local_device()), W_o.detach().to(local_device()), n_heads, n_kv, head_dim,
-                               rank_i, adapter.config.ridge_vo)
+        record = getattr(adapter, "attention_margin", None)       # (a duck-typed adapter without it: no spectrum report)
+        if record is None:
+            return ops.vo_compress(C, W_v.detach().to(local_device()), W_o.detach().to(local_device()), n_heads, n_kv, head_dim,
+                                   rank_i, adapter.config.ridge_vo)
+        # sigma_r against sigma_r+1 of the spectrum just truncated: stays on the device until report_attention_margins
+        eps = attention_error_eps(adapter)
+        V_heads, O_heads, spectrum = ops.vo_compress(C, W_v.detach().to(local_device()), W_o.detach().to(local_device()), n_heads,
+                                                     n_kv, head_dim, rank_i, adapter.config.ridge_vo, want_spectrum=True,
+                                                     spectrum_eps=eps)
+        record(layer, "vo", spectrum, eps)
+        return V_heads, O_heads
 
     def retire(layer, result):
         if result is None:

@@ -189,6 +189,153 @@ __global__ __launch_bounds__(128) void qk_select_kernel(const double* cov_q, con
   }
 }
 
+// ||C||_inf (largest absolute row sum) of one hd x hd matrix by the whole 256-thread workgroup: a wave per row, lanes along the row
+// (coalesced), butterfly sum; 16 rows of a wave are loaded together (the kernel is latency-bound: few round trips matter, not
+// bytes).  vec: hd even and C 16-byte aligned -> two columns per lane and load.  Every thread returns the value; `part` is 4
+// doubles of LDS.  An upper bound on lambda_max.
+__device__ __forceinline__ double block_norm_inf(const double* C, int hd, int vec, double* part) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double m = 0.;
+  for (int r0 = w; r0 < hd; r0 += 64) {
+    double s[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) s[k] = 0.;
+    if (vec) {
+      for (int c = 2 * lane; c < hd; c += 128)
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+          if (r0 + 4 * k < hd) {
+            const d2 v = *(const d2*)(C + (int64_t)(r0 + 4 * k) * hd + c);
+            s[k] += fabs(v.x) + fabs(v.y);
+          }
+    } else {
+      for (int c = lane; c < hd; c += 64)
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+          if (r0 + 4 * k < hd) s[k] += fabs(C[(int64_t)(r0 + 4 * k) * hd + c]);
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+      m = fmax(m, s[k]);
+    }
+  }
+  __syncthreads();  // (`part` may still be read from the previous call)
+  if (lane == 0) part[w] = m;
+  __syncthreads();
+  return fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
+}
+
+// One squared column norm C_jj + rho of qk_select_kernel and the two ends of what it can be when C_jj is known to within
+// delta = eps_rel |C_jj| + eps_abs (||C||_inf + rho): v[0] centre (the expression qk_select_kernel evaluates), v[1] low, v[2] high.
+__device__ __forceinline__ void norm2_interval(double c, double ridge, double norm, double eps_rel, double eps_abs, double v[3]) {
+  const double delta = eps_rel * fabs(c) + eps_abs * (norm + ridge);
+  v[0] = fmax(c + ridge, 0.);
+  v[1] = fmax(c - delta + ridge, 0.);
+  v[2] = fmax(c + delta + ridge, 0.);
+}
+
+// The certificate of qk_select_kernel's selection (mask: what that kernel wrote) against an uncertainty of every diagonal entry of
+// every sigma_q / sigma_k head: one workgroup per kv head.  Every score of the three modes is monotone non-decreasing in every
+// diagonal entry, so [s_lo, s_hi] = the score formula at the low / high ends of all its factors is interval arithmetic, not a
+// first-order bound.  out[h][8]: see mdg_qk_select_margin (include/modegpt_hip.h).
+__global__ __launch_bounds__(256) void qk_select_margin_kernel(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd,
+                                                               double ridge_q, double ridge_k, int rank, int mode, const int64_t* mask,
+                                                               double eps_rel, double eps_abs, int vec, double* out) {
+  __shared__ double sc[3][128];   // [centre, low, high][unit]
+  __shared__ int selected[128];
+  __shared__ double part[4];
+  __shared__ double red[5][256];
+  __shared__ int cnt[3][256];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const int g = n_heads / n_kv;
+  const int ns = (mode == MDG_QK_OPT) ? hd : hd / 2;
+  const int take = (mode == MDG_QK_OPT) ? rank : rank / 2;
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  const double* Ck = cov_k + (int64_t)h * hd * hd;
+  const int j1 = tid, j2 = (mode == MDG_QK_OPT) ? tid : tid + hd / 2;
+  const bool unit = tid < ns;
+  double k1[3] = {0., 0., 0.}, k2[3] = {0., 0., 0.}, acc[3] = {0., 0., 0.};
+  // (the diagonal entries are fetched before the norm's barrier so that they travel with its loads)
+  const double ck1 = unit ? Ck[j1 * hd + j1] : 0., ck2 = unit ? Ck[j2 * hd + j2] : 0.;
+  const double norm_k = block_norm_inf(Ck, hd, vec, part);
+  if (unit) {
+    norm2_interval(ck1, ridge_k, norm_k, eps_rel, eps_abs, k1);
+    norm2_interval(ck2, ridge_k, norm_k, eps_rel, eps_abs, k2);
+  }
+  for (int q = 0; q < g; q++) {   // (OPT / ROPE_MHA: g == 1)
+    const double* Cq = cov_q + (int64_t)(h * g + q) * hd * hd;
+    const double cq1 = unit ? Cq[j1 * hd + j1] : 0., cq2 = unit ? Cq[j2 * hd + j2] : 0.;
+    const double norm_q = block_norm_inf(Cq, hd, vec, part);
+    if (!unit) continue;
+    double q1[3], q2[3];
+    norm2_interval(cq1, ridge_q, norm_q, eps_rel, eps_abs, q1);
+    norm2_interval(cq2, ridge_q, norm_q, eps_rel, eps_abs, q2);
+    for (int v = 0; v < 3; v++) {
+      if (mode == MDG_QK_OPT) {
+        acc[v] = sqrt(q1[v]) * sqrt(k1[v]);  // compress_qk.py:458-461
+      } else {
+        const double nq1 = q1[v], nk1 = k1[v], nq2 = q2[v], nk2 = k2[v];
+        acc[v] += nq1 * nk1 + nq2 * nk2;  // compress_qk.py:360-362 / :414-416
+      }
+    }
+  }
+  if (unit) {
+    for (int v = 0; v < 3; v++) sc[v][tid] = (mode == MDG_QK_ROPE_GROUPED) ? sqrt(acc[v]) : acc[v];  // :364
+    selected[tid] = 0;
+  }
+  __syncthreads();
+  int bad = 0;                    // a mask entry outside the units, or a NaN score: nothing is certified
+  if (tid < take) {
+    const int64_t j = mask[(int64_t)h * rank + tid];
+    if (j >= 0 && j < ns) selected[j] = 1; else bad = 1;
+  }
+  __syncthreads();
+  double s_sel = inf, s_unsel = -inf, lo_sel = inf, hi_unsel = -inf, width = 0.;
+  if (unit) {
+    const double s = sc[0][tid], lo = sc[1][tid], hi = sc[2][tid];
+    if (s != s || lo != lo || hi != hi) bad = 1;
+    if (selected[tid]) { s_sel = s; lo_sel = lo; } else { s_unsel = s; hi_unsel = hi; }
+    width = s > 0. ? (hi - lo) / (2. * s) : (hi > lo ? inf : 0.);
+  }
+  red[0][tid] = s_sel; red[1][tid] = s_unsel; red[2][tid] = lo_sel; red[3][tid] = hi_unsel; red[4][tid] = width;
+  cnt[0][tid] = bad;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      red[0][tid] = fmin(red[0][tid], red[0][tid + o]); red[1][tid] = fmax(red[1][tid], red[1][tid + o]);
+      red[2][tid] = fmin(red[2][tid], red[2][tid + o]); red[3][tid] = fmax(red[3][tid], red[3][tid + o]);
+      red[4][tid] = fmax(red[4][tid], red[4][tid + o]);
+      cnt[0][tid] |= cnt[0][tid + o];
+    }
+    __syncthreads();
+  }
+  const double mid = 0.5 * (red[0][0] + red[1][0]);
+  int at_risk = 0, overlap = 0;
+  if (unit && red[0][0] < inf && red[1][0] > -inf) {
+    const double lo = sc[1][tid], hi = sc[2][tid];
+    at_risk = (lo != lo || hi != hi || (lo <= mid && mid <= hi)) ? 1 : 0;
+  }
+  if (tid + 1 < take) {           // neighbours in the selected (score-descending) order: does the lower one's interval reach the upper's?
+    const int64_t a = mask[(int64_t)h * rank + tid], b = mask[(int64_t)h * rank + tid + 1];
+    if (a >= 0 && a < ns && b >= 0 && b < ns) overlap = !(sc[1][a] > sc[2][b]) ? 1 : 0;
+    else overlap = 1;
+  }
+  cnt[1][tid] = at_risk; cnt[2][tid] = overlap;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) { cnt[1][tid] += cnt[1][tid + o]; cnt[2][tid] += cnt[2][tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double* o8 = out + (int64_t)h * 8;
+    for (int i = 0; i < 5; i++) o8[i] = red[i][0];
+    o8[5] = (double)cnt[1][0];
+    o8[6] = (double)cnt[2][0];
+    o8[7] = (!cnt[0][0] && red[2][0] > red[3][0]) ? 1. : 0.;
+  }
+}
+
 // out[j][i] = bf16(in[i][j]) through a 32x32 LDS tile.
 __global__ __launch_bounds__(256) void cast_transpose_kernel(const double* in, int64_t rows, int64_t cols,
                                                              int64_t ld_in, bf16_t* out, int64_t ld_out) {
@@ -261,6 +408,30 @@ extern "C" int mdg_qk_select(const double* cov_q, const double* cov_k, int n_hea
   if (mode == MDG_QK_ROPE_MHA) MDG_CHECK_ARG(n_heads == n_kv, "mdg_qk_select: ROPE_MHA needs n_heads == n_kv");
   hipLaunchKernelGGL(qk_select_kernel, dim3(n_kv), dim3(128), 0, (hipStream_t)stream, cov_q, cov_k, n_heads, n_kv, hd,
                      ridge_q, ridge_k, rank, mode, mask, q_rows, k_rows);
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}
+
+extern "C" int mdg_qk_select_margin(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q,
+                                    double ridge_k, int rank, int mode, const int64_t* mask, double eps_rel, double eps_abs,
+                                    double* out, void* stream) {
+  MDG_CLEAR();
+  MDG_CHECK_ARG(cov_q && cov_k && mask && out, "mdg_qk_select_margin: null pointer");
+  MDG_CHECK_ARG(n_kv > 0 && n_heads >= n_kv && n_heads % n_kv == 0, "mdg_qk_select_margin: n_heads %d not a multiple of n_kv %d",
+                n_heads, n_kv);
+  MDG_CHECK_ARG(hd > 0 && hd <= 256 && rank >= 1 && rank <= hd, "mdg_qk_select_margin: bad head_dim %d / rank %d", hd, rank);
+  MDG_CHECK_ARG(mode >= MDG_QK_ROPE_GROUPED && mode <= MDG_QK_OPT, "mdg_qk_select_margin: unknown mode %d", mode);
+  if (mode != MDG_QK_OPT) {
+    MDG_CHECK_ARG(hd % 2 == 0 && rank % 2 == 0, "mdg_qk_select_margin: RoPE modes need even head_dim and rank");
+    MDG_CHECK_ARG(hd / 2 <= 128, "mdg_qk_select_margin: head_dim %d too large", hd);
+  } else {
+    MDG_CHECK_ARG(hd <= 128 && n_heads == n_kv, "mdg_qk_select_margin: OPT mode needs head_dim <= 128 and n_heads == n_kv");
+  }
+  if (mode == MDG_QK_ROPE_MHA) MDG_CHECK_ARG(n_heads == n_kv, "mdg_qk_select_margin: ROPE_MHA needs n_heads == n_kv");
+  MDG_CHECK_ARG(eps_rel >= 0. && eps_abs >= 0., "mdg_qk_select_margin: negative error bound");
+  const int vec = hd % 2 == 0 && (uintptr_t)cov_q % 16 == 0 && (uintptr_t)cov_k % 16 == 0;   // two columns per load
+  hipLaunchKernelGGL(qk_select_margin_kernel, dim3(n_kv), dim3(256), 0, (hipStream_t)stream, cov_q, cov_k, n_heads, n_kv, hd,
+                     ridge_q, ridge_k, rank, mode, mask, eps_rel, eps_abs, vec, out);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

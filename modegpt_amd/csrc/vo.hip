@@ -83,6 +83,83 @@ __global__ __launch_bounds__(256) void vo_factors_mha_kernel(const double* evals
   }
 }
 
+// What the truncation at `rank` did to the spectrum mdg_vo_compress left in its workspace (lam: [n_kv][hd], descending): one
+// workgroup per kv head, out[h][8] as documented at mdg_vo_spectrum.  grouped: also the Weyl bound eps * || |W_v,h| s ||_2^2,
+// s_a = sqrt(sigma_x,aa).  The diagonal of sigma_x is a strided read: it is staged through LDS once per chunk of VO_SPEC_CHUNK
+// columns; a wave owns every fourth row of the head's hd x d slice of W_v (hd <= 128: at most 32 rows, their partial sums in
+// registers), lanes along the row (coalesced), fixed summation order.  vec (bf16 weights, 16-byte aligned rows, d % 8 == 0): eight
+// weights per lane and load.
+constexpr int VO_SPEC_CHUNK = 2048;
+template <int DT>
+__global__ __launch_bounds__(256) void vo_spectrum_kernel(const double* lam_all, const double* cov_x, int64_t d, int64_t ldc,
+                                                          const void* Wv, int64_t ld_wv, int hd, int rank, int grouped, double eps,
+                                                          int vec, double* out) {
+  __shared__ double s_[VO_SPEC_CHUNK];
+  __shared__ double part[4];
+  const int h = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const double* lam = lam_all + (int64_t)h * hd;
+  double mine = 0.;
+  if (grouped) {
+    double acc[32];
+#pragma unroll
+    for (int ii = 0; ii < 32; ii++) acc[ii] = 0.;
+    for (int64_t a0 = 0; a0 < d; a0 += VO_SPEC_CHUNK) {
+      const int len = (int)(d - a0 < VO_SPEC_CHUNK ? d - a0 : VO_SPEC_CHUNK);
+      __syncthreads();
+      for (int e = tid; e < len; e += 256) s_[e] = sqrt(fmax(cov_x[(a0 + e) * ldc + a0 + e], 0.));
+      __syncthreads();
+#pragma unroll
+      for (int ii = 0; ii < 32; ii++) {
+        const int i = w + 4 * ii;
+        if (i < hd) {
+          const int64_t row = ((int64_t)h * hd + i) * ld_wv + a0;
+          double s = 0.;
+          if (DT == MDG_BF16 && vec) {
+            const uint4* rp = (const uint4*)((const bf16_t*)Wv + row);
+            for (int v = lane; v < len / 8; v += 64) {
+              const uint4 u = rp[v];
+              const double* sp = s_ + 8 * v;
+              const unsigned q[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+              for (int t = 0; t < 4; t++)   // (|x|: the sign bit masked off; element 2t in the low half)
+                s += bf16_to_f64((bf16_t)(q[t] & 0x7fffu)) * sp[2 * t] + bf16_to_f64((bf16_t)((q[t] >> 16) & 0x7fffu)) * sp[2 * t + 1];
+            }
+          } else {
+            for (int e = lane; e < len; e += 64) s += fabs(load_f64<DT>(Wv, row + e)) * s_[e];
+          }
+          acc[ii] += s;
+        }
+      }
+    }
+#pragma unroll
+    for (int ii = 0; ii < 32; ii++) {
+      double s = acc[ii];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      mine += s * s;     // (rows beyond hd contribute exact zeros)
+    }
+  }
+  if (lane == 0) part[w] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double l_r = lam[rank - 1], l_next = rank < hd ? lam[rank] : 0.;
+    const double s_r = sqrt(fmax(l_r, 0.)), s_next = sqrt(fmax(l_next, 0.));
+    double kept = 0., all = 0.;
+    for (int i = 0; i < hd; i++) {
+      all += lam[i];
+      if (i == rank - 1) kept = all;
+    }
+    const double b = eps * (((part[0] + part[1]) + part[2]) + part[3]);
+    double* o8 = out + (int64_t)h * 8;
+    o8[0] = l_r; o8[1] = l_next;
+    o8[2] = s_r > 0. ? (s_r - s_next) / s_r : 0.;
+    o8[3] = kept / all;
+    o8[4] = grouped ? b : nan;
+    o8[5] = grouped ? (l_r - l_next > 2. * b ? 1. : 0.) : nan;
+    o8[6] = lam[0]; o8[7] = lam[hd - 1];
+  }
+}
+
 struct VoWs {
   double *T, *G, *evals, *evecs, *P, *Q, *Mh, *tmp, *Y, *evals2, *evecs2;
   int* flag;
@@ -186,4 +263,31 @@ extern "C" int mdg_vo_compress(const double* cov_x, int64_t d, int64_t ldc, cons
     }
   }
   return check_flag(w.flag, st, "mdg_vo_compress");
+}
+
+extern "C" int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_t d, int64_t ldc, const void* Wv,
+                               int64_t ld_wv, int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, double eps,
+                               double* out, void* stream) {
+  MDG_CLEAR();
+  MDG_CHECK_ARG(cov_x && Wv && out, "mdg_vo_spectrum: null pointer");
+  MDG_CHECK_ARG(w_dtype == MDG_BF16 || w_dtype == MDG_F64, "mdg_vo_spectrum: weights must be bf16 or f64 (got %d)", w_dtype);
+  MDG_CHECK_ARG(n_kv > 0 && n_heads % n_kv == 0 && hd >= 2 && hd <= 128 && hd % 2 == 0,
+                "mdg_vo_spectrum: unsupported head layout (n_heads=%d n_kv=%d hd=%d)", n_heads, n_kv, hd);
+  MDG_CHECK_ARG(rank >= 1 && rank <= hd, "mdg_vo_spectrum: rank %d outside [1, %d]", rank, hd);
+  MDG_CHECK_ARG(d > 0 && ldc >= d && ld_wv >= d, "mdg_vo_spectrum: bad leading dimensions");
+  MDG_CHECK_ARG(eps >= 0. && ridge == ridge, "mdg_vo_spectrum: bad error bound / ridge");
+  MDG_CHECK_ARG(ws && ws_bytes >= mdg_vo_compress_ws_bytes(d, n_heads, n_kv, hd), "mdg_vo_spectrum: workspace too small");
+  VoWs w = vo_layout(const_cast<void*>(ws), d, n_heads, n_kv, hd);
+  const int grouped = n_heads != n_kv;
+  // the spectrum the last mdg_vo_compress on this workspace truncated: the Gram matrix's (grouped) / the second SVD's (MHA)
+  const double* lam = grouped ? w.evals : w.evals2;
+  const int vec = w_dtype == MDG_BF16 && (uintptr_t)Wv % 16 == 0 && ld_wv % 8 == 0 && d % 8 == 0;   // eight weights per load
+  if (w_dtype == MDG_BF16)
+    hipLaunchKernelGGL(vo_spectrum_kernel<MDG_BF16>, dim3(n_kv), dim3(256), 0, (hipStream_t)stream, lam, cov_x, d, ldc, Wv, ld_wv, hd,
+                       rank, grouped, eps, vec, out);
+  else
+    hipLaunchKernelGGL(vo_spectrum_kernel<MDG_F64>, dim3(n_kv), dim3(256), 0, (hipStream_t)stream, lam, cov_x, d, ldc, Wv, ld_wv, hd,
+                       rank, grouped, eps, 0, out);
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
 }

@@ -727,9 +727,65 @@ def qk_select(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: int, ri
     return mask, q_rows, k_rows
 
 
+QK_MARGIN_FIELDS = ("s_selected_min", "s_unselected_max", "selected_lower", "unselected_upper", "score_halfwidth", "units_at_risk",
+                    "order_at_risk", "certified")
+
+
+def qk_select_margin(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: int, ridge_q: float, ridge_k: float,
+                     mask: torch.Tensor, eps_rel: float, eps_abs: float) -> torch.Tensor:
+    """The certificate of a qk_select selection (mdg_qk_select_margin): [n_kv, 8] fp64 ON THE DEVICE (QK_MARGIN_FIELDS), enqueued
+    only -- read it when the stream is waited for anyway (decode_qk_margin).  mask: what qk_select returned for these arguments.
+    Every diagonal entry c of a sigma_q / sigma_k head is taken as known to within eps_rel |c| + eps_abs (||C||_inf + ridge)."""
+    _need_gpu(cov_q, cov_k, mask)
+    lib = _lib.load()
+    cq = cov_q.to(torch.float64).contiguous()
+    ck = cov_k.to(torch.float64).contiguous()
+    n_heads, hd, _ = cq.shape
+    n_kv = ck.shape[0]
+    if mask.dtype != torch.int64 or tuple(mask.shape) != (n_kv, rank):
+        raise ValueError(f"qk_select_margin: mask must be int64 [{n_kv}, {rank}], got {mask.dtype} {tuple(mask.shape)}")
+    mask = mask.contiguous()
+    out = torch.empty(n_kv, 8, dtype=torch.float64, device=cq.device)
+    with torch.cuda.device(cq.device):
+        check(lib.mdg_qk_select_margin(cq.data_ptr(), ck.data_ptr(), n_heads, n_kv, hd, float(ridge_q), float(ridge_k), rank, mode,
+                                       mask.data_ptr(), float(eps_rel), float(eps_abs), out.data_ptr(), _stream(cq)),
+              "mdg_qk_select_margin")
+    return out
+
+
+def decode_qk_margin(rows, eps_rel: float, eps_abs: float) -> dict:
+    """Host-side reading of qk_select_margin's [n_kv, 8] numbers (nested list / CPU tensor).  Per kv head: the relative margin
+    between the weakest selected and the strongest unselected unit, the relative half-width a score can move within the error
+    model, how many units sit within reach of the threshold, how many neighbours of the selected order could swap, and whether set
+    and order are certified.  Layer summary: the weakest head (smallest margin among the uncertified heads, else among all), its
+    margin and half-width, and whether every head is certified."""
+    heads = []
+    for row in rows:
+        v = [float(x) for x in row]
+        s_sel, s_unsel = v[0], v[1]
+        separable = s_unsel > float("-inf") and s_sel < float("inf")
+        margin = (s_sel - s_unsel) / s_sel if separable and s_sel > 0 else (float("inf") if not separable else float("-inf"))
+        certified = v[7] == 1.0
+        heads.append({"margin": margin, "score_halfwidth": v[4], "units_at_risk": int(v[5]), "order_at_risk": int(v[6]),
+                      "certified": certified, "order_certified": certified and v[6] == 0.0,
+                      **{k: x for k, x in zip(QK_MARGIN_FIELDS[:4], v[:4])}})
+    weakest = min(range(len(heads)), key=lambda i: (heads[i]["certified"], heads[i]["margin"])) if heads else None
+    return {"heads": heads, "eps_rel": float(eps_rel), "eps_abs": float(eps_abs), "weakest_head": weakest,
+            "margin": heads[weakest]["margin"] if heads else float("inf"),
+            "score_halfwidth": heads[weakest]["score_halfwidth"] if heads else 0.0,
+            "certified": all(h["certified"] for h in heads), "order_certified": all(h["order_certified"] for h in heads)}
+
+
+VO_SPECTRUM_FIELDS = ("lambda_r", "lambda_next", "gap", "energy", "bound", "separated", "lambda_max", "lambda_min")
+
+
 def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
-                ridge: float, want_f64: bool = False):
-    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64])."""
+                ridge: float, want_f64: bool = False, want_spectrum: bool = False, spectrum_eps: Optional[float] = None):
+    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum]).
+    want_spectrum: what the truncation at `rank` did to the spectrum (mdg_vo_spectrum: [n_kv, 8] fp64 ON THE DEVICE,
+    VO_SPECTRUM_FIELDS; decode_vo_spectrum), enqueued behind the factorisation on the same stream while its workspace is alive;
+    spectrum_eps: the entry-wise relative error bound of cov_x its Weyl bound is taken against (None: 0, the gap alone).  The
+    factors are the same bits with or without it."""
     _need_gpu(cov_x, W_v, W_o)
     lib = _lib.load()
     Wv, Wo = _as_weight(W_v), _as_weight(W_o)
@@ -742,6 +798,7 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
     o_out = torch.empty(d, n_heads * rank, dtype=torch.bfloat16, device=dev)
     v64 = torch.empty(n_kv * rank, d, dtype=torch.float64, device=dev) if want_f64 else None
     o64 = torch.empty(d, n_heads * rank, dtype=torch.float64, device=dev) if want_f64 else None
+    spectrum = torch.empty(n_kv, 8, dtype=torch.float64, device=dev) if want_spectrum else None
     nbytes = lib.mdg_vo_compress_ws_bytes(d, n_heads, n_kv, hd)
     ws, wsp = _ws(nbytes, dev)
     with torch.cuda.device(dev):
@@ -749,7 +806,29 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
                                   Wo.stride(0), _DT[Wv.dtype], n_heads, n_kv, hd, rank, float(ridge), v_out.data_ptr(),
                                   v_out.stride(0), o_out.data_ptr(), o_out.stride(0), _p(v64), _p(o64), wsp, nbytes,
                                   _stream(Cx)), "mdg_vo_compress")
-    return (v_out, o_out, v64, o64) if want_f64 else (v_out, o_out)
+        if want_spectrum:
+            check(lib.mdg_vo_spectrum(wsp, nbytes, Cx.data_ptr(), d, Cx.stride(0), Wv.data_ptr(), Wv.stride(0), _DT[Wv.dtype],
+                                      n_heads, n_kv, hd, rank, float(ridge), float(spectrum_eps or 0.0), spectrum.data_ptr(),
+                                      _stream(Cx)), "mdg_vo_spectrum")
+    out = (v_out, o_out, v64, o64) if want_f64 else (v_out, o_out)
+    return out + (spectrum,) if want_spectrum else out
+
+
+def decode_vo_spectrum(rows, eps: float) -> dict:
+    """Host-side reading of vo_compress(want_spectrum=True)'s [n_kv, 8] numbers.  Per kv head VO_SPECTRUM_FIELDS ("separated": True /
+    False for the grouped variant, None for the two-SVD MHA variant, whose second spectrum has no bound here).  Layer summary: the
+    head with the smallest relative gap, that gap, the smallest retained energy, and "separated" (False as soon as one grouped head
+    is not; None for MHA)."""
+    heads = []
+    for row in rows:
+        v = [float(x) for x in row]
+        sep = None if v[5] != v[5] else v[5] == 1.0
+        heads.append({**{k: x for k, x in zip(VO_SPECTRUM_FIELDS, v)}, "bound": None if v[4] != v[4] else v[4], "separated": sep})
+    weakest = min(range(len(heads)), key=lambda i: heads[i]["gap"]) if heads else None
+    seps = [h["separated"] for h in heads]
+    return {"heads": heads, "eps": float(eps), "weakest_head": weakest, "gap": heads[weakest]["gap"] if heads else float("inf"),
+            "energy_min": min((h["energy"] for h in heads), default=1.0),
+            "separated": None if (not seps or any(x is None for x in seps)) else all(seps)}
 
 
 def rope_gather(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor], n_heads: int,
