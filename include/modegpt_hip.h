@@ -107,11 +107,11 @@ typedef struct {
 } mdg_cov_problem;
 size_t mdg_cov_accum_multi_ws_bytes(int n, const mdg_cov_problem* problems, int dtype);
 int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void* ws, size_t ws_bytes, void* stream);
-/* The same accumulation for ONE bf16 matrix through the int8 matrix cores (csrc/cov_i8.hip): an ERROR-FREE SPLIT of every bf16 value
+/* The same accumulation for ONE bf16 matrix through the int8 matrix cores (csrc/cov_i8*.hip; the map of the units is at the head of cov_i8.hip): an ERROR-FREE SPLIT of every bf16 value
  * into six balanced base-256 digits against a per-column power-of-two scale, and a TRUNCATED PRODUCT -- the digit-plane products with
  * s + t < P are formed by v_mfma_i32_32x32x32_i8 with exact int32 accumulation and folded into sigma in fp64 every 65504 tokens (the
  * exact int32 bound); the pairs with s + t >= P are dropped.  What the dropped pairs can amount to is bounded per call from integer
- * plane energies the split pass accumulates (Cauchy-Schwarz over the tokens; derivation in csrc/cov_i8.hip at i8_route_kernel and
+ * plane energies the split pass accumulates (Cauchy-Schwarz over the tokens; derivation in csrc/cov_i8_route.hip at i8_route_kernel and
  * DESIGN.md section 7, host model tests/i8_model.py):
  *     |sigma_ij - exact| <= (SQ_P + X_P) sqrt(sigma_ii sigma_jj)   entry-wise, for any input,
  * and the route is the smallest P in {5, 6} with SQ_P <= 1e-12 (the part of the bound that is attained) and X_P <= 1e-11 (cross
@@ -139,8 +139,9 @@ int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void*
  *   not process state: concurrent callers with different factors do not see each other.  Not in the reference (plain fp64 there).
  * n_feat must be a multiple of 128, n_tokens < 2^28.  ws: mdg_cov_accum_i8_ws_bytes (about 10 bytes per element of x: six digit planes, the
  * exact route's event lists and its bf16 copy of x).
- * ev_start / ev_stop: optional hipEvent_t recorded on `stream` right before / after the two product launches (bench.py times
- * the dominant kernel alone with them); NULL otherwise. */
+ * ev_start / ev_stop: optional hipEvent_t recorded on `stream` right before / after the three int8 product launches and their tail
+ * combines -- the split, the route and the exact route's list building come before ev_start, the remainder, column and fallback
+ * kernels after ev_stop (bench.py times the dominant kernels alone with them); NULL otherwise. */
 /* THE EXACT ROUTE (since ABI 9.  flags = 0: taken where it is the faster product -- launches the route kernel classes as six planes,
  * i.e. SiLU- / GELU-gated MLP activations, and five-plane launches whose first statistic has >= 4096 features; MDG_I8_EXACT_ALWAYS:
  * wherever the remainder lists fit; MDG_I8_NO_EXACT: never).  Planes 3 .. 5 are reached only by elements 17

@@ -11,7 +11,7 @@ TYPICAL -- an EMPIRICAL figure: <= 1e-12 (times the factor) on the distribution 
     tests/test_gpu_i8_fullwidth.py).  It is a property of those data, not of the method: columns whose digit sequences are
     proportional over the tokens reach the guaranteed bound (tests/test_i8_bound.py builds one).  It was also TUNED: the first
     bound-derived route measured 1.46e-12 ... 3.1e-12 on 33- and 142-token calls, and the tau_x(T_eff) schedule of
-    csrc/cov_i8.hip is what brought those under 1e-12.  A test therefore asserts it only where it names one of the measured
+    csrc/cov_i8_route.hip is what brought those under 1e-12.  A test therefore asserts it only where it names one of the measured
     families, and a failure of that part on new data is a finding about the data, not a defect of the kernel.
 """
 GUARANTEED = 1.1e-11

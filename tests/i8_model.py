@@ -1,4 +1,4 @@
-"""Host model of the int8 digit-plane covariance route (modegpt_amd/csrc/cov_i8.hip): the split pass's per-column integer
+"""Host model of the int8 digit-plane covariance route (modegpt_amd/csrc/cov_i8_split.hip, cov_i8_route.hip, cov_i8_exact.hip): the split pass's per-column integer
 statistics, the Cauchy-Schwarz error bound built from them, and the greedy choice of (planes, columns sent to the fp64 column
 kernel).  Test infrastructure: the CPU tests check the bound against the exact truncation error of the modelled product, the
 GPU tests check the device's decisions against this model on the same inputs.
@@ -32,7 +32,7 @@ TAU_SQ, TAU_X, JMAX = 1e-12, 1e-11, 32            # TAU_X: the cross-term thresh
 
 def tau_x_of(tokens):
     """The threshold on X_P grows with the EFFECTIVE token count -- the fewest nonzero elements any column has, at most the tokens
-    of the call (cov_i8.hip tau_x_of): for uncorrelated columns the measured error sits ~4.5 / sqrt(tokens) below X_P, an
+    of the call (cov_i8_route.hip tau_x_of): for uncorrelated columns the measured error sits ~4.5 / sqrt(tokens) below X_P, an
     averaging a short call or a sparse column does not have.  1e-12 up to 1024 tokens, 1e-11 from 10240."""
     return min(TAU_X, max(1e-12, 1e-12 * tokens / 1024.0))
 
@@ -158,7 +158,7 @@ def product(d, E, P):
     return acc * sc[:, None] * sc[None, :]
 
 
-LO_CHUNK_TOKENS, LO_CAP, EXACT_ROUNDING = 64 * 32, 128, 5e-15      # cov_i8.hip: LO_CHUNK_STEPS x KS, LO_CAP; modegpt_hip.h: MDG_I8_EXACT_ROUNDING
+LO_CHUNK_TOKENS, LO_CAP, EXACT_ROUNDING = 64 * 32, 128, 5e-15      # cov_i8_exact.hip: LO_CHUNK_STEPS x KS, LO_CAP; modegpt_hip.h: MDG_I8_EXACT_ROUNDING
 
 
 def list_counts(lo):
@@ -180,7 +180,7 @@ def route_of(X, chunk=1024, tolerance=1.0, offer_exact=True):
     """Route of a whole bf16 activation matrix (torch CPU tensor [T, n]): the statistics are taken in column chunks (int64
     temporaries of a 32768 x 14336 batch would not fit), the decision over all columns.  -> dict like ops.cov_accum_i8's
     route_info: planes, columns (in the order the greedy took them), sq, x, bound, exact.  exact (the exact route: nine plane
-    pairs + the fp64 remainder products, cov_i8.hip "the exact route"): the route kernel's decision stands, and when no event list
+    pairs + the fp64 remainder products, cov_i8_exact.hip "the exact route"): the route kernel's decision stands, and when no event list
     of the columns that stayed overflows its segment the truncated product is replaced -- the bound is then the rounded-element
     term 2 R + R^2 plus fp64 rounding.  offer_exact: True (MDG_I8_EXACT_ALWAYS), False (MDG_I8_NO_EXACT) or "auto" (flags 0: only
     for the six-plane class)."""
@@ -195,7 +195,7 @@ def route_of(X, chunk=1024, tolerance=1.0, offer_exact=True):
     planes, cols, (sq, x) = route(st, sort=False, tokens=min(X.shape[0], int(nz.min()) if nz.size else X.shape[0]), tolerance=tolerance)
     exact = False
     if offer_exact == "auto":          # the library's default: the exact route where it is the faster product -- the six-plane class,
-        offer_exact = planes == 6 or X.shape[1] >= 4096     # and large five-plane statistics (cov_i8.hip lo_offered)
+        offer_exact = planes == 6 or X.shape[1] >= 4096     # and large five-plane statistics (cov_i8_exact.hip lo_offered)
     if planes and offer_exact and X.shape[1] % 32 == 0:
         lo = np.concatenate(lo, axis=1)
         lo[:, cols] = False                            # the digits of the columns that left are cleared before the lists are made

@@ -999,7 +999,7 @@ def _exact_sigma(X):
 
 
 def test_exact_route_against_exact_integer_arithmetic(ops, dev, monkeypatch):
-    """The default product of the int8 covariance drops no plane pair (cov_i8.hip, "the exact route"): X^T X = X_d^T X_d (nine plane
+    """The default product of the int8 covariance drops no plane pair (cov_i8_exact.hip, "the exact route"): X^T X = X_d^T X_d (nine plane
     pairs on the matrix cores) + X_lo^T X + X_d^T X_lo (fp64 sums over the listed remainder elements).  Checked against the EXACT
     sum in integer arithmetic -- not against an fp64 reference, which is less accurate than the thing under test: SiLU-gated columns
     with deep elements of both signs, elements whose low 24 bits are exactly the rounding tie of the balanced digits (and the value

@@ -1,4 +1,4 @@
-"""CPU: the error bound behind the int8 covariance route (cov_i8.hip's i8_route_kernel, modelled by tests/i8_model.py).
+"""CPU: the error bound behind the int8 covariance route (cov_i8_route.hip's i8_route_kernel, modelled by tests/i8_model.py).
 
 For every distribution family of scripts/probes/i8_fuzz.py the modelled P-plane product is formed exactly (integer class sums)
 and compared with the fp64 product:  measured entry-wise error <= the Cauchy-Schwarz bound computed from the per-column plane
@@ -123,7 +123,7 @@ def test_tolerance_factor_trades_planes_for_a_looser_but_still_kept_bound():
 
 
 def test_exact_route_decomposition_is_an_identity_in_integer_arithmetic():
-    """cov_i8.hip, "the exact route": N = N_d + L with N_d the top three balanced digits and L = d_3 2^16 + d_4 2^8 + d_5, and
+    """cov_i8_exact.hip, "the exact route": N = N_d + L with N_d the top three balanced digits and L = d_3 2^16 + d_4 2^8 + d_5, and
         sum_t N_ti N_tj  =  sum_t N_d,ti N_d,tj  +  sum_t L_ti N_tj  +  sum_t N_d,ti L_tj        (nothing dropped)
     in exact integer arithmetic, for data with deep elements of both signs; the remainder kernel's partner value x_d, recomputed from
     the bf16 value as 2^24 q floor(x / (2^24 q) + 8421504 / 2^24), IS N_d (the balanced digits' rounding, ties included); L lies in

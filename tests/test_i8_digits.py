@@ -1,4 +1,4 @@
-"""Host-side facts the int8 digit-plane covariance kernel (modegpt_amd/csrc/cov_i8.hip) relies on, checked by enumeration over
+"""Host-side facts the int8 digit-plane covariance kernel (modegpt_amd/csrc/cov_i8*.hip, constants in cov_i8.hpp) relies on, checked by enumeration over
 EVERY digit vector its split pass can emit (the arithmetic below restates i8_split_kernel's: a signed 8-bit significand
 shifted to 48 bits, six balanced base-256 digits taken from the low end).  No GPU needed."""
 import numpy as np
@@ -57,6 +57,6 @@ def test_int32_classes_cannot_overflow_within_the_fold_interval():
 def test_fold_interval_in_the_kernel_source_matches():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(__file__), "..", "modegpt_amd", "csrc", "cov_i8.hip")).read()
+    src = open(os.path.join(os.path.dirname(__file__), "..", "modegpt_amd", "csrc", "cov_i8.hpp")).read()
     assert int(re.search(r"constexpr int FLUSH_STEPS = (\d+);", src).group(1)) == FLUSH_STEPS
     assert int(re.search(r"constexpr int TOP_SHIFT = 8 \* NP - (\d+)", src).group(1)) == 8 * NP_ - TOP_SHIFT
