@@ -107,10 +107,11 @@ typedef struct {
 } mdg_cov_problem;
 size_t mdg_cov_accum_multi_ws_bytes(int n, const mdg_cov_problem* problems, int dtype);
 int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void* ws, size_t ws_bytes, void* stream);
-/* The same accumulation for ONE bf16 matrix through the int8 matrix cores (csrc/cov_i8*.hip; the map of the units is at the head of cov_i8.hip): an ERROR-FREE SPLIT of every bf16 value
+/* The same accumulation for ONE bf16 (or, with MDG_I8_F16, fp16) matrix through the int8 matrix cores (csrc/cov_i8*.hip; the map of the units is at the head of cov_i8.hip): an ERROR-FREE SPLIT of every bf16 value
  * into six balanced base-256 digits against a per-column power-of-two scale, and a TRUNCATED PRODUCT -- the digit-plane products with
- * s + t < P are formed by v_mfma_i32_32x32x32_i8 with exact int32 accumulation and folded into sigma in fp64 every 65504 tokens (the
- * exact int32 bound); the pairs with s + t >= P are dropped.  What the dropped pairs can amount to is bounded per call from integer
+ * s + t < P are formed by v_mfma_i32_32x32x32_i8 with exact int32 accumulation and folded into sigma in fp64 every 65504 tokens (2047 k-steps of 32: the
+ * exact int32 bound -- a class sum grows by at most 32768 per token for bf16 AND for fp16 elements, enumerated in
+ * scripts/probes/i8_int32_bound.py and i8_int32_bound_f16.py); the pairs with s + t >= P are dropped.  What the dropped pairs can amount to is bounded per call from integer
  * plane energies the split pass accumulates (Cauchy-Schwarz over the tokens; derivation in csrc/cov_i8_route.hip at i8_route_kernel and
  * DESIGN.md section 7, host model tests/i8_model.py):
  *     |sigma_ij - exact| <= (SQ_P + X_P) sqrt(sigma_ii sigma_jj)   entry-wise, for any input,
@@ -138,7 +139,7 @@ int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void*
  *   reports its own bound (mdg_cov_accum_i8_route), so what was guaranteed for a given input is known, whatever f.  An argument,
  *   not process state: concurrent callers with different factors do not see each other.  Not in the reference (plain fp64 there).
  * n_feat must be a multiple of 128, n_tokens < 2^28.  ws: mdg_cov_accum_i8_ws_bytes (about 10 bytes per element of x: six digit planes, the
- * exact route's event lists and its bf16 copy of x).
+ * exact route's event lists and its copy of x in x's own element type).
  * ev_start / ev_stop: optional hipEvent_t recorded on `stream` right before / after the three int8 product launches and their tail
  * combines -- the split, the route and the exact route's list building come before ev_start, the remainder, column and fallback
  * kernels after ev_stop (bench.py times the dominant kernels alone with them); NULL otherwise. */
@@ -160,6 +161,21 @@ int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void*
 #define MDG_I8_MAX_COLUMNS 32
 #define MDG_I8_NO_EXACT 1             /* flags: never the exact route (the truncated five- / six-plane product with its bound) */
 #define MDG_I8_EXACT_ALWAYS 2         /* flags: the exact route wherever the remainder lists fit, also for launches of the five-plane class */
+/* ELEMENT TYPE AND ReLU (flag bits of the same `flags` argument; each works alone, both together, and beside either bit above):
+ * MDG_I8_F16: x holds IEEE fp16 instead of bf16, for EVERY statistic of the call.  An fp16 value is a signed 11-bit significand
+ *   with an effective exponent in 1 .. 30; with the column maximum's significand below bit 46 every finite element of the column
+ *   is an exact 48-bit integer, subnormals included -- nothing is rounded, the rho term is identically 0, and a call on the exact
+ *   route reports exactly MDG_I8_EXACT_ROUNDING.  Elements reach below the top three planes from 12 binades under their column
+ *   maximum (bf16: 15), so the exact route's lists are longer than for bf16 data of the same distribution; the device's choice
+ *   between the exact route and the truncated product is the same code.  Exponent field 31 (Inf / NaN) sends the column to the
+ *   fp64 column kernel as bf16's 255 does.  Workspace sizes are unchanged (2-byte elements; the x_d copy is an fp16 copy).
+ * MDG_I8_RELU: max(x, 0) is applied wherever x is read, as `relu != 0` of mdg_cov_accum (OPT's fc1 statistic): anything with the
+ *   sign bit set counts as +0, -0 and -Inf included; a NaN stays a NaN whatever its sign bit (its column leaves for the fp64
+ *   column kernel and poisons its row and column of sigma as in torch.relu(x) followed by the fp64 product).  ONE
+ *   DIFFERENCE: a statistic the bound cannot certify goes through mdg_cov_accum as a whole, whose ReLU (v > 0 ? v : 0) turns a NaN
+ *   into 0 -- on that fallback route, and there only, a NaN column contributes zeros instead of NaNs. */
+#define MDG_I8_F16 4                  /* flags: x is fp16 */
+#define MDG_I8_RELU 8                 /* flags: max(x, 0) on load */
 #define MDG_I8_EXACT_ROUNDING 5e-15   /* what mdg_cov_accum_i8_route reports beside the rho term for a call on the exact route */
 size_t mdg_cov_accum_i8_ws_bytes(int64_t n_tokens, int64_t n_feat);
 int mdg_cov_accum_i8(const void* x, int64_t n_tokens, int64_t n_feat, int64_t ld, double* sigma, int64_t ld_sigma, void* ws,
@@ -184,7 +200,7 @@ int mdg_cov_accum_i8_route(int count, const mdg_cov_problem* problems, int stat,
  * one's last round leaves idle instead of ending launches of their own, and one route -- the deepest any statistic on the int8 path
  * asks for (more planes never loosen a bound); every statistic has its own bound, its own columns for the fp64 column kernel, and
  * leaves the launch alone for mdg_cov_accum when its bound cannot be met (its tiles are skipped on the device).  `problems` is a HOST
- * array, largest statistic first, all with the same n_tokens, bf16.  batch == 1: sigma [n_feat][ld_sigma], n_feat a multiple of 128.
+ * array, largest statistic first, all with the same n_tokens, all bf16 (or all fp16 with MDG_I8_F16).  batch == 1: sigma [n_feat][ld_sigma], n_feat a multiple of 128.
  * batch > 1: per-head Grams of an activation [n_tokens][batch * 128] -- n_feat must be 128, sigma contiguous
  * [batch][128][128] (ld_sigma 128, sigma_batch_stride 16384); only the diagonal tiles are computed.  Several statistics need a
  * 256-CU device (the schedule is cut for 8 XCDs x 32 CUs); otherwise call mdg_cov_accum_i8 per statistic.

@@ -371,10 +371,12 @@ class ModelAdapter(ABC):
     # ---- statistic hooks shared by adapters (model_adapter.py:546-567) ----
     @staticmethod
     def _make_fc_hook(layer_idx, cov_mlp_list):
-        """sigma_mlp += ReLU(fc1 out)^T ReLU(fc1 out) -- ReLU fused into the kernel's load."""
+        """sigma_mlp += ReLU(fc1 out)^T ReLU(fc1 out) -- ReLU fused into the kernel's load.  bf16 / fp16 activations of at least
+        ops.FC_I8_MIN_FEATURES features (a multiple of 128) take the int8 digit planes with ReLU on load; everything else the fp64
+        kernel, as before (ops.cov_accum_fc_relu)."""
         @torch.no_grad()
         def hook(module, inp, out):
-            ops.cov_accum(cov_mlp_list[layer_idx], out, relu=True)
+            ops.cov_accum_fc_relu(cov_mlp_list[layer_idx], out)
         return hook
 
     @staticmethod

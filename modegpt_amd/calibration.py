@@ -141,6 +141,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.bi_scores = bi_scores
     adapter.calib_tokens = n_tokens       # (how many tokens each statistic summed over: the fp64 route's rounding bound scales with it)
     sig.finalize(n_texts)
+    adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         adapter.cov_routes = ops.i8_route_counts(reset=True)
         logger.info(f"covariance routes (int8 five planes / six planes / fp64 fallback): {adapter.cov_routes}")

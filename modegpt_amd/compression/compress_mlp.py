@@ -33,21 +33,30 @@ I8_GUARANTEED_EPS = 1.1e-11      # mdg_cov_accum_i8: entry-wise over sqrt(sigma_
 
 def covariance_error_eps(adapter, n_features: int) -> float:
     """The entry-wise relative error bound eps of the sigma_mlp this run accumulated, |sigma_ij - exact| <= eps sqrt(sigma_ii sigma_jj)
-    -- what the selection certificate is taken against.  `adapter.cov_error_eps` when the caller states it; else from the route:
-    int8 digit planes -> the route's guarantee 1.1e-11 x the tolerance factor (+ one fp64 rounding per fold); fp64 matrix cores ->
-    the worst case of an fp64 sum of exact products over the calibration tokens, (tokens / 4 + 4) 2^-53 (v_mfma_f64_16x16x4 adds four
-    products per step; typical errors are ~sqrt of that count: 6e-14 at 10^6 tokens).  A run whose statistics took both routes
-    (a fallback) gets the larger."""
+    -- what the selection certificate is taken against.  `adapter.cov_error_eps` when the caller states it; else from the route
+    the statistics TOOK -- `adapter.cov_routes`, the device's own counts (ops.i8_route_counts) that calibration leaves there:
+    no statistic on the int8 digit planes (an fp32 model, a narrow one, OPT's fc1 statistic below 4096 features, MODEGPT_COV_MODE=f64)
+    -> the worst case of an fp64 sum of exact products over the calibration tokens, (tokens / 4 + 4) 2^-53 (v_mfma_f64_16x16x4 adds
+    four products per step; typical errors are ~sqrt of that count: 6e-14 at 10^6 tokens); some on them -> the route's guarantee
+    1.1e-11 x the tolerance factor (+ one fp64 rounding per fold); a mix -- a statistic or single columns fell back to fp64 -- the
+    larger of the two.  A statistic of a width the int8 route never takes is on fp64 whatever the counts say.  Without counts (no
+    calibration ran on this adapter) the route is predicted from the mode, the width and the hook the architecture uses."""
     stated = getattr(adapter, "cov_error_eps", None)
     if stated is not None:
         return float(stated)
     tokens = int(getattr(adapter, "calib_tokens", 0) or getattr(adapter.config, "calib_size", 32) * 2048)
     eps_f64 = (tokens / 4 + 4) * 2.0 ** -53
-    routes = getattr(adapter, "cov_routes", None) or {}
-    int8 = ops.COV_MODE == "i8" and n_features % 128 == 0 and n_features >= ops.I8_MIN_FEATURES and adapter.arch != "opt"
-    if not int8:
-        return eps_f64
     eps_i8 = I8_GUARANTEED_EPS * ops.i8_tolerance() + 64 * 2.0 ** -53
+    if n_features % 128 != 0 or n_features < ops.I8_MIN_FEATURES:
+        return eps_f64
+    routes = getattr(adapter, "cov_routes", None)
+    if routes is None:       # (OPT's fc1 statistic takes the int8 route from ops.FC_I8_MIN_FEATURES features only: ops.cov_accum_fc_relu)
+        wide_enough = n_features >= ops.FC_I8_MIN_FEATURES or getattr(adapter, "arch", None) != "opt"
+        return eps_i8 if ops.COV_MODE == "i8" and wide_enough else eps_f64
+    if routes.get("i8_5", 0) + routes.get("i8_6", 0) == 0:
+        return eps_f64
+    if getattr(adapter, "arch", None) == "opt" and n_features < ops.FC_I8_MIN_FEATURES:
+        return max(eps_i8, eps_f64)      # (the counts are another statistic's, sigma_x's: OPT's fc1 statistic of this width ran on fp64)
     return max(eps_i8, eps_f64) if routes.get("fallback_f64", 0) or routes.get("fp64_columns", 0) else eps_i8
 
 

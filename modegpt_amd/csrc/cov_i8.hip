@@ -1,5 +1,8 @@
-// sigma += X^T X through the int8 matrix cores: an ERROR-FREE SPLIT of the bf16 activations into digit planes and a TRUNCATED
-// plane-pair product whose error is bounded per call.
+// sigma += X^T X through the int8 matrix cores: an ERROR-FREE SPLIT of the bf16 (or fp16: flag MDG_I8_F16) activations into digit
+// planes and a TRUNCATED plane-pair product whose error is bounded per call.  What follows is written for bf16; an fp16 value is a
+// signed 11-bit significand, placed 35 instead of 38 bits up so that the column's unit is 2^(E_j - 172) for both (E_j on the fp32
+// exponent scale: the element traits in cov_i8.hpp) -- every finite fp16 element is then an exact integer, and only the kernels
+// that read x itself differ.  MDG_I8_RELU applies max(x, 0) wherever x is read.
 //
 // A bf16 value is a signed 8-bit significand times a power of two.  Against a per-column scale 2^(E_j - 172), E_j the largest
 // exponent in column j of this call, it is a 48-bit fixed-point integer N = sig << (38 - (E_j - e)): six balanced base-256
@@ -138,7 +141,8 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   if (used_i8) *used_i8 = 0;
   MDG_CHECK_ARG(tolerance >= 1.0 && tolerance <= 1e6, "mdg_cov_accum_i8_multi: tolerance factor %g outside [1, 1e6] (1 = guaranteed <= 1.1e-11)",
                 tolerance);
-  MDG_CHECK_ARG((flags & ~(MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS)) == 0 && flags != (MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS),
+  MDG_CHECK_ARG((flags & ~(MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS | MDG_I8_F16 | MDG_I8_RELU)) == 0 &&
+                    (flags & (MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS)) != (MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS),
                 "mdg_cov_accum_i8_multi: bad flags 0x%x", flags);
   bool offer_exact = !(flags & MDG_I8_NO_EXACT);
   const bool exact_always = (flags & MDG_I8_EXACT_ALWAYS) != 0;
@@ -156,6 +160,8 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   MDG_CHECK_ARG(ws && ws_bytes >= need, "mdg_cov_accum_i8_multi: workspace %zu < required %zu", ws_bytes, need);
   c.route_counts = route_counts;
   c.st = (hipStream_t)stream;
+  c.f16 = (flags & MDG_I8_F16) != 0;
+  c.relu = (flags & MDG_I8_RELU) != 0;
   MDG_HIP(hipMemsetAsync(c.shared, 0, SHARED_BYTES, c.st));
   for (int i = 0; i < count; i++) {
     MDG_TRY(enqueue_split(c, i));
@@ -169,7 +175,7 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   // statistic, and only that one -- goes through the fp64 kernel
   for (int i = 0; i < count; i++) {
     const mdg_cov_problem& q = problems[i];
-    MDG_TRY(cov_accum_gated(q.x, MDG_BF16, c.n_tokens, q.n_feat, q.batch, q.ld, 0, q.sigma, q.ld_sigma, q.sigma_batch_stride, (char*)ws + fb_off,
+    MDG_TRY(cov_accum_gated(q.x, c.f16 ? MDG_F16 : MDG_BF16, c.n_tokens, q.n_feat, q.batch, q.ld, c.relu ? 1 : 0, q.sigma, q.ld_sigma, q.sigma_batch_stride, (char*)ws + fb_off,
                             ws_bytes - fb_off, c.stat[i].route_flag, 2, 2, stream));
   }
   MDG_TRY(report_product_diagnostics(c));

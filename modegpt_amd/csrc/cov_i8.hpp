@@ -13,19 +13,98 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int NP = 6;            // digit planes written by the split pass; the product kernel uses the top 3, the top 5 or all 6
 constexpr int TI = 128;          // output tile rows (rows of the I operand); its width TJ is 64 or 128, see TileShape
 constexpr int KS = 32;           // tokens per k-step (one v_mfma_i32_32x32x32_i8)
-// k-steps between folds of the int32 classes into sigma.  An element is an 8-bit significand at some shift, so its balanced
+// k-steps between folds of the int32 classes into sigma.  A bf16 element is an 8-bit significand at some shift, so its balanced
 // digits are two full digits and a carry digit at most, and a class sum grows by at most 32768 per token (enumerated over
 // every digit vector the split pass can produce: scripts/probes/i8_int32_bound.py) -- 65535 tokens = 2047 k-steps stay below
 // 2^31.  (First versions: 512, from the cruder bound 6 pairs x 128 x 128 per token; one fold per launch costs 0.65 ms at the
 // sigma_mlp shape.)
 constexpr int FLUSH_STEPS = 2047;
-constexpr int TOP_SHIFT = 8 * NP - 10;  // 38: the column maximum's significand sits below bit 46 of the 48-bit integer
+// The same enumeration for fp16 (scripts/probes/i8_int32_bound_f16.py): an 11-bit significand spreads over three digits, but where
+// two of them are full the third holds at most 3 bits and a carry -- the worst pair is still (c, -128, -128) against itself,
+// 2 x 128 x 128 = 32768 per token, so fp16 allows the same 2047 k-steps.  The product kernels read planes only and fold every
+// FLUSH_STEPS k-steps whatever the element type: that interval must not exceed what either type allows.
+constexpr int FLUSH_STEPS_F16 = 2047;
+static_assert(FLUSH_STEPS <= FLUSH_STEPS_F16, "the product kernels' fold interval must hold for fp16 elements too");
+constexpr int TOP_SHIFT = 8 * NP - 10;  // 38: the column maximum's significand sits below bit 46 of the 48-bit integer (bf16: 8 bits)
+constexpr int TOP_SHIFT_F16 = 8 * NP - 13;  // 35: the same place for fp16's 11 bits
+
+// ---- element traits of the kernels that interpret the bits of x (split, lists, remainder products, column kernel).  Both types
+// are decoded to (signed significand, effective exponent ee) ON ONE EXPONENT SCALE -- the fp32 exponent field of the value's
+// binade, 255 for Inf / NaN -- such that with the type's top shift the column's unit is 2^(E_j - 172) for both: everything behind
+// the split (planes, emax, the route, the product kernels' fold, the lists' scale) is the same code for either type.
+//   bf16: value = sig 2^(ee - 134), |sig| < 2^8;   N = sig << (38 - (E - ee))
+//   fp16: value = sig 2^(ee - 137), |sig| < 2^11;  N = sig << (35 - (E - ee)),  ee = exponent field + 112 in 113 .. 142 (subnormals: 113)
+// A finite fp16 column spans at most 29 binades (<= 35): every element is an exact integer, subnormals included; nothing is
+// ever rounded and the bound's rho term is identically 0.
+struct Bf16Elem {
+  static constexpr int TOP = TOP_SHIFT, SIG_BITS = 8;
+  static __device__ __forceinline__ void parts(unsigned b, int& sig, int& ee) {
+    const int e = (b >> 7) & 0xFF, m = b & 0x7F;
+    sig = e ? (128 | m) : m;
+    ee = e ? e : 1;
+    if (b & 0x8000) sig = -sig;
+  }
+  static __device__ __forceinline__ int ee_if_nonzero(unsigned b) {  // effective exponent of a nonzero value, 0 for +-0
+    const int e = (b >> 7) & 0xFF;
+    return (b & 0x7FFF) ? (e ? e : 1) : 0;
+  }
+  static __device__ __forceinline__ bool is_nan(unsigned b) { return (b & 0x7FFFu) > 0x7F80u; }
+  static __device__ __forceinline__ double to_f64(unsigned b) { return (double)__uint_as_float(b << 16); }
+  // the two elements of a dword, exactly
+  static __device__ __forceinline__ double lo_f64(unsigned w) { return (double)__uint_as_float(w << 16); }
+  static __device__ __forceinline__ double hi_f64(unsigned w) { return (double)__uint_as_float(w & 0xFFFF0000u); }
+  static __device__ __forceinline__ unsigned from_f64(double v) { return __float_as_uint((float)v) >> 16; }   // v representable: exact
+  // an element has a digit below plane 2 iff it lies more than 38 - 24 binades under E (and is not zero): 0 < |bits| < deep_limit(E)
+  static __device__ __forceinline__ unsigned deep_limit(int E) { return (unsigned)max(E - 14, 1) << 7; }
+};
+struct F16Elem {
+  static constexpr int TOP = TOP_SHIFT_F16, SIG_BITS = 11;
+  static __device__ __forceinline__ void parts(unsigned b, int& sig, int& ee) {
+    const int e = (b >> 10) & 0x1F, m = b & 0x3FF;
+    sig = e ? (1024 | m) : m;
+    ee = e == 31 ? 255 : (e ? e : 1) + 112;     // Inf / NaN: the exponent the route kernel takes a column out for
+    if (b & 0x8000) sig = -sig;
+  }
+  static __device__ __forceinline__ int ee_if_nonzero(unsigned b) {
+    const int e = (b >> 10) & 0x1F;
+    return (b & 0x7FFF) ? (e == 31 ? 255 : (e ? e : 1) + 112) : 0;
+  }
+  static __device__ __forceinline__ bool is_nan(unsigned b) { return (b & 0x7FFFu) > 0x7C00u; }
+  static __device__ __forceinline__ double to_f64(unsigned b) { return f16_to_f64((f16_t)b); }
+  static __device__ __forceinline__ double lo_f64(unsigned w) { return f16_to_f64((f16_t)(w & 0xFFFFu)); }
+  static __device__ __forceinline__ double hi_f64(unsigned w) { return f16_to_f64((f16_t)(w >> 16)); }
+  static __device__ __forceinline__ unsigned from_f64(double v) { return __half_as_ushort(__float2half((float)v)); }   // v representable: exact
+  // ... more than 35 - 24 = 11 binades under E: exponent field below (E - 112) - 11
+  static __device__ __forceinline__ unsigned deep_limit(int E) { return (unsigned)max(E - 123, 1) << 10; }
+};
+// max(x, 0) on the bits of one element / of the two elements of a dword (MDG_I8_RELU): anything with the sign bit set becomes +0
+// -- -0 and -Inf included -- except a NaN, which stays the NaN it is.
+template <class EL, bool RELU>
+__device__ __forceinline__ unsigned relu_bits(unsigned b) {
+  return (RELU && (b & 0x8000u) && !EL::is_nan(b)) ? 0u : b;
+}
+template <class EL, bool RELU>
+__device__ __forceinline__ unsigned relu_pair(unsigned w) {
+  if (!RELU) return w;
+  return relu_bits<EL, true>(w & 0xFFFFu) | (relu_bits<EL, true>(w >> 16) << 16);
+}
+// Host side: one launch statement for the four (element type, ReLU) instantiations of a kernel template.
+#define MDG_I8_DISPATCH(c, KERNEL, ...)                                                   \
+  do {                                                                                    \
+    if ((c).f16) {                                                                        \
+      if ((c).relu) hipLaunchKernelGGL((KERNEL<F16Elem, true>), __VA_ARGS__);             \
+      else hipLaunchKernelGGL((KERNEL<F16Elem, false>), __VA_ARGS__);                     \
+    } else {                                                                              \
+      if ((c).relu) hipLaunchKernelGGL((KERNEL<Bf16Elem, true>), __VA_ARGS__);            \
+      else hipLaunchKernelGGL((KERNEL<Bf16Elem, false>), __VA_ARGS__);                    \
+    }                                                                                     \
+  } while (0)
 
 // Per-column integers the split pass accumulates for the route (i8_route_kernel; host model: tests/i8_model.py), as [NSTAT][n]
 // unsigned long long: q_s = sum over tokens of d_s^2 for the six planes, the signed sum of d_0 d_1 (so that the energy of the top
 // two digits together, hence a lower bound on the column's norm, is an integer too), and two counters packed into one word.
 constexpr int NSTAT = 8;
-constexpr int STAT_D0D1 = 6, STAT_COUNTS = 7;     // [7]: (elements rounded to an integer: more than 38 binades down) << 32 | nonzero elements
+constexpr int STAT_D0D1 = 6, STAT_COUNTS = 7;     // [7]: (elements rounded to an integer: more than 38 binades down; fp16: never) << 32 | nonzero elements
 constexpr int EMAX_COLUMN_OUT = 0x100;            // bit set in emax[j] by the route kernel: column j is computed by the fp64 column kernel
 
 // Planes the product kernels may read even where the piece mask says "all zero": both load every plane below their MIN_DEPTH
@@ -84,7 +163,7 @@ struct I8Stat {
   double* colpart;               // chunk partials of the fp64 column kernel
   LoEntry *lo_entries, *lo_rentries;   // the exact route: event lists per column; sparse mode: merged (group, residue) lists
   int *lo_counts, *lo_rtotals;         // ... and their lengths
-  bf16_t* lo_xd;                 // the x_d copy of the exact route: [tokens][n] bf16
+  bf16_t* lo_xd;                 // the x_d copy of the exact route: [tokens][n] of x's element type
   bool vec() const { return (uintptr_t)x % 16 == 0 && ld % 8 == 0; }   // rows are 16-byte addressable
   unsigned long long* stats() const { return (unsigned long long*)(emax + (n + 1) / 2 * 2); }
 };
@@ -92,6 +171,7 @@ struct I8Call {
   int count, nk;                 // statistics; k-steps of KS tokens
   int64_t n_tokens;
   I8Stat stat[MAX_PROBLEMS];
+  bool f16, relu;                // MDG_I8_F16: x holds fp16 (else bf16); MDG_I8_RELU: max(x, 0) on load -- every statistic of the call
   SharedBlock* shared;
   double* partial;               // PARTIAL_BYTES behind the shared block
   int* route_counts;             // optional device counters [five planes, six planes, fp64 fallback, columns out, exact route]

@@ -107,6 +107,8 @@ __device__ __forceinline__ bool lo_offered(const LoArgs& a) {
 // One wave per (32-column group, segment of LO_CHUNK_STEPS k-steps): reads the pieces of planes 3 .. 5 the piece masks say are
 // there -- as the product kernel would -- and appends every element with L != 0 to ITS COLUMN's segment, in token order (lane r
 // holds tokens 0 .. 15 of a k-step of column r, lane 32 + r tokens 16 .. 31: the second appends behind the first).
+// (Reads planes and emax only -- the unit 2^(E - 172) is the same for bf16 and fp16, see the element traits -- so it is one kernel
+// for both element types.)
 __global__ __launch_bounds__(64) void i8_extract_lo_kernel(LoArgs a) {
   const LoProblem& pr = a.prob[blockIdx.z];
   const int64_t groups = pr.n / 32;
@@ -240,8 +242,14 @@ __global__ __launch_bounds__(64) void i8_residue_lo_kernel(LoArgs a) {
 }
 
 // DENSE: x_d starts as a copy of x (16 bytes per thread and step; n is a multiple of 128), then every listed element is replaced by
-// x_d = x - x_lo -- exactly (both are multiples of the column's unit, below 2^48 of them), and a bf16 again (a rounding of 8
-// significant bits to a coarser grid).  One wave per column for the second step.
+// x_d = x - x_lo -- exactly (both are multiples of the column's unit, below 2^48 of them), and a value of x's type again: a
+// rounding of x's significand to a coarser grid.  bf16: 8 significant bits at most, exponent range of the column.  fp16: a listed
+// element lies k = sh - 11 >= 1 bits under the grid 2^24 units = 2^(E - 148), so x_d = M 2^(E - 148) with |M| = round(|sig| / 2^k) <=
+// 2^(11 - k): at most 11 significant bits, no larger than the column maximum, and the grid is no finer than fp16's own 2^-24 -- in a
+// column with E < 124 every element is a multiple of 2^24 units and nothing is listed.  (Checked over every bit pattern and shift:
+// tests/test_i8_f16_host.py.)  ReLU is applied by the copy; a listed element is nonzero after it, hence positive and unchanged.
+// One wave per column for the second step.
+template <class EL, bool RELU>
 __global__ __launch_bounds__(256) void i8_copy_xd_kernel(LoArgs a) {
   if (a.state[EXACT_MODE] != 2) return;
   const LoProblem& pr = a.prob[blockIdx.y];
@@ -251,9 +259,10 @@ __global__ __launch_bounds__(256) void i8_copy_xd_kernel(LoArgs a) {
     const int64_t t = i / per_row, c = (i - t * per_row) * 8;
     typedef unsigned u32x4u __attribute__((ext_vector_type(4), aligned(2)));
     const u32x4u v = *(const u32x4u*)(pr.x + t * pr.ld + c);
-    *(u32x4*)(pr.xd + t * pr.n + c) = (u32x4){v[0], v[1], v[2], v[3]};
+    *(u32x4*)(pr.xd + t * pr.n + c) = (u32x4){relu_pair<EL, RELU>(v[0]), relu_pair<EL, RELU>(v[1]), relu_pair<EL, RELU>(v[2]), relu_pair<EL, RELU>(v[3])};
   }
 }
+template <class EL, bool RELU>
 __global__ __launch_bounds__(64) void i8_patch_xd_kernel(LoArgs a) {
   if (a.state[EXACT_MODE] != 2) return;
   const LoProblem& pr = a.prob[blockIdx.y];
@@ -263,8 +272,8 @@ __global__ __launch_bounds__(64) void i8_patch_xd_kernel(LoArgs a) {
   const LoEntry* list = pr.entries + (int64_t)col * a.nch * LO_CAP;
   for (int i = lane; i < total; i += 64) {
     const LoEntry e = list[i];
-    const double xd = bf16_to_f64(*(const bf16_t*)((const char*)pr.x + e.off + 2 * col)) - e.v;
-    *(bf16_t*)((char*)pr.xd + e.aux + 2 * col) = (bf16_t)(__float_as_uint((float)xd) >> 16);
+    const double xd = EL::to_f64(*(const bf16_t*)((const char*)pr.x + e.off + 2 * col)) - e.v;
+    *(bf16_t*)((char*)pr.xd + e.aux + 2 * col) = (bf16_t)EL::from_f64(xd);
   }
 }
 
@@ -306,7 +315,7 @@ __device__ __forceinline__ LoFirst lo_first(const LoProblem& pr, const int G, co
   }
   return f;
 }
-template <bool COLS>
+template <class EL, bool RELU, bool COLS>
 __device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, const int G, const int sub, const int partner0, const int g,
                                           const int lane, double* acc, const LoFirst& first) {
   const unsigned short* xs = (const unsigned short*)pr.x;
@@ -318,9 +327,9 @@ __device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, co
     qb = ldexp(1.0, eb - 148);
     ia = 1.0 / qa;
     ib = 1.0 / qb;
-    // an element has a digit below plane 2 iff its exponent field is below E - 14 (and it is not zero): 0 < |bits| < (E - 14) << 7
-    lim_a = (unsigned)max(ea - 14, 1) << 7;
-    lim_b = (unsigned)max(eb - 14, 1) << 7;
+    // an element has a digit below plane 2 iff its exponent field is below a limit set by E (and it is not zero): 0 < |bits| < deep_limit(E)
+    lim_a = EL::deep_limit(ea);
+    lim_b = EL::deep_limit(eb);
   }
   const int list_id = G * LO_SUB + sub;
   const int cnt = first.cnt;
@@ -335,7 +344,7 @@ __device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, co
     for (int u = 0; u < LO_UN; u++) {
       const unsigned off = (unsigned)__builtin_amdgcn_readlane((int)m.off, u);
       const unsigned short* row = (const unsigned short*)((const char*)xs + off) + partner0 + 2 * lane;
-      xv[u] = pr.pairs ? *(const unsigned*)row : ((unsigned)row[0] | ((unsigned)row[1] << 16));
+      xv[u] = relu_pair<EL, RELU>(pr.pairs ? *(const unsigned*)row : ((unsigned)row[0] | ((unsigned)row[1] << 16)));
     }
   };
   auto multiply = [&](const LoEntry& m, const unsigned (&xv)[LO_UN]) {
@@ -343,7 +352,7 @@ __device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, co
     for (int u = 0; u < LO_UN; u++) {
       const double v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m.v), u), __builtin_amdgcn_readlane(__double2loint(m.v), u));
       const int col = __builtin_amdgcn_readlane((int)m.aux, u);
-      double pa = bf16_to_f64(xv[u] & 0xFFFFu), pb = bf16_to_f64(xv[u] >> 16);
+      double pa = EL::to_f64(xv[u] & 0xFFFFu), pb = EL::to_f64(xv[u] >> 16);
       if (COLS) {
         const bool deep = ((xv[u] & 0x7FFFu) - 1u < lim_a - 1u) || (((xv[u] >> 16) & 0x7FFFu) - 1u < lim_b - 1u);
         if (__ballot(deep)) {
@@ -383,6 +392,7 @@ __device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, co
 // One workgroup of sixteen waves per 128 x 128 tile of the lower triangle (per-head statistics: the diagonal tiles): wave (g, sub)
 // takes the list `sub` of row group g, then of column group g.
 constexpr int LO_THREADS = 1024;
+template <class EL, bool RELU>
 __global__ __launch_bounds__(LO_THREADS) void i8_lo_product_kernel(LoArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lo_acc[];     // [128][LO_PITCH]
   if (a.state[EXACT_RAN] != 1 || a.state[EXACT_OVERFLOW] != 0 || a.state[EXACT_MODE] != 1) return;
@@ -410,9 +420,9 @@ __global__ __launch_bounds__(LO_THREADS) void i8_lo_product_kernel(LoArgs a) {
   const LoFirst first_rows = lo_first(pr, 4 * bi + g, sub, lane), first_cols = lo_first(pr, 4 * bj + g, sub, lane);
   for (int i = tid; i < LO_TILE * LO_PITCH; i += LO_THREADS) lo_acc[i] = 0.;
   __syncthreads();
-  lo_events<false>(pr, a.nch, 4 * bi + g, sub, bj * LO_TILE, g, lane, lo_acc, first_rows);
+  lo_events<EL, RELU, false>(pr, a.nch, 4 * bi + g, sub, bj * LO_TILE, g, lane, lo_acc, first_rows);
   __syncthreads();      // an accumulator changes owner between the two passes: the wave of its row, then the wave of its column
-  lo_events<true>(pr, a.nch, 4 * bj + g, sub, bi * LO_TILE, g, lane, lo_acc, first_cols);
+  lo_events<EL, RELU, true>(pr, a.nch, 4 * bj + g, sub, bi * LO_TILE, g, lane, lo_acc, first_cols);
   __syncthreads();
   // the tile's 16 elements of a thread: all their sigma loads first, then the additions and the stores (written as `*s += v` behind
   // the tests, every element paid a memory round trip of its own: 16 in series per tile, most of the kernel's time on sparse lists)
@@ -460,7 +470,7 @@ __global__ __launch_bounds__(LO_THREADS) void i8_lo_product_kernel(LoArgs a) {
 #define LW_OCC_ATTR
 #endif
 constexpr int LW_COLS = 8, LW_BLOCK = 64 * LW_COLS, LW_UN = MDG_LW_UN, LW_GROUP = 16, LW_TP = LW_GROUP + 1;
-template <bool TR>
+template <class EL, bool RELU, bool TR>
 __global__ __launch_bounds__(LO_THREADS) LW_OCC_ATTR void i8_lo_wide_kernel(LoArgs a) {
   if (a.state[EXACT_RAN] != 1 || a.state[EXACT_OVERFLOW] != 0 || a.state[EXACT_MODE] != 2) return;
   int p = 0;
@@ -536,8 +546,9 @@ __global__ __launch_bounds__(LO_THREADS) LW_OCC_ATTR void i8_lo_wide_kernel(LoAr
                                               __builtin_amdgcn_readlane(__double2loint(m.v), b * LW_UN + u));
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-              acc[2 * q] = fma(v, (double)__uint_as_float(xv[u][q] << 16), acc[2 * q]);
-              acc[2 * q + 1] = fma(v, (double)__uint_as_float(xv[u][q] & 0xFFFF0000u), acc[2 * q + 1]);
+              const unsigned w = TR ? xv[u][q] : relu_pair<EL, RELU>(xv[u][q]);      // (the x_d copy has the ReLU in it)
+              acc[2 * q] = fma(v, EL::lo_f64(w), acc[2 * q]);
+              acc[2 * q + 1] = fma(v, EL::hi_f64(w), acc[2 * q + 1]);
             }
           }
         };
@@ -594,6 +605,18 @@ __global__ __launch_bounds__(LO_THREADS) LW_OCC_ATTR void i8_lo_wide_kernel(LoAr
           if (s[k]) *s[k] = old[k] + v[k];
       }
     }
+  }
+}
+
+template <bool TR>
+void launch_lo_wide(const I8Call& c, const LoArgs& lo) {
+  const dim3 grid((unsigned)lo.tiles[TR]), block(LO_THREADS);
+  if (c.f16) {
+    if (c.relu) hipLaunchKernelGGL((i8_lo_wide_kernel<F16Elem, true, TR>), grid, block, 0, c.st, lo);
+    else hipLaunchKernelGGL((i8_lo_wide_kernel<F16Elem, false, TR>), grid, block, 0, c.st, lo);
+  } else {
+    if (c.relu) hipLaunchKernelGGL((i8_lo_wide_kernel<Bf16Elem, true, TR>), grid, block, 0, c.st, lo);
+    else hipLaunchKernelGGL((i8_lo_wide_kernel<Bf16Elem, false, TR>), grid, block, 0, c.st, lo);
   }
 }
 
@@ -663,8 +686,8 @@ int enqueue_lo_lists(const I8Call& c, bool always) {
   hipLaunchKernelGGL(i8_compact_lo_kernel, dim3((unsigned)(max_groups * 32), count), dim3(64), 0, c.st, lo);
   hipLaunchKernelGGL(i8_lo_mode_kernel, dim3(1), dim3(1024), 0, c.st, lo);
   hipLaunchKernelGGL(i8_residue_lo_kernel, dim3((unsigned)(max_groups * LO_SUB), count), dim3(64), 0, c.st, lo);
-  hipLaunchKernelGGL(i8_copy_xd_kernel, dim3(2048u, count), dim3(256), 0, c.st, lo);
-  hipLaunchKernelGGL(i8_patch_xd_kernel, dim3((unsigned)(max_groups * 32), count), dim3(64), 0, c.st, lo);
+  MDG_I8_DISPATCH(c, i8_copy_xd_kernel, dim3(2048u, count), dim3(256), 0, c.st, lo);
+  MDG_I8_DISPATCH(c, i8_patch_xd_kernel, dim3((unsigned)(max_groups * 32), count), dim3(64), 0, c.st, lo);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }
@@ -673,10 +696,12 @@ int enqueue_lo_lists(const I8Call& c, bool always) {
 int enqueue_lo_products(const I8Call& c, bool always) {
   const LoArgs lo = lo_args(c, always);
   const size_t lds = (size_t)LO_TILE * LO_PITCH * sizeof(double);
-  MDG_HIP(hipFuncSetAttribute((const void*)i8_lo_product_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(i8_lo_product_kernel, dim3((unsigned)lo.tiles[2]), dim3(LO_THREADS), lds, c.st, lo);          // sparse lists
-  hipLaunchKernelGGL(i8_lo_wide_kernel<false>, dim3((unsigned)lo.tiles[0]), dim3(LO_THREADS), 0, c.st, lo);        // dense lists
-  hipLaunchKernelGGL(i8_lo_wide_kernel<true>, dim3((unsigned)lo.tiles[1]), dim3(LO_THREADS), 0, c.st, lo);
+  const void* tile_kernel = c.f16 ? (c.relu ? (const void*)i8_lo_product_kernel<F16Elem, true> : (const void*)i8_lo_product_kernel<F16Elem, false>)
+                                  : (c.relu ? (const void*)i8_lo_product_kernel<Bf16Elem, true> : (const void*)i8_lo_product_kernel<Bf16Elem, false>);
+  MDG_HIP(hipFuncSetAttribute(tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  MDG_I8_DISPATCH(c, i8_lo_product_kernel, dim3((unsigned)lo.tiles[2]), dim3(LO_THREADS), lds, c.st, lo);          // sparse lists
+  launch_lo_wide<false>(c, lo);       // dense lists: X_lo^T X,
+  launch_lo_wide<true>(c, lo);        // then X_d^T X_lo
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

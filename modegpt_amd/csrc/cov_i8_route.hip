@@ -20,6 +20,12 @@ namespace {
 // holding an Inf / NaN always leave (only the fp64 arithmetic propagates those the way the reference does).
 // ||N_j|| enters through the integer lower bound 2^32 (||256 d_0 + d_1|| - sqrt(nonzeros) / 2): every decision is a function of
 // integer sums, hence run-to-run bit-identical.  One workgroup per statistic.
+// Element type: checked for fp16 (F16Elem, cov_i8.hpp) -- nothing here assumes an 8-bit significand.  The kernel sees integer plane
+// energies and emax only.  The lower bound on ||N_j|| holds for any integers below 2^47 (what lies under the top two digits is at
+// most half a unit of d_1 per nonzero element); it is positive because the column maximum's significand sits right below bit 46
+// for either type (|d_0| >= 16 there, or a column of subnormals whose N are multiples of 2^35: |256 d_0 + d_1| >= 8 per nonzero
+// element against the 1/2 subtracted).  Inf / NaN columns are recognised by emax 255, which is what F16Elem reports for exponent
+// field 31; a finite fp16 column never counts a rounded element, so its rho is 0.
 // TAU_SQ bounds the attained part.  The cross part is attained only by columns whose digit sequences are proportional over the
 // tokens; for uncorrelated columns the sums behind it grow like sqrt(tokens) where Cauchy-Schwarz allows tokens, so the measured
 // error sits ~4.5 / sqrt(tokens) below X_P (0.02 - 0.035 at 32768 tokens on every family of scripts/probes/i8_error_bound.py).
@@ -378,6 +384,7 @@ struct ColArgs {
   double* part;               // [ROUTE_JMAX][COLK_CHUNKS][n]
 };
 
+template <class EL, bool RELU>
 __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
   const int pass = blockIdx.z;
   const int n_out = a.route->n_out;
@@ -396,7 +403,7 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
 #pragma unroll
     for (int i = 0; i < COLK_STAGE / 8; i++) {
       const int64_t tok = t + lane / COLK_GROUP + 8 * i;
-      g[i] = (my_col >= 0 && tok < t1) ? xs[tok * a.ld + my_col] : (unsigned short)0;
+      g[i] = (my_col >= 0 && tok < t1) ? (unsigned short)relu_bits<EL, RELU>(xs[tok * a.ld + my_col]) : (unsigned short)0;
     }
   };
   double acc[COLK_GROUP][8] = {};
@@ -405,7 +412,7 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
   for (int64_t t = t0; t < t1; t += COLK_STAGE) {
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < COLK_STAGE / 8; i++) xj[lane / COLK_GROUP + 8 * i][my_k] = bf16_to_f64(g[i]);
+    for (int i = 0; i < COLK_STAGE / 8; i++) xj[lane / COLK_GROUP + 8 * i][my_k] = EL::to_f64(g[i]);
     __syncthreads();
     if (t + COLK_STAGE < t1) fetch_group(t + COLK_STAGE, g);
     if (!active) continue;
@@ -433,8 +440,9 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
         double xc[8];
 #pragma unroll
         for (int h = 0; h < 4; h++) {
-          xc[2 * h] = bf16_to_f64(w[i][h] & 0xFFFFu);
-          xc[2 * h + 1] = bf16_to_f64(w[i][h] >> 16);
+          const unsigned wr = relu_pair<EL, RELU>(w[i][h]);
+          xc[2 * h] = EL::to_f64(wr & 0xFFFFu);
+          xc[2 * h + 1] = EL::to_f64(wr >> 16);
         }
 #pragma unroll
         for (int k = 0; k < COLK_GROUP; k++) {
@@ -498,7 +506,7 @@ int enqueue_columns(const I8Call& c, int i) {
   a.route = s.route;
   a.flag = s.route_flag;
   a.part = s.colpart;
-  hipLaunchKernelGGL(i8_columns_kernel, dim3((unsigned)ceil_div(s.n, COLK_WG_COLS), COLK_CHUNKS, ROUTE_JMAX / COLK_GROUP), dim3(64), 0, c.st, a);
+  MDG_I8_DISPATCH(c, i8_columns_kernel, dim3((unsigned)ceil_div(s.n, COLK_WG_COLS), COLK_CHUNKS, ROUTE_JMAX / COLK_GROUP), dim3(64), 0, c.st, a);
   hipLaunchKernelGGL(i8_columns_reduce_kernel, dim3((unsigned)ceil_div(s.n, 256), ROUTE_JMAX), dim3(256), 0, c.st, a, (const int*)s.emax, s.sigma,
                      s.ld_sigma, s.block);
   MDG_LAUNCH_CHECK();

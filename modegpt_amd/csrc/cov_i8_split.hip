@@ -1,5 +1,6 @@
-// int8 covariance, first stage (the map of the units is at the head of cov_i8.hip): column maxima, the split of the bf16
-// activations into six digit planes with the route statistics and the piece masks.
+// int8 covariance, first stage (the map of the units is at the head of cov_i8.hip): column maxima, the split of the bf16 or fp16
+// activations into six digit planes with the route statistics and the piece masks.  Every kernel here is a template on the
+// element traits (EL: Bf16Elem / F16Elem, cov_i8.hpp) and on ReLU-on-load.
 #include <algorithm>
 
 #include "cov_i8.hpp"
@@ -7,14 +8,18 @@
 namespace mdg {
 namespace {
 
-// bf16 bits -> (signed 9-bit significand, effective exponent >= 1);  value = sig * 2^(ee - 134)
-__device__ __forceinline__ void bf16_parts(unsigned b, int& sig, int& ee) {
-  const int e = (b >> 7) & 0xFF, m = b & 0x7F;
-  sig = e ? (128 | m) : m;
-  ee = e ? e : 1;
-  if (b & 0x8000) sig = -sig;
+// An element more than EL::TOP binades under its column maximum (bf16 only; in an fp16 column only beside an Inf / NaN, and such a
+// column leaves the int8 path) is rounded to an integer: the magnitude half up; nothing survives a shift by more than SIG_BITS + 1.
+template <class EL>
+__device__ __forceinline__ long long fixed_point(int sig, int sh, bool& rounded) {
+  rounded = sh > EL::TOP;
+  if (!rounded) return (long long)sig << (EL::TOP - sh);
+  const int dn = sh - EL::TOP;
+  const int mag = dn > EL::SIG_BITS + 1 ? 0 : ((sig < 0 ? -sig : sig) + (1 << (dn - 1))) >> dn;
+  return sig < 0 ? -mag : mag;
 }
 
+template <class EL, bool RELU>
 __global__ __launch_bounds__(256) void i8_colmax_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int64_t rows_per_block,
                                                         int* emax) {
   const int j = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -24,7 +29,7 @@ __global__ __launch_bounds__(256) void i8_colmax_kernel(const bf16_t* x, int64_t
   if (j < n)
     for (int64_t t = t0; t < t1; t += 4) {
       int sig, ee;
-      bf16_parts(x[t * ld + j], sig, ee);
+      EL::parts(relu_bits<EL, RELU>(x[t * ld + j]), sig, ee);
       if (sig != 0) best = max(best, ee);
     }
   if (j < n) atomicMax(emax + j, best);
@@ -49,6 +54,7 @@ __device__ __forceinline__ unsigned write_piece_mask(const unsigned (&any)[NP], 
 // One thread = one feature row of a 32-row group x one k-step (32 tokens) at a time: two 16-byte stores per plane and
 // k-step.  A workgroup walks SPLIT_STEPS k-steps of its row group, 8 at a time.
 constexpr int SPLIT_STEPS = 64;
+template <class EL, bool RELU>
 __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int nk, const int* emax,
                                                        signed char* planes, unsigned long long* stats, unsigned char* zmask) {
   __shared__ unsigned long long st_lds[NSTAT][32];
@@ -71,17 +77,10 @@ __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t 
       for (int qq = 0; qq < 16; qq++) {
         const int64_t t = (int64_t)kt * KS + h * 16 + qq;
         int sig = 0, ee = 1;
-        if (t < T) bf16_parts(x[t * ld + j], sig, ee);
-        const int sh = E - ee;
-        q[STAT_COUNTS] += (long long)(sig != 0) + ((long long)(sig != 0 && sh > TOP_SHIFT) << 32);
-        long long N;
-        if (sh <= TOP_SHIFT) {
-          N = (long long)sig << (TOP_SHIFT - sh);
-        } else {
-          const int dn = sh - TOP_SHIFT;  // round the magnitude half up; nothing survives a shift by more than 9
-          const int mag = dn > 9 ? 0 : ((sig < 0 ? -sig : sig) + (1 << (dn - 1))) >> dn;
-          N = sig < 0 ? -mag : mag;
-        }
+        if (t < T) EL::parts(relu_bits<EL, RELU>(x[t * ld + j]), sig, ee);
+        bool rounded;
+        long long N = fixed_point<EL>(sig, E - ee, rounded);
+        q[STAT_COUNTS] += (long long)(sig != 0) + ((long long)(sig != 0 && rounded) << 32);
         int d[NP];
 #pragma unroll
         for (int s = NP - 1; s >= 1; s--) {
@@ -115,14 +114,10 @@ __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t 
 // ---- the same two passes for the usual case of 16-byte addressable rows (ld % 8 == 0, aligned base): 16-byte loads.
 // The scalar kernels above read 2 bytes per lane in 64-byte row segments and run at ~2 TB/s; these read whole 256-byte
 // segments and are bound by the 6 bytes per element the split writes.
-__device__ __forceinline__ int bf16_ee_if_nonzero(unsigned b) {  // effective exponent of a nonzero value, 0 for +-0
-  const int e = (b >> 7) & 0xFF;
-  return (b & 0x7FFF) ? (e ? e : 1) : 0;
-}
-
 #ifndef MDG_COLMAX_WGS
 #define MDG_COLMAX_WGS 4096
 #endif
+template <class EL, bool RELU>
 __global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int64_t ld, int64_t T, int64_t rows_per_block, int* emax) {
   __shared__ int best_lds[128];
   const int cg = threadIdx.x & 15, tl = threadIdx.x >> 4;  // 16 column groups of 8 columns x 16 token lanes
@@ -136,9 +131,9 @@ __global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int
     const i32x4 v = *(const i32x4*)(x + t * ld + j0);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const unsigned w = (unsigned)v[q];
-      best[2 * q] = max(best[2 * q], bf16_ee_if_nonzero(w & 0xFFFF));
-      best[2 * q + 1] = max(best[2 * q + 1], bf16_ee_if_nonzero(w >> 16));
+      const unsigned w = relu_pair<EL, RELU>((unsigned)v[q]);
+      best[2 * q] = max(best[2 * q], EL::ee_if_nonzero(w & 0xFFFF));
+      best[2 * q + 1] = max(best[2 * q + 1], EL::ee_if_nonzero(w >> 16));
     }
   }
 #pragma unroll
@@ -151,6 +146,7 @@ __global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int
 // loads are in flight meanwhile), one thread then owns one feature of one k-step.  The column statistics of the route are kept
 // in registers over the tiles and leave the workgroup as 8 atomics per feature.
 constexpr int SPLIT_TILES = 8;
+template <class EL, bool RELU>
 __global__ __launch_bounds__(256) void i8_split_vec_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int nk, const int* emax,
                                                            signed char* planes, unsigned long long* stats, unsigned char* zmask) {
   __shared__ __attribute__((aligned(16))) bf16_t tile[64 * 128];
@@ -199,18 +195,11 @@ __global__ __launch_bounds__(256) void i8_split_vec_kernel(const bf16_t* x, int6
 #pragma unroll
         for (int e = 0; e < 4; e++) {
           int sig, ee;
-          bf16_parts(tile[(ks * 32 + h * 16 + q4 * 4 + e) * 128 + f], sig, ee);
-          const int sh = E - ee;
+          EL::parts(relu_bits<EL, RELU>(tile[(ks * 32 + h * 16 + q4 * 4 + e) * 128 + f]), sig, ee);
           q[NSTAT - 1] += (sig != 0);
-          long long N;
-          if (sh <= TOP_SHIFT) {
-            N = (long long)sig << (TOP_SHIFT - sh);
-          } else {
-            const int dn = sh - TOP_SHIFT;
-            const int mag = dn > 9 ? 0 : ((sig < 0 ? -sig : sig) + (1 << (dn - 1))) >> dn;
-            N = sig < 0 ? -mag : mag;
-            q[NSTAT] += (sig != 0);      // rounded to an integer: the remainder term rho of the bound
-          }
+          bool rounded;
+          const long long N = fixed_point<EL>(sig, E - ee, rounded);
+          if (rounded) q[NSTAT] += (sig != 0);      // rounded to an integer: the remainder term rho of the bound
           const unsigned long long biased = (unsigned long long)N + 0x0000008080808080ull;
           lo[e] = (unsigned)biased;
           hi[e] = (unsigned)(biased >> 32);
@@ -282,15 +271,15 @@ int enqueue_split(const I8Call& c, int i) {
     //  16-byte loads each -- 82 us for 67 MB.  Token slabs sized for ~MDG_COLMAX_WGS workgroups in all, 64 tokens at least)
     const int64_t slabs = std::min(ceil_div(c.n_tokens, (int64_t)64), std::max((int64_t)1, (int64_t)MDG_COLMAX_WGS / (n / 128)));
     const int64_t rows_vec = ceil_div(ceil_div(c.n_tokens, slabs), (int64_t)16) * 16;
-    hipLaunchKernelGGL(i8_colmax_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(c.n_tokens, rows_vec)), dim3(256), 0, c.st, s.x,
+    MDG_I8_DISPATCH(c, i8_colmax_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(c.n_tokens, rows_vec)), dim3(256), 0, c.st, s.x,
                        s.ld, c.n_tokens, rows_vec, s.emax);
-    hipLaunchKernelGGL(i8_split_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(nk, 2 * SPLIT_TILES)), dim3(256), 0, c.st, s.x,
+    MDG_I8_DISPATCH(c, i8_split_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(nk, 2 * SPLIT_TILES)), dim3(256), 0, c.st, s.x,
                        s.ld, c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask);
   } else {
     const int64_t rows_per_block = 2048;
-    hipLaunchKernelGGL(i8_colmax_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(c.n_tokens, rows_per_block)), dim3(256), 0,
+    MDG_I8_DISPATCH(c, i8_colmax_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(c.n_tokens, rows_per_block)), dim3(256), 0,
                        c.st, s.x, s.ld, c.n_tokens, n, rows_per_block, s.emax);
-    hipLaunchKernelGGL(i8_split_kernel, dim3((unsigned)(n / 32), (unsigned)ceil_div(nk, SPLIT_STEPS)), dim3(256), 0, c.st, s.x, s.ld,
+    MDG_I8_DISPATCH(c, i8_split_kernel, dim3((unsigned)(n / 32), (unsigned)ceil_div(nk, SPLIT_STEPS)), dim3(256), 0, c.st, s.x, s.ld,
                        c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask);
   }
   MDG_LAUNCH_CHECK();

@@ -74,7 +74,7 @@ def accumulate(covs: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], sh
     defer sigma_x / sigma_q / sigma_k to the layer's last hook for exactly this); OPT's ReLU statistic stays separate.
     mode: None = ops.COV_MODE; "i8" routes sigma_mlp and sigma_x through the int8 digit-plane kernel."""
     if shape["arch"] == "opt":
-        ops.cov_accum(covs["mlp"], batch["h"], relu=True)
+        ops.cov_accum_fc_relu(covs["mlp"], batch["h"], mode=mode)
         ops.cov_accum_multi([(covs["x"], batch["x"], 1), (covs["q"], batch["q"], shape["n_heads"]),
                              (covs["k"], batch["k"], shape["n_kv_heads"])], mode=mode)
         return

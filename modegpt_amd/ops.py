@@ -106,8 +106,9 @@ def cov_accum(sigma: torch.Tensor, x: torch.Tensor, n_heads: int = 1, relu: bool
 
 
 def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: Optional[dict] = None,
-                 report: bool = True, route_info: Optional[dict] = None, tolerance: Optional[float] = None) -> Optional[int]:
-    """sigma (lower triangle) += X^T X for one bf16 matrix through the int8 digit-plane kernel (csrc/cov_i8.hip): error-free
+                 report: bool = True, route_info: Optional[dict] = None, tolerance: Optional[float] = None,
+                 relu: bool = False) -> Optional[int]:
+    """sigma (lower triangle) += X^T X for one bf16 or fp16 matrix (relu=True: of max(x, 0), applied on load) through the int8 digit-plane kernel (csrc/cov_i8.hip): error-free
     split into digit planes, truncated plane-pair product.  The route -- five planes or six, which columns leave the int8 path
     for the fp64 column kernel (at most 32), or the fp64 kernel for the whole statistic -- is derived on the device from a
     per-call error bound (guaranteed <= 1.1e-11 of sqrt(sigma_ii sigma_jj) entry-wise, typically 1e-13; include/modegpt_hip.h);
@@ -128,8 +129,8 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     lib = _lib.load()
     if sigma.dtype != torch.float64 or not sigma.is_contiguous() or sigma.dim() != 2:
         raise ValueError("sigma must be a contiguous 2-D float64 tensor")
-    if x.dtype != torch.bfloat16:
-        raise ValueError("cov_accum_i8 takes bf16 activations")
+    if x.dtype not in _I8_DTYPES:
+        raise ValueError("cov_accum_i8 takes bf16 or fp16 activations")
     x2 = x.detach().reshape(-1, x.shape[-1])
     if x2.stride(-1) != 1:
         x2 = x2.contiguous()
@@ -142,7 +143,7 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     used = C.c_int(0)
     with torch.cuda.device(x.device):
         check(lib.mdg_cov_accum_i8(x2.data_ptr(), x2.shape[0], n, x2.stride(0), sigma.data_ptr(), sigma.stride(0), wsp, nbytes,
-                                   i8_tolerance() if tolerance is None else float(tolerance), _i8_flags(), C.byref(used) if report else None, _route_counters(x.device).data_ptr(),
+                                   i8_tolerance() if tolerance is None else float(tolerance), _i8_flags(x2.dtype, relu), C.byref(used) if report else None, _route_counters(x.device).data_ptr(),
                                    None if events is None else events[0].cuda_event,
                                    None if events is None else events[1].cuda_event, _stream(x)), "mdg_cov_accum_i8")
         info = None
@@ -183,15 +184,19 @@ def _read_route(lib, count, arr, stat, wsp, stream) -> dict:
 I8_EXACT = {"1": True, "always": True, "0": False, "never": False}.get(os.environ.get("MODEGPT_I8_EXACT", "auto").lower(), "auto")
 
 
-def _i8_flags() -> int:
-    return {True: _lib.MDG_I8_EXACT_ALWAYS, False: _lib.MDG_I8_NO_EXACT}.get(I8_EXACT, 0)
+_I8_DTYPES = (torch.bfloat16, torch.float16)       # element types the int8 digit-plane kernels split (include/modegpt_hip.h, MDG_I8_F16)
+
+
+def _i8_flags(dtype=torch.bfloat16, relu: bool = False) -> int:
+    return ({True: _lib.MDG_I8_EXACT_ALWAYS, False: _lib.MDG_I8_NO_EXACT}.get(I8_EXACT, 0)
+            | (_lib.MDG_I8_F16 if dtype == torch.float16 else 0) | (_lib.MDG_I8_RELU if relu else 0))
 
 
 def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, report: bool = False,
-                       route_info: Optional[list] = None, tolerance: Optional[float] = None) -> Optional[int]:
+                       route_info: Optional[list] = None, tolerance: Optional[float] = None, relu: bool = False) -> Optional[int]:
     """Several statistics of ONE calibration batch through the int8 digit-plane kernels in one persistent product launch
-    (mdg_cov_accum_i8_multi): items = sequence of (sigma, x, n_heads), largest first, at most 4, all bf16 with the same token
-    count.  n_heads == 1: sigma [n, n], n a multiple of 128; n_heads > 1: per-head Grams, sigma [n_heads, 128, 128] of an
+    (mdg_cov_accum_i8_multi): items = sequence of (sigma, x, n_heads), largest first, at most 4, all bf16 or all fp16, with the same
+    token count (relu=True: max(x, 0) on load, for every statistic of the call).  n_heads == 1: sigma [n, n], n a multiple of 128; n_heads > 1: per-head Grams, sigma [n_heads, 128, 128] of an
     activation [tokens, n_heads * 128].  The tiles of all statistics share one tile schedule -- the small ones fill what the
     large one's last round leaves idle -- and one route: the deepest any column of any of them asks for (more planes are
     never less exact); a statistic too heavy-tailed for six planes leaves the launch alone (fp64 kernel).  events / mfma_stats /
@@ -206,8 +211,8 @@ def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, re
         _need_gpu(sigma, x)
         if sigma.dtype != torch.float64 or not sigma.is_contiguous():
             raise ValueError("sigma must be a contiguous float64 tensor")
-        if x.dtype != torch.bfloat16:
-            raise ValueError("cov_accum_i8_multi takes bf16 activations")
+        if x.dtype not in _I8_DTYPES or x.dtype != items[0][1].dtype:
+            raise ValueError("cov_accum_i8_multi takes bf16 or fp16 activations, one element type per call")
         x2 = x.detach().reshape(-1, x.shape[-1])
         if x2.stride(-1) != 1:
             x2 = x2.contiguous()
@@ -227,7 +232,7 @@ def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, re
     used = C.c_int(0)
     with torch.cuda.device(dev):
         check(lib.mdg_cov_accum_i8_multi(len(items), arr, wsp, nbytes, i8_tolerance() if tolerance is None else float(tolerance),
-                                         _i8_flags(), C.byref(used) if report else None,
+                                         _i8_flags(keep[0].dtype, relu), C.byref(used) if report else None,
                                          _route_counters(dev).data_ptr(), None if events is None else events[0].cuda_event,
                                          None if events is None else events[1].cuda_event, _stream(keep[0])),
               "mdg_cov_accum_i8_multi")
@@ -347,7 +352,7 @@ def cov_accum_multi(items, mode: Optional[str] = None) -> None:
     """One launch for several covariance problems of the same calibration batch.  items: sequence of
     (sigma, x, n_heads), largest problem first.  Falls back to one cov_accum call per item when the fused kernel's
     preconditions do not hold (mixed dtypes, feature count not a multiple of 128, unaligned rows).
-    mode (default ops.COV_MODE): "i8" sends every bf16 statistic the int8 digit-plane kernels can take -- single matrices of
+    mode (default ops.COV_MODE): "i8" sends every bf16 or fp16 statistic the int8 digit-plane kernels can take -- single matrices of
     at least I8_MIN_FEATURES features (a multiple of 128) and, beside one of those, per-head statistics of head_dim 128 --
     through them: the largest in a launch of its own (cov_accum_i8), the others together in one (cov_accum_i8_multi); only the
     rest goes through the fp64 kernel."""
@@ -362,16 +367,17 @@ def cov_accum_multi(items, mode: Optional[str] = None) -> None:
         for sigma, x, n_heads in items:
             # below ~2048 features the 128 x 128 tiles do not fill the 256 CUs and the fp64 kernel is the faster one
             # (scripts/probes/i8_small_n.py: 1536 features 1.35 vs 1.23 ms, 2048 features 1.40 vs 2.14 ms)
-            if n_heads == 1 and x.dtype == torch.bfloat16 and sigma.dim() == 2 and sigma.shape[-1] % 128 == 0 \
+            if n_heads == 1 and x.dtype in _I8_DTYPES and sigma.dim() == 2 and sigma.shape[-1] % 128 == 0 \
                     and sigma.shape[-1] >= I8_MIN_FEATURES:
                 planes.append((sigma, x, 1))
-            elif n_heads > 1 and x.dtype == torch.bfloat16 and sigma.dim() == 3 and sigma.shape[-1] == 128:
+            elif n_heads > 1 and x.dtype in _I8_DTYPES and sigma.dim() == 3 and sigma.shape[-1] == 128:
                 heads.append((sigma, x, n_heads))      # per-head statistics of head_dim 128: diagonal tiles of the same launch
             else:
                 rest.append((sigma, x, n_heads))
         tokens = {x.reshape(-1, x.shape[-1]).shape[0] for _, x, _ in planes + heads}
         group = ((planes[1:] if len(planes) > 1 else planes) + heads) if planes else []
-        if planes and I8_FUSE and len(tokens) == 1 and len(group) <= 4 and _fusable_device(planes[0][1].device):
+        one_type = len({x.dtype for _, x, _ in group}) == 1          # (a fused launch has one element type)
+        if planes and I8_FUSE and len(tokens) == 1 and one_type and len(group) <= 4 and _fusable_device(planes[0][1].device):
             # The largest statistic (sigma_mlp) keeps a launch and a route of its own -- on a real gated MLP it is the heavy-tailed
             # one (six planes) while the others take five, and a shared launch would drag them along (measured: -2 % on SiLU-gated
             # data).  Everything else -- sigma_x and the per-head sigma_q / sigma_k tiles -- shares ONE persistent int8 launch: one
@@ -414,6 +420,22 @@ def cov_accum_multi(items, mode: Optional[str] = None) -> None:
         if not items:
             return
     _cov_accum_fused(items)
+
+
+# Width from which OPT's fc1 statistic (ReLU on load) takes the int8 digit planes: where the exact route is offered by default
+# (cov_i8_exact.hip LO_AUTO_MIN_N), i.e. where the statistic keeps fp64-rounding accuracy whenever its remainder lists fit.
+FC_I8_MIN_FEATURES = 4096
+
+
+def cov_accum_fc_relu(sigma: torch.Tensor, x: torch.Tensor, mode: Optional[str] = None) -> None:
+    """sigma += ReLU(x)^T ReLU(x), the ReLU fused into the kernels' loads (OPT's fc1 statistic): bf16 / fp16 activations of at
+    least FC_I8_MIN_FEATURES features (a multiple of 128) through the int8 digit planes (cov_accum_i8(relu=True)) unless mode is
+    "f64"; everything else through the fp64 kernel (cov_accum(relu=True))."""
+    n = x.shape[-1]
+    if (mode or COV_MODE) == "i8" and x.dtype in _I8_DTYPES and n % 128 == 0 and n >= FC_I8_MIN_FEATURES and x.numel() > 0:
+        cov_accum_i8(sigma, x, report=False, relu=True)
+    else:
+        cov_accum(sigma, x, relu=True)
 
 
 _SIDE_STREAMS = {}
