@@ -39,7 +39,8 @@ extern "C" {
                                 process-wide setter / getter of ABI 8 are gone: no accuracy state in the library);
                                 mdg_ridge_scores takes `sens`, mdg_select_margin added (certificate of the MLP rank selection);
                                 the exact route of the int8 covariance (`flags`, route_counts[4], mdg_cov_accum_i8_route's `exact`);
-                                added under 9: mdg_qk_select_margin, mdg_vo_spectrum */
+                                added under 9: mdg_qk_select_margin, mdg_vo_spectrum; MDG_I8_ROWS / MDG_I8_MAX_ROWS (a flag bit of the int8
+                                covariance, route_counts[5] with that bit), mdg_cov_accum_i8_rows */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -126,7 +127,7 @@ int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void*
  * The route is chosen ON THE DEVICE: the call enqueues the five-plane product, the six-plane product, the column kernel and the fp64
  * kernel back to back, and the launches the route does not select exit at once -- the call only enqueues and never waits for the host
  * (it can be captured in a hipGraph) when used_i8 is NULL.  Every decision is a function of integer sums: run-to-run bit-identical.
- * route_counts (DEVICE pointer to 5 ints, optional): [0] += 1 when five planes ran, [1] six planes, [2] the fp64 kernel for the whole
+ * route_counts (DEVICE pointer to 5 ints -- 6 with MDG_I8_ROWS, see there --, optional): [0] += 1 when five planes ran, [1] six planes, [2] the fp64 kernel for the whole
  *   statistic, [3] += the number of columns handed to the fp64 column kernel, [4] += 1 when the exact route ran (see below; such a
  *   call is also booked under [0] or [1], the class the route kernel gave it); the caller keeps it across calls and reads it
  *   whenever it likes (calibration reads it once, at the end).
@@ -176,6 +177,36 @@ int mdg_cov_accum_multi(int n, const mdg_cov_problem* problems, int dtype, void*
  *   into 0 -- on that fallback route, and there only, a NaN column contributes zeros instead of NaNs. */
 #define MDG_I8_F16 4                  /* flags: x is fp16 */
 #define MDG_I8_RELU 8                 /* flags: max(x, 0) on load */
+/* OUTLIER TOKEN ROWS (added under ABI 9; a flag bit of the same `flags` argument, combines with every bit above, applies to EVERY
+ * statistic of the call; off by default, and without it every launch, every bit of sigma and every reported value is what it was).
+ * MDG_I8_ROWS: up to MDG_I8_MAX_ROWS token rows per statistic leave the int8 path.  Why: the split measures every element against its
+ *   COLUMN's maximum exponent, so a handful of tokens that are large across many columns raise every maximum at once, push the bulk of
+ *   every column deeper under it, overflow the exact route's event lists and break the truncated product's bound in more columns than
+ *   the fp64 column kernel takes -- the whole statistic then drops to mdg_cov_accum (about five times the time at the sigma_mlp shape).
+ *   X^T X = sum_t x_t x_t^T is additive over tokens: X^T X = X_rest^T X_rest + X_R^T X_R for any row set R, without cross terms.  The
+ *   int8 path (column maxima, split, route statistics, event lists, fp64 column kernel) reads the rows of R as +0, and an fp64 row
+ *   kernel (v_mfma_f64_16x16x4_f64, one workgroup per 128 x 128 tile of the lower triangle, rows in ascending token order, no atomics)
+ *   adds X_R^T X_R for all columns in the reference's arithmetic (LlamaAdapter.py:127-147).
+ *   THE RULE, decided on the device from the exponent fields of x alone -- integers, no floating-point sum, no host round trip,
+ *   bit-identical from run to run, the call still only enqueues (csrc/cov_i8_rows.hip; host model tests/i8_rows_model.py):
+ *     1. E_j = the column maxima over all rows.  2. v_t = the number of columns j where x_tj != 0 and ee(x_tj) >= E_j - 4 (ee: the
+ *     element's effective exponent; ReLU on load honoured).  3. row t is DOMINANT when v_t >= n / 8.  4. if 1 .. MDG_I8_MAX_ROWS rows
+ *     are dominant and they are at most an eighth of the call's tokens, they leave (ascending token order; a row bitmask in the
+ *     workspace).  5. otherwise nothing leaves and the call proceeds exactly as without the flag (on ordinary data most rows are
+ *     dominant: far more than 64).  6. the column maxima are then recomputed over the rows that stayed.
+ *   ONE ROUND: two tiers of outliers (rows x 2^16 and rows x 2^8 together) and a continuum of token scales (lognormal per-token
+ *   scales, scripts/probes/i8_fuzz.py kind 7) are out of scope -- those statistics take the route they took without the flag.
+ *   A statistic that goes to mdg_cov_accum as a whole even so is computed there from every row of x; the row kernel does not run for it.
+ *   route_counts: with this bit set the array has 6 ints, [5] += the rows handed to the fp64 row kernel (callers that never set the bit
+ *   keep passing 5).  mdg_cov_accum_i8_rows reads the rows of the last call back.
+ *   BOUND: on a call where rows left mdg_cov_accum_i8_route's bound[0] additionally carries the rounding of the row update.  The product
+ *   of two bf16 or two fp16 values is exact in fp64 (16 / 22 significand bits), so the update of entry (i, j) is a sum of |R| exact
+ *   terms x_ti x_tj: each of the |R| additions (the last one into sigma) rounds once, by at most 2^-53 of a partial sum, and every
+ *   partial sum obeys |sum_{t in S} x_ti x_tj| <= sqrt(sum_S x_ti^2 sum_S x_tj^2) <= sqrt(sigma_ii sigma_jj) (Cauchy-Schwarz; sigma of
+ *   this call's tokens): at most |R| 2^-53 sqrt(sigma_ii sigma_jj), reported as (|R| + 1) 2^-53 -- one more for the sum of the two
+ *   parts.  The bound of the int8 part holds relative to sigma of the rows that stayed, which is no larger than that of all rows. */
+#define MDG_I8_ROWS 16                /* flags: outlier token rows may leave the int8 path for the fp64 row kernel */
+#define MDG_I8_MAX_ROWS 64            /* rows per statistic and call the fp64 row kernel takes */
 #define MDG_I8_EXACT_ROUNDING 5e-15   /* what mdg_cov_accum_i8_route reports beside the rho term for a call on the exact route */
 size_t mdg_cov_accum_i8_ws_bytes(int64_t n_tokens, int64_t n_feat);
 int mdg_cov_accum_i8(const void* x, int64_t n_tokens, int64_t n_feat, int64_t ld, double* sigma, int64_t ld_sigma, void* ws,
@@ -195,6 +226,11 @@ int mdg_cov_accum_i8_stats(const void* ws, int64_t n_tokens, int64_t n_feat, uns
  * and then bound[0] = the rho term + MDG_I8_EXACT_ROUNDING, bound[1] = 0.  Any output pointer may be NULL.  Copies device -> host on `stream` and synchronises it: tests and measurements only. */
 int mdg_cov_accum_i8_route(int count, const mdg_cov_problem* problems, int stat, const void* ws, int* planes, int* n_columns,
                            int* columns, double* bound, int* exact, void* stream);
+/* The token rows statistic `stat` of the LAST call on workspace `ws` handed to the fp64 row kernel (MDG_I8_ROWS): *n_rows and
+ * rows[MDG_I8_MAX_ROWS], ascending, -1 padded.  0 rows when that call did not set the flag, when nothing left, or when the statistic
+ * went through mdg_cov_accum as a whole.  Either output pointer may be NULL.  Copies device -> host on `stream` and synchronises it:
+ * tests and measurements only. */
+int mdg_cov_accum_i8_rows(int count, const mdg_cov_problem* problems, int stat, const void* ws, int* n_rows, int* rows, void* stream);
 /* Up to 4 statistics of ONE calibration batch (the four hooks of a layer) through the int8 digit-plane kernels with ONE
  * persistent product launch: the tiles of all statistics share one static tile schedule, so the small ones fill what the large
  * one's last round leaves idle instead of ending launches of their own, and one route -- the deepest any statistic on the int8 path

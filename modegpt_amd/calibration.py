@@ -143,6 +143,9 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     sig.finalize(n_texts)
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
+        if ops.I8_ROWS:        # (before the reset below, which clears this counter too)
+            adapter.cov_rows_left = ops.i8_rows_left()
+            logger.info(f"token rows handed to the fp64 row kernel (MODEGPT_I8_ROWS): {adapter.cov_rows_left}")
         adapter.cov_routes = ops.i8_route_counts(reset=True)
         logger.info(f"covariance routes (int8 five planes / six planes / fp64 fallback): {adapter.cov_routes}")
     logger.info("Finished calibration and computed BI scores.")

@@ -2,7 +2,8 @@
 // planes and a TRUNCATED plane-pair product whose error is bounded per call.  What follows is written for bf16; an fp16 value is a
 // signed 11-bit significand, placed 35 instead of 38 bits up so that the column's unit is 2^(E_j - 172) for both (E_j on the fp32
 // exponent scale: the element traits in cov_i8.hpp) -- every finite fp16 element is then an exact integer, and only the kernels
-// that read x itself differ.  MDG_I8_RELU applies max(x, 0) wherever x is read.
+// that read x itself differ.  MDG_I8_RELU applies max(x, 0) wherever x is read.  MDG_I8_ROWS lets up to 64 outlier token rows per
+// statistic leave the int8 path for an fp64 row kernel (cov_i8_rows.hip has the rule); without the flag none of that is launched.
 //
 // A bf16 value is a signed 8-bit significand times a power of two.  Against a per-column scale 2^(E_j - 172), E_j the largest
 // exponent in column j of this call, it is a 48-bit fixed-point integer N = sig << (38 - (E_j - e)): six balanced base-256
@@ -22,9 +23,13 @@
 // The units, and the kernels of a call in launch order (all are enqueued for every call; the device picks: each workgroup of a
 // launch whose route was not taken exits on its first instruction):
 //   cov_i8.hpp           shared constants, the workspace's shared block (SharedBlock), I8Call / I8Stat, the units' host functions
-//   cov_i8.hip           this file: workspace layout, argument checks, the five extern "C" entry points
+//   cov_i8.hip           this file: workspace layout, argument checks, the six extern "C" entry points
 //   cov_i8_split.hip     per statistic:
 //     i8_colmax_kernel / i8_colmax_vec_kernel   E_j = max exponent per column (_vec: rows are 16-byte addressable, the usual case)
+//   cov_i8_rows.hip      per statistic, with MDG_I8_ROWS only:
+//     i8_row_votes_kernel, i8_row_select_kernel   which token rows leave (list + bitmask); then the maximum pass again, over the
+//                        rows that stayed (exits at once when none left).  Every kernel below that reads x reads those rows as +0
+//   cov_i8_split.hip     per statistic:
 //     i8_split_kernel / i8_split_vec_kernel     six digit planes, written in the blocked layout the product kernel streams: [plane]
 //                        [32-row group][k-step][k-half][row][16 tokens] -- each 1 KB piece is one contiguous global_load_lds_dwordx4
 //                        per wave; accumulates the per-column integers of the route (sum of d_s^2 per plane, sum of d_0 d_1, nonzero /
@@ -61,6 +66,8 @@
 //     i8_lo_wide_kernel<false>, i8_lo_wide_kernel<true>   dense lists: X_lo^T X, then X_d^T X_lo
 //   cov_i8_route.hip     per statistic:
 //     i8_columns_kernel, i8_columns_reduce_kernel   rows / columns of sigma of the columns that left, in plain fp64
+//   cov_i8_rows.hip      per statistic, with MDG_I8_ROWS only:
+//     i8_rows_product_kernel                        sigma += X_R^T X_R of the rows that left, v_mfma_f64 (not for a statistic on the fallback)
 //   cov.hip              per statistic: the gated fp64 kernel (cov_accum_gated), for a statistic whose flag has bit 1 set
 // ev_start / ev_stop bracket the three int8 product launches and their tail combines -- not the split, the route or the list
 // building before them, nor the remainder, column and fallback kernels after them.
@@ -74,8 +81,8 @@ namespace mdg {
 namespace {
 
 // Workspace layout of a call: [shared block][partial tiles], then per statistic [digit planes][column maxima, route statistics]
-// [alpha / rho][RouteOut][column-kernel partials][piece masks][the exact route's lists, counts, x_d copy, merged lists], then the
-// fp64 fallback's split-K space.  Returns the bytes a call needs; with `out`, the call's pointers into `ws`.
+// [alpha / rho][RouteOut][column-kernel partials][piece masks][the exact route's lists, counts, x_d copy, merged lists][MDG_I8_ROWS:
+// row bitmask, votes, row list -- reserved always, zeroed and used only with the flag], then the fp64 fallback's split-K space.  Returns the bytes a call needs; with `out`, the call's pointers into `ws`.
 size_t layout(int count, const mdg_cov_problem* pr, void* ws, I8Call* out, size_t* fallback_off) {
   size_t off = SHARED_BYTES + PARTIAL_BYTES, fb = 0;
   char* const base = (char*)ws;
@@ -106,6 +113,10 @@ size_t layout(int count, const mdg_cov_problem* pr, void* ws, I8Call* out, size_
     s.lo_xd = (bf16_t*)take(align_up(lo.xd, 256));
     s.lo_rentries = (LoEntry*)take(lo.rentries);
     s.lo_rtotals = (int*)take(align_up(lo.rtotals, 256));
+    const RowsWsBytes rw = rows_ws_bytes(T);
+    s.rowmask = (unsigned*)take(rw.mask);
+    s.votes = (int*)take(rw.votes);
+    s.rows_out = (RowsOut*)take(rw.out);
     if (out) out->stat[i] = s;
     fb = std::max(fb, mdg_cov_accum_ws_bytes(T, pr[i].n_feat, pr[i].batch));
   }
@@ -141,7 +152,7 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   if (used_i8) *used_i8 = 0;
   MDG_CHECK_ARG(tolerance >= 1.0 && tolerance <= 1e6, "mdg_cov_accum_i8_multi: tolerance factor %g outside [1, 1e6] (1 = guaranteed <= 1.1e-11)",
                 tolerance);
-  MDG_CHECK_ARG((flags & ~(MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS | MDG_I8_F16 | MDG_I8_RELU)) == 0 &&
+  MDG_CHECK_ARG((flags & ~(MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS | MDG_I8_F16 | MDG_I8_RELU | MDG_I8_ROWS)) == 0 &&
                     (flags & (MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS)) != (MDG_I8_NO_EXACT | MDG_I8_EXACT_ALWAYS),
                 "mdg_cov_accum_i8_multi: bad flags 0x%x", flags);
   bool offer_exact = !(flags & MDG_I8_NO_EXACT);
@@ -162,7 +173,10 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   c.st = (hipStream_t)stream;
   c.f16 = (flags & MDG_I8_F16) != 0;
   c.relu = (flags & MDG_I8_RELU) != 0;
+  c.rows = (flags & MDG_I8_ROWS) != 0;
   MDG_HIP(hipMemsetAsync(c.shared, 0, SHARED_BYTES, c.st));
+  // (remembered for the read-backs: without the flag the rows' part of the workspace holds nothing of this call; one byte -> the int 1)
+  if (c.rows) MDG_HIP(hipMemsetAsync(&c.shared->rows_flag, 1, 1, c.st));
   for (int i = 0; i < count; i++) {
     MDG_TRY(enqueue_split(c, i));
     MDG_TRY(enqueue_route(c, i, tolerance));
@@ -171,6 +185,8 @@ extern "C" int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems
   MDG_TRY(enqueue_products(c, offer_exact, ev_start, ev_stop));
   if (offer_exact) MDG_TRY(enqueue_lo_products(c, exact_always));
   for (int i = 0; i < count; i++) MDG_TRY(enqueue_columns(c, i));
+  if (c.rows)
+    for (int i = 0; i < count; i++) MDG_TRY(enqueue_rows_product(c, i));
   // a statistic the bound cannot certify on six planes even without its ROUTE_JMAX worst columns (its flag's bit 1) -- that
   // statistic, and only that one -- goes through the fp64 kernel
   for (int i = 0; i < count; i++) {
@@ -233,6 +249,13 @@ extern "C" int mdg_cov_accum_i8_route(int count, const mdg_cov_problem* problems
   MDG_HIP(hipMemcpyAsync(&shared, c.shared, sizeof(shared), hipMemcpyDeviceToHost, st));
   MDG_HIP(hipStreamSynchronize(st));
   const bool was_exact = r.planes != 0 && shared.exact_ran == 1 && shared.exact_overflow == 0;
+  int rows_left = 0;
+  if (shared.rows_flag && r.planes != 0) {
+    RowsOut ro;
+    MDG_HIP(hipMemcpyAsync(&ro, c.stat[stat].rows_out, sizeof(ro), hipMemcpyDeviceToHost, st));
+    MDG_HIP(hipStreamSynchronize(st));
+    rows_left = ro.n_rows;
+  }
   if (exact) *exact = was_exact ? shared.exact_mode : 0;      // 1: the remainder ran on the tile kernel (sparse lists), 2: on the wide kernels
   if (planes) *planes = r.planes;
   if (n_columns) *n_columns = r.n_out;
@@ -241,7 +264,35 @@ extern "C" int mdg_cov_accum_i8_route(int count, const mdg_cov_problem* problems
   if (bound) {   // the exact route drops no plane pair: the rounded-element term and fp64 rounding are what is left
     bound[0] = was_exact ? r.rho + MDG_I8_EXACT_ROUNDING : r.sq;
     bound[1] = was_exact ? 0.0 : r.x;
+    if (rows_left) bound[0] += (double)(rows_left + 1) * 0x1p-53;     // the fp64 row update's rounding (cov_i8_rows.hip)
   }
+  return MDG_OK;
+}
+
+// the rows statistic `stat` handed to the fp64 row kernel in the last call on `ws`; none when that call did not set MDG_I8_ROWS
+// (the shared block remembers) or sent the statistic to the fp64 kernel as a whole
+static int read_rows(const I8Call& c, int stat, RowsOut* out, hipStream_t st) {
+  SharedBlock shared;
+  MDG_HIP(hipMemcpyAsync(&shared, c.shared, sizeof(shared), hipMemcpyDeviceToHost, st));
+  MDG_HIP(hipStreamSynchronize(st));
+  out->n_rows = out->n_dominant = 0;
+  if (!shared.rows_flag || (shared.route_flag[stat] & 2)) return MDG_OK;
+  MDG_HIP(hipMemcpyAsync(out, c.stat[stat].rows_out, sizeof(*out), hipMemcpyDeviceToHost, st));
+  MDG_HIP(hipStreamSynchronize(st));
+  return MDG_OK;
+}
+
+extern "C" int mdg_cov_accum_i8_rows(int count, const mdg_cov_problem* problems, int stat, const void* ws, int* n_rows, int* rows,
+                                     void* stream) {
+  MDG_CLEAR();
+  MDG_CHECK_ARG(problems_ok(count, problems) && stat >= 0 && stat < count && ws, "mdg_cov_accum_i8_rows: bad arguments");
+  I8Call c;
+  layout(count, problems, const_cast<void*>(ws), &c, nullptr);
+  RowsOut r;
+  MDG_TRY(read_rows(c, stat, &r, (hipStream_t)stream));
+  if (n_rows) *n_rows = r.n_rows;
+  if (rows)
+    for (int i = 0; i < MDG_I8_MAX_ROWS; i++) rows[i] = i < r.n_rows ? r.rows[i] : -1;
   return MDG_OK;
 }
 

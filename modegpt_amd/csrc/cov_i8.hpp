@@ -100,6 +100,32 @@ __device__ __forceinline__ unsigned relu_pair(unsigned w) {
     }                                                                                     \
   } while (0)
 
+// The same for the kernels that also honour the row bitmask of MDG_I8_ROWS (template <EL, RELU, ROWS>): without the flag the
+// ROWS = false instantiations run, which are the code the kernels had before the flag existed.
+#define MDG_I8_DISPATCH_ROWS(c, KERNEL, ...)                                              \
+  do {                                                                                    \
+    if ((c).rows) {                                                                       \
+      if ((c).f16) {                                                                      \
+        if ((c).relu) hipLaunchKernelGGL((KERNEL<F16Elem, true, true>), __VA_ARGS__);     \
+        else hipLaunchKernelGGL((KERNEL<F16Elem, false, true>), __VA_ARGS__);             \
+      } else {                                                                            \
+        if ((c).relu) hipLaunchKernelGGL((KERNEL<Bf16Elem, true, true>), __VA_ARGS__);    \
+        else hipLaunchKernelGGL((KERNEL<Bf16Elem, false, true>), __VA_ARGS__);            \
+      }                                                                                   \
+    } else if ((c).f16) {                                                                 \
+      if ((c).relu) hipLaunchKernelGGL((KERNEL<F16Elem, true, false>), __VA_ARGS__);      \
+      else hipLaunchKernelGGL((KERNEL<F16Elem, false, false>), __VA_ARGS__);              \
+    } else {                                                                              \
+      if ((c).relu) hipLaunchKernelGGL((KERNEL<Bf16Elem, true, false>), __VA_ARGS__);     \
+      else hipLaunchKernelGGL((KERNEL<Bf16Elem, false, false>), __VA_ARGS__);             \
+    }                                                                                     \
+  } while (0)
+// MDG_I8_ROWS: is token t one of the rows that left the int8 path (cov_i8_rows.hip)?  Such a row reads as +0.
+template <bool ROWS>
+__device__ __forceinline__ bool row_left(const unsigned* rowmask, int64_t t) {
+  return ROWS && ((rowmask[t >> 5] >> (t & 31)) & 1u);
+}
+
 // Per-column integers the split pass accumulates for the route (i8_route_kernel; host model: tests/i8_model.py), as [NSTAT][n]
 // unsigned long long: q_s = sum over tokens of d_s^2 for the six planes, the signed sum of d_0 d_1 (so that the energy of the top
 // two digits together, hence a lower bound on the column's norm, is an integer too), and two counters packed into one word.
@@ -125,6 +151,12 @@ struct RouteOut {                           // per statistic, in the workspace (
   double sq, x;                             // SQ_P, X_P of the columns that stay (the guaranteed bound is their sum)
   double rho;                               // 2 R + R^2 alone: what is left of the bound when no plane pair is dropped (the exact route)
 };
+constexpr int ROWS_MAX = MDG_I8_MAX_ROWS;   // token rows per statistic and call the fp64 row kernel takes (64)
+struct RowsOut {                            // per statistic, in the workspace, with MDG_I8_ROWS (mdg_cov_accum_i8_rows reads it back)
+  int n_rows;                               // rows that left the int8 path: 0, or 1 .. ROWS_MAX
+  int n_dominant;                           // rows the vote found dominant (diagnostic: 0 or more than the limits -> nothing left)
+  int rows[ROWS_MAX];                       // ... ascending
+};
 struct RouteScratch {            // behind the route statistics, zeroed with them before every call
   int ticket, forced;
 };
@@ -138,6 +170,7 @@ struct SharedBlock {
   int xcd_queue[8];                  // the persistent launch's per-XCD tile-queue counters
   int route_flag[MAX_PROBLEMS];      // per statistic, i8_route_kernel: bit 0 -> needs six planes, bit 1 -> the fp64 kernel
   int exact_overflow, exact_ran, exact_mode;   // the exact route: a list overflowed; lists were built; 1 sparse lists, 2 dense
+  int rows_flag;                     // the call set MDG_I8_ROWS (read back by mdg_cov_accum_i8_route / _rows)
 };
 static_assert(offsetof(SharedBlock, mfma_count) == 8 && offsetof(SharedBlock, xcd_queue) == 16 && offsetof(SharedBlock, route_flag) == 48 &&
                   offsetof(SharedBlock, exact_overflow) == 64 && offsetof(SharedBlock, exact_ran) == 68 &&
@@ -164,6 +197,9 @@ struct I8Stat {
   LoEntry *lo_entries, *lo_rentries;   // the exact route: event lists per column; sparse mode: merged (group, residue) lists
   int *lo_counts, *lo_rtotals;         // ... and their lengths
   bf16_t* lo_xd;                 // the x_d copy of the exact route: [tokens][n] of x's element type
+  unsigned* rowmask;             // MDG_I8_ROWS: bit t of the mask = token t left for the fp64 row kernel; then the votes and the list,
+  int* votes;                    // [tokens]                                                     (one region, zeroed per call when the
+  RowsOut* rows_out;             //                                                               flag is set, untouched otherwise)
   bool vec() const { return (uintptr_t)x % 16 == 0 && ld % 8 == 0; }   // rows are 16-byte addressable
   unsigned long long* stats() const { return (unsigned long long*)(emax + (n + 1) / 2 * 2); }
 };
@@ -172,9 +208,11 @@ struct I8Call {
   int64_t n_tokens;
   I8Stat stat[MAX_PROBLEMS];
   bool f16, relu;                // MDG_I8_F16: x holds fp16 (else bf16); MDG_I8_RELU: max(x, 0) on load -- every statistic of the call
+  bool rows;                     // MDG_I8_ROWS: outlier token rows may leave for the fp64 row kernel -- every statistic of the call
   SharedBlock* shared;
   double* partial;               // PARTIAL_BYTES behind the shared block
-  int* route_counts;             // optional device counters [five planes, six planes, fp64 fallback, columns out, exact route]
+  int* route_counts;             // optional device counters [five planes, six planes, fp64 fallback, columns out, exact route] and,
+                                 // with MDG_I8_ROWS, [5]: rows handed to the fp64 row kernel
   hipStream_t st;
 };
 
@@ -184,8 +222,16 @@ inline size_t ints_bytes(int64_t n) { return (size_t)((n + 1) / 2 * 2) * sizeof(
 // ---- what each unit exposes: workspace sizes of its own structures, and the functions that enqueue its stage.  All return MDG_OK
 // or an error code with the message set.  (Hidden: the library's exported symbols stay what they were.)
 #pragma GCC visibility push(hidden)
-// cov_i8_split.hip: zero the statistic's integers, column maxima, digit planes + route statistics + piece masks
+// cov_i8_split.hip: zero the statistic's integers, column maxima, digit planes + route statistics + piece masks; with MDG_I8_ROWS the
+// row selection (enqueue_row_selection) and the second maximum pass run between the first maximum pass and the split
 int enqueue_split(const I8Call& c, int i);
+int enqueue_colmax(const I8Call& c, int i, bool masked);
+// cov_i8_rows.hip (MDG_I8_ROWS only): the rows of statistic i that leave the int8 path -- votes, selection, row bitmask -- from the
+// column maxima over all rows; after the products, sigma += X_R^T X_R of those rows in fp64
+struct RowsWsBytes { size_t mask, votes, out; };
+RowsWsBytes rows_ws_bytes(int64_t n_tokens);
+int enqueue_row_selection(const I8Call& c, int i);
+int enqueue_rows_product(const I8Call& c, int i);
 // cov_i8_route.hip: the route of statistic i and the clearing of the columns it hands out; after the products, those columns in fp64
 size_t route_vals_bytes(int64_t n);
 size_t column_partials_bytes(int64_t n);

@@ -382,9 +382,10 @@ struct ColArgs {
   const RouteOut* route;
   const int* flag;            // the statistic's route bits (bit 1: the whole statistic went to the fp64 kernel)
   double* part;               // [ROUTE_JMAX][COLK_CHUNKS][n]
+  const unsigned* rowmask;    // MDG_I8_ROWS: tokens that left for the fp64 row kernel read as +0 here (the row kernel adds them for ALL columns)
 };
 
-template <class EL, bool RELU>
+template <class EL, bool RELU, bool ROWS>
 __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
   const int pass = blockIdx.z;
   const int n_out = a.route->n_out;
@@ -403,7 +404,8 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
 #pragma unroll
     for (int i = 0; i < COLK_STAGE / 8; i++) {
       const int64_t tok = t + lane / COLK_GROUP + 8 * i;
-      g[i] = (my_col >= 0 && tok < t1) ? (unsigned short)relu_bits<EL, RELU>(xs[tok * a.ld + my_col]) : (unsigned short)0;
+      g[i] = (my_col >= 0 && tok < t1 && !row_left<ROWS>(a.rowmask, tok)) ? (unsigned short)relu_bits<EL, RELU>(xs[tok * a.ld + my_col])
+                                                                         : (unsigned short)0;
     }
   };
   double acc[COLK_GROUP][8] = {};
@@ -421,8 +423,9 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
       unsigned w[COLK_BATCH][4];
 #pragma unroll
       for (int i = 0; i < COLK_BATCH; i++) {
-        const bool live = t + tb + i < t1;
-        const int64_t tok = live ? t + tb + i : t1 - 1;        // (the address stays inside the chunk ...)
+        const bool in_chunk = t + tb + i < t1;
+        const int64_t tok = in_chunk ? t + tb + i : t1 - 1;    // (the address stays inside the chunk ...)
+        const bool live = in_chunk && !row_left<ROWS>(a.rowmask, tok);
         if (a.vec) {
           const i32x4 v = *(const i32x4*)(xs + tok * a.ld + c0);
           w[i][0] = v[0]; w[i][1] = v[1]; w[i][2] = v[2]; w[i][3] = v[3];
@@ -432,7 +435,7 @@ __global__ __launch_bounds__(64) void i8_columns_kernel(ColArgs a) {
         }
         // ... and a slot beyond the chunk's end contributes exact zeros: the group's staged values are zero there, but the re-read
         // last token may hold an Inf / NaN -- the very columns this kernel exists for -- and 0 * Inf would turn the +-Inf the
-        // reference's fp64 product gives into NaN
+        // reference's fp64 product gives into NaN (the same holds for a token that left for the row kernel)
         if (!live) w[i][0] = w[i][1] = w[i][2] = w[i][3] = 0u;
       }
 #pragma unroll
@@ -506,7 +509,8 @@ int enqueue_columns(const I8Call& c, int i) {
   a.route = s.route;
   a.flag = s.route_flag;
   a.part = s.colpart;
-  MDG_I8_DISPATCH(c, i8_columns_kernel, dim3((unsigned)ceil_div(s.n, COLK_WG_COLS), COLK_CHUNKS, ROUTE_JMAX / COLK_GROUP), dim3(64), 0, c.st, a);
+  a.rowmask = s.rowmask;
+  MDG_I8_DISPATCH_ROWS(c, i8_columns_kernel, dim3((unsigned)ceil_div(s.n, COLK_WG_COLS), COLK_CHUNKS, ROUTE_JMAX / COLK_GROUP), dim3(64), 0, c.st, a);
   hipLaunchKernelGGL(i8_columns_reduce_kernel, dim3((unsigned)ceil_div(s.n, 256), ROUTE_JMAX), dim3(256), 0, c.st, a, (const int*)s.emax, s.sigma,
                      s.ld_sigma, s.block);
   MDG_LAUNCH_CHECK();

@@ -1,6 +1,7 @@
 // int8 covariance, first stage (the map of the units is at the head of cov_i8.hip): column maxima, the split of the bf16 or fp16
 // activations into six digit planes with the route statistics and the piece masks.  Every kernel here is a template on the
-// element traits (EL: Bf16Elem / F16Elem, cov_i8.hpp) and on ReLU-on-load.
+// element traits (EL: Bf16Elem / F16Elem, cov_i8.hpp), on ReLU-on-load and on ROWS (MDG_I8_ROWS: a token whose bit is set in
+// `rowmask` reads as +0; the ROWS = false instantiations never look at the pointer).
 #include <algorithm>
 
 #include "cov_i8.hpp"
@@ -19,9 +20,10 @@ __device__ __forceinline__ long long fixed_point(int sig, int sh, bool& rounded)
   return sig < 0 ? -mag : mag;
 }
 
-template <class EL, bool RELU>
+template <class EL, bool RELU, bool ROWS>
 __global__ __launch_bounds__(256) void i8_colmax_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int64_t rows_per_block,
-                                                        int* emax) {
+                                                        int* emax, const unsigned* rowmask, const RowsOut* rows_out) {
+  if (ROWS && rows_out->n_rows == 0) return;     // (the second maximum pass: no row left, the first pass's maxima stand)
   const int j = blockIdx.x * 64 + (threadIdx.x & 63);
   const int64_t t0 = (int64_t)blockIdx.y * rows_per_block + (threadIdx.x >> 6);
   const int64_t t1 = min(T, (int64_t)(blockIdx.y + 1) * rows_per_block);
@@ -30,7 +32,7 @@ __global__ __launch_bounds__(256) void i8_colmax_kernel(const bf16_t* x, int64_t
     for (int64_t t = t0; t < t1; t += 4) {
       int sig, ee;
       EL::parts(relu_bits<EL, RELU>(x[t * ld + j]), sig, ee);
-      if (sig != 0) best = max(best, ee);
+      if (sig != 0 && !row_left<ROWS>(rowmask, t)) best = max(best, ee);
     }
   if (j < n) atomicMax(emax + j, best);
 }
@@ -54,9 +56,10 @@ __device__ __forceinline__ unsigned write_piece_mask(const unsigned (&any)[NP], 
 // One thread = one feature row of a 32-row group x one k-step (32 tokens) at a time: two 16-byte stores per plane and
 // k-step.  A workgroup walks SPLIT_STEPS k-steps of its row group, 8 at a time.
 constexpr int SPLIT_STEPS = 64;
-template <class EL, bool RELU>
+template <class EL, bool RELU, bool ROWS>
 __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int nk, const int* emax,
-                                                       signed char* planes, unsigned long long* stats, unsigned char* zmask) {
+                                                       signed char* planes, unsigned long long* stats, unsigned char* zmask,
+                                                       const unsigned* rowmask) {
   __shared__ unsigned long long st_lds[NSTAT][32];
   const int r = threadIdx.x & 31;
   const int G = blockIdx.x;
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t 
       for (int qq = 0; qq < 16; qq++) {
         const int64_t t = (int64_t)kt * KS + h * 16 + qq;
         int sig = 0, ee = 1;
-        if (t < T) EL::parts(relu_bits<EL, RELU>(x[t * ld + j]), sig, ee);
+        if (t < T && !row_left<ROWS>(rowmask, t)) EL::parts(relu_bits<EL, RELU>(x[t * ld + j]), sig, ee);
         bool rounded;
         long long N = fixed_point<EL>(sig, E - ee, rounded);
         q[STAT_COUNTS] += (long long)(sig != 0) + ((long long)(sig != 0 && rounded) << 32);
@@ -117,9 +120,11 @@ __global__ __launch_bounds__(256) void i8_split_kernel(const bf16_t* x, int64_t 
 #ifndef MDG_COLMAX_WGS
 #define MDG_COLMAX_WGS 4096
 #endif
-template <class EL, bool RELU>
-__global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int64_t ld, int64_t T, int64_t rows_per_block, int* emax) {
+template <class EL, bool RELU, bool ROWS>
+__global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int64_t ld, int64_t T, int64_t rows_per_block, int* emax,
+                                                            const unsigned* rowmask, const RowsOut* rows_out) {
   __shared__ int best_lds[128];
+  if (ROWS && rows_out->n_rows == 0) return;     // (the second maximum pass: no row left, the first pass's maxima stand)
   const int cg = threadIdx.x & 15, tl = threadIdx.x >> 4;  // 16 column groups of 8 columns x 16 token lanes
   const int j0 = blockIdx.x * 128 + cg * 8;
   const int64_t t0 = (int64_t)blockIdx.y * rows_per_block + tl;
@@ -128,7 +133,8 @@ __global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int
   __syncthreads();
   int best[8] = {1, 1, 1, 1, 1, 1, 1, 1};
   for (int64_t t = t0; t < t1; t += 16) {
-    const i32x4 v = *(const i32x4*)(x + t * ld + j0);
+    i32x4 v = *(const i32x4*)(x + t * ld + j0);
+    if (row_left<ROWS>(rowmask, t)) v = (i32x4)0;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const unsigned w = relu_pair<EL, RELU>((unsigned)v[q]);
@@ -146,9 +152,10 @@ __global__ __launch_bounds__(256) void i8_colmax_vec_kernel(const bf16_t* x, int
 // loads are in flight meanwhile), one thread then owns one feature of one k-step.  The column statistics of the route are kept
 // in registers over the tiles and leave the workgroup as 8 atomics per feature.
 constexpr int SPLIT_TILES = 8;
-template <class EL, bool RELU>
+template <class EL, bool RELU, bool ROWS>
 __global__ __launch_bounds__(256) void i8_split_vec_kernel(const bf16_t* x, int64_t ld, int64_t T, int n, int nk, const int* emax,
-                                                           signed char* planes, unsigned long long* stats, unsigned char* zmask) {
+                                                           signed char* planes, unsigned long long* stats, unsigned char* zmask,
+                                                           const unsigned* rowmask) {
   __shared__ __attribute__((aligned(16))) bf16_t tile[64 * 128];
   __shared__ int st_lds[NSTAT + 1][128];
   const int f0 = blockIdx.x * 128;
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(256) void i8_split_vec_kernel(const bf16_t* x, int6
       const int c = threadIdx.x + 256 * c4;  // 16-byte chunk: token c / 16, columns (c % 16) * 8 ..
       const int64_t t = tok0 + (c >> 4);
       v[c4] = (i32x4)0;
-      if (t < T) v[c4] = *(const i32x4*)(x + t * ld + f0 + (c & 15) * 8);
+      if (t < T && !row_left<ROWS>(rowmask, t)) v[c4] = *(const i32x4*)(x + t * ld + f0 + (c & 15) * 8);
     }
   };
   const int tile0 = blockIdx.y * SPLIT_TILES, tiles = (nk + 1) / 2;
@@ -262,25 +269,46 @@ __global__ __launch_bounds__(256) void i8_split_vec_kernel(const bf16_t* x, int6
 
 }  // namespace
 
-int enqueue_split(const I8Call& c, int i) {
+// The column maxima of statistic i into its (zeroed) emax.  masked (MDG_I8_ROWS, the second pass): over the rows that stayed --
+// every workgroup exits at once when no row left; the selection kernel zeroed emax again when one did.
+int enqueue_colmax(const I8Call& c, int i, bool masked) {
   const I8Stat& s = c.stat[i];
-  const int n = s.n, nk = c.nk;
-  MDG_HIP(hipMemsetAsync(s.emax, 0, ints_bytes(n), c.st));
+  const int n = s.n;
+  I8Call k = c;
+  k.rows = masked;
+  const unsigned* mask = masked ? s.rowmask : nullptr;
+  const RowsOut* ro = masked ? s.rows_out : nullptr;
   if (s.vec()) {
     // (the maximum pass of a NARROW statistic: with 2048 tokens per workgroup 1024 columns are 128 workgroups walking 128 dependent
     //  16-byte loads each -- 82 us for 67 MB.  Token slabs sized for ~MDG_COLMAX_WGS workgroups in all, 64 tokens at least)
     const int64_t slabs = std::min(ceil_div(c.n_tokens, (int64_t)64), std::max((int64_t)1, (int64_t)MDG_COLMAX_WGS / (n / 128)));
     const int64_t rows_vec = ceil_div(ceil_div(c.n_tokens, slabs), (int64_t)16) * 16;
-    MDG_I8_DISPATCH(c, i8_colmax_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(c.n_tokens, rows_vec)), dim3(256), 0, c.st, s.x,
-                       s.ld, c.n_tokens, rows_vec, s.emax);
-    MDG_I8_DISPATCH(c, i8_split_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(nk, 2 * SPLIT_TILES)), dim3(256), 0, c.st, s.x,
-                       s.ld, c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask);
+    MDG_I8_DISPATCH_ROWS(k, i8_colmax_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(c.n_tokens, rows_vec)), dim3(256), 0, c.st,
+                         s.x, s.ld, c.n_tokens, rows_vec, s.emax, mask, ro);
   } else {
     const int64_t rows_per_block = 2048;
-    MDG_I8_DISPATCH(c, i8_colmax_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(c.n_tokens, rows_per_block)), dim3(256), 0,
-                       c.st, s.x, s.ld, c.n_tokens, n, rows_per_block, s.emax);
-    MDG_I8_DISPATCH(c, i8_split_kernel, dim3((unsigned)(n / 32), (unsigned)ceil_div(nk, SPLIT_STEPS)), dim3(256), 0, c.st, s.x, s.ld,
-                       c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask);
+    MDG_I8_DISPATCH_ROWS(k, i8_colmax_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(c.n_tokens, rows_per_block)), dim3(256),
+                         0, c.st, s.x, s.ld, c.n_tokens, n, rows_per_block, s.emax, mask, ro);
+  }
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}
+
+int enqueue_split(const I8Call& c, int i) {
+  const I8Stat& s = c.stat[i];
+  const int n = s.n, nk = c.nk;
+  MDG_HIP(hipMemsetAsync(s.emax, 0, ints_bytes(n), c.st));
+  MDG_TRY(enqueue_colmax(c, i, false));
+  if (c.rows) {     // which rows leave is decided against the maxima over ALL rows; the split then runs against those of the rest
+    MDG_TRY(enqueue_row_selection(c, i));
+    MDG_TRY(enqueue_colmax(c, i, true));
+  }
+  if (s.vec()) {
+    MDG_I8_DISPATCH_ROWS(c, i8_split_vec_kernel, dim3((unsigned)(n / 128), (unsigned)ceil_div(nk, 2 * SPLIT_TILES)), dim3(256), 0, c.st, s.x,
+                         s.ld, c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask, (const unsigned*)s.rowmask);
+  } else {
+    MDG_I8_DISPATCH_ROWS(c, i8_split_kernel, dim3((unsigned)(n / 32), (unsigned)ceil_div(nk, SPLIT_STEPS)), dim3(256), 0, c.st, s.x, s.ld,
+                         c.n_tokens, n, nk, s.emax, s.planes, s.stats(), s.zmask, (const unsigned*)s.rowmask);
   }
   MDG_LAUNCH_CHECK();
   return MDG_OK;

@@ -107,7 +107,7 @@ def cov_accum(sigma: torch.Tensor, x: torch.Tensor, n_heads: int = 1, relu: bool
 
 def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: Optional[dict] = None,
                  report: bool = True, route_info: Optional[dict] = None, tolerance: Optional[float] = None,
-                 relu: bool = False) -> Optional[int]:
+                 relu: bool = False, rows: Optional[bool] = None) -> Optional[int]:
     """sigma (lower triangle) += X^T X for one bf16 or fp16 matrix (relu=True: of max(x, 0), applied on load) through the int8 digit-plane kernel (csrc/cov_i8.hip): error-free
     split into digit planes, truncated plane-pair product.  The route -- five planes or six, which columns leave the int8 path
     for the fp64 column kernel (at most 32), or the fp64 kernel for the whole statistic -- is derived on the device from a
@@ -124,7 +124,9 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     events: optional pair of torch.cuda.Event(enable_timing=True), each recorded once already, re-recorded around the product
     launches alone.  mfma_stats: optional dict; its "executed" entry is increased by the number of v_mfma instructions the
     product kernel issued (it skips digit planes that are all-zero over a tile panel) and "dense" by what a kernel without
-    that skipping issues -- costs a stream synchronisation, for measurement only (implies report)."""
+    that skipping issues -- costs a stream synchronisation, for measurement only (implies report).
+    rows: let up to 64 outlier token rows leave the int8 path for the fp64 row kernel (MDG_I8_ROWS, include/modegpt_hip.h; None:
+    ops.I8_ROWS); route_info then also holds "rows", the tokens that left, ascending."""
     _need_gpu(sigma, x)
     lib = _lib.load()
     if sigma.dtype != torch.float64 or not sigma.is_contiguous() or sigma.dim() != 2:
@@ -141,16 +143,17 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     ws, wsp = _ws(nbytes, x.device)
     report = report or mfma_stats is not None or route_info is not None
     used = C.c_int(0)
+    flags = _i8_flags(x2.dtype, relu, rows)
     with torch.cuda.device(x.device):
         check(lib.mdg_cov_accum_i8(x2.data_ptr(), x2.shape[0], n, x2.stride(0), sigma.data_ptr(), sigma.stride(0), wsp, nbytes,
-                                   i8_tolerance() if tolerance is None else float(tolerance), _i8_flags(x2.dtype, relu), C.byref(used) if report else None, _route_counters(x.device).data_ptr(),
+                                   i8_tolerance() if tolerance is None else float(tolerance), flags, C.byref(used) if report else None, _route_counters(x.device).data_ptr(),
                                    None if events is None else events[0].cuda_event,
                                    None if events is None else events[1].cuda_event, _stream(x)), "mdg_cov_accum_i8")
         info = None
         if route_info is not None or mfma_stats is not None:
             arr = (_lib.CovProblem * 1)(_lib.CovProblem(x2.data_ptr(), x2.shape[0], n, 1, x2.stride(0), sigma.data_ptr(),
                                                         sigma.stride(0), 0))
-            info = _read_route(lib, 1, arr, 0, wsp, _stream(x))
+            info = _read_route(lib, 1, arr, 0, wsp, _stream(x), flags)
         if mfma_stats is not None and used.value in (5, 6):
             done = C.c_ulonglong(0)
             check(lib.mdg_cov_accum_i8_stats(wsp, x2.shape[0], n, C.byref(done), _stream(x)), "mdg_cov_accum_i8_stats")
@@ -166,15 +169,21 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     return used.value
 
 
-def _read_route(lib, count, arr, stat, wsp, stream) -> dict:
+def _read_route(lib, count, arr, stat, wsp, stream, flags: int = 0) -> dict:
     planes, ncol, exact = C.c_int(0), C.c_int(0), C.c_int(0)
     cols = (C.c_int * 32)()
     bound = (C.c_double * 2)()
     check(lib.mdg_cov_accum_i8_route(count, arr, stat, wsp, C.byref(planes), C.byref(ncol), cols, bound, C.byref(exact), stream),
           "mdg_cov_accum_i8_route")
-    return {"planes": planes.value, "columns": [cols[i] for i in range(ncol.value)], "sq": bound[0], "x": bound[1],
+    info = {"planes": planes.value, "columns": [cols[i] for i in range(ncol.value)], "sq": bound[0], "x": bound[1],
             "bound": bound[0] + bound[1], "exact": bool(exact.value),
             "remainder": {0: None, 1: "tiles", 2: "wide"}.get(exact.value)}
+    if flags & _lib.MDG_I8_ROWS:       # the token rows the fp64 row kernel computed
+        n_rows = C.c_int(0)
+        rows = (C.c_int * _lib.MDG_I8_MAX_ROWS)()
+        check(lib.mdg_cov_accum_i8_rows(count, arr, stat, wsp, C.byref(n_rows), rows, stream), "mdg_cov_accum_i8_rows")
+        info["rows"] = [rows[i] for i in range(n_rows.value)]
+    return info
 
 
 # The exact route of the int8 covariance (include/modegpt_hip.h, "THE EXACT ROUTE"): "auto" (default) takes it where it is the
@@ -184,16 +193,23 @@ def _read_route(lib, count, arr, stat, wsp, stream) -> dict:
 I8_EXACT = {"1": True, "always": True, "0": False, "never": False}.get(os.environ.get("MODEGPT_I8_EXACT", "auto").lower(), "auto")
 
 
+# Outlier token rows (include/modegpt_hip.h, "OUTLIER TOKEN ROWS"): when on, a handful of tokens that are large across many columns
+# leave the int8 path for an fp64 row kernel instead of dragging the whole statistic to the fp64 kernel.  Opt-in: MODEGPT_I8_ROWS=1.
+I8_ROWS = os.environ.get("MODEGPT_I8_ROWS", "0").lower() in ("1", "on", "true")
+
+
 _I8_DTYPES = (torch.bfloat16, torch.float16)       # element types the int8 digit-plane kernels split (include/modegpt_hip.h, MDG_I8_F16)
 
 
-def _i8_flags(dtype=torch.bfloat16, relu: bool = False) -> int:
+def _i8_flags(dtype=torch.bfloat16, relu: bool = False, rows: Optional[bool] = None) -> int:
     return ({True: _lib.MDG_I8_EXACT_ALWAYS, False: _lib.MDG_I8_NO_EXACT}.get(I8_EXACT, 0)
-            | (_lib.MDG_I8_F16 if dtype == torch.float16 else 0) | (_lib.MDG_I8_RELU if relu else 0))
+            | (_lib.MDG_I8_F16 if dtype == torch.float16 else 0) | (_lib.MDG_I8_RELU if relu else 0)
+            | (_lib.MDG_I8_ROWS if (I8_ROWS if rows is None else rows) else 0))
 
 
 def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, report: bool = False,
-                       route_info: Optional[list] = None, tolerance: Optional[float] = None, relu: bool = False) -> Optional[int]:
+                       route_info: Optional[list] = None, tolerance: Optional[float] = None, relu: bool = False,
+                       rows: Optional[bool] = None) -> Optional[int]:
     """Several statistics of ONE calibration batch through the int8 digit-plane kernels in one persistent product launch
     (mdg_cov_accum_i8_multi): items = sequence of (sigma, x, n_heads), largest first, at most 4, all bf16 or all fp16, with the same
     token count (relu=True: max(x, 0) on load, for every statistic of the call).  n_heads == 1: sigma [n, n], n a multiple of 128; n_heads > 1: per-head Grams, sigma [n_heads, 128, 128] of an
@@ -201,7 +217,8 @@ def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, re
     large one's last round leaves idle -- and one route: the deepest any column of any of them asks for (more planes are
     never less exact); a statistic too heavy-tailed for six planes leaves the launch alone (fp64 kernel).  events / mfma_stats /
     report as in cov_accum_i8 (report: the planes of the statistics that stayed, 0 if none did; the executed / dense counts cover
-    all statistics and assume none fell back).  route_info: optional list, extended by one dict per statistic (see cov_accum_i8)."""
+    all statistics and assume none fell back).  route_info: optional list, extended by one dict per statistic (see cov_accum_i8).
+    rows as in cov_accum_i8, for every statistic of the call."""
     lib = _lib.load()
     items = list(items)
     arr = (_lib.CovProblem * len(items))()
@@ -230,15 +247,16 @@ def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, re
     ws, wsp = _ws(nbytes, dev)
     report = report or mfma_stats is not None or route_info is not None
     used = C.c_int(0)
+    flags = _i8_flags(keep[0].dtype, relu, rows)
     with torch.cuda.device(dev):
         check(lib.mdg_cov_accum_i8_multi(len(items), arr, wsp, nbytes, i8_tolerance() if tolerance is None else float(tolerance),
-                                         _i8_flags(keep[0].dtype, relu), C.byref(used) if report else None,
+                                         flags, C.byref(used) if report else None,
                                          _route_counters(dev).data_ptr(), None if events is None else events[0].cuda_event,
                                          None if events is None else events[1].cuda_event, _stream(keep[0])),
               "mdg_cov_accum_i8_multi")
         infos = None
         if route_info is not None or mfma_stats is not None:
-            infos = [_read_route(lib, len(items), arr, i, wsp, _stream(keep[0])) for i in range(len(items))]
+            infos = [_read_route(lib, len(items), arr, i, wsp, _stream(keep[0]), flags) for i in range(len(items))]
         if mfma_stats is not None and used.value in (5, 6):
             done = C.c_ulonglong(0)
             check(lib.mdg_cov_accum_i8_stats(wsp, 0, 0, C.byref(done), _stream(keep[0])), "mdg_cov_accum_i8_stats")
@@ -258,12 +276,13 @@ _ROUTE_COUNTERS = {}
 
 
 def _route_counters(device) -> torch.Tensor:
-    """Per-device int32[5] the kernels bump: [five planes, six planes, fp64 fallback of a whole statistic, columns handed to the
-    fp64 column kernel, statistics on the exact route] (mdg_cov_accum_i8 route_counts)."""
+    """Per-device int32[6] the kernels bump: [five planes, six planes, fp64 fallback of a whole statistic, columns handed to the
+    fp64 column kernel, statistics on the exact route, token rows handed to the fp64 row kernel (MDG_I8_ROWS calls only)]
+    (mdg_cov_accum_i8 route_counts)."""
     dev = torch.device(device)
     key = dev.index if dev.index is not None else torch.cuda.current_device()
     if key not in _ROUTE_COUNTERS:
-        _ROUTE_COUNTERS[key] = torch.zeros(5, dtype=torch.int32, device=torch.device("cuda", key))
+        _ROUTE_COUNTERS[key] = torch.zeros(6, dtype=torch.int32, device=torch.device("cuda", key))
     return _ROUTE_COUNTERS[key]
 
 
@@ -317,13 +336,25 @@ def i8_route_counts(device=None, reset: bool = False) -> dict:
     kernels that ran: {"i8_5", "i8_6", "fallback_f64"} count statistics (by the class the route kernel gave them), "fp64_columns"
     the single columns the route handed to the fp64 column kernel, "exact" how many of the i8_5 / i8_6 statistics ran the exact
     route (nine plane pairs + the fp64 remainder products) instead of the truncated product.  One small device -> host copy;
-    calibration reads it once, at the end."""
+    calibration reads it once, at the end.  (The sixth counter, the rows of MDG_I8_ROWS calls, is read by i8_rows_left; reset
+    clears it too.)"""
     key = torch.cuda.current_device() if device is None else (torch.device(device).index or 0)
     t = _route_counters(torch.device("cuda", key))
     v = t.cpu().tolist()
     if reset:
         t.zero_()
     return {"i8_5": v[0], "i8_6": v[1], "fallback_f64": v[2], "fp64_columns": v[3], "exact": v[4]}
+
+
+def i8_rows_left(device=None, reset: bool = False) -> int:
+    """Token rows the int8 covariance calls on `device` (default: the current one) handed to the fp64 row kernel so far (calls with
+    the rows option, MDG_I8_ROWS; counted on the device).  reset clears this counter only."""
+    key = torch.cuda.current_device() if device is None else (torch.device(device).index or 0)
+    t = _route_counters(torch.device("cuda", key))
+    v = int(t[5].item())
+    if reset:
+        t[5] = 0
+    return v
 
 
 def i8_dense_mfma_count(n_tokens: int, n: int, planes: int, n_heads: int = 1) -> int:
