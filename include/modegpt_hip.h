@@ -251,6 +251,16 @@ int mdg_cov_accum_i8_multi(int count, const mdg_cov_problem* problems, void* ws,
  * reproduces calibration.py:141-146. */
 int mdg_cov_finalize(double* sigma, int64_t n, int64_t batch, int64_t ld_sigma, int64_t sigma_batch_stride,
                      double scale, void* stream);
+/* Packed storage of a finalized statistic -- what load_calibs' calibs_save_path / load_calibs_from (calibration.py:23-24; declared
+ * and never read upstream) write and read.  packed holds `batch` matrices of n(n+1)/2 contiguous doubles each, the LOWER triangle
+ * in row-major packed order: row i contributes its entries 0..i at offset i(i+1)/2, so a file of it reads with numpy alone
+ * (full[np.tril_indices(n)] = np.fromfile(path, "<f8")).  full: `batch` matrices [n][ld], ld >= n, batch_stride elements apart.
+ * mdg_sym_pack_lower reads nothing above the diagonal (a buffer mdg_cov_finalize has not mirrored yet packs the same).
+ * mdg_sym_unpack_lower writes both triangles in one pass and leaves elements [n, ld) of every row, and whatever lies between two
+ * matrices, untouched.  Both move raw 64-bit patterns: NaN payloads, +-Inf, -0.0 and subnormals survive bit for bit.  All offsets
+ * are 64-bit (a packed matrix passes 4 GiB at n = 23 170).  full and packed must not overlap. */
+int mdg_sym_pack_lower(const double* full, int64_t n, int64_t batch, int64_t ld, int64_t batch_stride, double* packed, void* stream);
+int mdg_sym_unpack_lower(const double* packed, int64_t n, int64_t batch, double* full, int64_t ld, int64_t batch_stride, void* stream);
 /* Block-Influence partial: *out += sum over tokens of (1 - cos(x_in[t], x_out[t])) in fp64
  * (calibration.py:118-124; the caller divides by T and n_texts).  ws: mdg_bi_ws_bytes(n_tokens). */
 size_t mdg_bi_ws_bytes(int64_t n_tokens);

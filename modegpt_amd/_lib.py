@@ -53,6 +53,8 @@ SIGNATURES = {
     "mdg_cov_accum_multi_ws_bytes": (_sz, [_i32, C.POINTER(CovProblem), _i32]),
     "mdg_cov_accum_multi": (_i32, [_i32, C.POINTER(CovProblem), _i32, _ptr, _sz, _ptr]),
     "mdg_cov_finalize": (_i32, [_ptr, _i64, _i64, _i64, _i64, _f64, _ptr]),
+    "mdg_sym_pack_lower": (_i32, [_ptr, _i64, _i64, _i64, _i64, _ptr, _ptr]),
+    "mdg_sym_unpack_lower": (_i32, [_ptr, _i64, _i64, _ptr, _i64, _i64, _ptr]),
     "mdg_bi_ws_bytes": (_sz, [_i64]),
     "mdg_bi_accum": (_i32, [_ptr, _ptr, _i32, _i64, _i64, _i64, _ptr, _ptr, _sz, _ptr]),
     "mdg_gemm_f64": (_i32, [_i64, _i64, _i64, _f64, _ptr, _i32, _i64, _i64, _ptr, _ptr, _i32, _i64, _i64, _f64,

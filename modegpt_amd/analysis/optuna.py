@@ -5,6 +5,7 @@ every trial runs the whole driver with a sampled CompressionConfig and reports t
 
 `optuna` is imported lazily: the package is optional (it is not installed in the build image).  Each trial costs one
 full calibration + compression; on one MI355X that is minutes for an 8B model, which is what makes a sweep practical.
+Set MODEGPT_CALIBS_SAVE=<dir> for the first trial and MODEGPT_CALIBS_LOAD=<dir> from then on and the later trials skip calibration.
 """
 from __future__ import annotations
 

@@ -83,8 +83,23 @@ def _stop_forward(module, args, output):
 
 def load_calibs(adapter: ModelAdapter, n_samples: int, batch_size: int, dataset: str = "wikitext",
                 load_calibs_from="", calibs_save_path="", target_layers: List[int] = []):
-    return _calibrate_model(adapter, n_samples=n_samples, batch_size=batch_size, dataset=dataset,
-                            target_layers=target_layers)
+    """load_calibs_from / calibs_save_path (declared and never read upstream, src/calibration.py:23-24): a directory of per-layer
+    statistic records (calib_cache.py).  With calibs_save_path the target layers' statistics are written there after calibration;
+    with load_calibs_from they are read from there and the model is not run at all; with both, loaded and written again (a copy or
+    a subset).  The return value is the same five-tuple in every case."""
+    if not load_calibs_from and not calibs_save_path:
+        return _calibrate_model(adapter, n_samples=n_samples, batch_size=batch_size, dataset=dataset,
+                                target_layers=target_layers)
+    from . import calib_cache
+    loaded = None
+    if load_calibs_from:
+        calibs, loaded = calib_cache.load(adapter, load_calibs_from, n_samples, batch_size, dataset, target_layers)
+    else:
+        calibs = _calibrate_model(adapter, n_samples=n_samples, batch_size=batch_size, dataset=dataset,
+                                  target_layers=target_layers)
+    if calibs_save_path:
+        calib_cache.save(adapter, calibs_save_path, calibs, n_samples, batch_size, dataset, target_layers, loaded)
+    return calibs
 
 
 @torch.no_grad()

@@ -538,6 +538,52 @@ def cov_finalize(sigma: torch.Tensor, scale: float) -> None:
               "mdg_cov_finalize")
 
 
+def _sym_view(full: torch.Tensor):
+    """(n, batch, ld, batch stride) of a [n, n] or [batch, n, n] fp64 view whose rows are contiguous."""
+    if full.dtype != torch.float64 or full.dim() not in (2, 3) or full.shape[-1] != full.shape[-2] or full.stride(-1) != 1:
+        raise ValueError("a symmetric statistic is a float64 [n, n] or [batch, n, n] tensor with contiguous rows")
+    n = full.shape[-1]
+    batch = 1 if full.dim() == 2 else full.shape[0]
+    ld = full.stride(-2) if n > 1 else max(full.stride(-2), 1)
+    bs = full.stride(0) if full.dim() == 3 and batch > 1 else n * ld
+    if ld < n or (batch > 1 and bs < (n - 1) * ld + n):
+        raise ValueError("the matrices of a symmetric statistic must not overlap")
+    return n, batch, ld, bs
+
+
+def sym_pack_lower(full: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The lower triangle (diagonal included) of `full` -- fp64 [n, n] or [batch, n, n], any row / batch stride -- as n(n+1)/2
+    contiguous doubles per matrix in row-major packed order (row i at offset i(i+1)/2): out[np.tril_indices(n)] order.  Nothing
+    above the diagonal is read; bit patterns are moved, not values.  out: a contiguous fp64 device tensor of batch * n(n+1)/2
+    elements to write into (default: a new one).  Returns it, shaped [n(n+1)/2] or [batch, n(n+1)/2]."""
+    _need_gpu(full, out)
+    n, batch, ld, bs = _sym_view(full)
+    m = n * (n + 1) // 2
+    shape = (m,) if full.dim() == 2 else (batch, m)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=full.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != batch * m or out.device != full.device:
+        raise ValueError(f"out must be a contiguous float64 tensor of {batch * m} elements on {full.device}")
+    with torch.cuda.device(full.device):
+        check(_lib.load().mdg_sym_pack_lower(full.data_ptr(), n, batch, ld, bs, out.data_ptr(), _stream(full)),
+              "mdg_sym_pack_lower")
+    return out.view(shape)
+
+
+def sym_unpack_lower(packed: torch.Tensor, full: torch.Tensor) -> torch.Tensor:
+    """The inverse of sym_pack_lower: both triangles of `full` (fp64 [n, n] or [batch, n, n], any row / batch stride) from the
+    packed lower triangles in `packed` (contiguous, batch * n(n+1)/2 doubles).  Only the n x n entries are written."""
+    _need_gpu(packed, full)
+    n, batch, ld, bs = _sym_view(full)
+    m = n * (n + 1) // 2
+    if packed.dtype != torch.float64 or not packed.is_contiguous() or packed.numel() != batch * m or packed.device != full.device:
+        raise ValueError(f"packed must be a contiguous float64 tensor of {batch * m} elements on {full.device}")
+    with torch.cuda.device(full.device):
+        check(_lib.load().mdg_sym_unpack_lower(packed.data_ptr(), n, batch, full.data_ptr(), ld, bs, _stream(full)),
+              "mdg_sym_unpack_lower")
+    return full
+
+
 def bi_accum(out: torch.Tensor, x_in: torch.Tensor, x_out: torch.Tensor) -> None:
     """out[0] += sum_tokens (1 - cos(x_in, x_out)); out: 1-element fp64 device tensor."""
     _need_gpu(out, x_in, x_out)

@@ -78,17 +78,27 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
         adapter.calib_want_bi = rank == bi_rank and getattr(adapter, "bi_scores_cached", None) is None
         adapter.calib_stop_after = mine[-1] if mine else chunk[0]
         adapter.calib_no_hooks = not mine          # (`target_layers=[]` means "all layers" upstream: say "none" explicitly)
+    # Statistics directories (calib_cache.py; CompressionConfig's flags are the reference's, so these come from the environment as
+    # MODEGPT_I8_ROWS does): MODEGPT_CALIBS_SAVE writes every layer's statistics after calibration, MODEGPT_CALIBS_LOAD reads them
+    # instead of calibrating -- a rank loads the layers it owns and every rank reads the BI scores, nothing is broadcast.
+    calibs_save = os.environ.get("MODEGPT_CALIBS_SAVE", "")
+    calibs_load = os.environ.get("MODEGPT_CALIBS_LOAD", "")
+    if chunk[0] == 0 and (calibs_save or calibs_load):
+        logger.info(f"calibration statistics: MODEGPT_CALIBS_LOAD={calibs_load!r} MODEGPT_CALIBS_SAVE={calibs_save!r}")
+    cache = {k: v for k, v in (("load_calibs_from", calibs_load), ("calibs_save_path", calibs_save)) if v}   # (unset: the call as it always was)
     try:
         cov_mlp, cov_q, cov_k, cov_x, bi_scores = load_calibs(
             adapter=adapter, n_samples=config.calib_size, batch_size=config.calibs_batch_size, dataset=config.dataset,
-            target_layers=mine)
+            target_layers=mine, **cache)
     finally:
         # the three switches belong to THIS call: a later load_calibs on the same adapter (another trial, a one-rank re-run, a test
         # reusing the adapter) must get the full forward, its hooks and its BI scores again
         for name in ("calib_want_bi", "calib_stop_after", "calib_no_hooks"):
             if hasattr(adapter, name):
                 delattr(adapter, name)
-    if world > 1:
+    if world > 1 and calibs_load:
+        adapter.bi_scores_cached = bi_scores       # (every rank read the same file)
+    elif world > 1:
         bi_scores = _share_bi_scores(adapter, bi_scores, bi_rank, rank)
     keep = allocate_global_sparsity(bi_scores, compression_ratio=config.compression_ratio,
                                     smoothing=config.sparsity_smoothing, max_sparsity=config.max_sparsity,

@@ -81,7 +81,10 @@ if a.price:
         torch.cuda.synchronize(); t0 = time.time(); real_save(self, *args, **kw); io[0] += time.time() - t0
     type(ad).save_layer = timed_save
 torch.cuda.synchronize(); t0 = time.time()
-cov_mlp, cov_q, cov_k, cov_x, bi = load_calibs(ad, a.calib_size, a.batch, dataset="synthetic", target_layers=[])
+# MODEGPT_CALIBS_SAVE / MODEGPT_CALIBS_LOAD as the driver reads them: write the statistics after calibrating / read them instead of calibrating
+cov_mlp, cov_q, cov_k, cov_x, bi = load_calibs(ad, a.calib_size, a.batch, dataset="synthetic", target_layers=[],
+                                               load_calibs_from=os.environ.get("MODEGPT_CALIBS_LOAD", ""),
+                                               calibs_save_path=os.environ.get("MODEGPT_CALIBS_SAVE", ""))
 torch.cuda.synchronize(); t_cal = time.time() - t0
 if a.price:
     price["hook_kernels_s"] = sum(e0.elapsed_time(e1) for e0, e1 in ev) * 1e-3
