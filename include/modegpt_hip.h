@@ -286,9 +286,14 @@ int mdg_gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const void* A, i
                  int64_t a_batch_stride, int64_t b_batch_stride, int64_t c_batch_stride, int flags,
                  void* stream);
 
-/* In-place lower Cholesky A = L L^T (upper triangle left untouched), blocked right-looking with 128-wide
- * panels; inv_diag receives the inverses of the 128x128 diagonal blocks of L ([ceil(n/128)][128][128],
- * identity-padded).  SYNCHRONISES the stream once at the end to read the pivot flag.
+/* In-place lower Cholesky A = L L^T, blocked right-looking with 128-wide panels; inv_diag receives the inverses of
+ * the 128x128 diagonal blocks of L ([ceil(n/128)][128][128], identity-padded).  Strictly above the diagonal: entries
+ * outside the 128x128 diagonal blocks are neither read nor written (they may hold anything, NaN too); entries inside
+ * the diagonal blocks are not read for the result either, but MAY BE OVERWRITTEN with unspecified values (the rank-128
+ * and outer updates store a diagonal tile whole) -- factorise a copy if the upper
+ * triangle matters, as mdg_ridge_scores and mdg_nystrom_down do in their workspace.  Nothing beyond column n of a row
+ * (lda > n) or beyond row n is touched.  SYNCHRONISES the stream once at the end to read the pivot flag (the first
+ * leading minor that is not positive definite; a zero or NaN pivot counts).
  * Replaces torch.linalg.cholesky at compress_mlp.py:20,56. */
 size_t mdg_potrf_inv_diag_elems(int64_t n);
 int mdg_potrf_lower(double* A, int64_t n, int64_t lda, double* inv_diag, void* stream);
