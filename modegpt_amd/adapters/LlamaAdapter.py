@@ -30,9 +30,12 @@ class LlamaAdapter(ModelAdapter):
     def register_hooks(self, layer_idx, block, cov_mlp_list, cov_q_list, cov_k_list, cov_x_list, handles, logger):
         """Same four hook sites as the reference.  The three attention-side statistics are not launched when their hook
         fires: the hook only parks a reference to the activation, and the layer's last hook (the pre-hook of
-        mlp.down_proj) sends all four problems of the layer to the device in ONE fused launch
-        (ops.cov_accum_multi -> mdg_cov_accum_multi), so the small problems' workgroups run in the slots the large one
-        leaves free.  Nothing is copied; the parked tensors live until the end of the layer's forward."""
+        mlp.down_proj) hands all four problems of the layer to ops.cov_accum_multi together, which plans their launches
+        (ops.plan_cov_launches).  By default (mode "i8", a wide bf16 / fp16 layer with heads of 128): sigma_mlp in an int8 launch
+        of its own, sigma_x + sigma_q + sigma_k in ONE persistent int8 launch (mdg_cov_accum_i8_multi), whose small problems'
+        tiles fill what the large one's last round leaves idle; what the int8 planes cannot take, and everything in mode
+        "f64", goes to the fp64 kernel in one launch (mdg_cov_accum_multi).  Nothing is copied; the parked tensors live until
+        the end of the layer's forward."""
         parked = {}
 
         def park(kind):

@@ -47,15 +47,16 @@ def covariance_error_eps(adapter, n_features: int) -> float:
     tokens = int(getattr(adapter, "calib_tokens", 0) or getattr(adapter.config, "calib_size", 32) * 2048)
     eps_f64 = (tokens / 4 + 4) * 2.0 ** -53
     eps_i8 = I8_GUARANTEED_EPS * ops.i8_tolerance() + 64 * 2.0 ** -53
-    if n_features % 128 != 0 or n_features < ops.I8_MIN_FEATURES:
+    if not ops.takes_i8_planes(n_features):
         return eps_f64
+    # (OPT's fc1 statistic goes through ops.cov_accum_fc_relu, ReLU on load: the int8 planes from ops.FC_I8_MIN_FEATURES features only)
+    takes_i8 = ops.takes_i8_planes(n_features, relu=getattr(adapter, "arch", None) == "opt")
     routes = getattr(adapter, "cov_routes", None)
-    if routes is None:       # (OPT's fc1 statistic takes the int8 route from ops.FC_I8_MIN_FEATURES features only: ops.cov_accum_fc_relu)
-        wide_enough = n_features >= ops.FC_I8_MIN_FEATURES or getattr(adapter, "arch", None) != "opt"
-        return eps_i8 if ops.COV_MODE == "i8" and wide_enough else eps_f64
+    if routes is None:
+        return eps_i8 if ops.COV_MODE == "i8" and takes_i8 else eps_f64
     if routes.get("i8_5", 0) + routes.get("i8_6", 0) == 0:
         return eps_f64
-    if getattr(adapter, "arch", None) == "opt" and n_features < ops.FC_I8_MIN_FEATURES:
+    if not takes_i8:
         return max(eps_i8, eps_f64)      # (the counts are another statistic's, sigma_x's: OPT's fc1 statistic of this width ran on fp64)
     return max(eps_i8, eps_f64) if routes.get("fallback_f64", 0) or routes.get("fp64_columns", 0) else eps_i8
 

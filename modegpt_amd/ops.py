@@ -9,7 +9,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -81,28 +81,50 @@ class DeferredStatus:
 
 
 # ------------------------------------------------------------------ covariance
+_I8_DTYPES = (torch.bfloat16, torch.float16)       # element types the int8 digit-plane kernels split (include/modegpt_hip.h, MDG_I8_F16)
+
+
+def _cov_problem(sigma: torch.Tensor, x: torch.Tensor, n_heads: int = 1, i8: Optional[str] = None, dtype=None):
+    """The prologue of every covariance front end: checks the pair and returns (x as [tokens, n_heads * feat] with contiguous rows,
+    its mdg_cov_problem with sigma's leading dimension feat and batch stride feat * feat).  i8: the int8 entry that asks
+    ("cov_accum_i8": sigma is one matrix; "cov_accum_i8_multi": per-head statistics need a [n_heads, feat, feat] sigma) -- x must
+    then be bf16 or fp16, and of `dtype` when the call already has an element type."""
+    _need_gpu(sigma, x)
+    single = i8 == "cov_accum_i8"
+    if sigma.dtype != torch.float64 or not sigma.is_contiguous() or (single and sigma.dim() != 2):
+        raise ValueError(f"sigma must be a contiguous {'2-D ' if single else ''}float64 tensor")
+    if i8 and (x.dtype not in _I8_DTYPES or x.dtype != (dtype or x.dtype)):
+        raise ValueError(f"{i8} takes bf16 or fp16 activations" + ("" if single else ", one element type per call"))
+    x2 = x.detach().reshape(-1, x.shape[-1])
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    shape, (n_tok, width) = sigma.shape, x2.shape
+    feat = shape[-1]
+    per_head_ok = not i8 or n_heads == 1 or (len(shape) == 3 and shape[0] == n_heads)
+    if shape[-2] != feat or width != n_heads * feat or not per_head_ok:
+        raise ValueError(f"shape mismatch: sigma {tuple(shape)}, x {tuple(x2.shape)}" if single else
+                         f"shape mismatch: x {tuple(x.shape)} vs sigma {tuple(shape)} with n_heads={n_heads}")
+    if len(shape) == 3 and shape[0] != n_heads:
+        raise ValueError("sigma batch dimension must equal n_heads")
+    return x2, _lib.CovProblem(x2.data_ptr(), n_tok, feat, n_heads, x2.stride(0), sigma.data_ptr(), feat, feat * feat)
+
+
 def cov_accum(sigma: torch.Tensor, x: torch.Tensor, n_heads: int = 1, relu: bool = False) -> None:
     """sigma (lower triangle) += X^T X in fp64.  x: [..., n_heads*feat] (bf16/f16/f32/f64, last dim
     contiguous, viewed as [tokens, n_heads*feat]); sigma: [feat, feat] or [n_heads, feat, feat] fp64.
     Only the lower triangle is valid until cov_finalize()."""
-    _need_gpu(sigma, x)
+    _cov_f64_call(*_cov_problem(sigma, x, n_heads), relu)
+
+
+def _cov_f64_call(x2: torch.Tensor, p: "_lib.CovProblem", relu: bool = False) -> None:
+    """mdg_cov_accum on one problem _cov_problem built (x2: the activation p.x points into)."""
     lib = _lib.load()
-    if sigma.dtype != torch.float64 or not sigma.is_contiguous():
-        raise ValueError("sigma must be a contiguous float64 tensor")
-    x2 = x.detach().reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
-    feat = sigma.shape[-1]
-    if sigma.shape[-2] != feat or x2.shape[1] != n_heads * feat:
-        raise ValueError(f"shape mismatch: x {tuple(x.shape)} vs sigma {tuple(sigma.shape)} with n_heads={n_heads}")
-    if sigma.dim() == 3 and sigma.shape[0] != n_heads:
-        raise ValueError("sigma batch dimension must equal n_heads")
-    n_tok = x2.shape[0]
+    n_tok, feat, n_heads = p.n_tokens, p.n_feat, p.batch
     nbytes = lib.mdg_cov_accum_ws_bytes(n_tok, feat, n_heads)
-    ws, wsp = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        check(lib.mdg_cov_accum(x2.data_ptr(), _DT[x2.dtype], n_tok, feat, n_heads, x2.stride(0), int(relu),
-                                sigma.data_ptr(), feat, feat * feat, wsp, nbytes, _stream(x)), "mdg_cov_accum")
+    ws, wsp = _ws(nbytes, x2.device)
+    with torch.cuda.device(x2.device):
+        check(lib.mdg_cov_accum(p.x, _DT[x2.dtype], n_tok, feat, n_heads, p.ld, int(relu), p.sigma, p.ld_sigma, p.sigma_batch_stride,
+                                wsp, nbytes, _stream(x2)), "mdg_cov_accum")
 
 
 def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: Optional[dict] = None,
@@ -127,46 +149,49 @@ def cov_accum_i8(sigma: torch.Tensor, x: torch.Tensor, events=None, mfma_stats: 
     that skipping issues -- costs a stream synchronisation, for measurement only (implies report).
     rows: let up to 64 outlier token rows leave the int8 path for the fp64 row kernel (MDG_I8_ROWS, include/modegpt_hip.h; None:
     ops.I8_ROWS); route_info then also holds "rows", the tokens that left, ascending."""
-    _need_gpu(sigma, x)
+    x2, p = _cov_problem(sigma, x, i8="cov_accum_i8")
+    nbytes = _lib.load().mdg_cov_accum_i8_ws_bytes(p.n_tokens, p.n_feat)
+    used, infos = _cov_i8_call("mdg_cov_accum_i8", (x2.data_ptr(), p.n_tokens, p.n_feat, p.ld, sigma.data_ptr(), sigma.stride(0)),
+                               (_lib.CovProblem * 1)(p), nbytes, x2, events, mfma_stats, report, route_info is not None, tolerance,
+                               relu, rows)
+    if route_info is not None:
+        route_info.update(infos[0])
+    return used
+
+
+def _cov_i8_call(entry: str, head: tuple, arr, nbytes: int, x2: torch.Tensor, events, mfma_stats: Optional[dict], report: bool,
+                 want_infos: bool, tolerance: Optional[float], relu: bool, rows: Optional[bool]):
+    """An int8 covariance call once its problems are built: lib.<entry>(*head, workspace, tolerance, flags, route, counters, events,
+    stream) on x2's device and stream, then the read-backs that were asked for.  arr: the call's mdg_cov_problem array (the
+    read-backs address a statistic through it), nbytes: its workspace.  Returns (the route -- None unless the call reports --, one
+    route dict per statistic -- None unless want_infos or mfma_stats) and does the mfma_stats / I8_STATS bookkeeping described at
+    cov_accum_i8."""
     lib = _lib.load()
-    if sigma.dtype != torch.float64 or not sigma.is_contiguous() or sigma.dim() != 2:
-        raise ValueError("sigma must be a contiguous 2-D float64 tensor")
-    if x.dtype not in _I8_DTYPES:
-        raise ValueError("cov_accum_i8 takes bf16 or fp16 activations")
-    x2 = x.detach().reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
-    n = sigma.shape[0]
-    if sigma.shape[1] != n or x2.shape[1] != n:
-        raise ValueError(f"shape mismatch: sigma {tuple(sigma.shape)}, x {tuple(x2.shape)}")
-    nbytes = lib.mdg_cov_accum_i8_ws_bytes(x2.shape[0], n)
-    ws, wsp = _ws(nbytes, x.device)
-    report = report or mfma_stats is not None or route_info is not None
+    count, dev = len(arr), x2.device
+    ws, wsp = _ws(nbytes, dev)
+    report = report or mfma_stats is not None or want_infos
     used = C.c_int(0)
     flags = _i8_flags(x2.dtype, relu, rows)
-    with torch.cuda.device(x.device):
-        check(lib.mdg_cov_accum_i8(x2.data_ptr(), x2.shape[0], n, x2.stride(0), sigma.data_ptr(), sigma.stride(0), wsp, nbytes,
-                                   i8_tolerance() if tolerance is None else float(tolerance), flags, C.byref(used) if report else None, _route_counters(x.device).data_ptr(),
-                                   None if events is None else events[0].cuda_event,
-                                   None if events is None else events[1].cuda_event, _stream(x)), "mdg_cov_accum_i8")
-        info = None
-        if route_info is not None or mfma_stats is not None:
-            arr = (_lib.CovProblem * 1)(_lib.CovProblem(x2.data_ptr(), x2.shape[0], n, 1, x2.stride(0), sigma.data_ptr(),
-                                                        sigma.stride(0), 0))
-            info = _read_route(lib, 1, arr, 0, wsp, _stream(x), flags)
+    infos = None
+    with torch.cuda.device(dev):
+        stream = _stream(x2)
+        check(getattr(lib, entry)(*head, wsp, nbytes, i8_tolerance() if tolerance is None else float(tolerance), flags,
+                                  C.byref(used) if report else None, _route_counters(dev).data_ptr(),
+                                  None if events is None else events[0].cuda_event,
+                                  None if events is None else events[1].cuda_event, stream), entry)
+        if want_infos or mfma_stats is not None:
+            infos = [_read_route(lib, count, arr, i, wsp, stream, flags) for i in range(count)]
         if mfma_stats is not None and used.value in (5, 6):
             done = C.c_ulonglong(0)
-            check(lib.mdg_cov_accum_i8_stats(wsp, x2.shape[0], n, C.byref(done), _stream(x)), "mdg_cov_accum_i8_stats")
-            ran = 3 if info["exact"] else used.value           # (the exact route: the three-plane product launch, all nine pairs)
+            check(lib.mdg_cov_accum_i8_stats(wsp, 0, 0, C.byref(done), stream), "mdg_cov_accum_i8_stats")    # (the whole launch's count)
+            ran = 3 if any(i_["exact"] for i_ in infos) else used.value      # (the exact route: the three-plane product launch, all nine pairs)
             mfma_stats["executed"] = mfma_stats.get("executed", 0) + done.value
-            mfma_stats["dense"] = mfma_stats.get("dense", 0) + i8_dense_mfma_count(x2.shape[0], n, ran)
+            mfma_stats["dense"] = mfma_stats.get("dense", 0) + sum(i8_dense_mfma_count(q.n_tokens, q.n_feat, ran, q.batch) for q in arr)
             mfma_stats["planes_run"] = ran
-        if route_info is not None:
-            route_info.update(info)
     if not report:
-        return None
-    I8_STATS[{5: "i8_5", 6: "i8_6"}.get(used.value, "fallback_f64")] += 1
-    return used.value
+        return None, infos
+    I8_STATS[{5: "i8_5", 6: "i8_6"}.get(used.value, "fallback_f64")] += count
+    return used.value, infos
 
 
 def _read_route(lib, count, arr, stat, wsp, stream, flags: int = 0) -> dict:
@@ -198,9 +223,6 @@ I8_EXACT = {"1": True, "always": True, "0": False, "never": False}.get(os.enviro
 I8_ROWS = os.environ.get("MODEGPT_I8_ROWS", "0").lower() in ("1", "on", "true")
 
 
-_I8_DTYPES = (torch.bfloat16, torch.float16)       # element types the int8 digit-plane kernels split (include/modegpt_hip.h, MDG_I8_F16)
-
-
 def _i8_flags(dtype=torch.bfloat16, relu: bool = False, rows: Optional[bool] = None) -> int:
     return ({True: _lib.MDG_I8_EXACT_ALWAYS, False: _lib.MDG_I8_NO_EXACT}.get(I8_EXACT, 0)
             | (_lib.MDG_I8_F16 if dtype == torch.float16 else 0) | (_lib.MDG_I8_RELU if relu else 0)
@@ -219,57 +241,25 @@ def cov_accum_i8_multi(items, events=None, mfma_stats: Optional[dict] = None, re
     report as in cov_accum_i8 (report: the planes of the statistics that stayed, 0 if none did; the executed / dense counts cover
     all statistics and assume none fell back).  route_info: optional list, extended by one dict per statistic (see cov_accum_i8).
     rows as in cov_accum_i8, for every statistic of the call."""
-    lib = _lib.load()
     items = list(items)
-    arr = (_lib.CovProblem * len(items))()
-    dense_shapes = []
-    keep = []
-    for i, (sigma, x, n_heads) in enumerate(items):
-        _need_gpu(sigma, x)
-        if sigma.dtype != torch.float64 or not sigma.is_contiguous():
-            raise ValueError("sigma must be a contiguous float64 tensor")
-        if x.dtype not in _I8_DTYPES or x.dtype != items[0][1].dtype:
-            raise ValueError("cov_accum_i8_multi takes bf16 or fp16 activations, one element type per call")
-        x2 = x.detach().reshape(-1, x.shape[-1])
-        if x2.stride(-1) != 1:
-            x2 = x2.contiguous()
-        feat = sigma.shape[-1]
-        if sigma.shape[-2] != feat or x2.shape[1] != n_heads * feat or (n_heads > 1 and (sigma.dim() != 3 or sigma.shape[0] != n_heads)):
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)} vs sigma {tuple(sigma.shape)} with n_heads={n_heads}")
-        keep.append(x2)
-        arr[i] = _lib.CovProblem(x2.data_ptr(), x2.shape[0], feat, n_heads, x2.stride(0), sigma.data_ptr(), feat, feat * feat)
-        dense_shapes.append((x2.shape[0], feat, n_heads))
-    dev = keep[0].device
-    nbytes = lib.mdg_cov_accum_i8_multi_ws_bytes(len(items), arr)
-    if nbytes == 0 and keep[0].shape[0] > 0:
+    built = [_cov_problem(sigma, x, n_heads, i8="cov_accum_i8_multi", dtype=items[0][1].dtype) for sigma, x, n_heads in items]
+    arr = (_lib.CovProblem * len(built))(*(p for _, p in built))
+    x2 = built[0][0]                 # (`built` keeps every row-contiguous copy alive until the launch is enqueued)
+    nbytes = _lib.load().mdg_cov_accum_i8_multi_ws_bytes(len(built), arr)
+    if nbytes == 0 and x2.shape[0] > 0:
         raise ValueError("these statistics cannot share an int8 launch (token counts differ, widths not multiples of 128, or "
                          "per-head statistics with head_dim != 128)")
-    ws, wsp = _ws(nbytes, dev)
-    report = report or mfma_stats is not None or route_info is not None
-    used = C.c_int(0)
-    flags = _i8_flags(keep[0].dtype, relu, rows)
-    with torch.cuda.device(dev):
-        check(lib.mdg_cov_accum_i8_multi(len(items), arr, wsp, nbytes, i8_tolerance() if tolerance is None else float(tolerance),
-                                         flags, C.byref(used) if report else None,
-                                         _route_counters(dev).data_ptr(), None if events is None else events[0].cuda_event,
-                                         None if events is None else events[1].cuda_event, _stream(keep[0])),
-              "mdg_cov_accum_i8_multi")
-        infos = None
-        if route_info is not None or mfma_stats is not None:
-            infos = [_read_route(lib, len(items), arr, i, wsp, _stream(keep[0]), flags) for i in range(len(items))]
-        if mfma_stats is not None and used.value in (5, 6):
-            done = C.c_ulonglong(0)
-            check(lib.mdg_cov_accum_i8_stats(wsp, 0, 0, C.byref(done), _stream(keep[0])), "mdg_cov_accum_i8_stats")
-            ran = 3 if any(i_["exact"] for i_ in infos) else used.value
-            mfma_stats["executed"] = mfma_stats.get("executed", 0) + done.value
-            mfma_stats["dense"] = mfma_stats.get("dense", 0) + sum(i8_dense_mfma_count(t, f, ran, h) for t, f, h in dense_shapes)
-            mfma_stats["planes_run"] = ran
-        if route_info is not None:
-            route_info.extend(infos)
-    if not report:
-        return None
-    I8_STATS[{5: "i8_5", 6: "i8_6"}.get(used.value, "fallback_f64")] += len(items)
-    return used.value
+    used, infos = _cov_i8_call("mdg_cov_accum_i8_multi", (len(built), arr), arr, nbytes, x2, events, mfma_stats, report,
+                               route_info is not None, tolerance, relu, rows)
+    if route_info is not None:
+        route_info.extend(infos)
+    return used
+
+
+def _device_index(device=None) -> int:
+    """The index of a CUDA device; None and a device without an index ("cuda") stand for the current device."""
+    index = None if device is None else torch.device(device).index
+    return torch.cuda.current_device() if index is None else index
 
 
 _ROUTE_COUNTERS = {}
@@ -279,8 +269,7 @@ def _route_counters(device) -> torch.Tensor:
     """Per-device int32[6] the kernels bump: [five planes, six planes, fp64 fallback of a whole statistic, columns handed to the
     fp64 column kernel, statistics on the exact route, token rows handed to the fp64 row kernel (MDG_I8_ROWS calls only)]
     (mdg_cov_accum_i8 route_counts)."""
-    dev = torch.device(device)
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = _device_index(device)
     if key not in _ROUTE_COUNTERS:
         _ROUTE_COUNTERS[key] = torch.zeros(6, dtype=torch.int32, device=torch.device("cuda", key))
     return _ROUTE_COUNTERS[key]
@@ -338,8 +327,7 @@ def i8_route_counts(device=None, reset: bool = False) -> dict:
     route (nine plane pairs + the fp64 remainder products) instead of the truncated product.  One small device -> host copy;
     calibration reads it once, at the end.  (The sixth counter, the rows of MDG_I8_ROWS calls, is read by i8_rows_left; reset
     clears it too.)"""
-    key = torch.cuda.current_device() if device is None else (torch.device(device).index or 0)
-    t = _route_counters(torch.device("cuda", key))
+    t = _route_counters(device)
     v = t.cpu().tolist()
     if reset:
         t.zero_()
@@ -349,8 +337,7 @@ def i8_route_counts(device=None, reset: bool = False) -> dict:
 def i8_rows_left(device=None, reset: bool = False) -> int:
     """Token rows the int8 covariance calls on `device` (default: the current one) handed to the fp64 row kernel so far (calls with
     the rows option, MDG_I8_ROWS; counted on the device).  reset clears this counter only."""
-    key = torch.cuda.current_device() if device is None else (torch.device(device).index or 0)
-    t = _route_counters(torch.device("cuda", key))
+    t = _route_counters(device)
     v = int(t[5].item())
     if reset:
         t[5] = 0
@@ -379,78 +366,102 @@ I8_MIN_FEATURES = 2048
 I8_STATS = {"i8_5": 0, "i8_6": 0, "fallback_f64": 0}      # routes of the REPORTING cov_accum_i8 calls (tests, bench); all calls: i8_route_counts()
 
 
+def takes_i8_planes(width: int, dtype=torch.bfloat16, n_heads: int = 1, relu: bool = False, min_features: Optional[int] = None) -> bool:
+    """Whether a statistic runs on the int8 digit planes when the mode is "i8" -- the one rule the launch plan, cov_accum_fc_relu
+    and the error bound the selection certificate is taken against (compress_mlp.covariance_error_eps) share.  width: the side of
+    one Gram matrix (the head_dim of a per-head statistic).  bf16 / fp16 only; per-head statistics (which run beside a plane, as
+    diagonal tiles of its launch) need head_dim 128; a single matrix a multiple of 128 of at least min_features (default
+    ops.I8_MIN_FEATURES) features, with ReLU on load (OPT's fc1 statistic) of at least FC_I8_MIN_FEATURES.
+    Below ~2048 features the 128 x 128 tiles do not fill the 256 CUs and the fp64 kernel is the faster one
+    (scripts/probes/i8_small_n.py: 1536 features 1.35 vs 1.23 ms, 2048 features 1.40 vs 2.14 ms)."""
+    if dtype not in _I8_DTYPES:
+        return False
+    if n_heads > 1:
+        return width == 128
+    least = FC_I8_MIN_FEATURES if relu else I8_MIN_FEATURES if min_features is None else min_features
+    return width % 128 == 0 and width >= least
+
+
+class CovStat(NamedTuple):
+    """What the launch plan looks at of one statistic (sigma, x, n_heads)."""
+    width: int          # sigma.shape[-1]
+    n_heads: int
+    dtype: torch.dtype  # of x
+    sigma_dim: int
+    tokens: int
+
+
+COV_JOIN = ("join",)       # the step of a plan at which the caller's stream waits for the side stream
+
+
+def plan_cov_launches(stats: Sequence[CovStat], mode: str, *, fuse: bool, overlap: bool, fusable_device: bool,
+                      min_features: int) -> list:
+    """The launches of cov_accum_multi for the statistics `stats` (largest first), in the order they are enqueued -- a pure
+    function of its arguments (the ops.* switches come in as arguments).  Steps, over indices into stats:
+    ("i8", [i]) one statistic in an int8 launch of its own, ("i8_multi", [i, ...]) two to four in one persistent int8 launch,
+    ("f64", [i, ...], on_side_stream) the fp64 kernel -- on the side stream, forked off the caller's stream at this step, or on
+    the caller's --, COV_JOIN the caller's stream waits for the side stream.  tests/test_cov_plan_host.py is the table of cases.
+    Fused (fuse, on a device the persistent launch's tile schedule is cut for): the largest plane (sigma_mlp) keeps a launch and a
+    route of its own -- on a real gated MLP it is the heavy-tailed one (six planes) while the others take five, and a shared launch
+    would drag them along (measured: -2 % on SiLU-gated data); the other planes and the per-head statistics of head_dim 128 share
+    ONE launch (one tile schedule, one k-split last round, no fp64 launch for the heads) when they are at most four of one
+    element type and all int8 statistics have one token count; what is left runs on fp64 beside all of that.  Otherwise every
+    plane has its launch and the heads join the rest, which runs beside the LAST -- smallest -- plane, whose few hundred tiles
+    leave CUs idle in their final round; the large planes keep the chip to themselves."""
+    if mode not in ("f64", "i8"):
+        raise ValueError(f"covariance mode must be 'f64' or 'i8', got {mode!r}")
+    planes, heads, rest = [], [], []
+    for i, s in enumerate(stats):
+        takes = mode == "i8" and s.sigma_dim == (2 if s.n_heads == 1 else 3) and \
+            takes_i8_planes(s.width, s.dtype, s.n_heads, min_features=min_features)
+        (rest if not takes else planes if s.n_heads == 1 else heads).append(i)
+    group = ((planes[1:] if len(planes) > 1 else planes) + heads) if planes else []
+    fused = bool(planes) and fuse and fusable_device and len(group) <= 4 and len({stats[i].dtype for i in group}) == 1 and \
+        len({stats[i].tokens for i in planes + heads}) == 1
+    if fused:
+        i8 = ([("i8", planes[:1])] if len(planes) > 1 else []) + [("i8_multi" if len(group) > 1 else "i8", group)]
+    else:
+        i8, rest = [("i8", [i]) for i in planes], heads + rest
+    if not rest:
+        return i8
+    if not (planes and overlap):
+        return i8 + [("f64", rest, False)]
+    before = 0 if fused else len(i8) - 1
+    return i8[:before] + [("f64", rest, True)] + i8[before:] + [COV_JOIN]
+
+
 def cov_accum_multi(items, mode: Optional[str] = None) -> None:
-    """One launch for several covariance problems of the same calibration batch.  items: sequence of
-    (sigma, x, n_heads), largest problem first.  Falls back to one cov_accum call per item when the fused kernel's
-    preconditions do not hold (mixed dtypes, feature count not a multiple of 128, unaligned rows).
-    mode (default ops.COV_MODE): "i8" sends every bf16 or fp16 statistic the int8 digit-plane kernels can take -- single matrices of
-    at least I8_MIN_FEATURES features (a multiple of 128) and, beside one of those, per-head statistics of head_dim 128 --
-    through them: the largest in a launch of its own (cov_accum_i8), the others together in one (cov_accum_i8_multi); only the
-    rest goes through the fp64 kernel."""
+    """The covariance problems of one calibration batch.  items: sequence of (sigma, x, n_heads), largest problem first.
+    mode (default ops.COV_MODE): "f64" sends all of them through the fp64 kernel; "i8" sends every bf16 or fp16 statistic the int8
+    digit-plane kernels can take (takes_i8_planes: single matrices of at least I8_MIN_FEATURES features, a multiple of 128, and,
+    beside one of those, per-head statistics of head_dim 128) through them and only the rest through the fp64 kernel.  Which
+    launches that makes, in which order and on which stream: plan_cov_launches.  The fp64 part is one launch, or one cov_accum call
+    per item when the fused kernel's preconditions do not hold (mixed dtypes, feature count not a multiple of 128, unaligned rows)."""
     items = [(s_, x_, h_) for (s_, x_, h_) in items if x_.numel() > 0]
     if not items:
         return
     mode = mode or COV_MODE
-    if mode not in ("f64", "i8"):
-        raise ValueError(f"covariance mode must be 'f64' or 'i8', got {mode!r}")
-    if mode == "i8":
-        rest, planes, heads = [], [], []
-        for sigma, x, n_heads in items:
-            # below ~2048 features the 128 x 128 tiles do not fill the 256 CUs and the fp64 kernel is the faster one
-            # (scripts/probes/i8_small_n.py: 1536 features 1.35 vs 1.23 ms, 2048 features 1.40 vs 2.14 ms)
-            if n_heads == 1 and x.dtype in _I8_DTYPES and sigma.dim() == 2 and sigma.shape[-1] % 128 == 0 \
-                    and sigma.shape[-1] >= I8_MIN_FEATURES:
-                planes.append((sigma, x, 1))
-            elif n_heads > 1 and x.dtype in _I8_DTYPES and sigma.dim() == 3 and sigma.shape[-1] == 128:
-                heads.append((sigma, x, n_heads))      # per-head statistics of head_dim 128: diagonal tiles of the same launch
-            else:
-                rest.append((sigma, x, n_heads))
-        tokens = {x.reshape(-1, x.shape[-1]).shape[0] for _, x, _ in planes + heads}
-        group = ((planes[1:] if len(planes) > 1 else planes) + heads) if planes else []
-        one_type = len({x.dtype for _, x, _ in group}) == 1          # (a fused launch has one element type)
-        if planes and I8_FUSE and len(tokens) == 1 and one_type and len(group) <= 4 and _fusable_device(planes[0][1].device):
-            # The largest statistic (sigma_mlp) keeps a launch and a route of its own -- on a real gated MLP it is the heavy-tailed
-            # one (six planes) while the others take five, and a shared launch would drag them along (measured: -2 % on SiLU-gated
-            # data).  Everything else -- sigma_x and the per-head sigma_q / sigma_k tiles -- shares ONE persistent int8 launch: one
-            # tile schedule, one k-split last round, no fp64 launch for the heads.
-            side_rest = rest and COV_OVERLAP_SMALL   # (per-head statistics of another head_dim: fp64 kernel, on a side stream)
-            if side_rest:
-                dev = planes[0][1].device
-                main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    _cov_accum_fused(rest)
-            if len(planes) > 1:
-                cov_accum_i8(planes[0][0], planes[0][1], report=False)
-            if len(group) > 1:
-                cov_accum_i8_multi(group, report=False)
-            else:
-                cov_accum_i8(group[0][0], group[0][1], report=False)
-            if side_rest:
-                main.wait_stream(side)
-            elif rest:
-                _cov_accum_fused(rest)
-            return
-        rest = heads + rest
-        if planes and rest and COV_OVERLAP_SMALL:
-            # the small fp64 problems (per-head sigma_q / sigma_k) run on a side stream next to the LAST -- smallest -- int8
-            # problem, whose few hundred tiles leave CUs idle in their final round; the large problem keeps the chip to itself
-            for sigma, x, _ in planes[:-1]:
-                cov_accum_i8(sigma, x, report=False)
-            dev = planes[-1][1].device
+    dev = items[0][1].device
+    stats = [CovStat(s_.shape[-1], h_, x_.dtype, s_.dim(), x_.numel() // x_.shape[-1]) for s_, x_, h_ in items]
+    steps = plan_cov_launches(stats, mode, fuse=I8_FUSE, overlap=COV_OVERLAP_SMALL, min_features=I8_MIN_FEATURES,
+                              fusable_device=mode == "i8" and I8_FUSE and _fusable_device(dev))
+    main = side = None
+    for step in steps:
+        if step == COV_JOIN:
+            main.wait_stream(side)       # later work on the caller's stream (and any reuse of these buffers) is ordered after both
+            continue
+        chosen = [items[i] for i in step[1]]
+        if step[0] == "i8":
+            cov_accum_i8(chosen[0][0], chosen[0][1], report=False)
+        elif step[0] == "i8_multi":
+            cov_accum_i8_multi(chosen, report=False)
+        elif step[2]:
             main, side = torch.cuda.current_stream(dev), _side_stream(dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                _cov_accum_fused(rest)
-            cov_accum_i8(planes[-1][0], planes[-1][1], report=False)
-            main.wait_stream(side)       # later work on the caller's stream (and any reuse of these buffers) is ordered after both
-            return
-        for sigma, x, _ in planes:
-            cov_accum_i8(sigma, x, report=False)
-        items = rest
-        if not items:
-            return
-    _cov_accum_fused(items)
+                _cov_accum_fused(chosen)
+        else:
+            _cov_accum_fused(chosen)
 
 
 # Width from which OPT's fc1 statistic (ReLU on load) takes the int8 digit planes: where the exact route is offered by default
@@ -462,8 +473,7 @@ def cov_accum_fc_relu(sigma: torch.Tensor, x: torch.Tensor, mode: Optional[str] 
     """sigma += ReLU(x)^T ReLU(x), the ReLU fused into the kernels' loads (OPT's fc1 statistic): bf16 / fp16 activations of at
     least FC_I8_MIN_FEATURES features (a multiple of 128) through the int8 digit planes (cov_accum_i8(relu=True)) unless mode is
     "f64"; everything else through the fp64 kernel (cov_accum(relu=True))."""
-    n = x.shape[-1]
-    if (mode or COV_MODE) == "i8" and x.dtype in _I8_DTYPES and n % 128 == 0 and n >= FC_I8_MIN_FEATURES and x.numel() > 0:
+    if (mode or COV_MODE) == "i8" and takes_i8_planes(x.shape[-1], x.dtype, relu=True) and x.numel() > 0:
         cov_accum_i8(sigma, x, report=False, relu=True)
     else:
         cov_accum(sigma, x, relu=True)
@@ -485,7 +495,7 @@ NYSTROM_OVERLAP = os.environ.get("MODEGPT_NYSTROM_OVERLAP", "1") != "0"   # cros
 def _side_stream(device, purpose: str = "cov", beside=None) -> "torch.cuda.Stream":
     """One helper stream per (device, purpose[, the stream it runs beside]): two layers' chains on two streams of the caller's
     get a helper each and stay independent of one another."""
-    dev = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
+    dev = _device_index(device)
     key = (dev, purpose, None if beside is None else beside.cuda_stream)
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
@@ -493,38 +503,20 @@ def _side_stream(device, purpose: str = "cov", beside=None) -> "torch.cuda.Strea
 
 
 def _cov_accum_fused(items) -> None:
-    """The fp64 part of cov_accum_multi: one fused launch when the preconditions hold, else one cov_accum per item."""
-    lib = _lib.load()
-    prepared = []
-    dtype = items[0][1].dtype
-    fusable = len(items) <= 4
-    for sigma, x, n_heads in items:
-        _need_gpu(sigma, x)
-        if sigma.dtype != torch.float64 or not sigma.is_contiguous():
-            raise ValueError("sigma must be a contiguous float64 tensor")
-        x2 = x.detach().reshape(-1, x.shape[-1])
-        if x2.stride(-1) != 1:
-            x2 = x2.contiguous()
-        feat = sigma.shape[-1]
-        if x2.shape[1] != n_heads * feat:
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)} vs sigma {tuple(sigma.shape)} with n_heads={n_heads}")
-        esz = x2.element_size()
-        fusable = fusable and x2.dtype == dtype and feat % 128 == 0 and x2.data_ptr() % 16 == 0 and \
-            (x2.stride(0) * esz) % 16 == 0 and x2.device == items[0][1].device
-        prepared.append((sigma, x2, n_heads, feat))
-    if not fusable:
-        for sigma, x2, n_heads, _ in prepared:
-            cov_accum(sigma, x2, n_heads=n_heads)
+    """The fp64 part of cov_accum_multi: one fused launch when the preconditions hold, else one mdg_cov_accum call per item."""
+    built = [_cov_problem(sigma, x, n_heads) for sigma, x, n_heads in items]
+    x0 = built[0][0]
+    if not (len(built) <= 4 and all(x2.dtype == x0.dtype and p.n_feat % 128 == 0 and x2.data_ptr() % 16 == 0 and
+                                    (x2.stride(0) * x2.element_size()) % 16 == 0 and x2.device == x0.device for x2, p in built)):
+        for x2, p in built:
+            _cov_f64_call(x2, p)
         return
-    arr = (_lib.CovProblem * len(prepared))()
-    for i, (sigma, x2, n_heads, feat) in enumerate(prepared):
-        arr[i] = _lib.CovProblem(x2.data_ptr(), x2.shape[0], feat, n_heads, x2.stride(0), sigma.data_ptr(), feat, feat * feat)
-    dev = prepared[0][1].device
-    nbytes = lib.mdg_cov_accum_multi_ws_bytes(len(prepared), arr, _DT[dtype])
-    ws, wsp = _ws(nbytes, dev)
-    with torch.cuda.device(dev):
-        check(lib.mdg_cov_accum_multi(len(prepared), arr, _DT[dtype], wsp, nbytes, _stream(prepared[0][1])),
-              "mdg_cov_accum_multi")
+    lib = _lib.load()
+    arr = (_lib.CovProblem * len(built))(*(p for _, p in built))
+    nbytes = lib.mdg_cov_accum_multi_ws_bytes(len(built), arr, _DT[x0.dtype])
+    ws, wsp = _ws(nbytes, x0.device)
+    with torch.cuda.device(x0.device):
+        check(lib.mdg_cov_accum_multi(len(built), arr, _DT[x0.dtype], wsp, nbytes, _stream(x0)), "mdg_cov_accum_multi")
 
 
 def cov_finalize(sigma: torch.Tensor, scale: float) -> None:
