@@ -47,7 +47,7 @@ enum mdg_status {
   MDG_ERR_BAD_ARG = -1,     /* shape / pointer / alignment / workspace-size problem */
   MDG_ERR_HIP = -2,         /* a HIP runtime call failed */
   MDG_ERR_NOT_PD = -3,      /* Cholesky met a non-positive pivot (torch.linalg.cholesky would raise) */
-  MDG_ERR_NO_CONVERGE = -4, /* Jacobi eigensolver hit its sweep limit */
+  MDG_ERR_NO_CONVERGE = -4, /* Jacobi eigensolver hit its sweep limit, or was given a NaN / Inf (the message says which) */
   MDG_ERR_NO_DEVICE = -5    /* no gfx950 device visible */
 };
 
@@ -313,7 +313,19 @@ int mdg_chol_inverse_diag(const double* L, int64_t n, int64_t ldl, const double*
 /* Batched symmetric eigensolver, n <= 128 and even: cyclic Jacobi in LDS, one workgroup per matrix.
  * A [batch][n][n] (symmetric, destroyed), evals [batch][n] DESCENDING, evecs [batch][n][n] with eigenvector j
  * in COLUMN j.  SYNCHRONISES to read the convergence flag.  (The reference reaches torch.linalg.eigh / svd
- * through sqrt_M, compression_utils.py:21, and compress_vo.py:130,187,194.) */
+ * through sqrt_M, compression_utils.py:21, and compress_vo.py:130,187,194.)
+ * Only the lower triangle of a matrix is read; what stands above the diagonal, NaN included, has no effect.
+ * Order: descending, ties by index (-0.0 == 0.0 is a tie), a NaN eigenvalue before everything else -- a total order for every bit
+ * pattern, so every element of evals and evecs is written whatever the input.
+ * Non-finite input: a matrix with a NaN or Inf in its lower triangle is not iterated.  Its evals and evecs are all NaN, the other
+ * matrices of the batch are solved as usual, and the call returns MDG_ERR_NO_CONVERGE with a message that names the non-finite
+ * input (status detail 2; 1 is the limit of 40 sweeps; the larger one of a batch is reported).  In deferred-status mode the same
+ * code and message come out of mdg_deferred_status_decode, and every later kernel of the chain stays within its buffers.
+ * Scale: a pair is rotated while |a_pq| > 2^-52 sqrt|a_pp| sqrt|a_qq|, the two roots taken separately, so the test neither
+ * overflows nor underflows and the results of A and 2^k A agree bit for bit (evals scaled by 2^k) as long as no entry of 2^k A
+ * overflows or becomes subnormal: roughly ||A||_2 within [2^-900, 2^1000].  Because the test is relative to the pair's own diagonal,
+ * a graded positive definite matrix D B D (D diagonal, B well conditioned) gets every eigenvalue, and the eigenvectors of its
+ * small eigenvalues, to a relative accuracy of order cond(B) n 2^-52, independent of cond(D). */
 int mdg_syevj_batched(double* A, int64_t n, int64_t batch, double* evals, double* evecs, void* stream);
 
 /* ------------------------------------------------------------------ MLP: ridge-leverage + Nystrom
@@ -402,7 +414,11 @@ int mdg_qk_select_margin(const double* cov_q, const double* cov_k, int n_heads, 
  * W_o [d, n_heads*hd], both of dtype w_dtype (MDG_BF16 or MDG_F64).  n_kv == n_heads selects the two-SVD MHA variant (compress_vo.py:162-223), else the
  * grouped one (:112-159).  Works on the Gram matrix W_v (C + rho I) W_v^T (DESIGN.md "Identities"), so the
  * d x d eigensolve and inverse of compress_vo.py:43-45 never happen.  v_f64 / o_f64 optional fp64 copies of
- * the factors.  ws: mdg_vo_compress_ws_bytes.  SYNCHRONISES. */
+ * the factors.  ws: mdg_vo_compress_ws_bytes.  SYNCHRONISES.
+ * A NaN or Inf in cov_x (a poisoned statistic: one bad column is a NaN row and column) or in the weights reaches the Gram
+ * matrices, whose eigensolves report it: MDG_ERR_NO_CONVERGE with the non-finite-input message of mdg_syevj_batched, at once or,
+ * in deferred-status mode, from mdg_deferred_status_decode; the outputs are then to be discarded (all accesses stay in bounds).
+ * Scale: as mdg_syevj_batched, on W_v (C + rho I) W_v^T. */
 size_t mdg_vo_compress_ws_bytes(int64_t d, int n_heads, int n_kv, int hd);
 int mdg_vo_compress(const double* cov_x, int64_t d, int64_t ldc, const void* Wv, int64_t ld_wv, const void* Wo,
                     int64_t ld_wo, int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, void* v_out,
@@ -430,7 +446,10 @@ int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_
 /* ------------------------------------------------------------------ sqrt_M (compression_utils.py:15-55)
  * root = V diag(sqrt(max(lambda + ridge*scale, 0))) V^T, inv_root (optional) with the 1e-12 clamp;
  * scale = max eigenvalue if scaled else 1.  n <= 128 and even, batched.  evals_out optional [batch][n]
- * (pre-ridge, descending) for the caller's diagnostics.  SYNCHRONISES. */
+ * (pre-ridge, descending) for the caller's diagnostics.  SYNCHRONISES.
+ * Only the lower triangle of M is read.  A matrix with a NaN or Inf there: MDG_ERR_NO_CONVERGE with the non-finite-input message
+ * of mdg_syevj_batched (deferred-status mode: from mdg_deferred_status_decode), its root, inv_root and evals_out all NaN, the
+ * batch's other matrices computed as usual.  Scale: as mdg_syevj_batched; `ridge` and the 1e-12 clamp are absolute unless scaled. */
 int mdg_sqrt_psd_small(const double* M, int64_t n, int64_t batch, double ridge, int scaled, double* root,
                        double* inv_root, double* evals_out, void* ws, size_t ws_bytes, void* stream);
 size_t mdg_sqrt_psd_small_ws_bytes(int64_t n, int64_t batch);

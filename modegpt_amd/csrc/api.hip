@@ -31,6 +31,10 @@ static int status_to_error(int kind, int detail, const char* what) {
     return MDG_ERR_NOT_PD;
   }
   if (kind == STATUS_NO_CONVERGE) {
+    if (detail == SYEVJ_NONFINITE) {
+      set_error("%s: Jacobi eigensolver: the input holds non-finite values (NaN or Inf)", what ? what : "eigensolver");
+      return MDG_ERR_NO_CONVERGE;
+    }
     set_error("%s: Jacobi eigensolver did not converge in 40 sweeps", what ? what : "eigensolver");
     return MDG_ERR_NO_CONVERGE;
   }

@@ -31,6 +31,8 @@ void set_error(const char* fmt, ...);
 // nonzero.  Between mdg_deferred_status_begin / _end the word is merged into the caller's device status instead and MDG_OK is
 // returned at once: the chain of a whole layer then enqueues without a single host round trip (api.hip).
 enum { STATUS_NOT_PD = 1, STATUS_NO_CONVERGE = 2 };
+// detail of STATUS_NO_CONVERGE (the Jacobi flag): the sweep limit, or a NaN / Inf in the input; the larger one of a batch is kept
+enum { SYEVJ_SWEEP_LIMIT = 1, SYEVJ_NONFINITE = 2 };
 int finish_flag(int* dflag, hipStream_t st, int kind, const char* what);
 
 // mdg_cov_accum with a device-side gate (cov.hip): the launches are enqueued unconditionally, and every workgroup exits at once

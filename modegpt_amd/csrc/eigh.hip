@@ -14,6 +14,9 @@ constexpr int JP = JN + 1;   // LDS pitch
 constexpr int JT = 1024;     // threads (the passes are latency-bound per thread: 512 -> 1024 threads, 8.2 -> 7.0 ms for 8 x 128 x 128)
 
 // A [batch][n][n] (lower triangle read, buffer then reused as V^T scratch), evals desc, evecs columns.
+// info: 0, or the larger SYEVJ_* detail any matrix of the batch raised.  A matrix with a NaN / Inf in its lower triangle is not
+// swept: SYEVJ_NONFINITE, its evals and evecs all NaN.  The rotation test |a_pq| > eps sqrt|a_pp| sqrt|a_qq| is relative to the
+// pair's own diagonal, which is what gives graded positive definite matrices every eigenvalue to high relative accuracy.
 // sorted != 0: eigenvalues descending (ties by index); sorted == 0: eigenvalue j stays in position j, so for a
 // nearly diagonal input the eigenvector matrix is a small rotation -- what block Jacobi needs (a sorting solver acts
 // as a permutation there and shuffles off-diagonal mass around the schedule instead of annihilating it).
@@ -27,7 +30,7 @@ __global__ __launch_bounds__(JT) void syevj_kernel(double* Ag, int n_rt, double*
   __shared__ double a[JN * JP];
   __shared__ double cs_c[JN / 2], cs_s[JN / 2];
   __shared__ int pr[JN / 2], qr[JN / 2];
-  __shared__ int rotated;
+  __shared__ int rotated, nonfinite;
   __shared__ int order[JN];
   const int tid = threadIdx.x;
   const int m = n / 2;
@@ -35,11 +38,26 @@ __global__ __launch_bounds__(JT) void syevj_kernel(double* Ag, int n_rt, double*
   double* ev = evals + (int64_t)blockIdx.x * n;
   double* ec = evecs + (int64_t)blockIdx.x * n * n;
 
+  if (tid == 0) nonfinite = 0;
+  __syncthreads();
+  bool bad = false;  // a NaN or Inf among what is read (the lower triangle)
   for (int e = tid; e < n * n; e += JT) {
     int i = e / n, j = e % n;
-    a[i * JP + j] = (j <= i) ? Vt[i * n + j] : Vt[j * n + i];
+    const double v = (j <= i) ? Vt[i * n + j] : Vt[j * n + i];
+    a[i * JP + j] = v;
+    bad |= !(fabs(v) <= 1.7976931348623157e308);
   }
+  // Non-finite input: no pair would pass the rotation test (every comparison with NaN is false) and the sweeps would end as
+  // "converged" on garbage.  The matrix is reported instead (detail 2), its outputs are NaN, the batch's others are solved.
+  if (bad) nonfinite = 1;
   __syncthreads();
+  if (nonfinite) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int e = tid; e < n * n; e += JT) ec[e] = nan;
+    if (tid < n) ev[tid] = nan;
+    if (tid == 0) atomicMax(info, SYEVJ_NONFINITE);
+    return;
+  }
   for (int e = tid; e < n * n; e += JT) Vt[e] = (e / n == e % n) ? 1. : 0.;
   __syncthreads();
 
@@ -66,7 +84,7 @@ __global__ __launch_bounds__(JT) void syevj_kernel(double* Ag, int n_rt, double*
         }
         const double app = a[p * JP + p], aqq = a[q * JP + q], apq = a[p * JP + q];
         double c = 1., s = 0.;
-        mine_rot = fabs(apq) > eps * sqrt(fabs(app * aqq));
+        mine_rot = fabs(apq) > eps * sqrt(fabs(app)) * sqrt(fabs(aqq));  // (the product app * aqq would overflow / underflow)
         if (mine_rot) {
           const double tau = (aqq - app) / (2. * apq);
           const double t = (tau >= 0. ? 1. : -1.) / (fabs(tau) + sqrt(1. + tau * tau));
@@ -115,16 +133,22 @@ __global__ __launch_bounds__(JT) void syevj_kernel(double* Ag, int n_rt, double*
     a[p * JP + q] = 0.;
     a[q * JP + p] = 0.;
   }
-  if (tid == 0 && !converged) atomicExch(info, 1);
+  if (tid == 0 && !converged) atomicMax(info, SYEVJ_SWEEP_LIMIT);
   __syncthreads();
-  // descending order, ties by index
+  // descending order as in qk_select_kernel: NaN first, ties (-0. == 0. is one) by index.  A total order for every bit pattern
+  // (the sweeps can still overflow a finite input), so order[] is a permutation and every output element is written.
   if (tid < n) {
     const double mine = a[tid * JP + tid];
+    const bool mn = mine != mine;
     int pos = sorted ? 0 : tid;
     if (sorted)
       for (int k = 0; k < n; k++) {
         const double o = a[k * JP + k];
-        pos += (o > mine || (o == mine && k < tid)) ? 1 : 0;
+        const bool on = o != o;
+        bool ahead;
+        if (on || mn) ahead = on && (!mn || k < tid);
+        else ahead = o > mine || (o == mine && k < tid);
+        pos += ahead ? 1 : 0;
       }
     order[pos] = tid;
     ev[pos] = mine;
