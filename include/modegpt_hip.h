@@ -40,7 +40,8 @@ extern "C" {
                                 mdg_ridge_scores takes `sens`, mdg_select_margin added (certificate of the MLP rank selection);
                                 the exact route of the int8 covariance (`flags`, route_counts[4], mdg_cov_accum_i8_route's `exact`);
                                 added under 9: mdg_qk_select_margin, mdg_vo_spectrum; MDG_I8_ROWS / MDG_I8_MAX_ROWS (a flag bit of the int8
-                                covariance, route_counts[5] with that bit), mdg_cov_accum_i8_rows */
+                                covariance, route_counts[5] with that bit), mdg_cov_accum_i8_rows;
+                                added under 9: mdg_nystrom_rank_curve_ws_bytes, mdg_nystrom_rank_curve (the Nystrom refit's error at every rank) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -375,6 +376,32 @@ int mdg_nystrom_down_overlapped(const double* C, int64_t n, int64_t ldc, const i
                                 int64_t d, int64_t ld_wd, int w_dtype, double eps, void* down_out, int64_t ld_out,
                                 double* down_f64, void* ws, size_t ws_bytes, void* side_stream, void* ev_fork, void* ev_join,
                                 void* stream);
+/* What that refit costs, at EVERY rank, from one factorisation (added under ABI 9; not in the reference, which reports nothing
+ * about the objective compress_mlp.py:52-62 minimises).  With M = C + eps I, `order` = the columns in ascending ridge-score order
+ * (ties: lower index first, NaN last -- torch.argsort(scores, stable=True) -- so that order[:r], sorted, is what
+ * mdg_select_smallest_sorted(scores, r) returns, for every r), M[order, order] = L L^T, Z = W_d[:, order] L and c_j = ||Z[:, j]||^2:
+ *     curve[r] = sum_{j >= r} c_j = tr(W_d (M - M[:, S] M_SS^-1 M[S, :]) W_d^T),   S = order[:r],   r = 0 .. n
+ * -- the Nystrom residual energy of keeping the columns S, summed over the d output channels: the minimum over ALL refits of
+ * sum_k u_k^T M u_k, u_k = row k of W_d minus row k of the refit at the columns S.  curve[0] = tr(W_d M W_d^T), curve[n] = +0.0
+ * exactly, and the curve is non-increasing entry by entry (a suffix sum of squares, accumulated from the tail).  Against the
+ * refit D = down_f64 of mdg_nystrom_down (which solves with C[S, :], not M[S, :]), with E_D its output error under C and U the
+ * residual weights:  E_D + eps ||U||_F^2 - eps ||W_d[:, S]||_F^2 <= curve[r] <= E_D + eps ||U||_F^2  ("The error-versus-rank curve").
+ * C [n, n] fp64 (ldc; only the lower triangle is read, C is not modified), n <= 2^31 - 1 (beyond: MDG_ERR_BAD_ARG); order: DEVICE int64 [n], a permutation of 0 .. n-1 --
+ * out-of-range entries are clamped (memory safety only, as mdg_rope_gather clamps its mask) and an index that occurs twice makes
+ * the matrix singular: MDG_ERR_NOT_PD, reported at the first position of a repeated index.  W_d [d, n] (ld_wd) of dtype w_dtype,
+ * MDG_BF16 or MDG_F64 as in mdg_nystrom_down; a NaN in W_d gives NaN in curve[0 .. p] (p: at least the NaN column's position in
+ * `order`) and MDG_OK.  eps is added in fp64 with one rounding per diagonal entry, as mdg_nystrom_down adds it.  curve: [n + 1].
+ * No atomics, every sum in a fixed order: bit-identical from run to run.
+ * ws: mdg_nystrom_rank_curve_ws_bytes(n, d) = 8 n n' + 8 (2 d n') bytes, n' = n rounded up to 16 (the gathered matrix / its
+ * factor, W_d[:, order] and Z in fp64) + the inverted diagonal blocks of the factorisation (mdg_potrf_inv_diag_elems(n) doubles:
+ * 128 KB per 128 columns) + 20 n bytes: 2.6 GB at n = 14336, d = 4096 -- per call in flight.
+ * Status: follows the deferred-status convention.  Between mdg_deferred_status_begin / _end the call only enqueues and merges the
+ * factorisation's pivot word into the device status; outside, it SYNCHRONISES once, behind the factorisation, to return
+ * MDG_ERR_NOT_PD (curve is then not written), and enqueues the rest. */
+size_t mdg_nystrom_rank_curve_ws_bytes(int64_t n, int64_t d);
+int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, const int64_t* order, const void* Wd, int64_t d,
+                           int64_t ld_wd, int w_dtype, double eps, double* curve /* [n + 1] */, void* ws,
+                           size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ QK: CR selection
  * mask [n_kv, rank] (int64, score-descending, NOT sorted: compress_qk.py:366-367,418-419,464),

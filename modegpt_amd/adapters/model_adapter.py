@@ -9,6 +9,7 @@ once at the end (mdg_cov_finalize).
 from __future__ import annotations
 
 import logging
+import math
 import os
 from abc import ABC, abstractmethod
 from typing import Any, List, Optional, Tuple
@@ -106,6 +107,44 @@ class ModelAdapter(ABC):
                 self.metrics = {}
             store = self.metrics.setdefault("mlp_selection", {})
             store.update({str(k): v for k, v in report.items()})
+        return report
+
+    # ---- what the MLP compression costs, at every rank (not upstream; MODEGPT_RANK_CURVE=1) ----
+    def rank_curve(self, layer_idx: int, curve, rank: int) -> None:
+        """compress_nystrom hands over ops.nystrom_rank_curve's n + 1 numbers (still on the device) for layer `layer_idx`, which it
+        compressed to `rank`."""
+        self.__dict__.setdefault("_rank_curves", {})[int(layer_idx)] = (curve, int(rank))
+
+    def report_rank_curves(self, log=None) -> dict:
+        """Reads the recorded curves (8 (n + 1) bytes per layer; call it where the host waits for the chains anyway), keeps them as
+        CPU tensors in self.rank_curves[layer] and writes metrics["mlp_rank_curve"][str(layer)] = ops.decode_rank_curve(...): the
+        relative output error of the layer's MLP at the rank it got, at the keep ratios 0.05 .. 1.00, and the smallest rank that
+        reaches 1e-1 / 1e-2 / 1e-3 -- under sigma_mlp + eps I and for the fp64 refit ("The error-versus-rank
+        curve", says what that is not).  Logs one line per layer and the energy-weighted mean over the layers read by this call."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_rank_curves", {})
+        report = {}
+        for layer in sorted(pending):
+            curve, rank = pending[layer]
+            host = curve.detach().cpu()
+            self.__dict__.setdefault("rank_curves", {})[layer] = host
+            m = report[layer] = ops.decode_rank_curve(host.tolist(), rank)
+            if m["rel_error"] is None:
+                log.warning(f"[MLP] Layer {layer}: rank curve has no usable energy (curve[0] = {m['energy']!r})")
+                continue
+            log.info(f"[MLP] Layer {layer}: rank {rank} of {m['n']}: relative output error {m['rel_error']:.3e}; "
+                     f"rank for 1e-2: {m['rank_for_rel_error']['0.01']}")
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            # (a NaN / Inf energy would be written as the non-standard NaN / Infinity by json.dump: None there, as the relative fields)
+            finite = lambda m: m if math.isfinite(m["energy"]) else {**m, "energy": None}      # noqa: E731
+            self.metrics.setdefault("mlp_rank_curve", {}).update({str(k): finite(v) for k, v in report.items()})
+            usable = [m for m in report.values() if m["rel_error"] is not None]
+            energy = sum(m["energy"] for m in usable)
+            if usable and energy > 0:
+                mean = sum(m["energy"] * m["rel_error"] for m in usable) / energy
+                log.info(f"[MLP] rank curves of {len(usable)} layers: energy-weighted mean relative output error {mean:.3e}")
         return report
 
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----

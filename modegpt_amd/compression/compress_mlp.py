@@ -63,12 +63,14 @@ def covariance_error_eps(adapter, n_features: int) -> float:
 
 @torch.no_grad()
 def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_idx: int, ridge_lambda: float,
-                     margin_eps: float = None, margin_out: list = None):
+                     margin_eps: float = None, margin_out: list = None, curve_out: list = None):
     """compress_mlp.py:28-64.  Returns (W_u'^T [d, r], W_d' [r, d], W_g'^T [d, r] or None, rank), bf16 --
     the same orientation the reference returns (transposed views of the saved layout).
     margin_eps / margin_out (not upstream): with both given, the certificate of the rank selection against an entry-wise relative
     error margin_eps of C (ops.select_margin: 8 numbers on the device) is appended to margin_out -- two more passes over the
-    triangular inverse the scores come from, nothing else changes."""
+    triangular inverse the scores come from, nothing else changes.
+    curve_out (not upstream): a list, with MODEGPT_RANK_CURVE=1 -- the layer's error-versus-rank curve (ops.nystrom_rank_curve, n + 1
+    numbers on the device) is appended to it, enqueued behind the refit; the outputs are the same bits with or without it."""
     C = C.to(dtype=dtype_p, device=local_device())
     rank = int(C.shape[0] * keep_ratio)
     if margin_out is not None and margin_eps is not None:
@@ -86,6 +88,11 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         gate = ops.gather_rows(W_g, idx)                              # W_g[topk, :]               (:50)
     W_d = comps.down_proj.weight.detach().to(device=local_device())              # bf16 as is; fp16/fp32 widen exactly to fp64
     down = ops.nystrom_down(C, idx, W_d, eps=1e-6)                    # [d, r] bf16                (:52-62)
+    if curve_out is not None and ops.rank_curve_enabled():
+        # the selection is a prefix of the ridge-score order (ties: lower index first, NaN last, as select_smallest_sorted ranks them),
+        # so the factor of sigma_mlp in that order holds the refit's residual energy at every rank, this layer's included
+        order = torch.argsort(scores, stable=True)
+        curve_out.append(ops.nystrom_rank_curve(C, order, W_d, eps=1e-6))
     return up.T, down.T, (None if gate is None else gate.T), rank
 
 
@@ -98,14 +105,19 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
         # trip; the not-positive-definite status of both factorisations is read once (adapter.chain_status)
         comps = adapter.get_mlp_components(layer_idx)
         record = getattr(adapter, "selection_margin", None)          # (a duck-typed adapter without it: no certificate)
+        record_curve = getattr(adapter, "rank_curve", None)          # (... and without this: no error-versus-rank curve)
+        curve = [] if callable(record_curve) else None               # (filled only with MODEGPT_RANK_CURVE=1)
         if record is None:
-            return compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                    ridge_lambda=adapter.config.nystrom_ridge)
-        eps, margin = covariance_error_eps(adapter, cov[layer_idx].shape[0]), []
-        result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                  ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin)
-        # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
-        record(layer_idx, margin[0], eps)
+            result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
+                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve)
+        else:
+            eps, margin = covariance_error_eps(adapter, cov[layer_idx].shape[0]), []
+            result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
+                                      ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve)
+            # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
+            record(layer_idx, margin[0], eps)
+        if curve:
+            record_curve(layer_idx, curve[0], result[3])             # ... and so does the curve (report_rank_curves)
         return result
 
     def retire(layer_idx, result):

@@ -798,6 +798,73 @@ def nystrom_down(Cm: torch.Tensor, idx: torch.Tensor, W_down: torch.Tensor, eps:
     return (out, f64) if want_f64 else out
 
 
+# The Nystrom refit's error at every rank (mdg_nystrom_rank_curve).  Opt-in: MODEGPT_RANK_CURVE=1 makes compress_nystrom compute
+# it for every layer (one more factorisation of sigma_mlp and a triangular product per layer; DESIGN.md section 7, "The error-versus-rank curve").
+def rank_curve_enabled() -> bool:
+    """MODEGPT_RANK_CURVE as it stands when compress_nystrom asks (per layer; not frozen at import)."""
+    return os.environ.get("MODEGPT_RANK_CURVE", "0").lower() in ("1", "on", "true")
+
+
+def nystrom_rank_curve(Cm: torch.Tensor, order: torch.Tensor, W_down: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """curve [n + 1] fp64 ON THE DEVICE: curve[r] = tr(W (M - M[:, S] M_SS^-1 M[S, :]) W^T), M = C + eps I, S = order[:r] -- the
+    residual energy of the Nystrom refit that keeps the first r columns of `order`, for every r from one factorisation.  `order`:
+    a permutation of 0 .. n-1 (the ridge-score order: torch.argsort(scores, stable=True)).  W_down [d, n] as in nystrom_down.
+    Inside an ops.DeferredStatus the call only enqueues; outside it raises torch.linalg.LinAlgError for a matrix that is not
+    positive definite (a repeated index in `order` makes one).  Read it with decode_rank_curve."""
+    _need_gpu(Cm, order, W_down)
+    lib = _lib.load()
+    if Cm.dtype != torch.float64 or Cm.dim() != 2 or Cm.shape[0] != Cm.shape[1] or Cm.stride(1) != 1:
+        raise ValueError("C must be a square float64 matrix with unit column stride")
+    W_down = _as_weight(W_down)
+    n, d = Cm.shape[0], W_down.shape[0]
+    if order.numel() != n or W_down.dim() != 2 or W_down.shape[1] != n:
+        raise ValueError(f"nystrom_rank_curve: order needs {n} entries and W_down {n} columns")
+    order = order.to(torch.int64).contiguous()
+    curve = torch.empty(n + 1, dtype=torch.float64, device=Cm.device)
+    nbytes = lib.mdg_nystrom_rank_curve_ws_bytes(n, d)
+    ws, wsp = _ws(nbytes, Cm.device)
+    with torch.cuda.device(Cm.device):
+        check(lib.mdg_nystrom_rank_curve(Cm.data_ptr(), n, Cm.stride(0), order.data_ptr(), W_down.data_ptr(), d, W_down.stride(0),
+                                         _DT[W_down.dtype], float(eps), curve.data_ptr(), wsp, nbytes, _stream(Cm)),
+              "mdg_nystrom_rank_curve")
+    return curve
+
+
+RANK_CURVE_KEEP = tuple(k / 100 for k in range(5, 101, 5))          # 0.05, 0.10, ..., 1.00
+RANK_CURVE_TARGETS = (1e-1, 1e-2, 1e-3)
+
+
+def decode_rank_curve(curve, rank: int) -> dict:
+    """Host-side reading of a rank curve (a list / CPU tensor of n + 1 numbers) for a layer compressed to `rank`:
+    n, rank, energy = curve[0] (the output energy tr(W (C + eps I) W^T) of the uncompressed MLP), rel_error = curve[rank] / energy,
+    keep = RANK_CURVE_KEEP with rel_error_at_keep = the relative error at rank int(n * keep) (compress_weights' rounding), and
+    rank_for_rel_error = {target: the smallest rank whose relative error is at or under it} for RANK_CURVE_TARGETS.  A zero or
+    non-finite energy gives None in every relative field."""
+    v = [float(x) for x in curve]
+    n, rank, energy = len(v) - 1, int(rank), v[0]
+    if n < 0 or not 0 <= rank <= n:
+        raise ValueError(f"decode_rank_curve: rank {rank} outside 0 .. {n}")
+    ok = energy > 0 and energy < float("inf")         # (False for NaN)
+    rel = (lambda r: v[r] / energy) if ok else (lambda r: None)
+
+    def smallest_rank(target):       # the curve is non-increasing: the first rank at or under the target
+        if not ok:
+            return None
+        lo, hi = 0, n                # invariant: rel(hi) <= target (rel(n) = 0)
+        if not v[n] / energy <= target:
+            return None
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if v[mid] / energy <= target:
+                hi = mid
+            else:
+                lo = mid + 1
+        return hi
+    return {"n": n, "rank": rank, "energy": energy, "rel_error": rel(rank), "keep": list(RANK_CURVE_KEEP),
+            "rel_error_at_keep": [rel(int(n * k)) for k in RANK_CURVE_KEEP],
+            "rank_for_rel_error": {"%g" % t: smallest_rank(t) for t in RANK_CURVE_TARGETS}}
+
+
 # ------------------------------------------------------------------ QK / VO
 def qk_select(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: int, ridge_q: float, ridge_k: float):
     """Returns (mask [n_kv, rank] int64, q_rows [n_heads*rank], k_rows [n_kv*rank])."""
