@@ -41,7 +41,8 @@ extern "C" {
                                 the exact route of the int8 covariance (`flags`, route_counts[4], mdg_cov_accum_i8_route's `exact`);
                                 added under 9: mdg_qk_select_margin, mdg_vo_spectrum; MDG_I8_ROWS / MDG_I8_MAX_ROWS (a flag bit of the int8
                                 covariance, route_counts[5] with that bit), mdg_cov_accum_i8_rows;
-                                added under 9: mdg_nystrom_rank_curve_ws_bytes, mdg_nystrom_rank_curve (the Nystrom refit's error at every rank) */
+                                added under 9: mdg_nystrom_rank_curve_ws_bytes, mdg_nystrom_rank_curve (the Nystrom refit's error at every rank);
+                                added under 9: mdg_mlp_output_error_ws_bytes, mdg_mlp_output_error (the stored down projection's realised output error) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -402,6 +403,34 @@ size_t mdg_nystrom_rank_curve_ws_bytes(int64_t n, int64_t d);
 int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, const int64_t* order, const void* Wd, int64_t d,
                            int64_t ld_wd, int w_dtype, double eps, double* curve /* [n + 1] */, void* ws,
                            size_t ws_bytes, void* stream);
+
+/* What a STORED down projection lost, per output channel, on the calibration statistic (added under ABI 9; not in the reference:
+ * compress_mlp.py:52-62 computes the refit and reports nothing about it).  The rank curve above belongs to the fp64 minimiser under
+ * C + eps I; this call takes the tensor that goes into the checkpoint -- or any other `down`.  With U [d, n] the residual weights,
+ * column j of U = W_d[:, j] where j is not in idx and W_d[:, j] - down[:, p] where j = idx[p], and u_k = row k of U:
+ *     e[k] = u_k C u_k^T = sum_i C_ii u_ki^2 + 2 sum_{i > j} C_ij u_ki u_kj ,        unorm2[k] = ||u_k||^2   (optional, may be NULL)
+ * sum_k e[k] is the E_D and sum_k unorm2[k] the ||U||_F^2 of the sandwich  E_D + eps ||U||^2 - eps ||W_S||^2 <= curve[r] <= E_D + eps ||U||^2
+ * (DESIGN.md section 7); with down == NULL or r == 0 nothing is subtracted and e[k] = q_k = w_k C w_k^T, the channel's output energy.
+ * C [n, n] fp64 (ldc >= n; only the LOWER triangle is read -- NaN above the diagonal is harmless -- and C is not modified),
+ * n <= 2^31 - 1.  W_d [d, n] (ld_wd) of dtype w_dtype, MDG_BF16 or MDG_F64 as in mdg_nystrom_down.  down is addressed as
+ * down[k sd_row + p sd_col], k < d, p < r, of dtype down_dtype, MDG_BF16 or MDG_F64: the stored [d, r] bf16 artefact is
+ * (sd_row = ld_out, sd_col = 1), mdg_nystrom_down's down_f64 [r, d] is (sd_row = 1, sd_col = d).  The subtraction is done in fp64 on
+ * the exactly widened operands (a bf16 - bf16 difference is exact there).  idx: DEVICE int64 [r] (what mdg_select_smallest_sorted
+ * wrote; need not be sorted); entries outside 0 .. n-1 are clamped (memory safety only) and where an index occurs more than once
+ * its HIGHEST position is the one subtracted.  A NaN in row k of W_d or down gives NaN in e[k] and leaves the other rows alone; a
+ * NaN in the lower triangle of C may reach every row; MDG_OK either way.
+ * One 128-row block of U against the lower-triangle tiles of C on v_mfma_f64_16x16x4_f64, U formed while staging, the row dot
+ * product folded into the epilogue: d n (n + 1) flop, the product U C is never written.  No atomics, every sum in a fixed order:
+ * bit-identical from run to run.
+ * ws: mdg_mlp_output_error_ws_bytes(n, d) = 4 n (the inverse index map, int32, padded to 16 bytes) + 16 d ceil(n / 128) bytes (the
+ * per-tile-column partial sums of e and unorm2): 7.4 MB at n = 14336, d = 4096.
+ * Status: there is no factorisation -- the call only enqueues, never synchronises, and is the same inside and outside
+ * mdg_deferred_status_begin / _end.  MDG_ERR_BAD_ARG for n <= 0, d <= 0, r < 0, r > n, ldc < n, ld_wd < n, an unsupported dtype,
+ * a workspace that is too small, or r > 0 without down / idx. */
+size_t mdg_mlp_output_error_ws_bytes(int64_t n, int64_t d);
+int mdg_mlp_output_error(const double* C, int64_t n, int64_t ldc, const void* Wd, int64_t d, int64_t ld_wd, int w_dtype,
+                         const int64_t* idx, int64_t r, const void* down, int64_t sd_row, int64_t sd_col, int down_dtype,
+                         double* e /* [d] */, double* unorm2 /* [d], optional */, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ QK: CR selection
  * mask [n_kv, rank] (int64, score-descending, NOT sorted: compress_qk.py:366-367,418-419,464),

@@ -147,6 +147,43 @@ class ModelAdapter(ABC):
                 log.info(f"[MLP] rank curves of {len(usable)} layers: energy-weighted mean relative output error {mean:.3e}")
         return report
 
+    # ---- what the STORED MLP weights lose of the layer's output (not upstream; MODEGPT_OUTPUT_ERROR=1) ----
+    def output_error(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_nystrom hands over (q, e, unorm2) of ops.mlp_output_error (d numbers each, still on the device) for layer
+        `layer_idx`, which it compressed to `rank`."""
+        self.__dict__.setdefault("_output_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+
+    def report_output_errors(self, log=None) -> dict:
+        """Reads the recorded tensors (24 d bytes per layer; call it where the host waits for the chains anyway), keeps them as CPU
+        tensors in self.output_errors[layer] = (q, e, unorm2) and writes metrics["mlp_output_error"][str(layer)] =
+        ops.decode_output_error(...): the energy the layer's output carries on the calibration statistic, how much of it the bf16
+        tensor that was saved loses, the worst output channel -- and, where report_rank_curves has read the layer's curve before,
+        the distance from the best possible refit ("The realised output error of the stored MLP weights", says
+        what that is not).  Logs one line per layer."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_output_errors", {})
+        curves = self.__dict__.get("rank_curves", {})
+        report = {}
+        for layer in sorted(pending):
+            (q, e, unorm2), rank = pending[layer]
+            host = tuple(t.detach().cpu() for t in (q, e, unorm2))
+            self.__dict__.setdefault("output_errors", {})[layer] = host
+            curve = curves.get(layer)
+            m = report[layer] = ops.decode_output_error(host[1].tolist(), host[0].tolist(), host[2].tolist(), ops.NYSTROM_EPS, rank,
+                                                        curve=None if curve is None else curve.tolist())
+            if m["relative_error"] is None:
+                log.warning(f"[MLP] Layer {layer}: output error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
+                continue
+            excess = m.get("excess_over_optimum")
+            log.info(f"[MLP] Layer {layer}: rank {rank}: stored weights lose {m['relative_error']:.3e} of the output energy; "
+                     f"worst channel {m['worst_channel']} loses {m['worst_channel_relative_error']:.3e}"
+                     + ("" if excess is None else f"; {excess:.3e} of the energy above the best refit"))
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            self.metrics.setdefault("mlp_output_error", {}).update({str(k): v for k, v in report.items()})
+        return report
+
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
     def attention_margin(self, layer_idx: int, kind: str, tensor, *eps: float) -> None:
         """compress_qk (kind "qk": ops.qk_select_margin's [n_kv, 8], eps = (eps_rel, eps_abs)) and compress_vo (kind "vo":

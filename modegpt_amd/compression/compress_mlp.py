@@ -63,14 +63,17 @@ def covariance_error_eps(adapter, n_features: int) -> float:
 
 @torch.no_grad()
 def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_idx: int, ridge_lambda: float,
-                     margin_eps: float = None, margin_out: list = None, curve_out: list = None):
+                     margin_eps: float = None, margin_out: list = None, curve_out: list = None, error_out: list = None):
     """compress_mlp.py:28-64.  Returns (W_u'^T [d, r], W_d' [r, d], W_g'^T [d, r] or None, rank), bf16 --
     the same orientation the reference returns (transposed views of the saved layout).
     margin_eps / margin_out (not upstream): with both given, the certificate of the rank selection against an entry-wise relative
     error margin_eps of C (ops.select_margin: 8 numbers on the device) is appended to margin_out -- two more passes over the
     triangular inverse the scores come from, nothing else changes.
     curve_out (not upstream): a list, with MODEGPT_RANK_CURVE=1 -- the layer's error-versus-rank curve (ops.nystrom_rank_curve, n + 1
-    numbers on the device) is appended to it, enqueued behind the refit; the outputs are the same bits with or without it."""
+    numbers on the device) is appended to it, enqueued behind the refit; the outputs are the same bits with or without it.
+    error_out (not upstream): a list, with MODEGPT_OUTPUT_ERROR=1 -- (q, e, unorm2), d numbers each on the device
+    (ops.mlp_output_error: the output energy of the uncompressed weights, the output error and the squared residual norm per channel
+    of the bf16 tensor this call RETURNS, not of the fp64 solution) are appended to it; the outputs are the same bits either way."""
     C = C.to(dtype=dtype_p, device=local_device())
     rank = int(C.shape[0] * keep_ratio)
     if margin_out is not None and margin_eps is not None:
@@ -93,6 +96,10 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         # so the factor of sigma_mlp in that order holds the refit's residual energy at every rank, this layer's included
         order = torch.argsort(scores, stable=True)
         curve_out.append(ops.nystrom_rank_curve(C, order, W_d, eps=1e-6))
+    if error_out is not None and ops.output_error_enabled():
+        q = ops.mlp_output_error(C, W_d, None, None)                  # the channel's energy: nothing subtracted
+        e, unorm2 = ops.mlp_output_error(C, W_d, idx, down, want_unorm2=True)     # ... and what the tensor that is saved loses of it
+        error_out.extend((q, e, unorm2))
     return up.T, down.T, (None if gate is None else gate.T), rank
 
 
@@ -107,17 +114,22 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
         record = getattr(adapter, "selection_margin", None)          # (a duck-typed adapter without it: no certificate)
         record_curve = getattr(adapter, "rank_curve", None)          # (... and without this: no error-versus-rank curve)
         curve = [] if callable(record_curve) else None               # (filled only with MODEGPT_RANK_CURVE=1)
+        record_error = getattr(adapter, "output_error", None)        # (... and without this: no realised output error)
+        error = [] if callable(record_error) else None               # (filled only with MODEGPT_OUTPUT_ERROR=1)
         if record is None:
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve)
+                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error)
         else:
             eps, margin = covariance_error_eps(adapter, cov[layer_idx].shape[0]), []
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                      ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve)
+                                      ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve,
+                                      error_out=error)
             # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
             record(layer_idx, margin[0], eps)
         if curve:
             record_curve(layer_idx, curve[0], result[3])             # ... and so does the curve (report_rank_curves)
+        if error:
+            record_error(layer_idx, tuple(error), result[3])         # ... and the stored tensor's output error (report_output_errors)
         return result
 
     def retire(layer_idx, result):

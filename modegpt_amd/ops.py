@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 import threading
 from typing import NamedTuple, Optional, Sequence, Tuple
@@ -863,6 +864,88 @@ def decode_rank_curve(curve, rank: int) -> dict:
     return {"n": n, "rank": rank, "energy": energy, "rel_error": rel(rank), "keep": list(RANK_CURVE_KEEP),
             "rel_error_at_keep": [rel(int(n * k)) for k in RANK_CURVE_KEEP],
             "rank_for_rel_error": {"%g" % t: smallest_rank(t) for t in RANK_CURVE_TARGETS}}
+
+
+# The realised output error of the STORED down projection (mdg_mlp_output_error).  Opt-in: MODEGPT_OUTPUT_ERROR=1 makes
+# compress_nystrom compute it for every layer from the bf16 tensor it saves (two launches of d n (n + 1) flop per layer; DESIGN.md
+# section 7, "The realised output error of the stored MLP weights").
+def output_error_enabled() -> bool:
+    """MODEGPT_OUTPUT_ERROR as it stands when compress_nystrom asks (per layer; not frozen at import)."""
+    return os.environ.get("MODEGPT_OUTPUT_ERROR", "0").lower() in ("1", "on", "true")
+
+
+def mlp_output_error(Cm: torch.Tensor, W_down: torch.Tensor, idx: Optional[torch.Tensor], down: Optional[torch.Tensor],
+                     want_unorm2: bool = False):
+    """e [d] fp64 ON THE DEVICE: e[k] = u_k C u_k^T, u_k = row k of W_down with down[k, p] subtracted at column idx[p] -- what output
+    channel k of the MLP loses on the statistic C when `down` replaces W_down at the kept columns `idx`.  Only the lower triangle of C
+    is read.  W_down [d, n] as in nystrom_down.  down: the stored [d, r] bf16 tensor, or an fp64 tensor [d, r] of any strides
+    (nystrom_down's f64 solution [r, d] goes in as `f64.T`); any other dtype is widened exactly to fp64.  down=None (or an empty
+    idx): nothing is subtracted and e[k] = q_k, the channel's output energy.  want_unorm2: -> (e, unorm2), unorm2[k] = ||u_k||^2.
+    The call only enqueues; an index that occurs twice subtracts its highest position, entries outside 0 .. n-1 are clamped."""
+    _need_gpu(Cm, W_down, idx, down)
+    lib = _lib.load()
+    if Cm.dtype != torch.float64 or Cm.dim() != 2 or Cm.shape[0] != Cm.shape[1] or Cm.stride(1) != 1:
+        raise ValueError("C must be a square float64 matrix with unit column stride")
+    W_down = _as_weight(W_down)
+    n, d = Cm.shape[0], W_down.shape[0]
+    if W_down.dim() != 2 or W_down.shape[1] != n:
+        raise ValueError(f"mlp_output_error: W_down needs {n} columns")
+    r = 0 if (down is None or idx is None) else idx.numel()
+    if r:
+        if down.dim() != 2 or tuple(down.shape) != (d, r):
+            raise ValueError(f"mlp_output_error: down must be [{d}, {r}], got {tuple(down.shape)}")
+        down = down.detach()
+        if down.dtype not in (torch.bfloat16, torch.float64):
+            down = down.to(torch.float64)
+        idx = idx.to(torch.int64).contiguous()
+    e = torch.empty(d, dtype=torch.float64, device=Cm.device)
+    u2 = torch.empty(d, dtype=torch.float64, device=Cm.device) if want_unorm2 else None
+    nbytes = lib.mdg_mlp_output_error_ws_bytes(n, d)
+    ws, wsp = _ws(nbytes, Cm.device)
+    with torch.cuda.device(Cm.device):
+        check(lib.mdg_mlp_output_error(Cm.data_ptr(), n, Cm.stride(0), W_down.data_ptr(), d, W_down.stride(0), _DT[W_down.dtype],
+                                       idx.data_ptr() if r else None, r, down.data_ptr() if r else None,
+                                       down.stride(0) if r else 0, down.stride(1) if r else 0, _DT[down.dtype] if r else _lib.MDG_BF16,
+                                       e.data_ptr(), _p(u2), wsp, nbytes, _stream(Cm)), "mdg_mlp_output_error")
+    return (e, u2) if want_unorm2 else e
+
+
+OUTPUT_ERROR_LEVELS = (1e-1, 1e-2, 1e-3)
+NYSTROM_EPS = 1e-6          # the ridge of the refit compress_weights computes (compress_mlp.py:52,56): the eps of `objective`
+
+
+def decode_output_error(e, q, unorm2, eps: float, rank: int, curve=None) -> dict:
+    """Host-side reading of a layer's output error (lists / CPU tensors of d numbers each: e and unorm2 of the stored tensor, q of
+    the uncompressed weights; eps: the ridge of the refit; rank: the columns kept):
+    rank, energy = sum q, error = sum e, relative_error = error / energy, objective = error + eps sum unorm2 (what the refit
+    minimises, compress_mlp.py:52-62), worst_channel = the channel with the largest e_k / q_k among those with q_k > 0 and
+    worst_channel_relative_error that ratio, channels_above = {level: how many such channels exceed it} for OUTPUT_ERROR_LEVELS.
+    With the layer's rank curve (n + 1 numbers): predicted_objective = curve[rank], the minimum of the objective over all refits,
+    and excess_over_optimum = (objective - curve[rank]) / curve[0] -- what rounding to bf16 and solving with C[S, :] instead of
+    M[S, :] cost beyond the best refit.  A non-finite sum gives None in the fields derived from it."""
+    ev, qv, uv = ([float(x) for x in t] for t in (e, q, unorm2))
+    if not len(ev) == len(qv) == len(uv):
+        raise ValueError("decode_output_error: e, q and unorm2 must have one entry per output channel")
+    fin = lambda x: x if math.isfinite(x) else None                    # noqa: E731
+    total = lambda v: math.fsum(v) if all(map(math.isfinite, v)) else float("nan")      # noqa: E731
+    energy, error, u2 = total(qv), total(ev), total(uv)
+    objective = error + float(eps) * u2
+    ratios = [(ek / qk, k) for k, (ek, qk) in enumerate(zip(ev, qv)) if qk > 0 and math.isfinite(qk) and math.isfinite(ek)]
+    worst = max(ratios, key=lambda t: (t[0], -t[1])) if ratios and math.isfinite(error) and math.isfinite(energy) else None
+    out = {"rank": int(rank), "energy": fin(energy), "error": fin(error),
+           "relative_error": error / energy if math.isfinite(error) and math.isfinite(energy) and energy > 0 else None,
+           "objective": fin(objective),
+           "worst_channel": None if worst is None else worst[1],
+           "worst_channel_relative_error": None if worst is None else worst[0],
+           "channels_above": {"%g" % t: (None if worst is None else sum(1 for x, _ in ratios if x > t)) for t in OUTPUT_ERROR_LEVELS}}
+    if curve is not None:
+        cv = [float(x) for x in curve]
+        if not 0 <= int(rank) < len(cv):
+            raise ValueError(f"decode_output_error: rank {rank} outside the curve's 0 .. {len(cv) - 1}")
+        ok = math.isfinite(cv[int(rank)]) and math.isfinite(cv[0]) and cv[0] > 0
+        out["predicted_objective"] = cv[int(rank)] if ok else None
+        out["excess_over_optimum"] = (objective - cv[int(rank)]) / cv[0] if ok and math.isfinite(objective) else None
+    return out
 
 
 # ------------------------------------------------------------------ QK / VO
