@@ -42,7 +42,9 @@ extern "C" {
                                 added under 9: mdg_qk_select_margin, mdg_vo_spectrum; MDG_I8_ROWS / MDG_I8_MAX_ROWS (a flag bit of the int8
                                 covariance, route_counts[5] with that bit), mdg_cov_accum_i8_rows;
                                 added under 9: mdg_nystrom_rank_curve_ws_bytes, mdg_nystrom_rank_curve (the Nystrom refit's error at every rank);
-                                added under 9: mdg_mlp_output_error_ws_bytes, mdg_mlp_output_error (the stored down projection's realised output error) */
+                                added under 9: mdg_mlp_output_error_ws_bytes, mdg_mlp_output_error (the stored down projection's realised output error);
+                                added under 9: mdg_vo_output_error_ws_bytes, mdg_vo_output_error, mdg_vo_rank_curve_ws_bytes, mdg_vo_rank_curve
+                                (what the stored V/O factors lose of the attention output, and the truncation's cost at every rank) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -498,6 +500,61 @@ int mdg_vo_compress(const double* cov_x, int64_t d, int64_t ldc, const void* Wv,
  * it, the gap alone is reported.  Only enqueues; one workgroup per kv head. */
 int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_t d, int64_t ldc, const void* Wv, int64_t ld_wv,
                     int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, double eps, double* out, void* stream);
+
+/* What the STORED V/O factors lose of the attention output on the calibration statistic, per query head and output channel (added
+ * under ABI 9; not in the reference: compress_vo.py:112-223 cuts its SVD at `rank` and reports nothing about the product).  Field [3]
+ * of mdg_vo_spectrum is the retained energy of the VALUE stream of the fp64 factors (grouped: W_o is not in it); this call takes the
+ * tensors that go into the checkpoint -- or any other factors -- and weighs what they lose by W_o.  The objective is the one
+ * compress_vo works on, the map x -> W_o,h W_v,g x per query head h of kv group g (no token mixing by the attention weights).
+ * C = cov_x, the finalised sigma_x [d, d]; W_v,g = rows g hd .. of W_v; W_o,h = columns h hd .. of W_o; the factors
+ * v'_g = rows g rank .. of v_new [n_kv rank, d] (ld_v), o'_h = columns h rank .. of o_new [d, n_heads rank] (ld_o).  With
+ *     delta_{h,k} = W_o,h[k, :] W_v,g - o'_h[k, :] v'_g                              (a row of length d; never formed)
+ *     e[h][k] = delta C delta^T ,      dnorm2[h][k] = ||delta||^2   (optional, may be NULL)
+ * e + rho dnorm2 is the channel's objective under M = C + rho I, rho the ridge mdg_vo_compress was called with.  rank == 0 (v_new and
+ * o_new are then not read and may be NULL): nothing is subtracted and e[h][k] = q[h][k], the channel's output energy.
+ * Route: the stacked Gram.  V_g = [W_v,g ; -v'_g] [(hd + rank), d], y_{h,k} = [W_o,h[k, :], o'_h[k, :]]:
+ *     e[h][k] = y (V_g C V_g^T) y^T ,   dnorm2[h][k] = y (V_g V_g^T) y^T
+ * -- T = V_g C and the two Grams through the fp64 GEMM core (bf16 operands read directly, batched over the kv heads), then one
+ * fused kernel on v_mfma_f64_16x16x4_f64: a workgroup owns 128 output channels of one head, y is stitched from W_o and o_new while
+ * staging (both widened exactly), the LOWER triangle of the head's Gram is read with the factor 2 on its strict part, and the row dot
+ * product sits in the epilogue; y G is never written.  About 2 (hd + rank) d (n_kv d + n_heads (hd + rank)) flop: 0.07 TFLOP at
+ * d = 4096, 32 / 8 heads, hd = 128, rank = 88, where forming delta C would take 4.4.
+ * Accuracy: the result is a difference of Gram entries, so it is accurate relative to the scale
+ *     a[h][k] = (|y| |V_g|) |C| (|y| |V_g|)^T ,
+ * NOT relative to itself: where the factors reproduce W_o,h W_v,g (rank == hd, fp64 factors) e is rounding noise of EITHER SIGN.  It
+ * is returned raw; a reader takes 64 (d + hd + rank) 2^-53 a as the floor below which a value says nothing.
+ * w_dtype (W_v, W_o) and new_dtype (v_new, o_new): MDG_BF16 or MDG_F64, so mdg_vo_compress's v_out / o_out and its v_f64 / o_f64
+ * (ld_v = d, ld_o = n_heads rank) go in unchanged.  cov_x is read in full (both triangles), as mdg_vo_compress reads it; nothing
+ * is modified.  Head layout as mdg_vo_compress, 0 <= rank <= hd.
+ * A NaN in row k of one head's W_o or o' gives NaN in e[h][k] (and dnorm2[h][k]) of that head alone; a NaN in one kv head's W_v or
+ * v' reaches every channel of that group's heads and no other group; a NaN in cov_x reaches everything; MDG_OK in every case.
+ * No atomics, every sum in a fixed order: bit-identical from run to run, and e is the same bits with and without dnorm2.
+ * ws: mdg_vo_output_error_ws_bytes(d, n_heads, n_kv, hd, rank) = 8 (n_kv n d + 2 n_kv n^2 + 2 ceil(n / 128) n_heads d) bytes,
+ * n = hd + rank: T, the two Grams, the tile-column partials.
+ * Status: there is no factorisation -- the call only enqueues, never synchronises, and is the same inside and outside
+ * mdg_deferred_status_begin / _end.  MDG_ERR_BAD_ARG for a null pointer, an unsupported head layout or rank, a leading dimension
+ * that is too small (ldc, ld_wv, ld_v < d; ld_wo < n_heads hd; ld_o < n_heads rank), an unsupported dtype, a workspace that is too
+ * small, or rank > 0 without v_new / o_new. */
+size_t mdg_vo_output_error_ws_bytes(int64_t d, int n_heads, int n_kv, int hd, int rank);
+int mdg_vo_output_error(const double* cov_x, int64_t d, int64_t ldc, const void* Wv, int64_t ld_wv, const void* Wo, int64_t ld_wo,
+                        int w_dtype, int n_heads, int n_kv, int hd, int rank, const void* v_new, int64_t ld_v, const void* o_new,
+                        int64_t ld_o, int new_dtype, double* e /* [n_heads][d] */, double* dnorm2 /* [n_heads][d], optional */,
+                        void* ws, size_t ws_bytes, void* stream);
+/* What the V/O truncation costs the attention output at EVERY rank (added under ABI 9).  Reads the eigen-decomposition the LAST
+ * mdg_vo_compress call left in its workspace vo_ws (same shapes), as mdg_vo_spectrum does.  Per kv head g, r = 0 .. hd:
+ *     grouped:  c_i = max(lambda_i, 0) sum_{h in g} ||W_o,h v_i||^2 ,  (lambda_i, v_i) of G = W_v,g (C + rho I) W_v,g^T, descending
+ *     MHA (n_kv == n_heads):  c_i = max(lambda2_i, 0), the second SVD's spectrum (W_o is then not read)
+ *     curve[g][r] = sum_{i >= r} c_i
+ * accumulated from the tail, so the curve is non-increasing entry by entry and curve[g][hd] = +0.0 exactly.  For the fp64 factors of
+ * rank r, sum over the group's heads and channels of (e + rho dnorm2) of mdg_vo_output_error equals curve[g][r] in exact
+ * arithmetic.  Grouped: it is the error of the REFERENCE'S choice of subspace (which ignores W_o), not the minimum over all
+ * rank-r factorisations.  ||W_o,h v_i||^2 as the column norms of W_o,h V_g (fp64 GEMM): accurate to (hd + d) 2^-53 relative to
+ * itself.  ws: mdg_vo_rank_curve_ws_bytes = 8 n_heads hd (d + ceil(d / 256)) bytes (grouped), 0 (MHA; ws may then be NULL).
+ * A NaN eigenvalue stays a NaN.  Only enqueues.  MDG_ERR_BAD_ARG for a null pointer, an unsupported head layout or dtype,
+ * ld_wo < n_heads hd, or a workspace that is too small. */
+size_t mdg_vo_rank_curve_ws_bytes(int64_t d, int n_heads, int n_kv, int hd);
+int mdg_vo_rank_curve(const void* vo_ws, size_t vo_ws_bytes, const void* Wo, int64_t ld_wo, int w_dtype, int64_t d, int n_heads,
+                      int n_kv, int hd, double* curve /* [n_kv][hd + 1] */, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ sqrt_M (compression_utils.py:15-55)
  * root = V diag(sqrt(max(lambda + ridge*scale, 0))) V^T, inv_root (optional) with the 1e-12 clamp;

@@ -184,6 +184,43 @@ class ModelAdapter(ABC):
             self.metrics.setdefault("mlp_output_error", {}).update({str(k): v for k, v in report.items()})
         return report
 
+    # ---- what the STORED v_proj / o_proj lose of the attention output (not upstream; MODEGPT_VO_ERROR=1) ----
+    def vo_error(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_vo hands over (q, e, dnorm2, curve) -- ops.vo_output_error's [n_heads, d] tensors and
+        ops.vo_compress(want_curve=True)'s [n_kv, hd + 1], still on the device -- for layer `layer_idx`, truncated to `rank` per head."""
+        self.__dict__.setdefault("_vo_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+
+    def report_vo_errors(self, log=None) -> dict:
+        """Reads the recorded tensors (24 n_heads d + 8 n_kv (hd + 1) bytes per layer; call it where the host waits for the chains
+        anyway), keeps them as CPU tensors in self.vo_errors[layer] = (q, e, dnorm2, curve) and writes
+        metrics["vo_output_error"][str(layer)] = ops.decode_vo_output_error(...): the energy the attention output carries on the
+        calibration statistic, how much of it the bf16 v_proj / o_proj that were saved lose, per kv head and for the layer, the worst
+        head and channel, and the distance from the fp64 truncation's curve ("The realised output error of the
+        stored V/O factors", says what that is not).  Logs one line per layer."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_vo_errors", {})
+        report = {}
+        for layer in sorted(pending):
+            tensors, rank = pending[layer]
+            host = tuple(t.detach().cpu() for t in tensors)
+            self.__dict__.setdefault("vo_errors", {})[layer] = host
+            q, e, dnorm2, curve = host
+            m = report[layer] = ops.decode_vo_output_error(e.tolist(), q.tolist(), dnorm2.tolist(), self.config.ridge_vo, rank,
+                                                           curve.shape[0], curve=curve.tolist())
+            if m["relative_error"] is None:
+                log.warning(f"[VO] Layer {layer}: output error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
+                continue
+            excess = m.get("excess_over_curve")
+            log.info(f"[VO] Layer {layer}: rank {rank}: stored factors lose {m['relative_error']:.3e} of the output energy; "
+                     f"worst head {m['worst_head']} loses {m['worst_head_relative_error']:.3e}"
+                     + ("" if excess is None else f"; {excess:.3e} of the energy above the fp64 truncation"))
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            # (decode_vo_output_error maps every non-finite sum to None, so json.dump never meets a NaN)
+            self.metrics.setdefault("vo_output_error", {}).update({str(k): v for k, v in report.items()})
+        return report
+
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
     def attention_margin(self, layer_idx: int, kind: str, tensor, *eps: float) -> None:
         """compress_qk (kind "qk": ops.qk_select_margin's [n_kv, 8], eps = (eps_rel, eps_abs)) and compress_vo (kind "vo":

@@ -109,15 +109,21 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
             return None
         # (the eigensolver's convergence flag is read once per layer, by the adapter: over_layers)
         record = getattr(adapter, "attention_margin", None)       # (a duck-typed adapter without it: no spectrum report)
-        if record is None:
-            return ops.vo_compress(C, W_v.detach().to(local_device()), W_o.detach().to(local_device()), n_heads, n_kv, head_dim,
-                                   rank_i, adapter.config.ridge_vo)
+        record_error = getattr(adapter, "vo_error", None) if ops.vo_error_enabled() else None       # (... without this: no output error)
+        Wv_d, Wo_d = W_v.detach().to(local_device()), W_o.detach().to(local_device())
         # sigma_r against sigma_r+1 of the spectrum just truncated: stays on the device until report_attention_margins
-        eps = attention_error_eps(adapter)
-        V_heads, O_heads, spectrum = ops.vo_compress(C, W_v.detach().to(local_device()), W_o.detach().to(local_device()), n_heads,
-                                                     n_kv, head_dim, rank_i, adapter.config.ridge_vo, want_spectrum=True,
-                                                     spectrum_eps=eps)
-        record(layer, "vo", spectrum, eps)
+        eps = attention_error_eps(adapter) if record is not None else None
+        out = ops.vo_compress(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, adapter.config.ridge_vo, want_spectrum=record is not None,
+                              spectrum_eps=eps, want_curve=record_error is not None)
+        V_heads, O_heads = out[0], out[1]
+        if record is not None:
+            record(layer, "vo", out[2], eps)
+        if record_error is not None:
+            # what the bf16 tensors about to be saved lose of the attention output, beside the curve of the fp64 truncation: enqueued
+            # only, read by report_vo_errors
+            q = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, 0, None, None)
+            e, dnorm2 = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, V_heads, O_heads, want_dnorm2=True)
+            record_error(layer, (q, e, dnorm2, out[-1]), rank_i)
         return V_heads, O_heads
 
     def retire(layer, result):

@@ -9,6 +9,7 @@
 // :162-223) reduces the same way: B = S V^T W_o,h^T, B B^T = (S V^T)(W_o,h^T W_o,h)(V S) = U_p S_p^2 U_p^T,
 // W_v' = U_p,r^T S^-1 V^T W_v,h,  W_o' = W_o,h V S U_p,r.
 #include "common.hpp"
+#include "vo_ws.hpp"
 
 namespace mdg {
 int gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const void* A, int a_dtype, int64_t sa_i, int64_t sa_k,
@@ -158,32 +159,6 @@ __global__ __launch_bounds__(256) void vo_spectrum_kernel(const double* lam_all,
     o8[5] = grouped ? (l_r - l_next > 2. * b ? 1. : 0.) : nan;
     o8[6] = lam[0]; o8[7] = lam[hd - 1];
   }
-}
-
-struct VoWs {
-  double *T, *G, *evals, *evecs, *P, *Q, *Mh, *tmp, *Y, *evals2, *evecs2;
-  int* flag;
-  size_t bytes;
-};
-
-static VoWs vo_layout(void* ws, int64_t d, int n_heads, int n_kv, int hd) {
-  VoWs w;
-  double* p = (double*)ws;
-  const size_t hh = (size_t)hd * hd;
-  w.T = p;      p += (size_t)n_kv * hd * d;
-  w.G = p;      p += n_kv * hh;
-  w.evals = p;  p += (size_t)n_kv * hd;
-  w.evecs = p;  p += n_kv * hh;
-  w.P = p;      p += n_kv * hh;
-  w.Q = p;      p += n_kv * hh;
-  w.Mh = p;     p += n_kv * hh;
-  w.tmp = p;    p += n_kv * hh;
-  w.Y = p;      p += n_kv * hh;
-  w.evals2 = p; p += (size_t)n_kv * hd;
-  w.evecs2 = p; p += n_kv * hh;
-  w.flag = (int*)p; p += 8;
-  w.bytes = (size_t)((char*)p - (char*)ws);
-  return w;
 }
 
 }  // namespace mdg

@@ -1021,8 +1021,11 @@ VO_SPECTRUM_FIELDS = ("lambda_r", "lambda_next", "gap", "energy", "bound", "sepa
 
 
 def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
-                ridge: float, want_f64: bool = False, want_spectrum: bool = False, spectrum_eps: Optional[float] = None):
-    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum]).
+                ridge: float, want_f64: bool = False, want_spectrum: bool = False, spectrum_eps: Optional[float] = None,
+                want_curve: bool = False):
+    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum][, curve]).
+    want_curve: what the truncation costs the attention output at every rank (mdg_vo_rank_curve: [n_kv, hd + 1] fp64 ON THE DEVICE;
+    decode_vo_output_error reads it), enqueued like the spectrum, behind the factorisation while its workspace is alive.
     want_spectrum: what the truncation at `rank` did to the spectrum (mdg_vo_spectrum: [n_kv, 8] fp64 ON THE DEVICE,
     VO_SPECTRUM_FIELDS; decode_vo_spectrum), enqueued behind the factorisation on the same stream while its workspace is alive;
     spectrum_eps: the entry-wise relative error bound of cov_x its Weyl bound is taken against (None: 0, the gap alone).  The
@@ -1051,8 +1054,15 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
             check(lib.mdg_vo_spectrum(wsp, nbytes, Cx.data_ptr(), d, Cx.stride(0), Wv.data_ptr(), Wv.stride(0), _DT[Wv.dtype],
                                       n_heads, n_kv, hd, rank, float(ridge), float(spectrum_eps or 0.0), spectrum.data_ptr(),
                                       _stream(Cx)), "mdg_vo_spectrum")
+        if want_curve:
+            curve = torch.empty(n_kv, hd + 1, dtype=torch.float64, device=dev)
+            cbytes = lib.mdg_vo_rank_curve_ws_bytes(d, n_heads, n_kv, hd)
+            cws, cwsp = _ws(cbytes, dev)
+            check(lib.mdg_vo_rank_curve(wsp, nbytes, Wo.data_ptr(), Wo.stride(0), _DT[Wo.dtype], d, n_heads, n_kv, hd,
+                                        curve.data_ptr(), cwsp, cbytes, _stream(Cx)), "mdg_vo_rank_curve")
     out = (v_out, o_out, v64, o64) if want_f64 else (v_out, o_out)
-    return out + (spectrum,) if want_spectrum else out
+    out = out + (spectrum,) if want_spectrum else out
+    return out + (curve,) if want_curve else out
 
 
 def decode_vo_spectrum(rows, eps: float) -> dict:
@@ -1070,6 +1080,133 @@ def decode_vo_spectrum(rows, eps: float) -> dict:
     return {"heads": heads, "eps": float(eps), "weakest_head": weakest, "gap": heads[weakest]["gap"] if heads else float("inf"),
             "energy_min": min((h["energy"] for h in heads), default=1.0),
             "separated": None if (not seps or any(x is None for x in seps)) else all(seps)}
+
+
+# The realised output error of the STORED v_proj / o_proj (mdg_vo_output_error) and the truncation's cost at every rank
+# (mdg_vo_rank_curve).  Opt-in: MODEGPT_VO_ERROR=1 makes compress_vo compute both for every layer from the bf16 tensors it saves
+# ("The realised output error of the stored V/O factors").
+def vo_error_enabled() -> bool:
+    """MODEGPT_VO_ERROR as it stands when compress_vo asks (per layer; not frozen at import)."""
+    return os.environ.get("MODEGPT_VO_ERROR", "0").lower() in ("1", "on", "true")
+
+
+def vo_output_error(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
+                    v_new: Optional[torch.Tensor], o_new: Optional[torch.Tensor], want_dnorm2: bool = False):
+    """e [n_heads, d] fp64 ON THE DEVICE: e[h][k] = delta C delta^T, delta = W_o,h[k, :] W_v,g - o'_h[k, :] v'_g -- what output
+    channel k of query head h (kv group g) loses on the statistic C = cov_x when v_new [n_kv*rank, d] / o_new [d, n_heads*rank] replace
+    W_v [n_kv*hd, d] / W_o [d, n_heads*hd].  v_new / o_new: the stored bf16 tensors or vo_compress's v_f64 / o_f64 (row-strided views
+    are taken as they are; any other dtype is widened exactly to fp64).  v_new=None or rank=0: nothing is subtracted and e = q, the
+    channel's output energy.  want_dnorm2: -> (e, dnorm2), dnorm2[h][k] = ||delta||^2, so that e + ridge * dnorm2 is the channel's
+    objective under C + ridge I.  e is accurate relative to the scale a of include/modegpt_hip.h, not to itself (decode_vo_output_error
+    reports the floor).  The call only enqueues."""
+    _need_gpu(cov_x, W_v, W_o, v_new, o_new)
+    lib = _lib.load()
+    if cov_x.dtype != torch.float64 or cov_x.dim() != 2 or cov_x.shape[0] != cov_x.shape[1] or cov_x.stride(1) != 1:
+        raise ValueError("cov_x must be a square float64 matrix with unit column stride")
+    Wv, Wo = _as_weight(W_v), _as_weight(W_o)
+    if Wv.dtype != Wo.dtype:
+        Wv, Wo = Wv.to(torch.float64), Wo.to(torch.float64)
+    d = cov_x.shape[0]
+    if tuple(Wv.shape) != (n_kv * hd, d) or tuple(Wo.shape) != (d, n_heads * hd):
+        raise ValueError(f"vo_output_error: W_v must be [{n_kv * hd}, {d}] and W_o [{d}, {n_heads * hd}]")
+    r = 0 if (v_new is None or o_new is None) else int(rank)
+    if r:
+        if tuple(v_new.shape) != (n_kv * r, d) or tuple(o_new.shape) != (d, n_heads * r):
+            raise ValueError(f"vo_output_error: v_new must be [{n_kv * r}, {d}] and o_new [{d}, {n_heads * r}], got "
+                             f"{tuple(v_new.shape)} and {tuple(o_new.shape)}")
+        vn, on = _as_weight(v_new), _as_weight(o_new)
+        if vn.dtype != on.dtype:
+            vn, on = vn.to(torch.float64), on.to(torch.float64)
+    e = torch.empty(n_heads, d, dtype=torch.float64, device=cov_x.device)
+    dn = torch.empty(n_heads, d, dtype=torch.float64, device=cov_x.device) if want_dnorm2 else None
+    nbytes = lib.mdg_vo_output_error_ws_bytes(d, n_heads, n_kv, hd, r)
+    ws, wsp = _ws(nbytes, cov_x.device)
+    with torch.cuda.device(cov_x.device):
+        check(lib.mdg_vo_output_error(cov_x.data_ptr(), d, cov_x.stride(0), Wv.data_ptr(), Wv.stride(0), Wo.data_ptr(), Wo.stride(0),
+                                      _DT[Wv.dtype], n_heads, n_kv, hd, r, vn.data_ptr() if r else None, vn.stride(0) if r else 0,
+                                      on.data_ptr() if r else None, on.stride(0) if r else 0, _DT[vn.dtype] if r else _lib.MDG_BF16,
+                                      e.data_ptr(), _p(dn), wsp, nbytes, _stream(cov_x)), "mdg_vo_output_error")
+    return (e, dn) if want_dnorm2 else e
+
+
+VO_ERROR_TARGETS = (1e-1, 1e-2, 1e-3)
+
+
+def decode_vo_output_error(e, q, dnorm2, ridge: float, rank: int, n_kv: int, curve=None, hd: Optional[int] = None) -> dict:
+    """Host-side reading of a layer's V/O output error (nested lists / CPU tensors [n_heads][d]: e and dnorm2 of the stored factors, q
+    of the uncompressed weights; ridge: the ridge vo_compress was called with; rank: the components kept per head).  Layer and, under
+    "heads", per kv head (a kv head's numbers are the sums over its group's query heads):
+    energy = sum q, error = sum e, relative_error = error / energy, objective = error + ridge sum dnorm2 (what the truncation is
+    judged by under C + ridge I), noise_floor = 64 (d + hd + rank) 2^-53 energy -- e is accurate relative to a scale a >= q, not to
+    itself, so an error below the floor (of either sign) says nothing; hd is taken from the curve, else from `hd`, else as rank.
+    worst_head = the QUERY head with the largest error / energy, worst_head_relative_error, and worst_channel /
+    worst_channel_relative_error = the channel of that head with the largest e / q among those with q > 0.
+    With the layer's curve ([n_kv][hd + 1], vo_compress(want_curve=True)), per kv head: predicted_objective = curve[g][rank],
+    excess_over_curve = (objective - curve[g][rank]) / curve[g][0] (what rounding the factors to bf16 costs beyond the fp64
+    truncation; rounding noise of either sign for fp64 factors), relative_curve = curve[g][r] / curve[g][0] for every r, and
+    rank_for_rel_error = {target: the smallest rank at or under it} for VO_ERROR_TARGETS; the layer gets predicted_objective and
+    excess_over_curve of the sums.  A zero or non-finite sum gives None in the fields derived from it."""
+    ev, qv, nv = ([[float(x) for x in row] for row in t] for t in (e, q, dnorm2))
+    n_heads, rank, n_kv = len(ev), int(rank), int(n_kv)
+    if not (len(qv) == len(nv) == n_heads) or n_kv <= 0 or n_heads % n_kv or any(len(a) != len(b) or len(a) != len(c)
+                                                                                 for a, b, c in zip(ev, qv, nv)):
+        raise ValueError("decode_vo_output_error: e, q and dnorm2 must be [n_heads][d] with n_heads a multiple of n_kv")
+    group, d = n_heads // n_kv, (len(ev[0]) if n_heads else 0)
+    cv = None
+    if curve is not None:
+        cv = [[float(x) for x in row] for row in curve]
+        if len(cv) != n_kv or any(len(row) != len(cv[0]) or not 0 <= rank < len(row) for row in cv):
+            raise ValueError(f"decode_vo_output_error: the curve must be [{n_kv}][hd + 1] with rank {rank} <= hd")
+        hd = len(cv[0]) - 1
+    hd = rank if hd is None else int(hd)
+    unit = 64.0 * (d + hd + rank) * 2.0 ** -53
+    fin = lambda x: x if math.isfinite(x) else None                    # noqa: E731
+    total = lambda rows: math.fsum(x for row in rows for x in row) if all(math.isfinite(x) for row in rows for x in row) \
+        else float("nan")                                              # noqa: E731
+
+    def summary(heads_of, curves):
+        energy, error, n2 = (total([t[h] for h in heads_of]) for t in (qv, ev, nv))
+        objective = error + float(ridge) * n2
+        usable = math.isfinite(energy) and energy > 0
+        out = {"energy": fin(energy), "error": fin(error), "objective": fin(objective),
+               "relative_error": error / energy if usable and math.isfinite(error) else None,
+               "noise_floor": unit * energy if usable else None}
+        if curves is not None:
+            at, top = math.fsum(c[rank] for c in curves), math.fsum(c[0] for c in curves)
+            ok = math.isfinite(at) and math.isfinite(top) and top > 0
+            out["predicted_objective"] = at if ok else None
+            out["excess_over_curve"] = (objective - at) / top if ok and math.isfinite(objective) else None
+        return out
+
+    heads = []
+    for g in range(n_kv):
+        m = summary(range(g * group, (g + 1) * group), None if cv is None else [cv[g]])
+        if cv is not None:
+            c = cv[g]
+            ok = math.isfinite(c[0]) and c[0] > 0 and all(math.isfinite(x) for x in c)
+            m["relative_curve"] = [x / c[0] for x in c] if ok else None
+            # (non-increasing: the first rank at or under the target)
+            m["rank_for_rel_error"] = {"%g" % t: (next(r for r, x in enumerate(c) if x / c[0] <= t) if ok else None)
+                                       for t in VO_ERROR_TARGETS}
+        heads.append(m)
+    out = {"rank": rank, "n_kv": n_kv, **summary(range(n_heads), cv), "heads": heads}
+    ratios = []
+    for h in range(n_heads):
+        eh, qh = math.fsum(ev[h]) if all(map(math.isfinite, ev[h])) else float("nan"), \
+            math.fsum(qv[h]) if all(map(math.isfinite, qv[h])) else float("nan")
+        if math.isfinite(eh) and math.isfinite(qh) and qh > 0:
+            ratios.append((eh / qh, -h))
+    worst = max(ratios) if ratios and out["relative_error"] is not None else None
+    out["worst_head"] = None if worst is None else -worst[1]
+    out["worst_head_relative_error"] = None if worst is None else worst[0]
+    chan = None
+    if worst is not None:
+        h = -worst[1]
+        per = [(ek / qk, -k) for k, (ek, qk) in enumerate(zip(ev[h], qv[h])) if qk > 0]
+        chan = max(per) if per else None
+    out["worst_channel"] = None if chan is None else -chan[1]
+    out["worst_channel_relative_error"] = None if chan is None else chan[0]
+    return out
 
 
 def rope_gather(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor], n_heads: int,
