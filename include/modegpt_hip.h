@@ -44,7 +44,9 @@ extern "C" {
                                 added under 9: mdg_nystrom_rank_curve_ws_bytes, mdg_nystrom_rank_curve (the Nystrom refit's error at every rank);
                                 added under 9: mdg_mlp_output_error_ws_bytes, mdg_mlp_output_error (the stored down projection's realised output error);
                                 added under 9: mdg_vo_output_error_ws_bytes, mdg_vo_output_error, mdg_vo_rank_curve_ws_bytes, mdg_vo_rank_curve
-                                (what the stored V/O factors lose of the attention output, and the truncation's cost at every rank) */
+                                (what the stored V/O factors lose of the attention output, and the truncation's cost at every rank);
+                                changed under 9: mdg_nystrom_down_ws_bytes is larger (the compacted operands of the product over the
+                                unselected columns, see mdg_nystrom_down); no signature changed */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -365,13 +367,27 @@ int mdg_gather_rows_16(const void* src, int64_t ld_src, const int64_t* rows, int
  * MDG_BF16, or MDG_F64 for checkpoints in another precision (fp16 OPT: the caller widens exactly, as the reference's
  * .to(float64) does).
  * compress_mlp.py:52-62,97.  down_f64 (optional, [r, d] row-major) receives the fp64 solution before the
- * cast.  ws: mdg_nystrom_down_ws_bytes(n, r, d).  SYNCHRONISES. */
+ * cast; down_out is the cast of exactly those values.
+ * Evaluated as (k = idx, k' = its complement in 0 .. n-1 in ascending order, M = C_kk + eps I, so M^-1 C_kk = I - eps M^-1):
+ *     W_d[:,k]^T + M^-1 ( C[k,k'] W_d[:,k']^T - eps_p W_d[:,k]^T ),      eps_p = fl(c_pp + eps) - c_pp  (what fp64 really added)
+ * -- the selected columns' share of C[k,:] W_d^T is the weights themselves, exactly; only the n - r unselected columns of C are
+ * multiplied (2 r (n - r) d flop instead of 2 r n d), in a fixed order: the result does not depend on the order of the launches
+ * and is the same bits from call to call.  r == n: no product at all; eps == 0 then returns W_d^T entry for entry.
+ * PRECONDITION: the entries of idx are distinct and in 0 .. n-1 (any order).  A repeated index makes C_kk singular up to eps
+ * already; the result is then unspecified (nothing is written out of bounds: the complement list is cut at n - r entries, and
+ * an entry outside 0 .. n-1 names no column of the complement).
+ * ws: mdg_nystrom_down_ws_bytes(n, r, d) = 8 (r r' + mdg_potrf_inv_diag_elems(r) + r d) + mdg_potrs_lower_ws_bytes(r, d), r' = r
+ * rounded up to 16 -- C_kk, its inverted diagonal blocks, the right-hand side, the substitution's workspace -- rounded up to 16,
+ * + 16 + 8 r K' + 8 d K' + 8 (n - r) + 4 n, each term rounded up to 16: C[k,k'] as fp64 [r][K'], W_d[:,k'] as [d][K'] in W_d's
+ * own dtype (sized for fp64), the complement list and its marks; K' = n - r rounded up to 16, the padding columns written as
+ * zeros by the call (the workspace may hold anything).  SYNCHRONISES. */
 size_t mdg_nystrom_down_ws_bytes(int64_t n, int64_t r, int64_t d);
 int mdg_nystrom_down(const double* C, int64_t n, int64_t ldc, const int64_t* idx, int64_t r, const void* Wd,
                      int64_t d, int64_t ld_wd, int w_dtype, double eps, void* down_out, int64_t ld_out, double* down_f64,
                      void* ws, size_t ws_bytes, void* stream);
-/* The same with the gathered cross product C[idx,:] W_d^T on `side_stream`, beside the factorisation of C_kk on `stream` (they do
- * not depend on each other; the factorisation's 128-column steps leave most of the chip idle between their GEMMs).  Streams and the
+/* The same with the cross product C[k,k'] W_d[:,k']^T on `side_stream`, beside the factorisation of C_kk on `stream` (they do
+ * not depend on each other; the factorisation's 128-column steps leave most of the chip idle between their GEMMs); the complement
+ * list, the compaction of both operands and the -eps W right-hand side run on `side_stream` in front of the product.  Streams and the
  * two events are the CALLER'S (any two hipEvent_t, timing disabled is fine): ev_fork is recorded on `stream` and waited for by
  * `side_stream` before the product, ev_join is recorded behind the product and waited for by `stream` before the solve; when the
  * call returns everything later on `stream` is ordered behind both.  Results are bit-identical to mdg_nystrom_down. */

@@ -86,14 +86,31 @@ if "phases" in which:
     print(f"potrs_lower n={r} nrhs={d}: {t*1e3:.1f} ms  {2*r*r*d/t/1e12:.1f} TF")
     Wd = (torch.randn(d, n, device=dev, generator=g) * 0.02).to(torch.bfloat16)
     idx = torch.sort(torch.randperm(n, device=dev)[:r]).values
-    Xc = torch.empty(r, d, device=dev, dtype=F64)
-    t = timeit(lambda: ops.gemm(S, Wd, Xc, trans_b=True, a_rows=idx), n=2)
-    print(f"cross term [{r} x {n}] gathered rows x W_d^T [{n} x {d}]: {t*1e3:.1f} ms  {2*r*n*d/t/1e12:.1f} TF")
-    t = timeit(lambda: ops.gemm(S, Wd.to(F64), Xc, trans_b=True, a_rows=idx), n=2)
-    print(f"   the same with W_d widened to fp64 first (the conversion included): {t*1e3:.1f} ms")
-    Wt = Wd.to(F64).t().contiguous()
-    t = timeit(lambda: ops.gemm(S, Wt, Xc, a_rows=idx), n=2)
-    print(f"   W_d^T as a row-major fp64 [n x d] matrix (conversion and transpose NOT included): {t*1e3:.1f} ms")
+    # the refit's product runs over the UNSELECTED columns only: C[k,k'] and W_d[:,k'] compacted to a pitch of
+    # n - r rounded up to 16, added onto the -eps W right-hand side (beta = 1)
+    comp = torch.ones(n, dtype=torch.bool, device=dev); comp[idx] = False
+    comp = comp.nonzero().flatten()
+    Kp = (n - r + 15) // 16 * 16
+    Cb = torch.zeros(r, Kp, device=dev, dtype=F64); Cb[:, :n - r] = S[idx][:, comp]
+    Wb = torch.zeros(d, Kp, device=dev, dtype=torch.bfloat16); Wb[:, :n - r] = Wd[:, comp]
+    Xc = torch.zeros(r, d, device=dev, dtype=F64)
+    tg = timeit(lambda: ops.gemm(Cb, Wb, Xc, beta=1.0, trans_b=True), n=2)
+    print(f"complement product [{r} x {Kp}] x W_d[:,k']^T [{Kp} x {d}]: {tg*1e3:.1f} ms  {2*r*Kp*d/tg/1e12:.1f} TF")
+    del Cb, Wb
+    ops.NYSTROM_OVERLAP = False
+    tn = timeit(lambda: ops.nystrom_down(S, idx, Wd, eps=1e-4), n=2)
+    tf = timeit(lambda: (Ar.copy_(S[:r, :r]), Ar.diagonal().add_(1e-4), ops.potrf_lower(Ar)), n=2) \
+        - timeit(lambda: (Ar.copy_(S[:r, :r]), Ar.diagonal().add_(1e-4)), n=2)
+    print(f"nystrom_down, one stream: {tn*1e3:.1f} ms; less potrf {tf*1e3:.1f}, potrs {t*1e3:.1f} and the product {tg*1e3:.1f}: "
+          f"{(tn-tf-t-tg)*1e3:.1f} ms of gather, complement list, compaction, right-hand side and transpose-cast")
+if "nystrom" in which:          # the whole refit call, plain and with the product beside the factorisation (also for a kernel trace)
+    Wd = (torch.randn(d, n, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+    idx = torch.sort(torch.randperm(n, device=dev, generator=g)[:r]).values
+    for overlap in (False, True):
+        ops.NYSTROM_OVERLAP = overlap
+        ts = [timeit(lambda: ops.nystrom_down(S, idx, Wd, eps=1e-4), n=3) for _ in range(3)]
+        print(f"nystrom_down n={n} r={r} d={d} {'overlapped' if overlap else 'plain'}: "
+              + " ".join(f"{x*1e3:.2f}" for x in ts) + " ms")
 if "gemm" in which:
     A = torch.randn(n, n, device=dev, generator=g, dtype=F64)
     C = torch.zeros(n, n, device=dev, dtype=F64)
