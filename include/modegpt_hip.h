@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MDG_ABI_VERSION 9 /* 2: w_dtype on mdg_nystrom_down / mdg_vo_compress, mdg_rope_gather added; 3: mdg_cov_accum_i8_stats added;
+#define MDG_ABI_VERSION 10 /* 2: w_dtype on mdg_nystrom_down / mdg_vo_compress, mdg_rope_gather added; 3: mdg_cov_accum_i8_stats added;
                              4: mdg_cov_accum_i8 chooses its route on the device (route_counts argument, no host synchronisation);
                                 mdg_comm_* / mdg_allgather_layers added;
                              5: mdg_potrs_lower takes a workspace (mdg_potrs_lower_ws_bytes);
@@ -46,7 +46,8 @@ extern "C" {
                                 added under 9: mdg_vo_output_error_ws_bytes, mdg_vo_output_error, mdg_vo_rank_curve_ws_bytes, mdg_vo_rank_curve
                                 (what the stored V/O factors lose of the attention output, and the truncation's cost at every rank);
                                 changed under 9: mdg_nystrom_down_ws_bytes is larger (the compacted operands of the product over the
-                                unselected columns, see mdg_nystrom_down); no signature changed */
+                                unselected columns, see mdg_nystrom_down); no signature changed;
+                             10: mdg_rope_gather_plan added (the rotary kernel's dispatch as a device-free function) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -611,6 +612,31 @@ int mdg_sqrt_psd_large(const double* M, int64_t n, int64_t ld, double ridge, int
 int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r, int hd,
                     const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
                     const void* norm_w, double eps, void* out, void* stream);
+
+/* What mdg_rope_gather would launch for the same arguments: its whole dispatch, computed from the shapes, the dtype and the
+ * operands' ADDRESSES taken as integers.  Nothing is dereferenced and no device is needed, so the pointers may be synthetic
+ * (only their alignment and, for mask / norm_w, whether they are NULL matter).  mdg_rope_gather calls the same function and
+ * launches exactly this plan.  Refuses what mdg_rope_gather refuses (except NULL operands); B == 0 or T == 0 gives all zeros.
+ * plan[MDG_ROPE_PLAN_LEN]:
+ *    [0] route      0 = direct kernel (rope_gather_kernel<DT, VEC, NORM, HPT>), 1 = LDS tile kernel (rope_tile_kernel<DT, NORM, HALF_EVEN>)
+ *    [1] hpt        query heads of one kv head per thread group: 4, 2 or 1 (the tile kernel's CH)
+ *    [2] vec        elements per pack of the direct kernel, 4 or 2; 1 on the tile route
+ *    [3] norm       1 when norm_w is given
+ *    [4] half_even  tile route: r / 2 is even (HALF_EVEN); 0 on the direct route
+ *    [5] iters      direct route: passes over a row, ceil(r / 2 / (16 * vec)); > 1 with norm = the sum-of-squares pre-pass; 0 on the tile route
+ *    [6] one_shot   direct route: a cos / sin row is one 16-byte load per lane and is staged through registers
+ *    [7] cs_vec16   cos / sin rows are 16-byte aligned and a multiple of 16 bytes long
+ *    [8] nw_vec16   norm_w is given and 16-byte aligned
+ *    [9] tt         tokens per workgroup: 64 / hpt on the direct route; on the tile route halved from there until the tile fits 64 KB of LDS
+ *   [10] wi  [11] wo  tile route: chunk bytes of the copies in / out (16, 8, 4 or 2, never below the element size); 0 on the direct route
+ *   [12] hp1        tile route: ceil(r / 4) == 1, the row index is the item index (no magic division)
+ *   [13] lds        dynamic LDS bytes of the launch   [14] lds_attr  1 when they exceed 64 KB (the launch raises the kernel's limit first)
+ *   [15..17] grid x, y, z = (8 * n_kv, ceil(n_tiles / 8), (n_heads / n_kv) / hpt); 256 threads per workgroup
+ *   [18] t_tiles    token tiles per batch, ceil(T / tt)   [19] n_tiles = B * t_tiles */
+#define MDG_ROPE_PLAN_LEN 20
+int mdg_rope_gather_plan(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r, int hd,
+                         const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
+                         const void* norm_w, double eps, void* out, void* stream, int64_t* plan);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -29,7 +29,7 @@ class CovProblem(C.Structure):
                 ("ld_sigma", _i64), ("sigma_batch_stride", _i64)]
 
 
-ABI_VERSION = 9   # include/modegpt_hip.h MDG_ABI_VERSION this binding table was written against
+ABI_VERSION = 10  # include/modegpt_hip.h MDG_ABI_VERSION this binding table was written against
 
 # name -> (restype, argtypes); must list every symbol the header declares (tests/test_abi.py checks it)
 SIGNATURES = {
@@ -98,6 +98,8 @@ SIGNATURES = {
     "mdg_sqrt_psd_large": (_i32, [_ptr, _i64, _i64, _f64, _i32, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     "mdg_rope_gather": (_i32, [_ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _i64, _ptr, _ptr, _f64,
                                 _ptr, _ptr]),
+    "mdg_rope_gather_plan": (_i32, [_ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _i64, _ptr, _ptr, _f64,
+                                     _ptr, _ptr, C.POINTER(_i64)]),
     "mdg_comm_unique_id": (_i32, [_ptr]),
     "mdg_comm_init": (_i32, [C.POINTER(_ptr), _i32, _i32, _ptr]),
     "mdg_allgather_layers": (_i32, [_ptr, _ptr, _sz, _ptr, _ptr]),

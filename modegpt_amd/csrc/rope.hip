@@ -45,7 +45,13 @@ template <> struct Lp<MDG_BF16> {
 template <> struct Lp<MDG_F16> {
   typedef f16_t T;
   static __device__ __forceinline__ float up(T v) { return (float)__builtin_bit_cast(_Float16, v); }
-  static __device__ __forceinline__ T down(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+  // The empty asm hides where f came from.  Without it the compiler may select "f16(a * b)" as a mixed-precision FMA with
+  // an addend of +0, and (-0) + (+0) = +0: a product that is -0 (an all-zero row, a zero norm weight) lost its sign, and
+  // with it the sign of a zero result (the tile kernel with an odd half returned -0 where torch has +0).
+  static __device__ __forceinline__ T down(float f) {
+    asm("" : "+v"(f));
+    return __builtin_bit_cast(unsigned short, (_Float16)f);
+  }
 };
 template <> struct Lp<MDG_F32> {
   typedef float T;
@@ -78,6 +84,13 @@ struct RopeArgs {
   int nw_vec16;     // so is the norm weight
 };
 
+// Decisions the kernels and the host plan (rope_plan below) both take: one definition each, so they cannot drift.
+__host__ __device__ __forceinline__ int gather_iters(int half, int vec) { return (half + GROUP * vec - 1) / (GROUP * vec); }
+// a cos / sin row is exactly one 16-byte load per lane of the thread group
+__host__ __device__ __forceinline__ bool gather_one_shot(int cs_vec16, int hd, int per16) { return cs_vec16 && hd == GROUP * per16; }
+// tile kernel: items (two adjacent pairs) per row
+__host__ __device__ __forceinline__ int tile_hp(int half) { return (half + 1) >> 1; }
+
 template <typename E, int VEC> struct alignas(sizeof(E) * VEC) Pack { E v[VEC]; };
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // 16-byte register quad (HIP's uint4 is a union: it ends up in scratch)
 
@@ -102,7 +115,7 @@ __global__ __launch_bounds__(256) void rope_gather_kernel(RopeArgs a) {
   const int64_t t0 = (int64_t)(tile - bu * (unsigned)a.t_tiles) * (ROWS * TPT) + (threadIdx.x / GROUP);
   const int l = threadIdx.x % GROUP;
   const int half = a.r >> 1;
-  const int iters = (half + GROUP * VEC - 1) / (GROUP * VEC);
+  const int iters = gather_iters(half, VEC);
   const int64_t* mrow = a.mask ? a.mask + (int64_t)hk * a.r : nullptr;
   const E* nw = (const E*)a.norm_w;
 
@@ -148,7 +161,7 @@ __global__ __launch_bounds__(256) void rope_gather_kernel(RopeArgs a) {
   E* cs_lds = (E*)lds_raw;
   E* nw_lds = cs_lds + (size_t)ROWS * TPT * 2 * a.hd;
   constexpr int PER16 = 16 / (int)sizeof(E);
-  const bool one_shot = a.cs_vec16 && a.hd == GROUP * PER16;
+  const bool one_shot = gather_one_shot(a.cs_vec16, a.hd, PER16);
   u32x4 creg[TPT], sreg[TPT], wreg;
   if (one_shot) {
 #pragma unroll
@@ -305,6 +318,8 @@ static size_t tile_lds_bytes(int tt, int ch, int r, int hd, size_t es) {
   return 2 * al16((size_t)tt * ch * r * es) + al16((size_t)tt * 2 * hd * es) + al16((size_t)hd * es) +
          al16((size_t)tt * ch * sizeof(float)) + al16((size_t)r * sizeof(short));
 }
+// direct kernel: the cos and sin rows of the workgroup's ROWS * TPT tokens, then the norm weight
+static size_t gather_lds_bytes(int hpt, int hd, size_t es) { return ((size_t)ROWS * (UNITS / hpt) * 2 + 1) * hd * es; }
 
 template <int W> struct ChunkT;
 template <> struct ChunkT<16> { typedef u32x4 type; };
@@ -423,7 +438,7 @@ __global__ __launch_bounds__(256) void rope_tile_kernel(TileArgs ta) {
   }
 
   // ---- rotate: one (row, two adjacent pairs) item per lane and step; row = token * CH + head
-  const int hp = (half + 1) >> 1;
+  const int hp = tile_hp(half);
   const int items = rows * hp;
   const int ch_shift = CH == 4 ? 2 : CH == 2 ? 1 : 0;
   // IT items per lane in flight: the rotate step is a chain of dependent LDS reads (mask -> table, row -> math), so the
@@ -528,7 +543,7 @@ __global__ __launch_bounds__(256) void rope_tile_kernel(TileArgs ta) {
               (const unsigned char*)xout, (size_t)TT * r * sizeof(E), CH, tv * r * (int)sizeof(E));
 }
 
-template <int DT> hipError_t launch_rope_tile(const TileArgs& ta, dim3 grid, size_t lds, hipStream_t st) {
+template <int DT> hipError_t launch_rope_tile(const TileArgs& ta, bool even, dim3 grid, size_t lds, hipStream_t st) {
   auto launch = [&](auto kernel) -> hipError_t {
     if (lds > 64 * 1024) {
       hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -537,13 +552,11 @@ template <int DT> hipError_t launch_rope_tile(const TileArgs& ta, dim3 grid, siz
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, ta);
     return hipSuccess;
   };
-  const bool even = (ta.a.r / 2) % 2 == 0;
   if (ta.a.norm_w) return even ? launch(rope_tile_kernel<DT, true, true>) : launch(rope_tile_kernel<DT, true, false>);
   return even ? launch(rope_tile_kernel<DT, false, true>) : launch(rope_tile_kernel<DT, false, false>);
 }
 
-template <int DT, int VEC, int HPT> hipError_t launch_rope(const RopeArgs& a, dim3 grid, hipStream_t st) {
-  const size_t lds = ((size_t)ROWS * (UNITS / HPT) * 2 + 1) * a.hd * sizeof(typename Lp<DT>::T);
+template <int DT, int VEC, int HPT> hipError_t launch_rope(const RopeArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   auto launch = [&](auto kernel) -> hipError_t {
     if (lds > 64 * 1024) {  // fp32 tables of a 256-wide head with one head per thread group: above the default window
       hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -555,27 +568,40 @@ template <int DT, int VEC, int HPT> hipError_t launch_rope(const RopeArgs& a, di
   return a.norm_w ? launch(rope_gather_kernel<DT, VEC, true, HPT>) : launch(rope_gather_kernel<DT, VEC, false, HPT>);
 }
 
-template <int DT, int VEC> hipError_t launch_rope_hpt(const RopeArgs& a, int hpt, dim3 grid, hipStream_t st) {
-  if (hpt == 4) return launch_rope<DT, VEC, 4>(a, grid, st);
-  if (hpt == 2) return launch_rope<DT, VEC, 2>(a, grid, st);
-  return launch_rope<DT, VEC, 1>(a, grid, st);
+template <int DT, int VEC> hipError_t launch_rope_hpt(const RopeArgs& a, int hpt, dim3 grid, size_t lds, hipStream_t st) {
+  if (hpt == 4) return launch_rope<DT, VEC, 4>(a, grid, lds, st);
+  if (hpt == 2) return launch_rope<DT, VEC, 2>(a, grid, lds, st);
+  return launch_rope<DT, VEC, 1>(a, grid, lds, st);
 }
 
-
-template <int DT> hipError_t launch_rope_vec(const RopeArgs& a, int vec, int hpt, dim3 grid, hipStream_t st) {
-  if (vec == 4) return launch_rope_hpt<DT, 4>(a, hpt, grid, st);
-  return launch_rope_hpt<DT, 2>(a, hpt, grid, st);
+template <int DT> hipError_t launch_rope_vec(const RopeArgs& a, int vec, int hpt, dim3 grid, size_t lds, hipStream_t st) {
+  if (vec == 4) return launch_rope_hpt<DT, 4>(a, hpt, grid, lds, st);
+  return launch_rope_hpt<DT, 2>(a, hpt, grid, lds, st);
 }
 
-}  // namespace
-}  // namespace mdg
+// ---------------------------------------------------------------- the dispatch, as a function of shapes and addresses alone
+// Everything mdg_rope_gather decides before it launches.  Takes the operands' addresses as integers and dereferences
+// nothing, so it runs without a device (mdg_rope_gather_plan); mdg_rope_gather launches exactly what it returns.
+struct RopePlan {
+  int tile;                // 0: rope_gather_kernel, 1: rope_tile_kernel
+  int hpt;                 // query heads of one kv head per thread group (direct) / per workgroup (tile: CH)
+  int vec;                 // elements per pack of the direct kernel; 1 on the tile route
+  int half_even;           // tile kernel's HALF_EVEN
+  int iters, one_shot;     // direct kernel: passes over the row, cos / sin staged from registers
+  int cs_vec16, nw_vec16;
+  int tt;                  // tokens per workgroup
+  int wi, wo;              // tile kernel: chunk bytes of the copies in / out
+  int hp1;                 // tile kernel: one item per row (the magic division is bypassed)
+  unsigned half_magic;
+  size_t lds;
+  int t_tiles, chunks;
+  unsigned n_tiles;
+  dim3 grid;
+};
 
-using namespace mdg;
-
-extern "C" int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r,
-                               int hd, const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
-                               const void* norm_w, double eps, void* out, void* stream) {
-  MDG_CLEAR();
+static int rope_plan(uintptr_t x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r, int hd,
+                     uintptr_t cos, uintptr_t sin, int64_t cs_batch_stride, uintptr_t mask, uintptr_t norm_w, uintptr_t out,
+                     RopePlan& p) {
   MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16 || dtype == MDG_F32, "mdg_rope_gather: dtype %d (bf16, f16 or f32)",
                 dtype);
   MDG_CHECK_ARG(B >= 0 && T >= 0, "mdg_rope_gather: negative extent");
@@ -588,48 +614,43 @@ extern "C" int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B
                 (long long)n_heads * r);
   MDG_CHECK_ARG(cs_batch_stride == 0 || cs_batch_stride >= T * hd, "mdg_rope_gather: cos/sin batch stride %lld",
                 (long long)cs_batch_stride);
-  if (B == 0 || T == 0) return MDG_OK;
-  MDG_CHECK_ARG(x && cos && sin && out, "mdg_rope_gather: null pointer");
-  RopeArgs a;
-  a.x = x; a.ld_x = ld_x; a.B = B; a.T = T; a.n_heads = n_heads; a.group = n_heads / n_kv; a.r = r; a.hd = hd;
-  a.cos = cos; a.sin = sin; a.cs_bstride = cs_batch_stride; a.mask = mask; a.norm_w = norm_w; a.eps = (float)eps; a.out = out;
-  const int hpt = a.group % 4 == 0 ? 4 : a.group % 2 == 0 ? 2 : 1;  // query heads of one kv head per thread group
-  a.n_kv = n_kv;
-  a.chunks = a.group / hpt;
-  a.t_tiles = (int)ceil_div(T, ROWS * (UNITS / hpt));
-  a.n_tiles = (unsigned)(B * a.t_tiles);
-  const int64_t tiles8 = ceil_div(B * a.t_tiles, N_XCD);
-  MDG_CHECK_ARG(tiles8 <= 65535 && (int64_t)n_kv * N_XCD <= 0x7fffffff && a.chunks <= 65535,
+  p = RopePlan();
+  const int group = n_heads / n_kv;
+  const int hpt = group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 1;  // query heads of one kv head per thread group
+  p.hpt = hpt;
+  p.chunks = group / hpt;
+  p.tt = ROWS * (UNITS / hpt);
+  p.t_tiles = (int)ceil_div(T, p.tt);
+  p.n_tiles = (unsigned)(B * p.t_tiles);
+  const int64_t tiles8 = ceil_div(B * p.t_tiles, N_XCD);
+  MDG_CHECK_ARG(tiles8 <= 65535 && (int64_t)n_kv * N_XCD <= 0x7fffffff && p.chunks <= 65535,
                 "mdg_rope_gather: B*T = %lld tokens exceed one launch (%d tokens per workgroup row, 65535 * 8 rows)",
-                (long long)(B * T), ROWS * (UNITS / hpt));
+                (long long)(B * T), p.tt);
   const size_t es = dtype_size(dtype);
-  a.cs_vec16 = ((uintptr_t)cos % 16 == 0 && (uintptr_t)sin % 16 == 0 && (hd * es) % 16 == 0 &&
-                (cs_batch_stride * es) % 16 == 0)
-                   ? 1
-                   : 0;
-  a.nw_vec16 = norm_w && (uintptr_t)norm_w % 16 == 0;
+  p.cs_vec16 = (cos % 16 == 0 && sin % 16 == 0 && (hd * es) % 16 == 0 && (cs_batch_stride * es) % 16 == 0) ? 1 : 0;
+  p.nw_vec16 = norm_w && norm_w % 16 == 0;
   const int half = r / 2;
-  hipStream_t st = (hipStream_t)stream;
   int vec = 4;  // elements per pack of the direct kernel
-  while (vec > 1 && (half % vec || ld_x % vec || ((uintptr_t)x | (uintptr_t)out) % (es * vec) ||
-                     (mask && (uintptr_t)mask % (8 * vec))))
-    vec >>= 1;
+  while (vec > 1 && (half % vec || ld_x % vec || (x | out) % (es * vec) || (mask && mask % (8 * vec)))) vec >>= 1;
   // Packs of the rotate_half partners straight from / to memory when they are at least 4 bytes.  Measured on
   // [16, 2048, 32 x r] bf16, direct vs LDS route: r = 88 (8-byte packs) 84 vs 113 us; r = 76 (4-byte) 105 vs 99 us, a tie;
   // r = 102 (2-byte) 199 vs 132 us.  MDG_ROPE_TILE=1 forces the LDS route (experiment knob of scripts/bench_kernels.py).
   if (vec > 1 && !MDG_KNOB("MDG_ROPE_TILE")) {
-    const dim3 grid((unsigned)(N_XCD * n_kv), (unsigned)tiles8, (unsigned)a.chunks);
-    if (dtype == MDG_BF16) MDG_HIP(launch_rope_vec<MDG_BF16>(a, vec, hpt, grid, st));
-    else if (dtype == MDG_F16) MDG_HIP(launch_rope_vec<MDG_F16>(a, vec, hpt, grid, st));
-    else MDG_HIP(launch_rope_vec<MDG_F32>(a, vec, hpt, grid, st));
-  } else {       // through LDS (see rope_tile_kernel)
-    TileArgs ta;
+    p.vec = vec;
+    p.iters = gather_iters(half, vec);
+    p.one_shot = gather_one_shot(p.cs_vec16, hd, 16 / (int)es) ? 1 : 0;
+    p.lds = gather_lds_bytes(hpt, hd, es);
+    p.grid = dim3((unsigned)(N_XCD * n_kv), (unsigned)tiles8, (unsigned)p.chunks);
+  } else {  // through LDS (see rope_tile_kernel)
+    p.tile = 1;
+    p.vec = 1;
     int tt = 64 / hpt;
     while (tt > 1 && tile_lds_bytes(tt, hpt, r, hd, es) > 64 * 1024) tt >>= 1;
-    const size_t lds = tile_lds_bytes(tt, hpt, r, hd, es);
-    a.t_tiles = (int)ceil_div(T, tt);
-    a.n_tiles = (unsigned)(B * a.t_tiles);
-    const int64_t t8 = ceil_div(B * a.t_tiles, N_XCD);
+    p.tt = tt;
+    p.lds = tile_lds_bytes(tt, hpt, r, hd, es);
+    p.t_tiles = (int)ceil_div(T, tt);
+    p.n_tiles = (unsigned)(B * p.t_tiles);
+    const int64_t t8 = ceil_div(B * p.t_tiles, N_XCD);
     MDG_CHECK_ARG(t8 <= 65535, "mdg_rope_gather: B*T = %lld tokens exceed one launch (%d tokens per workgroup, 65535 * 8)",
                   (long long)(B * T), tt);
     auto widest = [&](uintptr_t base, size_t stride_a, size_t stride_b) {
@@ -637,16 +658,71 @@ extern "C" int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B
       while (w > (int)es && (base % w || stride_a % w || stride_b % w)) w >>= 1;
       return w;
     };
+    p.half_even = half % 2 == 0;
+    p.wi = widest(x, (size_t)ld_x * es, (size_t)hpt * r * es);
+    p.wo = widest(out, (size_t)T * r * es, (size_t)tt * r * es);
+    p.hp1 = tile_hp(half) == 1;
+    p.half_magic = (unsigned)((1ull << 32) / (unsigned)tile_hp(half)) + 1u;  // items index (row, pair of pairs)
+    p.grid = dim3((unsigned)(N_XCD * n_kv), (unsigned)t8, (unsigned)p.chunks);
+  }
+  return MDG_OK;
+}
+
+}  // namespace
+}  // namespace mdg
+
+using namespace mdg;
+
+extern "C" int mdg_rope_gather_plan(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r,
+                                    int hd, const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
+                                    const void* norm_w, double eps, void* out, void* stream, int64_t* plan) {
+  (void)eps;
+  (void)stream;
+  MDG_CHECK_ARG(plan, "mdg_rope_gather_plan: null plan");
+  RopePlan p;
+  MDG_TRY(rope_plan((uintptr_t)x, dtype, ld_x, B, T, n_heads, n_kv, r, hd, (uintptr_t)cos, (uintptr_t)sin, cs_batch_stride,
+                    (uintptr_t)mask, (uintptr_t)norm_w, (uintptr_t)out, p));
+  const int64_t v[MDG_ROPE_PLAN_LEN] = {p.tile, p.hpt, p.vec, norm_w != nullptr, p.half_even, p.iters, p.one_shot, p.cs_vec16,
+                                        p.nw_vec16, p.tt, p.wi, p.wo, p.hp1, (int64_t)p.lds, p.lds > 64 * 1024, p.grid.x,
+                                        p.grid.y, p.grid.z, p.t_tiles, p.n_tiles};
+  for (int i = 0; i < MDG_ROPE_PLAN_LEN; i++) plan[i] = (B == 0 || T == 0) ? 0 : v[i];  // an empty call launches nothing
+  return MDG_OK;
+}
+
+extern "C" int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r,
+                               int hd, const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
+                               const void* norm_w, double eps, void* out, void* stream) {
+  MDG_CLEAR();
+  RopePlan p;
+  MDG_TRY(rope_plan((uintptr_t)x, dtype, ld_x, B, T, n_heads, n_kv, r, hd, (uintptr_t)cos, (uintptr_t)sin, cs_batch_stride,
+                    (uintptr_t)mask, (uintptr_t)norm_w, (uintptr_t)out, p));
+  if (B == 0 || T == 0) return MDG_OK;
+  MDG_CHECK_ARG(x && cos && sin && out, "mdg_rope_gather: null pointer");
+  RopeArgs a;
+  a.x = x; a.ld_x = ld_x; a.B = B; a.T = T; a.n_heads = n_heads; a.group = n_heads / n_kv; a.r = r; a.hd = hd;
+  a.cos = cos; a.sin = sin; a.cs_bstride = cs_batch_stride; a.mask = mask; a.norm_w = norm_w; a.eps = (float)eps; a.out = out;
+  a.n_kv = n_kv;
+  a.chunks = p.chunks;
+  a.t_tiles = p.t_tiles;
+  a.n_tiles = p.n_tiles;
+  a.cs_vec16 = p.cs_vec16;
+  a.nw_vec16 = p.nw_vec16;
+  hipStream_t st = (hipStream_t)stream;
+  if (!p.tile) {
+    if (dtype == MDG_BF16) MDG_HIP(launch_rope_vec<MDG_BF16>(a, p.vec, p.hpt, p.grid, p.lds, st));
+    else if (dtype == MDG_F16) MDG_HIP(launch_rope_vec<MDG_F16>(a, p.vec, p.hpt, p.grid, p.lds, st));
+    else MDG_HIP(launch_rope_vec<MDG_F32>(a, p.vec, p.hpt, p.grid, p.lds, st));
+  } else {
+    TileArgs ta;
     ta.a = a;
-    ta.ch = hpt;
-    ta.tt = tt;
-    ta.wi = widest((uintptr_t)x, (size_t)ld_x * es, (size_t)hpt * r * es);
-    ta.wo = widest((uintptr_t)out, (size_t)T * r * es, (size_t)tt * r * es);
-    ta.half_magic = (unsigned)((1ull << 32) / (unsigned)((half + 1) / 2)) + 1u;   // items index (row, pair of pairs)
-    const dim3 grid((unsigned)(N_XCD * n_kv), (unsigned)t8, (unsigned)a.chunks);
-    if (dtype == MDG_BF16) MDG_HIP(launch_rope_tile<MDG_BF16>(ta, grid, lds, st));
-    else if (dtype == MDG_F16) MDG_HIP(launch_rope_tile<MDG_F16>(ta, grid, lds, st));
-    else MDG_HIP(launch_rope_tile<MDG_F32>(ta, grid, lds, st));
+    ta.ch = p.hpt;
+    ta.tt = p.tt;
+    ta.wi = p.wi;
+    ta.wo = p.wo;
+    ta.half_magic = p.half_magic;
+    if (dtype == MDG_BF16) MDG_HIP(launch_rope_tile<MDG_BF16>(ta, p.half_even, p.grid, p.lds, st));
+    else if (dtype == MDG_F16) MDG_HIP(launch_rope_tile<MDG_F16>(ta, p.half_even, p.grid, p.lds, st));
+    else MDG_HIP(launch_rope_tile<MDG_F32>(ta, p.half_even, p.grid, p.lds, st));
   }
   MDG_LAUNCH_CHECK();
   return MDG_OK;

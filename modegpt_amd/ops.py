@@ -1209,13 +1209,27 @@ def decode_vo_output_error(e, q, dnorm2, ridge: float, rank: int, n_kv: int, cur
     return out
 
 
-def rope_gather(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor], n_heads: int,
-                n_kv: int, head_dim: int, norm_weight: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
-    """Rotary embedding of a compressed q / k projection.  x: [B, T, n_heads*r] (bf16 / f16 / f32, last dim
-    contiguous); cos, sin: [B or 1, T, head_dim]; mask: int64 [n_kv, r] or None; returns [B, n_heads, T, r].
-    With `norm_weight` ([head_dim]) the Qwen3 masked RMSNorm runs first (DenseQwenRebuild.py:262-286)."""
-    _need_gpu(x, cos, sin)
+ROPE_PLAN_FIELDS = ("route", "hpt", "vec", "norm", "half_even", "iters", "one_shot", "cs_vec16", "nw_vec16", "tt", "wi", "wo",
+                    "hp1", "lds", "lds_attr", "grid_x", "grid_y", "grid_z", "t_tiles", "n_tiles")   # include/modegpt_hip.h
+
+
+def rope_plan_at(dtype, B: int, T: int, n_heads: int, n_kv: int, r: int, head_dim: int, ld_x: int, x: int, cos: int, sin: int,
+                 cs_batch_stride: int, mask: Optional[int], norm_weight: Optional[int], out: int) -> dict:
+    """mdg_rope_gather_plan on plain integers: what mdg_rope_gather launches for operands at the ADDRESSES x, cos, sin,
+    mask, norm_weight (None = absent) and out.  Nothing is dereferenced, no device is needed.  "route" is "direct" or
+    "tile", "grid" a tuple; every other field of the header's layout is an int under its name."""
     lib = _lib.load()
+    arr = (C.c_int64 * len(ROPE_PLAN_FIELDS))()
+    check(lib.mdg_rope_gather_plan(x, _DT[dtype], ld_x, B, T, n_heads, n_kv, r, head_dim, cos, sin, cs_batch_stride, mask or None,
+                                   norm_weight or None, 0.0, out, None, arr), "mdg_rope_gather_plan")
+    p = dict(zip(ROPE_PLAN_FIELDS, (int(v) for v in arr)))
+    p["route"] = "tile" if p["route"] else "direct"
+    p["grid"] = (p.pop("grid_x"), p.pop("grid_y"), p.pop("grid_z"))
+    return p
+
+
+def _rope_operands(x, cos, sin, mask, n_heads, n_kv, head_dim, norm_weight, out):
+    """The operands of mdg_rope_gather as it receives them (shared by rope_gather and rope_gather_plan)."""
     B, T, width = x.shape
     r = width // n_heads
     if r * n_heads != width:
@@ -1232,12 +1246,40 @@ def rope_gather(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Opt
         mask = mask.contiguous()
     if norm_weight is not None:
         norm_weight = norm_weight.detach().to(x.dtype).contiguous()
-    out = torch.empty(B, n_heads, T, r, dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, n_heads, T, r, dtype=x.dtype, device=x.device)
+    elif (tuple(out.shape) != (B, n_heads, T, r) or out.dtype != x.dtype or out.device != x.device
+          or not out.is_contiguous()):
+        raise ValueError(f"rope_gather: out must be a contiguous {x.dtype} [{B}, {n_heads}, {T}, {r}] on {x.device}, got "
+                         f"{out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    return x, cos, sin, mask, norm_weight, out, (B, T, r)
+
+
+def rope_gather(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor], n_heads: int,
+                n_kv: int, head_dim: int, norm_weight: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rotary embedding of a compressed q / k projection.  x: [B, T, n_heads*r] (bf16 / f16 / f32, last dim
+    contiguous); cos, sin: [B or 1, T, head_dim]; mask: int64 [n_kv, r] or None; returns [B, n_heads, T, r].
+    With `norm_weight` ([head_dim]) the Qwen3 masked RMSNorm runs first (DenseQwenRebuild.py:262-286).
+    `out`: a caller-owned contiguous [B, n_heads, T, r] tensor of x's dtype to write into (it is returned)."""
+    _need_gpu(x, cos, sin)
+    lib = _lib.load()
+    x, cos, sin, mask, norm_weight, out, (B, T, r) = _rope_operands(x, cos, sin, mask, n_heads, n_kv, head_dim, norm_weight, out)
     with torch.cuda.device(x.device):
         check(lib.mdg_rope_gather(x.data_ptr(), _DT[x.dtype], x.stride(1), B, T, n_heads, n_kv, r, head_dim,
                                   cos.data_ptr(), sin.data_ptr(), 0 if cos.shape[0] == 1 else T * head_dim, _p(mask),
                                   _p(norm_weight), float(eps), out.data_ptr(), _stream(x)), "mdg_rope_gather")
     return out
+
+
+def rope_gather_plan(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor], n_heads: int,
+                     n_kv: int, head_dim: int, norm_weight: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                     out: Optional[torch.Tensor] = None) -> dict:
+    """The kernel variant rope_gather(same arguments) launches, as rope_plan_at's dict.  The plan depends on the operands'
+    alignment: pass the `out` the call will use (without one, the plan is that of a freshly allocated output)."""
+    x, cos, sin, mask, norm_weight, out, (B, T, r) = _rope_operands(x, cos, sin, mask, n_heads, n_kv, head_dim, norm_weight, out)
+    return rope_plan_at(x.dtype, B, T, n_heads, n_kv, r, head_dim, x.stride(1), x.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                        0 if cos.shape[0] == 1 else T * head_dim, _p(mask), _p(norm_weight), out.data_ptr())
 
 
 def cast_transpose(x: torch.Tensor) -> torch.Tensor:
