@@ -96,8 +96,12 @@ int mdg_shutdown(void);
  * columns [b*n_feat, (b+1)*n_feat).  batch=1: replaces `H.T @ H` (LlamaAdapter.py:127-136, model_adapter.py:546-554)
  * and `sum(X.mT @ X, 0)` (LlamaAdapter.py:138-147); batch=n_heads, n_feat=head_dim: replaces the permute + bmm of
  * LlamaAdapter.py:115-125 / model_adapter.py:556-567 without the permute copy.
- * Only the lower triangle of sigma is valid until mdg_cov_finalize mirrors it.
- * relu != 0 applies max(x, 0) on load (OPT fc1 hook).  ws may be NULL when mdg_cov_accum_ws_bytes says 0;
+ * Only the lower triangle of sigma is valid until mdg_cov_finalize mirrors it.  Above the diagonal, the 128 x 128 tiles on the
+ * diagonal are accumulated whole (an entry above the diagonal inside one receives the same sum as its mirror image, added to
+ * whatever it held), the tiles strictly above the diagonal are neither read nor written; the lower triangle depends on neither.
+ * relu != 0 applies max(x, 0) on load (OPT fc1 hook) as v > 0 ? v : 0: -0.0, -Inf and NaN all count as +0.  Without it a
+ * non-finite element reaches row and column j of sigma only (NaN, or +-Inf / NaN as the fp64 sum of products gives), nothing else.
+ * n_tokens == 0 returns MDG_OK without touching sigma (x may be NULL).  ws may be NULL when mdg_cov_accum_ws_bytes says 0;
  * it holds split-K partials (reduced in fixed order -> run-to-run deterministic). */
 size_t mdg_cov_accum_ws_bytes(int64_t n_tokens, int64_t n_feat, int64_t batch);
 int mdg_cov_accum(const void* x, int dtype, int64_t n_tokens, int64_t n_feat, int64_t batch, int64_t ld,
@@ -106,7 +110,9 @@ int mdg_cov_accum(const void* x, int dtype, int64_t n_tokens, int64_t n_feat, in
 /* The same accumulate for up to 4 problems of one calibration batch in ONE launch (the four hooks of a layer:
  * sigma_mlp, sigma_x, sigma_q, sigma_k): the small problems' workgroups fill the slots the large one's last,
  * under-filled round leaves idle.  Put the largest problem first.  Every problem must have n_feat % 128 == 0 and
- * 16-byte aligned rows (otherwise call mdg_cov_accum per problem); no ReLU.  `problems` is a HOST array. */
+ * 16-byte aligned rows (otherwise call mdg_cov_accum per problem); no ReLU.  `problems` is a HOST array.  The problems may
+ * differ in n_tokens (each is split over its own tokens; the same-token rule below is mdg_cov_accum_i8_multi's), every n_tokens
+ * must be > 0, and ld_sigma / sigma_batch_stride may be padded as in mdg_cov_accum. */
 typedef struct {
   const void* x;   /* [n_tokens, >= batch*n_feat], ld elements per token */
   int64_t n_tokens, n_feat, batch, ld;
