@@ -47,7 +47,8 @@ extern "C" {
                                 (what the stored V/O factors lose of the attention output, and the truncation's cost at every rank);
                                 changed under 9: mdg_nystrom_down_ws_bytes is larger (the compacted operands of the product over the
                                 unselected columns, see mdg_nystrom_down); no signature changed;
-                             10: mdg_rope_gather_plan added (the rotary kernel's dispatch as a device-free function) */
+                             10: mdg_rope_gather_plan added (the rotary kernel's dispatch as a device-free function);
+                                added under 10: mdg_qk_rank_curve (what the Q/K pair selection costs the attention logits, per head and rank) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -489,6 +490,57 @@ int mdg_qk_select(const double* cov_q, const double* cov_k, int n_heads, int n_k
 int mdg_qk_select_margin(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q,
                          double ridge_k, int rank, int mode, const int64_t* mask, double eps_rel, double eps_abs,
                          double* out, void* stream);
+
+/* What the Q/K selection costs the attention LOGITS on the calibration statistic, per query head and at EVERY rank (added under ABI
+ * 10; not in the reference, whose scores -- compress_qk.py:355-367, 403-419, 452-464 -- read four diagonal entries of sigma_q / sigma_k
+ * and report nothing about what the selection loses).  mdg_qk_select_margin says whether the selection is DETERMINED; this says what
+ * it LOSES.  Drop the column set D of q and k of one query head: the logit of token pair (i, j) changes by sum_{c in D} q_ic k_jc, and
+ * its mean square over all token pairs of the calibration set is
+ *     E(D) = <C_q[D, D], C_k[D, D]>_F = sum_{a, b in D} P[a][b] ,      P_h = (sigma_q,h + rho_q I) (.) (sigma_k,kv(h) + rho_k I)
+ * (entry-wise product; sigma normalised as mdg_cov_finalize leaves it) -- the CR objective || C_q^1/2 (I - S S^T) C_k^1/2 ||_F^2 that
+ * the reference's scores approximate by its diagonal.  The stored q_proj / k_proj are row gathers (bit copies), so with rho = 0 this
+ * IS the realised error of the artefact on the statistic.  P is PSD (Schur product theorem), so E >= 0 in exact arithmetic; E is NOT
+ * monotone in D (P = [[1, -.81], [-.81, 1]]: 1 with one column dropped, 0.38 with both), and nothing here is clamped or made monotone.
+ * Shapes, modes and argument checks as mdg_qk_select (no rank): cov_q [n_heads, hd, hd], cov_k [n_kv, hd, hd] fp64 contiguous, both
+ * triangles are read; RoPE modes: unit u < ns = hd / 2 is the column pair {u, u + hd / 2}; OPT: unit u < ns = hd is column u.
+ * order (DEVICE, int64 [n_kv][ns]): the units of every kv head, keep-first -- the first ns mask entries per head of mdg_qk_select at
+ * rank = hd (all units, score-descending); nothing is ranked here.  Entries outside 0 .. ns-1 are clamped when read (memory safety
+ * only); for a head whose order is not a permutation the values of that head alone are unspecified.
+ * With g = n_heads / n_kv and D_m = {order[i] : i >= m}, outputs (DEVICE, fp64 unless stated):
+ *   curve_h [n_heads][ns + 1]   curve_h[h][m] = sum_{a, b in cols(D_m)} P_h[a][b]: the error of query head h when the first m units are
+ *                               kept.  [ns] = +0.0 exactly; [0] = the head's whole logit energy <C_q,h, C_k>.
+ *   curve [n_kv][ns + 1]        the group's: curve_h of its heads added in ascending h, ((c_0 + c_1) + c_2) + ..., to the bit.
+ *   terms [n_kv][ns]            (optional) the diagonal share of unit order[i],
+ *                               sum_{h in group} sum_{a in cols(u)} max(Cq_aa + tau_q, 0) max(Ck_aa + tau_k, 0), tau = terms_ridge_q /
+ *                               terms_ridge_k, by the expression and in the order of mdg_qk_select's score (whose GROUPED / OPT score is
+ *                               its square root, the MHA score the number itself; fmax drops a NaN, as there).  Its suffix sums are
+ *                               what the reference's rule believes the cost is.  The ridges of the terms are arguments of their own
+ *                               so that one call gives the error on the raw statistic (rho = 0) and the terms of the real scores.
+ *   scale [n_kv]                (optional) sum_{h in group} sum_{a, b} |P_h[a][b]| = sum_h A_h[0] below: what a reader multiplies the
+ *                               unit roundoff by to get the floor under which a value of this head says nothing.
+ *   greedy_curve [n_kv][ns + 1], greedy_order [n_kv][ns] (int64)   (optional, given together) a comparison order built on the FULL
+ *                               objective: start from nothing dropped and repeatedly drop the unit whose move into D raises the
+ *                               group's E least, Delta_u = B[u][u] + 2 sum_{v in D} B[u][v], B the group's unit-block sums of
+ *                               sum_h P_h (2 B[u][v] is taken as B[u][v] + B[v][u]).  Compared with <, ties to the lower unit index, a
+ *                               NaN increment never wins while another exists.  greedy_order is keep-first (the first unit dropped
+ *                               is last); greedy_curve[m] is E of the group with the first m units of greedy_order kept, evaluated
+ *                               from B along that order as curve is, [ns] = +0.0.  It is an UPPER BOUND on the best selection of
+ *                               each size, NOT the optimum (the problem is a quadratic subset selection).
+ * Accuracy: the sums have mixed sign, so a value is accurate relative to A_h[m] = sum_{a, b in cols(D_m)} |P_h[a][b]|, not to itself:
+ *     |curve_h - exact| <= (hd^2 + 2) 2^-53 A_h ,      group (curve, greedy_curve):  <= (g hd^2 + 2) 2^-53 sum_h A_h
+ * (one rounding per ridge addition, per product and per addition, in any order); terms: (2 g |cols| + 2) 2^-53 relative to itself.
+ * Non-finite input: an entry [a][b] of one query head's sigma_q reaches curve_h of THAT head at every m <= min(position of a's unit,
+ * position of b's unit), and the same entries of its group's curve, that group's scale and greedy outputs; a diagonal Inf also that
+ * unit's term (a diagonal NaN counts as 0 there).  An entry of one kv head's sigma_k does the same for every head of that group.
+ * Nothing of another kv head changes by a bit.  greedy_order stays a permutation.  MDG_OK in every case.
+ * One workgroup per kv head; the head's packed unit-block sums (and the group's, with the greedy outputs) live in LDS, up to 137 KB;
+ * no atomics, every sum in a fixed order: bit-identical from run to run.  Only enqueues, no workspace.  MDG_ERR_BAD_ARG for a null
+ * required pointer, a head layout / mode / hd that mdg_qk_select rejects, or only one of the greedy pair. */
+int mdg_qk_rank_curve(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q, double ridge_k,
+                      int mode, const int64_t* order, double terms_ridge_q, double terms_ridge_k,
+                      double* curve_h /* [n_heads][ns + 1] */, double* curve /* [n_kv][ns + 1] */, double* terms /* [n_kv][ns], optional */,
+                      double* scale /* [n_kv], optional */, double* greedy_curve /* [n_kv][ns + 1], optional */,
+                      int64_t* greedy_order /* [n_kv][ns], optional */, void* stream);
 
 /* ------------------------------------------------------------------ VO: SVD of sqrt(C) W_v^T
  * v_out [n_kv*rank, d] bf16, o_out [d, n_heads*rank] bf16 (compress_vo.py:89-90).  W_v [n_kv*hd, d],

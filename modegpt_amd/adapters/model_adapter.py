@@ -221,6 +221,45 @@ class ModelAdapter(ABC):
             self.metrics.setdefault("vo_output_error", {}).update({str(k): v for k, v in report.items()})
         return report
 
+    # ---- what the Q/K pair selection loses of the attention logits (not upstream; MODEGPT_QK_ERROR=1) ----
+    def qk_error(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_qk hands over ops.qk_rank_curve's (curve_h, curve, terms, scale, greedy_curve, greedy_order) and the order they
+        were taken along, still on the device, for layer `layer_idx`, whose heads keep `rank` columns."""
+        self.__dict__.setdefault("_qk_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+
+    def report_qk_errors(self, log=None) -> dict:
+        """Reads the recorded tensors (about 8 (n_heads + 4 n_kv) (ns + 1) bytes per layer; call it where the host waits for the
+        chains anyway), keeps them as CPU tensors in self.qk_errors[layer] = (curve_h, curve, terms, scale, greedy_curve,
+        greedy_order, order) and writes metrics["qk_logit_error"][str(layer)] = ops.decode_qk_logit_error(...): the mean-square
+        logit the layer's heads carry on the calibration statistic, how much of it the kept columns lose, per kv head and for the
+        layer, what the diagonal rule believed it would lose, and what a greedy order on the full objective loses at the same rank
+        ("What the Q/K selection costs the attention logits", says what that is not).  Logs one line per layer."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_qk_errors", {})
+        report = {}
+        for layer in sorted(pending):
+            tensors, rank = pending[layer]
+            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
+            self.__dict__.setdefault("qk_errors", {})[layer] = host
+            curve_h, curve, terms, scale, g_curve = host[:5]
+            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
+            m = report[layer] = ops.decode_qk_logit_error(curve_h.tolist(), curve.tolist(), rank, cols, terms=terms.tolist(),
+                                                          scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist())
+            if m["relative_error"] is None:
+                log.warning(f"[QK] Layer {layer}: logit error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
+                continue
+            greedy, diag = m["greedy_relative_error"], m["diagonal_ratio"]
+            log.info(f"[QK] Layer {layer}: rank {rank}: the kept columns lose {m['relative_error']:.3e} of the logit energy"
+                     + ("" if diag is None else f"; the diagonal rule's estimate is {diag:.3g} x that")
+                     + ("" if greedy is None else f"; a greedy order on the full objective loses {greedy:.3e}")
+                     + ("; NOT monotone in the rank" if m["non_monotone"] else ""))
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            # (decode_qk_logit_error maps every non-finite figure to None, so json.dump never meets a NaN)
+            self.metrics.setdefault("qk_logit_error", {}).update({str(k): v for k, v in report.items()})
+        return report
+
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
     def attention_margin(self, layer_idx: int, kind: str, tensor, *eps: float) -> None:
         """compress_qk (kind "qk": ops.qk_select_margin's [n_kv, 8], eps = (eps_rel, eps_abs)) and compress_vo (kind "vo":

@@ -83,6 +83,14 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
         eps_rel = attention_error_eps(adapter)
         record(layer_idx, "qk", ops.qk_select_margin(cq, ck, rank, mode, ridge_q, ridge_k, mask, eps_rel, EIGH_ROUTE_EPS_ABS),
                eps_rel, EIGH_ROUTE_EPS_ABS)
+    record_error = getattr(adapter, "qk_error", None) if ops.qk_error_enabled() else None      # (... without this: no logit error)
+    if record_error is not None:
+        # what the selection loses of the logits, at every rank: the order of ALL units from one more scoring call (the mask above is
+        # its prefix), then the curves on the RAW statistics (ridges 0: the stored rows are bit copies, so this is the artefact's
+        # error) with the diagonal terms under the ridges the scores really use.  Enqueued only, read by report_qk_errors.
+        ns, _ = ops.qk_units(mode, head_dim)
+        order = ops.qk_select(cq, ck, head_dim, mode, ridge_q, ridge_k)[0][:, :ns].contiguous()
+        record_error(layer_idx, ops.qk_rank_curve(cq, ck, mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,), rank)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

@@ -1017,6 +1017,125 @@ def decode_qk_margin(rows, eps_rel: float, eps_abs: float) -> dict:
             "certified": all(h["certified"] for h in heads), "order_certified": all(h["order_certified"] for h in heads)}
 
 
+# What the Q/K selection costs the attention logits on the calibration statistic, per query head and at every rank
+# (mdg_qk_rank_curve).  Opt-in: MODEGPT_QK_ERROR=1 makes compress_qk compute it for every layer from the statistics it holds anyway
+# ("What the Q/K selection costs the attention logits").
+def qk_error_enabled() -> bool:
+    """MODEGPT_QK_ERROR as it stands when compress_qk asks (per layer; not frozen at import)."""
+    return os.environ.get("MODEGPT_QK_ERROR", "0").lower() in ("1", "on", "true")
+
+
+def qk_units(mode: int, hd: int):
+    """(ns, columns per unit) of a scoring mode: RoPE pairs {u, u + hd/2} or, for OPT, single columns."""
+    return (hd, 1) if mode == _lib.MDG_QK_OPT else (hd // 2, 2)
+
+
+def qk_rank_curve(cov_q: torch.Tensor, cov_k: torch.Tensor, mode: int, ridge_q: float, ridge_k: float, order: torch.Tensor,
+                  want_greedy: bool = True, terms_ridges=None):
+    """Returns (curve_h [n_heads, ns + 1], curve [n_kv, ns + 1], terms [n_kv, ns], scale [n_kv], greedy_curve [n_kv, ns + 1] or None,
+    greedy_order [n_kv, ns] int64 or None), all ON THE DEVICE, enqueued only (mdg_qk_rank_curve; decode_qk_logit_error reads them).
+    curve_h[h][m]: the mean-square change of query head h's logits over all token pairs of the calibration set when only the first m
+    units of `order` are kept, under (cov_q + ridge_q I) (.) (cov_k + ridge_k I); curve: the kv group's sums.  order: int64 [n_kv, ns],
+    keep-first -- qk_select(..., rank=hd)[0][:, :ns].  terms: the diagonal share of every unit in that order, what qk_select's score
+    is made of, with terms_ridges = (ridge_q, ridge_k) of its own (None: the same ridges).  scale: the abs-sum the values are accurate
+    relative to.  want_greedy: the comparison order built on the full objective and its curve."""
+    _need_gpu(cov_q, cov_k, order)
+    lib = _lib.load()
+    if cov_q.dim() != 3 or cov_k.dim() != 3 or cov_q.shape[1] != cov_q.shape[2] or tuple(cov_k.shape[1:]) != tuple(cov_q.shape[1:]):
+        raise ValueError(f"qk_rank_curve: cov_q / cov_k must be [heads, hd, hd], got {tuple(cov_q.shape)} / {tuple(cov_k.shape)}")
+    if mode not in (_lib.MDG_QK_ROPE_GROUPED, _lib.MDG_QK_ROPE_MHA, _lib.MDG_QK_OPT):
+        raise ValueError(f"qk_rank_curve: unknown mode {mode!r}")
+    cq = cov_q.to(torch.float64).contiguous()
+    ck = cov_k.to(torch.float64).contiguous()
+    n_heads, hd, _ = cq.shape
+    n_kv = ck.shape[0]
+    ns, _ = qk_units(mode, hd)
+    if order.dtype != torch.int64 or tuple(order.shape) != (n_kv, ns):
+        raise ValueError(f"qk_rank_curve: order must be int64 [{n_kv}, {ns}], got {order.dtype} {tuple(order.shape)}")
+    order = order.contiguous()
+    tq, tk = (ridge_q, ridge_k) if terms_ridges is None else terms_ridges
+    dev = cq.device
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)      # noqa: E731
+    curve_h, curve, terms, scale = new(n_heads, ns + 1), new(n_kv, ns + 1), new(n_kv, ns), new(n_kv)
+    g_curve = new(n_kv, ns + 1) if want_greedy else None
+    g_order = torch.empty(n_kv, ns, dtype=torch.int64, device=dev) if want_greedy else None
+    with torch.cuda.device(dev):
+        check(lib.mdg_qk_rank_curve(cq.data_ptr(), ck.data_ptr(), n_heads, n_kv, hd, float(ridge_q), float(ridge_k), mode,
+                                    order.data_ptr(), float(tq), float(tk), curve_h.data_ptr(), curve.data_ptr(), terms.data_ptr(),
+                                    scale.data_ptr(), _p(g_curve), _p(g_order), _stream(cq)), "mdg_qk_rank_curve")
+    return curve_h, curve, terms, scale, g_curve, g_order
+
+
+QK_ERROR_TARGETS = (1e-1, 1e-2, 1e-3)
+
+
+def decode_qk_logit_error(curve_h, curve, rank: int, cols_per_unit: int, terms=None, scale=None, greedy_curve=None) -> dict:
+    """Host-side reading of qk_rank_curve's numbers (nested lists / CPU tensors: curve_h [n_heads][ns + 1], curve and greedy_curve
+    [n_kv][ns + 1], terms [n_kv][ns], scale [n_kv]); rank: the columns kept per head, cols_per_unit: 2 for the RoPE modes, 1 for OPT.
+    With m = rank / cols_per_unit units kept, per kv head under "heads":
+    energy = curve[0] (the mean-square logit of the group's heads), error = curve[m], relative_error = error / energy;
+    diagonal_estimate = sum_{i >= m} terms[i] (what the reference's rule believes the cost is) and diagonal_ratio = diagonal_estimate /
+    error (far from 1: the off-diagonal correlations the rule ignores matter); greedy_relative_error = greedy_curve[m] / energy;
+    rank_for_rel_error = {"selection" / "greedy": {target: the fewest columns per head at which the curve is at or under target x
+    energy}} for QK_ERROR_TARGETS (the curve need not be monotone: the FIRST such rank; None without a usable energy);
+    head_relative_error = [curve_h[h][m] / curve_h[h][0]] over the group's query heads; noise_floor = (g hd^2 + 2) 2^-53 scale / energy,
+    below which a relative value says nothing; non_monotone = some curve[i + 1] > curve[i] by more than that floor.
+    The layer: the sums over the kv heads (energy-weighted), non_monotone = any head's.  Values are reported raw, never clamped; a
+    non-finite figure, or one derived from an unusable energy, is None."""
+    ch = [[float(x) for x in row] for row in curve_h]
+    cv = [[float(x) for x in row] for row in curve]
+    n_heads, n_kv, rank, cols = len(ch), len(cv), int(rank), int(cols_per_unit)
+    if n_kv <= 0 or n_heads % n_kv or cols not in (1, 2) or any(len(row) != len(cv[0]) for row in cv + ch) or len(cv[0]) < 1:
+        raise ValueError("decode_qk_logit_error: curve_h must be [n_heads][ns + 1] and curve [n_kv][ns + 1], n_heads a multiple of n_kv")
+    ns, group = len(cv[0]) - 1, n_heads // n_kv
+    if rank % cols or not 0 <= rank // cols <= ns:
+        raise ValueError(f"decode_qk_logit_error: rank {rank} is not a whole number of units within 0 .. {ns * cols}")
+    m, hd = rank // cols, ns * cols
+    opt = lambda t, width: None if t is None else [[float(x) for x in row] for row in t] if width else [float(x) for x in t]  # noqa: E731
+    tv, gv, sv = opt(terms, ns), opt(greedy_curve, ns + 1), opt(scale, 0)
+    if (tv is not None and (len(tv) != n_kv or any(len(r) != ns for r in tv))) or (sv is not None and len(sv) != n_kv) or \
+            (gv is not None and (len(gv) != n_kv or any(len(r) != ns + 1 for r in gv))):
+        raise ValueError(f"decode_qk_logit_error: terms must be [{n_kv}][{ns}], scale [{n_kv}] and greedy_curve [{n_kv}][{ns + 1}]")
+    fin = lambda x: x if x is not None and math.isfinite(x) else None                    # noqa: E731
+    ratio = lambda a, b: a / b if fin(a) is not None and fin(b) is not None and b > 0 else None   # noqa: E731
+    unit = (group * hd * hd + 2) * 2.0 ** -53
+
+    def first_under(c, energy):
+        if fin(energy) is None or energy <= 0 or not all(map(math.isfinite, c)):
+            return {"%g" % t: None for t in QK_ERROR_TARGETS}
+        return {"%g" % t: next((i * cols for i, x in enumerate(c) if x <= t * energy), None) for t in QK_ERROR_TARGETS}
+
+    heads = []
+    for g in range(n_kv):
+        c = cv[g]
+        energy, error = c[0], c[m]
+        floor_abs = unit * sv[g] if sv is not None and fin(sv[g]) is not None else None
+        diag = None
+        if tv is not None:
+            diag = math.fsum(tv[g][m:]) if all(map(math.isfinite, tv[g][m:])) else float("nan")
+        h = {"energy": fin(energy), "error": fin(error), "relative_error": ratio(error, energy),
+             "diagonal_estimate": fin(diag), "diagonal_ratio": ratio(diag, error),
+             "greedy_relative_error": None if gv is None else ratio(gv[g][m], energy),
+             "rank_for_rel_error": {"selection": first_under(c, energy), "greedy": None if gv is None else first_under(gv[g], energy)},
+             "head_relative_error": [ratio(ch[q][m], ch[q][0]) for q in range(g * group, (g + 1) * group)],
+             "noise_floor": ratio(floor_abs, energy),
+             "non_monotone": (any(b > a + (floor_abs or 0.0) for a, b in zip(c, c[1:])) if all(map(math.isfinite, c)) else None)}
+        heads.append(h)
+
+    def total(key, source=None):
+        vals = [h[key] for h in heads] if source is None else source
+        return math.fsum(vals) if all(v is not None and math.isfinite(v) for v in vals) else None
+
+    energy, error, diag = total("energy"), total("error"), total("diagonal_estimate")
+    greedy = None if gv is None else total(None, [gv[g][m] for g in range(n_kv)])
+    floors = None if sv is None else total(None, [unit * s for s in sv])
+    flags = [h["non_monotone"] for h in heads]
+    return {"rank": rank, "units_kept": m, "n_kv": n_kv, "head_dim": hd, "energy": energy, "error": error,
+            "relative_error": ratio(error, energy), "diagonal_estimate": diag, "diagonal_ratio": ratio(diag, error),
+            "greedy_relative_error": ratio(greedy, energy), "noise_floor": ratio(floors, energy),
+            "non_monotone": None if any(f is None for f in flags) else any(flags), "heads": heads}
+
+
 VO_SPECTRUM_FIELDS = ("lambda_r", "lambda_next", "gap", "energy", "bound", "separated", "lambda_max", "lambda_min")
 
 

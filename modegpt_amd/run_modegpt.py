@@ -125,6 +125,9 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
     report = getattr(adapter, "report_vo_errors", None)
     if report is not None:
         report(logger)                          # ... what the stored v_proj / o_proj lose (MODEGPT_VO_ERROR=1) -> metrics["vo_output_error"]
+    report = getattr(adapter, "report_qk_errors", None)
+    if report is not None:
+        report(logger)                          # ... what the Q/K pair selections lose of the logits (MODEGPT_QK_ERROR=1) -> metrics["qk_logit_error"]
     report = getattr(adapter, "report_attention_margins", None)
     if report is not None:
         report(logger)                          # ... and of its QK pair selections / VO truncations -> metrics["qk_selection"], ["vo_spectrum"]
