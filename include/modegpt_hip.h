@@ -48,7 +48,8 @@ extern "C" {
                                 changed under 9: mdg_nystrom_down_ws_bytes is larger (the compacted operands of the product over the
                                 unselected columns, see mdg_nystrom_down); no signature changed;
                              10: mdg_rope_gather_plan added (the rotary kernel's dispatch as a device-free function);
-                                added under 10: mdg_qk_rank_curve (what the Q/K pair selection costs the attention logits, per head and rank) */
+                                added under 10: mdg_qk_rank_curve (what the Q/K pair selection costs the attention logits, per head and rank);
+                                added under 10: mdg_vo_bias (the v_proj / o_proj biases through the V/O truncation) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -575,6 +576,26 @@ int mdg_vo_compress(const double* cov_x, int64_t d, int64_t ldc, const void* Wv,
  * it, the gap alone is reported.  Only enqueues; one workgroup per kv head. */
 int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_t d, int64_t ldc, const void* Wv, int64_t ld_wv,
                     int w_dtype, int n_heads, int n_kv, int hd, int rank, double ridge, double eps, double* out, void* stream);
+/* The v_proj / o_proj biases through the truncation (added under ABI 10).  The reference's save_layer -> convert_model route rebuilds
+ * both projections bias-free (model_adapter.py:199-208) and compress_vo.py:112-223 never looks at a bias; its in-place route keeps
+ * b_o and drops b_v.  Softmax rows sum to one, so a v bias passes through attention unchanged and query head h adds the constant
+ * W_o,h b_v,kv(h) to the output.  With P_g [rank, hd] (W_v,g' = P_g W_v,g) and Q_g [hd, rank] (W_o,h' = W_o,h Q_g) the factors the
+ * LAST mdg_vo_compress call left in workspace `ws` (same shapes and rank; grouped and two-SVD MHA variant alike), Pi_g = Q_g P_g:
+ *   b_o given  (o_proj has a bias):  o_bias[i] = b_o[i] + sum_h W_o,h[i, :] b_v,kv(h)   -- exact at every rank; v_bias is not written
+ *   b_o NULL   (o_proj has none):    v_bias[g rank + a] = (P_g b_v,g)[a]                  -- o_bias is not written
+ *   resid[0] = ||rho||^2, rho = sum_h W_o,h (I - Pi_g) b_v,kv(h): what the second form cannot represent (0 at rank == hd up to rounding);
+ *   resid[1] = ||sum_h W_o,h b_v,kv(h)||^2.  Both are written in either form.
+ * Wo: the ORIGINAL o_proj weight [d, n_heads hd] (ld_wo), w_dtype MDG_BF16, MDG_F16 or MDG_F64; b_v [n_kv hd] and b_o [d] of b_dtype
+ * (any MDG_* element type).  o_bias [d], v_bias [n_kv rank], resid [2]: fp64 on the device; the caller rounds once to the model's
+ * dtype.  One read of W_o: lanes along a row (16-byte loads of 16-bit weights when Wo and ld_wo allow), a wave per group of rows,
+ * b_v and (I - Pi) b_v staged in LDS; every sum in a fixed order, no atomics: the same bits from run to run.  A NaN in one kv
+ * head's b_v reaches that head's v_bias entries only (and every o_bias entry, resid).
+ * Uses the T block of the workspace as scratch (dead after mdg_vo_compress; mdg_vo_spectrum / mdg_vo_rank_curve do not read it), so
+ * the calls on one workspace belong on one stream.  Only enqueues.  MDG_ERR_BAD_ARG for a null pointer, an unsupported dtype, head
+ * layout or rank, ld_wo < n_heads hd, a workspace smaller than mdg_vo_compress_ws_bytes, b_o without o_bias / no b_o without v_bias,
+ * or 2 (n_kv hd + d) > n_kv hd d (no room for the scratch). */
+int mdg_vo_bias(void* ws, size_t ws_bytes, const void* Wo, int64_t ld_wo, int w_dtype, int64_t d, const void* b_v, const void* b_o,
+                int b_dtype, int n_heads, int n_kv, int hd, int rank, double* o_bias, double* v_bias, double* resid, void* stream);
 
 /* What the STORED V/O factors lose of the attention output on the calibration statistic, per query head and output channel (added
  * under ABI 9; not in the reference: compress_vo.py:112-223 cuts its SVD at `rank` and reports nothing about the product).  Field [3]

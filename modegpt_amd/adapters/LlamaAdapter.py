@@ -167,4 +167,11 @@ class LlamaAdapter(ModelAdapter):
             cfg.auto_map = {"AutoModelForCausalLM": "LlamaRebuild.LlamaForCausalLM"}
         if "qwen" in mt:
             cfg.auto_map = {"AutoModelForCausalLM": "DenseQwenRebuild.Qwen3ForCausalLM"}
+        if mt == "qwen2":
+            cfg.auto_map = {"AutoModelForCausalLM": "Qwen2Rebuild.Qwen2ForCausalLM"}
+        # which projections of this checkpoint carry a bias, so that the modeling file builds exactly the parameters the state dict
+        # holds (not upstream; absent -- a run without carried biases -- the loader builds bias-free modules as before)
+        carried = self.projection_biases()
+        if carried:
+            cfg.projection_biases = carried
         return original

@@ -116,4 +116,9 @@ class OPTAdapter(ModelAdapter):
         cfg.gate_ranks = [self.get_mlp_tensors(i).up_proj.shape[0] for i in range(self.n_layers)]
         cfg.ffn_dim = -1
         cfg.auto_map = {"AutoModelForCausalLM": "OPTRebuild.OPTForCausalLM"}
+        # which projections of this checkpoint carry a bias (not upstream; see LlamaAdapter.patch_config).  v_proj never does: its
+        # bias is folded into out_proj's, and the reference's OPTRebuild zero-fills the v_proj.bias it creates from enable_bias.
+        carried = self.projection_biases()
+        if carried:
+            cfg.projection_biases = carried
         return original

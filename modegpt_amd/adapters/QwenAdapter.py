@@ -16,3 +16,14 @@ class QwenAdapter(LlamaAdapter):
     @property
     def arch(self) -> str:
         return self.ARCH_TAG
+
+
+class Qwen2Adapter(LlamaAdapter):
+    """Qwen2 / Qwen2.5 (not upstream): the Llama block again, without q_norm / k_norm and with biases on q_proj, k_proj and v_proj.
+    The tag "qwen2" selects what "qwen" selects for Qwen3 (RoPE-pair scoring, even ranks), the Qwen2Rebuild modeling file, and
+    -- whatever MODEGPT_KEEP_BIAS says -- the carrying of those biases through all three stages (ops.keep_bias_enabled)."""
+    ARCH_TAG = "qwen2"
+
+    @property
+    def arch(self) -> str:
+        return self.ARCH_TAG

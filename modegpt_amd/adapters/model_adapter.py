@@ -54,8 +54,12 @@ class ModelAdapter(ABC):
         if inner is not None and hasattr(inner, "decoder"):
             return OPTAdapter(model, tokenizer=tokenizer)
         if inner is not None and hasattr(inner, "layers"):
-            if "qwen3" in (getattr(model.config, "model_type", None) or ""):
+            model_type = getattr(model.config, "model_type", None) or ""
+            if "qwen3" in model_type:
                 return QwenAdapter(model, tokenizer=tokenizer)
+            if model_type == "qwen2":      # (Qwen2 / Qwen2.5: a Llama block with q/k/v biases, which are always carried)
+                from .QwenAdapter import Qwen2Adapter
+                return Qwen2Adapter(model, tokenizer=tokenizer)
             return LlamaAdapter(model, tokenizer=tokenizer)
         raise RuntimeError("Unsupported model architecture")
 
@@ -354,13 +358,16 @@ class ModelAdapter(ABC):
     @torch.no_grad()
     def convert_model(self, saved_layers_dir: str = "./compressed_output/layers/", suffixes=("mlp", "qk", "vo"),
                       device: str = "cuda"):
-        """Swap every layer's Linears for bias-free bf16 Linears built from the saved artefacts."""
+        """Swap every layer's Linears for bf16 Linears built from the saved artefacts: bias-free (model_adapter.py:199-208), except
+        where the artefact carries a bias (`<name>_bias`: the compressors write them with MODEGPT_KEEP_BIAS=1 and for Qwen2)."""
         saved_layers_dir = os.path.expandvars(saved_layers_dir)
         self.flush_artifacts()
 
-        def linear_of(w: Tensor) -> nn.Linear:
-            lin = nn.Linear(w.shape[1], w.shape[0], bias=False, device=device, dtype=torch.bfloat16)
+        def linear_of(w: Tensor, b: Optional[Tensor] = None) -> nn.Linear:
+            lin = nn.Linear(w.shape[1], w.shape[0], bias=b is not None, device=device, dtype=torch.bfloat16)
             lin.weight.data.copy_(w.to(torch.bfloat16))
+            if b is not None:
+                lin.bias.data.copy_(b.to(torch.bfloat16))
             return lin
 
         for suffix in suffixes:
@@ -368,14 +375,58 @@ class ModelAdapter(ABC):
                 art = torch.load(os.path.join(saved_layers_dir, f"layer_{i}_{suffix}"), map_location=device)
                 if suffix == "mlp":
                     gate = art.get("gate")
-                    self.replace_mlp_layers(i, new_up=linear_of(art["up"]), new_down=linear_of(art["down"]),
-                                            new_gate=None if gate is None else linear_of(gate))
+                    self.replace_mlp_layers(i, new_up=linear_of(art["up"], art.get("up_bias")),
+                                            new_down=linear_of(art["down"], art.get("down_bias")),
+                                            new_gate=None if gate is None else linear_of(gate, art.get("gate_bias")))
                 elif suffix == "qk":
-                    self.replace_attn_layers(i, new_q=linear_of(art["q_proj"]), new_k=linear_of(art["k_proj"]),
-                                             new_v=None, new_o=None)
+                    self.replace_attn_layers(i, new_q=linear_of(art["q_proj"], art.get("q_bias")),
+                                             new_k=linear_of(art["k_proj"], art.get("k_bias")), new_v=None, new_o=None)
                 elif suffix == "vo":
-                    self.replace_attn_layers(i, new_q=None, new_k=None, new_v=linear_of(art["v_proj"]),
-                                             new_o=linear_of(art["o_proj"]))
+                    self.replace_attn_layers(i, new_q=None, new_k=None, new_v=linear_of(art["v_proj"], art.get("v_bias")),
+                                             new_o=linear_of(art["o_proj"], art.get("o_bias")))
+
+    # ---- which projections of the converted model carry a bias (not upstream; patch_config records it) ----
+    BIAS_SLOTS = ("up", "gate", "down", "q", "k", "v", "o")
+
+    def projection_biases(self) -> list:
+        """Names out of BIAS_SLOTS whose Linear carries a bias in the model as it stands (uniform over the layers: they come from one
+        architecture and one switch); a model with layers that disagree is refused rather than written as a checkpoint that cannot
+        be loaded strictly."""
+        found = None
+        for i in range(self.n_layers):
+            mlp, attn = self.get_mlp_components(i), self.get_attn_components(i)
+            mods = {"up": mlp.up_proj, "gate": mlp.gate_proj, "down": mlp.down_proj, "q": attn.q_proj, "k": attn.k_proj,
+                    "v": attn.v_proj, "o": attn.o_proj}
+            here = [n for n in self.BIAS_SLOTS if mods[n] is not None and getattr(mods[n], "bias", None) is not None]
+            if found is not None and here != found:
+                raise RuntimeError(f"layer {i} carries biases on {here}, earlier layers on {found}")
+            found = here
+        return found or []
+
+    # ---- what the truncated v_proj cannot carry of a v bias where o_proj has no bias to fold it into (not upstream) ----
+    def vo_bias_residual(self, layer_idx: int, resid) -> None:
+        """compress_vo hands over ops.vo_bias's resid (2 numbers, still on the device) for layer `layer_idx`."""
+        self.__dict__.setdefault("_vo_bias_residuals", {})[int(layer_idx)] = resid
+
+    def report_vo_bias_residuals(self, log=None) -> dict:
+        """Reads the recorded pairs (16 bytes per layer; call it where the host waits for the chains anyway) and writes
+        metrics["vo_bias_residual"][str(layer)] = {"residual_norm2": ||rho||^2, "constant_norm2": ||sum_h W_o,h b_v||^2,
+        "relative": their ratio}: rho = sum_h W_o,h (I - Pi_g) b_v,kv(h) is the part of the constant a v bias adds to the attention
+        output that the rank-r v_proj cannot represent ("Projection biases").  Non-finite figures become None."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_vo_bias_residuals", {})
+        report = {}
+        for layer in sorted(pending):
+            rho2, const2 = (float(x) for x in pending[layer].cpu().tolist())
+            ok = math.isfinite(rho2) and math.isfinite(const2)
+            report[layer] = {"residual_norm2": rho2 if ok else None, "constant_norm2": const2 if ok else None,
+                             "relative": rho2 / const2 if ok and const2 > 0 else None}
+            log.info(f"[VO] Layer {layer}: the truncated v_proj loses {rho2:.3e} of the v bias's output constant {const2:.3e} (squared norms)")
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            self.metrics.setdefault("vo_bias_residual", {}).update({str(k): v for k, v in report.items()})
+        return report
 
     # ---- in-place slicing (model_adapter.py:394-542; upstream's call sites are commented out in favour of the
     #      save_layer -> convert_model route, the methods stay part of the adapter surface) ----

@@ -63,7 +63,8 @@ def covariance_error_eps(adapter, n_features: int) -> float:
 
 @torch.no_grad()
 def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_idx: int, ridge_lambda: float,
-                     margin_eps: float = None, margin_out: list = None, curve_out: list = None, error_out: list = None):
+                     margin_eps: float = None, margin_out: list = None, curve_out: list = None, error_out: list = None,
+                     bias_out: dict = None):
     """compress_mlp.py:28-64.  Returns (W_u'^T [d, r], W_d' [r, d], W_g'^T [d, r] or None, rank), bf16 --
     the same orientation the reference returns (transposed views of the saved layout).
     margin_eps / margin_out (not upstream): with both given, the certificate of the rank selection against an entry-wise relative
@@ -73,7 +74,10 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
     numbers on the device) is appended to it, enqueued behind the refit; the outputs are the same bits with or without it.
     error_out (not upstream): a list, with MODEGPT_OUTPUT_ERROR=1 -- (q, e, unorm2), d numbers each on the device
     (ops.mlp_output_error: the output energy of the uncompressed weights, the output error and the squared residual norm per channel
-    of the bf16 tensor this call RETURNS, not of the fp64 solution) are appended to it; the outputs are the same bits either way."""
+    of the bf16 tensor this call RETURNS, not of the fp64 solution) are appended to it; the outputs are the same bits either way.
+    bias_out (not upstream's save route, which drops every bias; its in-place slice_gate_dims keeps these three): a dict -- the biases
+    the projections have go into it as "up_bias" / "gate_bias" (the entries at the selected columns, in their order) and "down_bias"
+    (unchanged: the refit has no intercept), bit copies in the bias's own dtype; the weights are the same bits either way."""
     C = C.to(dtype=dtype_p, device=local_device())
     rank = int(C.shape[0] * keep_ratio)
     if margin_out is not None and margin_eps is not None:
@@ -100,6 +104,12 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         q = ops.mlp_output_error(C, W_d, None, None)                  # the channel's energy: nothing subtracted
         e, unorm2 = ops.mlp_output_error(C, W_d, idx, down, want_unorm2=True)     # ... and what the tensor that is saved loses of it
         error_out.extend((q, e, unorm2))
+    if bias_out is not None:
+        for name, proj, rows in (("up_bias", comps.up_proj, idx), ("gate_bias", comps.gate_proj, idx), ("down_bias", comps.down_proj, None)):
+            b = getattr(proj, "bias", None)
+            if b is not None:
+                b = b.detach().to(local_device())
+                bias_out[name] = b.clone() if rows is None else torch.index_select(b, 0, rows.to(torch.int64))
     return up.T, down.T, (None if gate is None else gate.T), rank
 
 
@@ -116,28 +126,30 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
         curve = [] if callable(record_curve) else None               # (filled only with MODEGPT_RANK_CURVE=1)
         record_error = getattr(adapter, "output_error", None)        # (... and without this: no realised output error)
         error = [] if callable(record_error) else None               # (filled only with MODEGPT_OUTPUT_ERROR=1)
+        biases = {} if ops.keep_bias_enabled(getattr(adapter, "arch", None)) else None     # (MODEGPT_KEEP_BIAS=1, or Qwen2)
         if record is None:
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error)
+                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error, bias_out=biases)
         else:
             eps, margin = covariance_error_eps(adapter, cov[layer_idx].shape[0]), []
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
                                       ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve,
-                                      error_out=error)
+                                      error_out=error, bias_out=biases)
             # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
             record(layer_idx, margin[0], eps)
         if curve:
             record_curve(layer_idx, curve[0], result[3])             # ... and so does the curve (report_rank_curves)
         if error:
             record_error(layer_idx, tuple(error), result[3])         # ... and the stored tensor's output error (report_output_errors)
-        return result
+        return result + (biases or {},)
 
     def retire(layer_idx, result):
-        up_T, down_T, gate_T, rank = result
+        up_T, down_T, gate_T, rank, biases = result
         logger.info(f"[MLP] Layer {layer_idx}  compressed to rank {rank}")
         weights = {"up": up_T.T, "down": down_T.T}
         if gate_T is not None:
             weights["gate"] = gate_T.T
+        weights.update(biases)
         adapter.save_layer(output_dir=adapter.config.temp_storage_dir, suffix="mlp", weights=weights,
                            layer_idx=layer_idx)
 

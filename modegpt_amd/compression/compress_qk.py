@@ -59,7 +59,7 @@ def qk_mode_and_ridges(arch: str, grouped: bool, ridge_qk: float):
     GQA: K gets config.ridge_qk, Q gets sqrt_M's default; MHA llama / OPT: defaults for both."""
     if (arch == "llama" or "qwen" in arch) and grouped:
         return _lib.MDG_QK_ROPE_GROUPED, _SQRT_M_DEFAULT_RIDGE, ridge_qk
-    if arch == "llama":
+    if arch in ("llama", "qwen2"):       # (qwen2 is not upstream's: its MHA checkpoints, Qwen1.5, are Llama blocks with q/k/v biases)
         return _lib.MDG_QK_ROPE_MHA, _SQRT_M_DEFAULT_RIDGE, _SQRT_M_DEFAULT_RIDGE
     if arch == "opt":
         return _lib.MDG_QK_OPT, _SQRT_M_DEFAULT_RIDGE, _SQRT_M_DEFAULT_RIDGE
@@ -97,8 +97,15 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     K_heads = ops.gather_rows(W_k, k_rows)   # [n_kv*rank, d]
     if (arch == "llama" or "qwen" in arch) and slice_dims:
         rotary_masks.append(mask)
-    adapter.save_layer(output_dir=adapter.config.temp_storage_dir, suffix="qk",
-                       weights={"q_proj": Q_heads, "k_proj": K_heads}, layer_idx=layer_idx)
+    weights = {"q_proj": Q_heads, "k_proj": K_heads}
+    if bias and ops.keep_bias_enabled(arch):         # (MODEGPT_KEEP_BIAS=1, or Qwen2)
+        # the bias entries at exactly the rows gathered above, in their order (compress_head_opt gathers them the same way,
+        # compress_qk.py:439-476; the save_layer route upstream drops them): bit copies in the bias's own dtype
+        for name, proj, rows in (("q_bias", comps.query_proj, q_rows), ("k_bias", comps.key_proj, k_rows)):
+            b = getattr(proj, "bias", None)
+            if b is not None:
+                weights[name] = torch.index_select(b.detach().to(local_device()), 0, rows)
+    adapter.save_layer(output_dir=adapter.config.temp_storage_dir, suffix="qk", weights=weights, layer_idx=layer_idx)
     return mask
 
 

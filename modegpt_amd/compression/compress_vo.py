@@ -92,7 +92,8 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
                 target_layers: Optional[List[int]] = None):
     """compress_vo.py:13-109.  Grouped (GQA) and two-SVD (MHA) variants are chosen by n_kv_heads != n_heads, as
     upstream; both run inside mdg_vo_compress on the head-sized Gram matrix.  Saves {"v_proj": [n_kv*r, d],
-    "o_proj": [d, n_heads*r]} bf16."""
+    "o_proj": [d, n_heads*r]} bf16 -- and, with the biases carried (ops.keep_bias_enabled), "o_bias" [d] (b_o + sum_h W_o,h b_v,kv(h):
+    v_proj becomes bias-free) or, where o_proj has no bias, "v_bias" [n_kv*r] (P_g b_v,g), in the bias's own dtype."""
     if target_layers is None:
         target_layers = list(range(adapter.n_layers))
     n_heads, head_dim, arch, n_kv = adapter.n_heads, adapter.head_dim, adapter.arch, adapter.n_kv_heads
@@ -113,8 +114,27 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
         Wv_d, Wo_d = W_v.detach().to(local_device()), W_o.detach().to(local_device())
         # sigma_r against sigma_r+1 of the spectrum just truncated: stays on the device until report_attention_margins
         eps = attention_error_eps(adapter) if record is not None else None
+        # the biases (MODEGPT_KEEP_BIAS=1, or Qwen2; DESIGN.md section 7, "Projection biases"): a v bias passes through the softmax
+        # unchanged, so it is folded into o_proj's bias where there is one (exact at every rank) and projected by P_g where there is none
+        b_v = b_o = None
+        if ops.keep_bias_enabled(arch):
+            b_v, b_o = getattr(comps.v_proj, "bias", None), getattr(comps.o_proj, "bias", None)
+            b_v = None if b_v is None else b_v.detach().to(local_device())
+            b_o = None if b_o is None else b_o.detach().to(local_device())
         out = ops.vo_compress(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, adapter.config.ridge_vo, want_spectrum=record is not None,
-                              spectrum_eps=eps, want_curve=record_error is not None)
+                              spectrum_eps=eps, want_curve=record_error is not None, bias=None if b_v is None else (b_v, b_o))
+        biases = {}
+        if b_v is not None:
+            (o_bias, v_bias, resid), out = out[-1], out[:-1]
+            if o_bias is not None:
+                biases["o_bias"] = o_bias.to(b_o.dtype)          # (one rounding of the fp64 sum)
+            else:
+                biases["v_bias"] = v_bias.to(b_v.dtype)
+                record_resid = getattr(adapter, "vo_bias_residual", None)
+                if record_resid is not None:
+                    record_resid(layer, resid)                   # stays on the device until report_vo_bias_residuals
+        elif b_o is not None:
+            biases["o_bias"] = b_o.clone()
         V_heads, O_heads = out[0], out[1]
         if record is not None:
             record(layer, "vo", out[2], eps)
@@ -124,14 +144,14 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
             q = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, 0, None, None)
             e, dnorm2 = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, V_heads, O_heads, want_dnorm2=True)
             record_error(layer, (q, e, dnorm2, out[-1]), rank_i)
-        return V_heads, O_heads
+        return V_heads, O_heads, biases
 
     def retire(layer, result):
         if result is None:
             return
-        V_heads, O_heads = result
+        V_heads, O_heads, biases = result
         adapter.save_layer(output_dir=adapter.config.temp_storage_dir, suffix="vo",
-                           weights={"v_proj": V_heads, "o_proj": O_heads}, layer_idx=layer)
+                           weights={"v_proj": V_heads, "o_proj": O_heads, **biases}, layer_idx=layer)
         logger.info(f"[VO] Compressed layer {layer} to rank {ranks[layer]} per head")
 
     over_layers(adapter, list(target_layers), enqueue, retire)

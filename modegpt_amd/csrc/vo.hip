@@ -161,6 +161,175 @@ __global__ __launch_bounds__(256) void vo_spectrum_kernel(const double* lam_all,
   }
 }
 
+// ---- the projection biases through the truncation (mdg_vo_bias) ----
+// Scratch of mdg_vo_bias inside the T block of the workspace (T = W_v C is dead once the Gram matrices are formed):
+// [0, a) b_v widened, [a, 2a) u = (I - Q P) b_v, [2a, 2a + d) s_i = W_o[i, :] b_v, [2a + d, 2a + 2d) rho_i = W_o[i, :] u;  a = n_kv hd.
+template <int DT>
+__global__ __launch_bounds__(128) void vo_bias_head_kernel(const double* P, const double* Q, const void* b_v, int hd, int r,
+                                                           double* v_bias, double* bw, double* u) {
+  __shared__ double b_[128], c_[128];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const double* Pg = P + (int64_t)g * r * hd;
+  const double* Qg = Q + (int64_t)g * hd * r;
+  if (tid < hd) bw[(int64_t)g * hd + tid] = b_[tid] = load_f64<DT>(b_v, (int64_t)g * hd + tid);
+  __syncthreads();
+  if (tid < r) {                       // c = P_g b_v,g: the bias of the truncated v_proj
+    double s = 0.;
+    for (int k = 0; k < hd; k++) s += Pg[tid * hd + k] * b_[k];
+    c_[tid] = s;
+    if (v_bias) v_bias[(int64_t)g * r + tid] = s;
+  }
+  __syncthreads();
+  if (tid < hd) {                      // u = b_v,g - Q_g c: what no bias of the truncated v_proj can carry
+    double s = 0.;
+    for (int a = 0; a < r; a++) s += Qg[tid * r + a] * c_[a];
+    u[(int64_t)g * hd + tid] = b_[tid] - s;
+  }
+}
+
+// s_i and rho_i for VO_BIAS_ROWS rows of W_o per workgroup: a wave owns VO_BIAS_ROWS / 4 rows, lanes go along the row (coalesced;
+// vec: eight 16-bit weights per lane and load), the two vectors are staged per chunk of VO_BIAS_CHUNK columns in LDS, already expanded
+// to the query heads' columns.  Every lane sums its columns in ascending order, the wave reduces by butterfly: a fixed order.
+constexpr int VO_BIAS_CHUNK = 2048, VO_BIAS_ROWS = 16;      // (d = 4096: 256 workgroups, one per CU)
+template <int DT>
+__global__ __launch_bounds__(256) void vo_bias_rows_kernel(const void* Wo, int64_t ld_wo, int64_t d, int n_cols, int hd, int group,
+                                                           const double* bw, const double* u, const void* b_o, int bo_dtype, int vec,
+                                                           double* o_bias, double* s_out, double* rho_out) {
+  __shared__ double sb_[VO_BIAS_CHUNK], su_[VO_BIAS_CHUNK];
+  constexpr int RPW = VO_BIAS_ROWS / 4;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int64_t row0 = (int64_t)blockIdx.x * VO_BIAS_ROWS + (int64_t)w * RPW;
+  double as[RPW], ar[RPW];
+#pragma unroll
+  for (int rr = 0; rr < RPW; rr++) as[rr] = ar[rr] = 0.;
+  for (int a0 = 0; a0 < n_cols; a0 += VO_BIAS_CHUNK) {
+    const int len = n_cols - a0 < VO_BIAS_CHUNK ? n_cols - a0 : VO_BIAS_CHUNK;
+    __syncthreads();
+    for (int e = tid; e < len; e += 256) {
+      const int j = a0 + e, src = (j / (group * hd)) * hd + j % hd;      // column j belongs to kv head j / (group hd)
+      sb_[e] = bw[src];
+      su_[e] = u[src];
+    }
+    __syncthreads();
+    // the wave's rows side by side, so that RPW loads per lane are in flight; a row beyond d reads row d - 1 and is dropped at the end
+    int64_t base[RPW];
+    double s[RPW], t[RPW];
+#pragma unroll
+    for (int rr = 0; rr < RPW; rr++) {
+      const int64_t row = row0 + rr < d ? row0 + rr : d - 1;
+      base[rr] = row * ld_wo + a0;
+      s[rr] = t[rr] = 0.;
+    }
+    int done = 0;
+    if ((DT == MDG_BF16 || DT == MDG_F16) && vec) {
+      for (int v = lane; v < len / 8; v += 64) {
+        uint4 q4[RPW];
+#pragma unroll
+        for (int rr = 0; rr < RPW; rr++) q4[rr] = ((const uint4*)((const unsigned short*)Wo + base[rr]))[v];
+        const double *bp = sb_ + 8 * v, *up = su_ + 8 * v;
+#pragma unroll
+        for (int rr = 0; rr < RPW; rr++) {
+          const unsigned q[4] = {q4[rr].x, q4[rr].y, q4[rr].z, q4[rr].w};
+#pragma unroll
+          for (int k = 0; k < 4; k++) {          // (element 2k in the low half)
+            const unsigned short lo = (unsigned short)(q[k] & 0xffffu), hi = (unsigned short)(q[k] >> 16);
+            const double x0 = DT == MDG_BF16 ? bf16_to_f64(lo) : f16_to_f64(lo);
+            const double x1 = DT == MDG_BF16 ? bf16_to_f64(hi) : f16_to_f64(hi);
+            s[rr] += x0 * bp[2 * k];
+            t[rr] += x0 * up[2 * k];
+            s[rr] += x1 * bp[2 * k + 1];
+            t[rr] += x1 * up[2 * k + 1];
+          }
+        }
+      }
+      done = len / 8 * 8;
+    }
+    for (int e = done + lane; e < len; e += 64) {
+      const double be = sb_[e], ue = su_[e];
+#pragma unroll
+      for (int rr = 0; rr < RPW; rr++) {
+        const double x = load_f64<DT>(Wo, base[rr] + e);
+        s[rr] += x * be;
+        t[rr] += x * ue;
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RPW; rr++) {
+      as[rr] += s[rr];
+      ar[rr] += t[rr];
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < RPW; rr++) {
+    double s = as[rr], t = ar[rr];
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o, 64);
+      t += __shfl_xor(t, o, 64);
+    }
+    const int64_t row = row0 + rr;
+    if (lane == 0 && row < d) {
+      s_out[row] = s;
+      rho_out[row] = t;
+      if (o_bias) {
+        double bo = 0.;
+        switch (bo_dtype) {
+          case MDG_BF16: bo = load_f64<MDG_BF16>(b_o, row); break;
+          case MDG_F16: bo = load_f64<MDG_F16>(b_o, row); break;
+          case MDG_F32: bo = load_f64<MDG_F32>(b_o, row); break;
+          default: bo = load_f64<MDG_F64>(b_o, row); break;
+        }
+        o_bias[row] = bo + s;
+      }
+    }
+  }
+}
+
+// resid = (sum_i rho_i^2, sum_i s_i^2): one workgroup, thread t sums rows t, t + 256, ... in ascending order, then a fixed tree
+__global__ __launch_bounds__(256) void vo_bias_norms_kernel(const double* s_in, const double* rho_in, int64_t d, double* resid) {
+  __shared__ double ps_[256], pr_[256];
+  const int tid = threadIdx.x;
+  double s = 0., r = 0.;
+  for (int64_t i = tid; i < d; i += 256) {
+    s += s_in[i] * s_in[i];
+    r += rho_in[i] * rho_in[i];
+  }
+  ps_[tid] = s;
+  pr_[tid] = r;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      ps_[tid] += ps_[tid + o];
+      pr_[tid] += pr_[tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    resid[0] = pr_[0];
+    resid[1] = ps_[0];
+  }
+}
+
+template <int DT>
+static int vo_bias_launch(const VoWs& w, const void* Wo, int64_t ld_wo, int64_t d, const void* b_v, const void* b_o, int b_dtype,
+                          int n_heads, int n_kv, int hd, int rank, double* o_bias, double* v_bias, double* resid, int vec,
+                          hipStream_t st) {
+  const int64_t a = (int64_t)n_kv * hd;
+  double *bw = w.T, *u = w.T + a, *s_rows = w.T + 2 * a, *rho_rows = s_rows + d;
+  switch (b_dtype) {
+    case MDG_BF16: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_BF16>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
+    case MDG_F16: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_F16>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
+    case MDG_F32: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_F32>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
+    default: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_F64>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
+  }
+  MDG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(vo_bias_rows_kernel<DT>, dim3((unsigned)ceil_div(d, VO_BIAS_ROWS)), dim3(256), 0, st, Wo, ld_wo, d, n_heads * hd, hd,
+                     n_heads / n_kv, bw, u, b_o, b_dtype, vec, o_bias, s_rows, rho_rows);
+  MDG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(vo_bias_norms_kernel, dim3(1), dim3(256), 0, st, s_rows, rho_rows, d, resid);
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}
+
 }  // namespace mdg
 
 using namespace mdg;
@@ -265,4 +434,35 @@ extern "C" int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* co
                        rank, grouped, eps, 0, out);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
+}
+
+extern "C" int mdg_vo_bias(void* ws, size_t ws_bytes, const void* Wo, int64_t ld_wo, int w_dtype, int64_t d, const void* b_v,
+                           const void* b_o, int b_dtype, int n_heads, int n_kv, int hd, int rank, double* o_bias, double* v_bias,
+                           double* resid, void* stream) {
+  MDG_CLEAR();
+  MDG_CHECK_ARG(Wo && b_v && resid, "mdg_vo_bias: null pointer");
+  MDG_CHECK_ARG(w_dtype == MDG_BF16 || w_dtype == MDG_F16 || w_dtype == MDG_F64, "mdg_vo_bias: W_o must be bf16, fp16 or f64 (got %d)",
+                w_dtype);
+  MDG_CHECK_ARG(b_dtype == MDG_BF16 || b_dtype == MDG_F16 || b_dtype == MDG_F32 || b_dtype == MDG_F64,
+                "mdg_vo_bias: unsupported bias dtype %d", b_dtype);
+  MDG_CHECK_ARG(n_kv > 0 && n_heads > 0 && n_heads % n_kv == 0 && hd >= 2 && hd <= 128 && hd % 2 == 0,
+                "mdg_vo_bias: unsupported head layout (n_heads=%d n_kv=%d hd=%d)", n_heads, n_kv, hd);
+  MDG_CHECK_ARG(rank >= 1 && rank <= hd, "mdg_vo_bias: rank %d outside [1, %d]", rank, hd);
+  MDG_CHECK_ARG(d > 0 && d < (1ll << 31) && ld_wo >= (int64_t)n_heads * hd && (int64_t)n_heads * hd < (1ll << 31),
+                "mdg_vo_bias: bad leading dimensions");
+  MDG_CHECK_ARG(b_o ? o_bias != nullptr : v_bias != nullptr, "mdg_vo_bias: o_bias is required with b_o, v_bias without it");
+  MDG_CHECK_ARG(ws && ws_bytes >= mdg_vo_compress_ws_bytes(d, n_heads, n_kv, hd), "mdg_vo_bias: workspace too small");
+  // (the scratch lives in the workspace's T block, n_kv hd d doubles: see vo_bias_head_kernel)
+  MDG_CHECK_ARG(2 * ((int64_t)n_kv * hd + d) <= (int64_t)n_kv * hd * d, "mdg_vo_bias: d = %lld too small for the scratch", (long long)d);
+  VoWs w = vo_layout(ws, d, n_heads, n_kv, hd);
+  hipStream_t st = (hipStream_t)stream;
+  const int vec = w_dtype != MDG_F64 && (uintptr_t)Wo % 16 == 0 && ld_wo % 8 == 0;
+  // with b_o the v bias is folded into o_bias and v_bias is not written; without it o_bias is not written
+  double* ob = b_o ? o_bias : nullptr;
+  double* vb = b_o ? nullptr : v_bias;
+  if (w_dtype == MDG_BF16)
+    return vo_bias_launch<MDG_BF16>(w, Wo, ld_wo, d, b_v, b_o, b_dtype, n_heads, n_kv, hd, rank, ob, vb, resid, vec, st);
+  if (w_dtype == MDG_F16)
+    return vo_bias_launch<MDG_F16>(w, Wo, ld_wo, d, b_v, b_o, b_dtype, n_heads, n_kv, hd, rank, ob, vb, resid, vec, st);
+  return vo_bias_launch<MDG_F64>(w, Wo, ld_wo, d, b_v, b_o, b_dtype, n_heads, n_kv, hd, rank, ob, vb, resid, 0, st);
 }

@@ -45,7 +45,8 @@ calib_device = d2
 # architecture -> modeling file the checkpoint ships with (this engine's own, modegpt_amd/patchers/; file and class
 # names are the reference's so config.auto_map is unchanged)
 PATCHERS_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "patchers")
-REBUILD_FILES = {"opt": "OPTRebuild.py", "llama": "LlamaRebuild.py", "qwen": "DenseQwenRebuild.py"}
+REBUILD_FILES = {"opt": "OPTRebuild.py", "llama": "LlamaRebuild.py", "qwen2": "Qwen2Rebuild.py",     # (first match wins: qwen2 before qwen)
+                 "qwen": "DenseQwenRebuild.py"}
 
 
 def rebuild_file_for(arch: str) -> str:

@@ -1139,10 +1139,55 @@ def decode_qk_logit_error(curve_h, curve, rank: int, cols_per_unit: int, terms=N
 VO_SPECTRUM_FIELDS = ("lambda_r", "lambda_next", "gap", "energy", "bound", "separated", "lambda_max", "lambda_min")
 
 
+def keep_bias_enabled(arch: Optional[str] = None) -> bool:
+    """Whether the compressors carry the projection biases into the artefacts ("Projection biases"): always
+    for Qwen2 / Qwen2.5 (model_type "qwen2": nothing of the reference's to preserve, and dropping q/k/v biases is never right),
+    otherwise MODEGPT_KEEP_BIAS as it stands when a compressor asks (per layer; not frozen at import).  Off: the reference's
+    behaviour, every rebuilt Linear bias-free (model_adapter.py:199-208)."""
+    if arch == "qwen2":
+        return True
+    return os.environ.get("MODEGPT_KEEP_BIAS", "0").lower() in ("1", "on", "true")
+
+
+def vo_bias(ws: torch.Tensor, W_o: torch.Tensor, b_v: torch.Tensor, b_o: Optional[torch.Tensor], n_heads: int, n_kv: int, hd: int,
+            rank: int):
+    """The v_proj / o_proj biases through the truncation the LAST mdg_vo_compress call on workspace `ws` computed (mdg_vo_bias; same
+    stream, same shapes and rank).  W_o: the ORIGINAL [d, n_heads*hd] weight (bf16 / fp16 as they are, anything else widened exactly to
+    fp64); b_v [n_kv*hd], b_o [d] or None.  Returns (o_bias, v_bias, resid), fp64 ON THE DEVICE: with b_o, o_bias [d] = b_o + sum_h
+    W_o,h b_v,kv(h) and v_bias is None (v_proj becomes bias-free, nothing is lost at any rank); without, v_bias [n_kv*rank] = P_g b_v,g
+    and o_bias is None.  resid [2] = (||rho||^2, ||sum_h W_o,h b_v||^2), rho the part of the constant the second form cannot carry.
+    The call only enqueues."""
+    _need_gpu(ws, W_o, b_v, b_o)
+    lib = _lib.load()
+    Wo = W_o.detach()
+    if Wo.dtype not in (torch.bfloat16, torch.float16, torch.float64):
+        Wo = Wo.to(torch.float64)
+    if Wo.stride(-1) != 1:
+        Wo = Wo.contiguous()
+    d = Wo.shape[0]
+    if Wo.dim() != 2 or Wo.shape[1] != n_heads * hd:
+        raise ValueError(f"vo_bias: W_o must be [d, {n_heads * hd}], got {tuple(Wo.shape)}")
+    bv = b_v.detach().contiguous()
+    bo = None if b_o is None else b_o.detach().to(bv.dtype).contiguous()
+    if bv.numel() != n_kv * hd or (bo is not None and bo.numel() != d):
+        raise ValueError(f"vo_bias: b_v must hold {n_kv * hd} entries and b_o {d}")
+    dev = Wo.device
+    o_bias = torch.empty(d, dtype=torch.float64, device=dev) if bo is not None else None
+    v_bias = torch.empty(n_kv * rank, dtype=torch.float64, device=dev) if bo is None else None
+    resid = torch.empty(2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mdg_vo_bias(ws.data_ptr(), ws.numel() * ws.element_size(), Wo.data_ptr(), Wo.stride(0), _DT[Wo.dtype], d,
+                              bv.data_ptr(), _p(bo), _DT[bv.dtype], n_heads, n_kv, hd, rank, _p(o_bias), _p(v_bias), resid.data_ptr(),
+                              _stream(Wo)), "mdg_vo_bias")
+    return o_bias, v_bias, resid
+
+
 def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
                 ridge: float, want_f64: bool = False, want_spectrum: bool = False, spectrum_eps: Optional[float] = None,
-                want_curve: bool = False):
-    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum][, curve]).
+                want_curve: bool = False, bias=None):
+    """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum][, curve][, bias]).
+    bias: (b_v, b_o or None) -- vo_bias's (o_bias, v_bias, resid) for this truncation comes last in the tuple, enqueued behind
+    everything else while the workspace is alive; the factors are the same bits with or without it.
     want_curve: what the truncation costs the attention output at every rank (mdg_vo_rank_curve: [n_kv, hd + 1] fp64 ON THE DEVICE;
     decode_vo_output_error reads it), enqueued like the spectrum, behind the factorisation while its workspace is alive.
     want_spectrum: what the truncation at `rank` did to the spectrum (mdg_vo_spectrum: [n_kv, 8] fp64 ON THE DEVICE,
@@ -1179,9 +1224,12 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
             cws, cwsp = _ws(cbytes, dev)
             check(lib.mdg_vo_rank_curve(wsp, nbytes, Wo.data_ptr(), Wo.stride(0), _DT[Wo.dtype], d, n_heads, n_kv, hd,
                                         curve.data_ptr(), cwsp, cbytes, _stream(Cx)), "mdg_vo_rank_curve")
+        if bias is not None:
+            carried = vo_bias(ws, W_o, bias[0], bias[1], n_heads, n_kv, hd, rank)
     out = (v_out, o_out, v64, o64) if want_f64 else (v_out, o_out)
     out = out + (spectrum,) if want_spectrum else out
-    return out + (curve,) if want_curve else out
+    out = out + (curve,) if want_curve else out
+    return out + (carried,) if bias is not None else out
 
 
 def decode_vo_spectrum(rows, eps: float) -> dict:

@@ -20,7 +20,7 @@ stock HF modules and gives their attention the compressed semantics, with the el
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
   shrink_to_config_ranks(model, arch)                   called by the modeling files shipped with a checkpoint
-                                                         (patchers/{LlamaRebuild,DenseQwenRebuild,OPTRebuild}.py)
+                                                         (patchers/{LlamaRebuild,DenseQwenRebuild,Qwen2Rebuild,OPTRebuild}.py)
 
 This file travels WITH a compressed checkpoint (model_utils.save_compressed_model copies it next to the *Rebuild.py that
 imports it relatively), the way the reference ships its self-contained modeling file (src/model_utils.py:103-124): it
@@ -134,7 +134,8 @@ def _attention_interface(module):
 
 
 def _rope_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
-    """Llama / Qwen3 (RoPE, optional GQA, optional per-head q/k RMSNorm)."""
+    """Llama / Qwen2 / Qwen3 (RoPE, optional GQA, optional per-head q/k RMSNorm; projection biases, where the modules carry them,
+    act before the norm and the rotation as in the stock modules)."""
     if torch.is_grad_enabled() and hidden_states.requires_grad:
         raise RuntimeError("compressed attention is inference-only (mdg_rope_gather has no backward); use torch.no_grad()")
     B, T, _ = hidden_states.shape
@@ -226,35 +227,43 @@ def install_compressed_attention(adapter, rotary_masks: Optional[List[torch.Tens
     _install(adapter.model, "opt" if adapter.arch == "opt" else adapter.arch, rotary_masks)
 
 
-def _resize(linear: nn.Linear, out_features: Optional[int] = None, in_features: Optional[int] = None) -> nn.Linear:
-    """A bias-free Linear of the compressed shape (ModelAdapter.convert_model builds bias-free modules,
-    model_adapter.py:199-208, so the checkpoint holds no bias for them), on the device / dtype of the one it replaces."""
+def _resize(linear: nn.Linear, out_features: Optional[int] = None, in_features: Optional[int] = None, bias: bool = False) -> nn.Linear:
+    """A Linear of the compressed shape on the device / dtype of the one it replaces: bias-free (ModelAdapter.convert_model builds
+    bias-free modules, model_adapter.py:199-208, so the checkpoint holds no bias for them) unless `bias` -- the checkpoint's
+    config.projection_biases names this projection: a run that carried the biases (MODEGPT_KEEP_BIAS=1, Qwen2)."""
     o = linear.out_features if out_features is None else out_features
     i = linear.in_features if in_features is None else in_features
-    if (o, i) == (linear.out_features, linear.in_features) and linear.bias is None:
+    if (o, i) == (linear.out_features, linear.in_features) and (linear.bias is not None) == bias:
         return linear
-    return nn.Linear(i, o, bias=False, device=linear.weight.device, dtype=linear.weight.dtype)
+    return nn.Linear(i, o, bias=bias, device=linear.weight.device, dtype=linear.weight.dtype)
 
 
 def shrink_to_config_ranks(model, arch: str) -> None:
     """Called from the constructor of a modeling file shipped with a compressed checkpoint, BEFORE the weights are loaded:
     give every projection the per-layer shape recorded by patch_config (q_ranks / k_ranks / v_ranks / o_ranks /
-    gate_ranks; qk_ranks / vo_ranks for OPT), read rotary_masks.pt from config.mask_path, install the forward."""
+    gate_ranks; qk_ranks / vo_ranks for OPT) and a bias exactly where config.projection_biases says the state dict holds
+    one, read rotary_masks.pt from config.mask_path, install the forward."""
     cfg = model.config
     attns = _attention_modules(model, arch)
     blocks = model.model.decoder.layers if arch == "opt" else model.model.layers
+    has = set(getattr(cfg, "projection_biases", None) or ())      # (absent: a checkpoint without carried biases, as before)
     for i, (block, attn) in enumerate(zip(blocks, attns)):
         if arch == "opt":
             qk, vo = cfg.qk_ranks[i], cfg.vo_ranks[i]
-            attn.q_proj, attn.k_proj = _resize(attn.q_proj, qk), _resize(attn.k_proj, qk)
-            attn.v_proj, attn.out_proj = _resize(attn.v_proj, vo), _resize(attn.out_proj, in_features=vo)
-            block.fc1, block.fc2 = _resize(block.fc1, cfg.gate_ranks[i]), _resize(block.fc2, in_features=cfg.gate_ranks[i])
+            attn.q_proj, attn.k_proj = _resize(attn.q_proj, qk, bias="q" in has), _resize(attn.k_proj, qk, bias="k" in has)
+            attn.v_proj = _resize(attn.v_proj, vo, bias="v" in has)
+            attn.out_proj = _resize(attn.out_proj, in_features=vo, bias="o" in has)
+            block.fc1 = _resize(block.fc1, cfg.gate_ranks[i], bias="up" in has)
+            block.fc2 = _resize(block.fc2, in_features=cfg.gate_ranks[i], bias="down" in has)
         else:
-            attn.q_proj, attn.k_proj = _resize(attn.q_proj, cfg.q_ranks[i]), _resize(attn.k_proj, cfg.k_ranks[i])
-            attn.v_proj, attn.o_proj = _resize(attn.v_proj, cfg.v_ranks[i]), _resize(attn.o_proj, in_features=cfg.o_ranks[i])
+            attn.q_proj = _resize(attn.q_proj, cfg.q_ranks[i], bias="q" in has)
+            attn.k_proj = _resize(attn.k_proj, cfg.k_ranks[i], bias="k" in has)
+            attn.v_proj = _resize(attn.v_proj, cfg.v_ranks[i], bias="v" in has)
+            attn.o_proj = _resize(attn.o_proj, in_features=cfg.o_ranks[i], bias="o" in has)
             g = cfg.gate_ranks[i]
-            block.mlp.gate_proj, block.mlp.up_proj = _resize(block.mlp.gate_proj, g), _resize(block.mlp.up_proj, g)
-            block.mlp.down_proj = _resize(block.mlp.down_proj, in_features=g)
+            block.mlp.gate_proj = _resize(block.mlp.gate_proj, g, bias="gate" in has)
+            block.mlp.up_proj = _resize(block.mlp.up_proj, g, bias="up" in has)
+            block.mlp.down_proj = _resize(block.mlp.down_proj, in_features=g, bias="down" in has)
     masks = None
     path = getattr(cfg, "mask_path", None)
     if arch != "opt" and path:

@@ -128,6 +128,9 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
     report = getattr(adapter, "report_qk_errors", None)
     if report is not None:
         report(logger)                          # ... what the Q/K pair selections lose of the logits (MODEGPT_QK_ERROR=1) -> metrics["qk_logit_error"]
+    report = getattr(adapter, "report_vo_bias_residuals", None)
+    if report is not None:
+        report(logger)                          # ... what a truncated v_proj loses of a carried v bias (Qwen2; MODEGPT_KEEP_BIAS=1) -> metrics["vo_bias_residual"]
     report = getattr(adapter, "report_attention_margins", None)
     if report is not None:
         report(logger)                          # ... and of its QK pair selections / VO truncations -> metrics["qk_selection"], ["vo_spectrum"]

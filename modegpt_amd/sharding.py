@@ -7,9 +7,10 @@ partition()) and no data-path collective is needed until the end, when ONE all-g
 compressed checkpoint on every rank.
 
 Packed record per layer (all 2-byte words, bf16 bit patterns or int16 quarters of int64s):
-    header  : 16 x int64  = [layer_idx, n_tensors, (rows, cols) x 7 tensors]   (up, gate, down, q, k, v, o)
+    header  : 24 x int64  = [layer_idx, n_tensors, (rows, cols) x 7 tensors, length x 7 biases, bias dtype code]
+                            (up, gate, down, q, k, v, o; a bias of length 0 is absent; code 0: the layer carries none)
     mask hdr:  2 x int64  = [n_kv, rank]  followed by the int64 rotary mask
-    payload : the tensors' bf16 words back to back
+    payload : the tensors' bf16 words back to back, then the biases' words (their own dtype, one dtype per layer) back to back
 Records are padded to the largest record of the call (per-layer ranks differ with the keep ratios); a rank sends as many
 records as it owns layers (the counts travel with the stride agreement), so uneven blocks do not pad to the largest block.
 """
@@ -22,7 +23,10 @@ import torch
 import torch.distributed as dist
 
 TENSOR_ORDER = ("up", "gate", "down", "q_proj", "k_proj", "v_proj", "o_proj")
-_HDR_I64 = 16
+BIAS_ORDER = ("up_bias", "gate_bias", "down_bias", "q_bias", "k_bias", "v_bias", "o_bias")     # slot for slot the biases of TENSOR_ORDER
+_BIAS_DTYPES = {1: torch.bfloat16, 2: torch.float16, 3: torch.float32, 4: torch.float64}
+_HDR_I64 = 24
+_BIAS_LEN0, _BIAS_CODE = 16, 23
 
 
 def init_from_env() -> Tuple[int, int]:
@@ -107,6 +111,17 @@ def pack_layer(layer_idx: int, tensors: Dict[str, Optional[torch.Tensor]], mask:
         parts.append(t.contiguous().view(torch.int16).reshape(-1))
         n += 1
     hdr[1] = n
+    for slot, name in enumerate(BIAS_ORDER):
+        b = tensors.get(name)
+        if b is None:
+            continue
+        code = next((c for c, dt in _BIAS_DTYPES.items() if dt == b.dtype), None)
+        if code is None or b.dim() != 1 or b.numel() == 0:
+            raise ValueError(f"{name}: expected a non-empty 1-D floating-point tensor")
+        if int(hdr[_BIAS_CODE]) not in (0, code):
+            raise ValueError(f"{name}: the biases of one layer must share a dtype")
+        hdr[_BIAS_CODE], hdr[_BIAS_LEN0 + slot] = code, b.numel()
+        parts.append(b.contiguous().view(torch.int16).reshape(-1))
     if mask is None:
         mh = torch.zeros(2, dtype=torch.int64)
         mparts = []
@@ -133,6 +148,14 @@ def unpack_layer(rec: torch.Tensor) -> Tuple[int, Dict[str, torch.Tensor], Optio
             continue
         out[name] = rec[off:off + rows * cols].contiguous().view(torch.bfloat16).reshape(rows, cols)
         off += rows * cols
+    dtype = _BIAS_DTYPES.get(int(head[_BIAS_CODE]))
+    for slot, name in enumerate(BIAS_ORDER):
+        n = int(head[_BIAS_LEN0 + slot])
+        if n == 0 or dtype is None:
+            continue
+        words = n * dtype.itemsize // 2
+        out[name] = rec[off:off + words].clone().view(dtype)       # (a copy: a wider dtype's view needs an aligned start)
+        off += words
     return layer_idx, out, mask
 
 
@@ -254,7 +277,8 @@ def gather_layer_artifacts(adapter, chunk: Sequence[int], mine: Sequence[int], r
         masks[layer] = mask
         if layer in mine or rank != writer_rank:
             continue
-        groups = {"mlp": ("up", "gate", "down"), "qk": ("q_proj", "k_proj"), "vo": ("v_proj", "o_proj")}
+        groups = {"mlp": ("up", "gate", "down", "up_bias", "gate_bias", "down_bias"), "qk": ("q_proj", "k_proj", "q_bias", "k_bias"),
+                  "vo": ("v_proj", "o_proj", "v_bias", "o_bias")}
         for suffix, names in groups.items():
             w = {k: tensors[k].clone() for k in names if k in tensors}
             if w:
