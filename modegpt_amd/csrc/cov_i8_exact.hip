@@ -43,7 +43,7 @@ namespace {
 // does -- and the exact route then REPLACES the truncated five- or six-plane product whenever every remainder list fits its
 // list (LO_CAP events per column and 2048 tokens = 6.2 % of the elements; cubed Gaussians, Student-t: no -- the truncated
 // product with its bound takes those as before).  Cost at the sigma_mlp shape (profiles/r04_exact_route_kernels_*.csv): lists 0.08 /
-// 0.25 ms, remainder products 1.0 ms (Gaussian) / 5.4 + 0.5 ms for the copy (SiLU-gated) against 0.4 x 2.1 ... 6.1 x 2.1 ms of
+// 0.25 ms, remainder products 0.7 ms (Gaussian; 1.0 with the tile kernel's longer chain of round trips) / 5.4 + 0.5 ms for the copy (SiLU-gated) against 0.4 x 2.1 ... 6.1 x 2.1 ms of
 // plane-pair products saved.
 constexpr int LO_CHUNK_STEPS = 64;       // k-steps (2048 tokens) per segment of a column's event list
 constexpr int LO_CAP = 128;              // events per segment: 6.2 % of its 2048 tokens
@@ -294,111 +294,160 @@ __device__ __forceinline__ int lo_perm(int i) { return (i >> 1) + 64 * (i & 1); 
 // partner's top three digit planes -- which IS x for every element within 14 binades of its column maximum (no digit below plane
 // 2), so the rounding is taken only when a lane meets a deeper one.  partner0: first column of the partner block.
 // The walk is bound by the latency of the partner loads (one 4-byte load per event and lane, rows scattered over the tokens) and
-// by the VALU (7 - 14 operations per event): the events go in batches of LO_UN whose loads are all issued before the previous
-// batch is multiplied (two batches in flight per wave, sixteen waves per CU).
-constexpr int LO_UN = 32;
-// The length of list (G, sub) and its first batch of entries, one per lane (lanes beyond the list's end: the last entry's token,
-// v = 0: exact zeros) -- fetched for BOTH passes of a tile before the first one starts, so that the second pass does not begin with
-// two dependent memory round trips of its own.
+// by the VALU and the LDS atomics (7 - 14 operations per event): the events go in batches of LO_UN whose loads are all issued
+// before the previous batch is multiplied (two batches in flight per wave, sixteen waves per CU).  A Gaussian list holds ~16
+// events: at 32 slots per batch half of them were padding -- a partner load and two ds_add_f64 of an exact zero each -- so a batch
+// is 16 slots, and a list's last (or only) batch 8 when no more are left (LO_SHORT; wave-uniform).  Leaving padding out changes
+// no bit: an accumulator is never -0 (it starts at +0, and a sum that cancels gives +0), so adding +-0 to it is the identity
+// (0 x Inf is not +-0, but a column that holds an Inf or a NaN has left for the fp64 column kernel and its sums are not stored).
+constexpr int LO_UN = 16;
+#ifndef MDG_LO_SHORT
+#define MDG_LO_SHORT 8
+#endif
+constexpr int LO_SHORT = MDG_LO_SHORT;       // 0: every batch LO_UN wide
+constexpr int LO_HEAD = 64;                  // entries of a list's head: one per lane, i.e. batches 0 .. LO_HEAD / LO_UN - 1
+// The length of a list and its head, one entry per lane (lanes beyond the list's end: the last entry's token, v = 0: exact
+// zeros) -- fetched for BOTH passes of a tile before the first one starts.  The kernel has the length already (its first round
+// trip), so the head is ONE dependent load, and a list of up to 64 events never fetches entries again.  The load is not
+// conditional (an empty list reads its slot's first entry, which is inside the buffer, and uses nothing of it): behind a branch
+// each of a wave's two heads was waited for inside its branch, one round trip after the other.
 struct LoFirst {
   int cnt;
   LoEntry m;
 };
-__device__ __forceinline__ LoFirst lo_first(const LoProblem& pr, const int G, const int sub, const int lane) {
-  const int list_id = G * LO_SUB + sub;
+__device__ __forceinline__ LoFirst lo_first(const LoProblem& pr, const int list_id, const int cnt, const int lane) {
   LoFirst f;
-  f.cnt = __builtin_amdgcn_readfirstlane(pr.rtotals[list_id]);
-  f.m = LoEntry{0., 0u, 0u};
-  if (f.cnt > 0) {
-    f.m = pr.rentries[(int64_t)list_id * LO_RCAP + min(lane & (LO_UN - 1), f.cnt - 1)];
-    if ((lane & (LO_UN - 1)) >= f.cnt) f.m.v = 0.;
-  }
+  f.cnt = cnt;
+  f.m = pr.rentries[(int64_t)list_id * LO_RCAP + min(lane, max(cnt, 1) - 1)];
+  if (lane >= cnt) f.m.v = 0.;
   return f;
 }
-template <class EL, bool RELU, bool COLS>
-__device__ __forceinline__ void lo_events(const LoProblem& pr, const int nch, const int G, const int sub, const int partner0, const int g,
-                                          const int lane, double* acc, const LoFirst& first) {
-  const unsigned short* xs = (const unsigned short*)pr.x;
-  unsigned lim_a = 0, lim_b = 0;
-  double qa = 1., qb = 1., ia = 1., ib = 1.;
-  if (COLS) {   // the partner rows' digit grid: 2^24 units of their own scale
-    const int ea = pr.emax[partner0 + 2 * lane] & 255, eb = pr.emax[partner0 + 2 * lane + 1] & 255;
-    qa = ldexp(1.0, ea - 148);
-    qb = ldexp(1.0, eb - 148);
-    ia = 1.0 / qa;
-    ib = 1.0 / qb;
-    // an element has a digit below plane 2 iff its exponent field is below a limit set by E (and it is not zero): 0 < |bits| < deep_limit(E)
-    lim_a = EL::deep_limit(ea);
-    lim_b = EL::deep_limit(eb);
+// The partner loads of the slots U0 .. U1 - 1 of a batch, whose entries sit in lanes e0 .. of m_off (the entries' row offsets);
+// col0 = the lane's first partner column.
+template <class EL, bool RELU, int U0, int U1>
+__device__ __forceinline__ void lo_issue_n(const LoProblem& pr, const unsigned m_off, const int e0, const int col0, unsigned (&xv)[LO_UN]) {
+  if (pr.pairs) {
+#pragma unroll
+    for (int u = U0; u < U1; u++) {
+      const unsigned off = (unsigned)__builtin_amdgcn_readlane((int)m_off, e0 + u);
+      xv[u] = relu_pair<EL, RELU>(*(const unsigned*)((const unsigned short*)((const char*)pr.x + off) + col0));
+    }
+  } else {
+#pragma unroll
+    for (int u = U0; u < U1; u++) {
+      const unsigned off = (unsigned)__builtin_amdgcn_readlane((int)m_off, e0 + u);
+      const unsigned short* row = (const unsigned short*)((const char*)pr.x + off) + col0;
+      xv[u] = relu_pair<EL, RELU>((unsigned)row[0] | ((unsigned)row[1] << 16));
+    }
   }
-  const int list_id = G * LO_SUB + sub;
-  const int cnt = first.cnt;
-  const LoEntry* list = pr.rentries + (int64_t)list_id * LO_RCAP;
-  // batch k: events [k LO_UN, ...) -- one entry per lane (lanes beyond the list's end: the last entry's token, v = 0: exact zeros)
-  auto fetch = [&](int k, LoEntry& m) {
-    m = list[min(k * LO_UN + (lane & (LO_UN - 1)), cnt - 1)];
-    if (k * LO_UN + (lane & (LO_UN - 1)) >= cnt) m.v = 0.;
-  };
-  auto issue = [&](const LoEntry& m, unsigned (&xv)[LO_UN]) {
+}
+// ... of a batch with `left` events still to go (wave-uniform): the short width when they fit it.  (Written as "the first slots,
+// then perhaps the rest", not as two whole batches of either width: hipcc merges the equal tails of two such branches into stores
+// at a variable index, and the batch then lives in scratch.)
+constexpr int LO_FIRST_SLOTS = LO_SHORT ? LO_SHORT : LO_UN;
+template <class EL, bool RELU>
+__device__ __forceinline__ void lo_issue(const LoProblem& pr, const unsigned m_off, const int e0, const int left, const int col0,
+                                         unsigned (&xv)[LO_UN]) {
+  lo_issue_n<EL, RELU, 0, LO_FIRST_SLOTS>(pr, m_off, e0, col0, xv);
+  if (LO_SHORT && left > LO_SHORT) lo_issue_n<EL, RELU, LO_FIRST_SLOTS, LO_UN>(pr, m_off, e0, col0, xv);
+}
+// ... and its products: acc += x_lo (the entry's v, broadcast) x partner, two per lane.  COLS: the partner's top three digit planes;
+// its rows' digit grid is 2^24 units of their own scale, q = 2^(E - 148) = 2^sa, 2^sb (kept as exponents: the scalings are
+// v_ldexp_f64 in the rare branch that needs them, not four fp64 registers held through the walk); an element has a digit below
+// plane 2 iff its exponent field is below a limit set by E (and it is not zero): 0 < |bits| < deep_limit(E) = lim_a, lim_b
+template <class EL, bool COLS, int U0, int U1>
+__device__ __forceinline__ void lo_multiply_n(double* acc, const LoEntry& m, const int e0, const unsigned (&xv)[LO_UN], const int g, const int lane,
+                                              const int sa, const int sb, const unsigned lim_a, const unsigned lim_b) {
 #pragma unroll
-    for (int u = 0; u < LO_UN; u++) {
-      const unsigned off = (unsigned)__builtin_amdgcn_readlane((int)m.off, u);
-      const unsigned short* row = (const unsigned short*)((const char*)xs + off) + partner0 + 2 * lane;
-      xv[u] = relu_pair<EL, RELU>(pr.pairs ? *(const unsigned*)row : ((unsigned)row[0] | ((unsigned)row[1] << 16)));
-    }
-  };
-  auto multiply = [&](const LoEntry& m, const unsigned (&xv)[LO_UN]) {
-#pragma unroll
-    for (int u = 0; u < LO_UN; u++) {
-      const double v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m.v), u), __builtin_amdgcn_readlane(__double2loint(m.v), u));
-      const int col = __builtin_amdgcn_readlane((int)m.aux, u);
-      double pa = EL::to_f64(xv[u] & 0xFFFFu), pb = EL::to_f64(xv[u] >> 16);
-      if (COLS) {
-        const bool deep = ((xv[u] & 0x7FFFu) - 1u < lim_a - 1u) || (((xv[u] >> 16) & 0x7FFFu) - 1u < lim_b - 1u);
-        if (__ballot(deep)) {
-          pa = floor(pa * ia + LO_ROUND) * qa;                             // exact (powers of two, one floor)
-          pb = floor(pb * ib + LO_ROUND) * qb;
-        }
-        lds_add_f64(acc + lane * LO_PITCH + lo_perm(g * 32 + col), v * pa);            // rows 2 lane, 2 lane + 1
-        lds_add_f64(acc + (64 + lane) * LO_PITCH + lo_perm(g * 32 + col), v * pb);
-      } else {
-        lds_add_f64(acc + lo_perm(g * 32 + col) * LO_PITCH + lane, v * pa);            // columns 2 lane, 2 lane + 1
-        lds_add_f64(acc + lo_perm(g * 32 + col) * LO_PITCH + 64 + lane, v * pb);
+  for (int u = U0; u < U1; u++) {
+    const double v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m.v), e0 + u), __builtin_amdgcn_readlane(__double2loint(m.v), e0 + u));
+    const int col = __builtin_amdgcn_readlane((int)m.aux, e0 + u);
+    double pa = EL::to_f64(xv[u] & 0xFFFFu), pb = EL::to_f64(xv[u] >> 16);
+    if (COLS) {
+      const bool deep = ((xv[u] & 0x7FFFu) - 1u < lim_a - 1u) || (((xv[u] >> 16) & 0x7FFFu) - 1u < lim_b - 1u);
+      if (__ballot(deep)) {
+        pa = ldexp(floor(ldexp(pa, -sa) + LO_ROUND), sa);                // exact (powers of two, one floor)
+        pb = ldexp(floor(ldexp(pb, -sb) + LO_ROUND), sb);
       }
+      lds_add_f64(acc + lane * LO_PITCH + lo_perm(g * 32 + col), v * pa);            // rows 2 lane, 2 lane + 1
+      lds_add_f64(acc + (64 + lane) * LO_PITCH + lo_perm(g * 32 + col), v * pb);
+    } else {
+      lds_add_f64(acc + lo_perm(g * 32 + col) * LO_PITCH + lane, v * pa);            // columns 2 lane, 2 lane + 1
+      lds_add_f64(acc + lo_perm(g * 32 + col) * LO_PITCH + 64 + lane, v * pb);
+    }
+  }
+}
+// x0: the partner loads of the list's first batch, issued by the kernel (lo_issue with e0 = 0, left = the list's length) before
+// the tile's first barrier -- for both passes, so that the second does not start with a memory round trip of its own.
+// ea, eb (COLS): emax of the lane's two partner rows.
+template <class EL, bool RELU, bool COLS>
+__device__ __forceinline__ void lo_events(const LoProblem& pr, const int list_id, const int partner0, const int g, const int lane, double* acc,
+                                          const LoFirst& first, const unsigned (&x0)[LO_UN], const int ea, const int eb) {
+  const int cnt = first.cnt;
+  if (cnt == 0) return;
+  const int sa = (ea & 255) - 148, sb = (eb & 255) - 148;
+  const unsigned lim_a = COLS ? EL::deep_limit(ea & 255) : 0u, lim_b = COLS ? EL::deep_limit(eb & 255) : 0u;
+  const int col0 = partner0 + 2 * lane;
+  const LoEntry* list = pr.rentries + (int64_t)list_id * LO_RCAP;
+  // batch k: events [k LO_UN, ...).  Its entries: lanes e0 .. of the head while that lasts, then one entry per lane (mod LO_UN) of
+  // a fetch of its own (lanes beyond the list's end: the last entry's token, v = 0: exact zeros)
+  auto entries = [&](int k, LoEntry& m, int& e0) {
+    if (k < LO_HEAD / LO_UN) {
+      m = first.m;
+      e0 = k * LO_UN;
+    } else {
+      m = list[min(k * LO_UN + (lane & (LO_UN - 1)), cnt - 1)];
+      if (k * LO_UN + (lane & (LO_UN - 1)) >= cnt) m.v = 0.;
+      e0 = 0;
     }
   };
-  if (cnt == 0) return;
+  auto multiply = [&](const LoEntry& m, const int e0, const int left, const unsigned (&xv)[LO_UN]) {
+    lo_multiply_n<EL, COLS, 0, LO_FIRST_SLOTS>(acc, m, e0, xv, g, lane, sa, sb, lim_a, lim_b);
+    if (LO_SHORT && left > LO_SHORT) lo_multiply_n<EL, COLS, LO_FIRST_SLOTS, LO_UN>(acc, m, e0, xv, g, lane, sa, sb, lim_a, lim_b);
+  };
   const int nb = (cnt + LO_UN - 1) / LO_UN;
-  LoEntry mA = first.m, mB;
+  LoEntry mA = first.m, mB = first.m;
+  int eA = 0, eB = 0;
   unsigned xA[LO_UN], xB[LO_UN];
-  issue(mA, xA);
+#pragma unroll
+  for (int u = 0; u < LO_UN; u++) xA[u] = x0[u];
   for (int k = 0; k < nb; k += 2) {
     if (k + 1 < nb) {
-      fetch(k + 1, mB);
-      issue(mB, xB);
+      entries(k + 1, mB, eB);
+      lo_issue<EL, RELU>(pr, mB.off, eB, cnt - (k + 1) * LO_UN, col0, xB);
     }
     __builtin_amdgcn_sched_barrier(0);    // (batch B's loads are out before batch A's are waited for: hipcc would sink each load to its use)
-    multiply(mA, xA);
+    multiply(mA, eA, cnt - k * LO_UN, xA);
     if (k + 1 >= nb) break;
     if (k + 2 < nb) {
-      fetch(k + 2, mA);
-      issue(mA, xA);
+      entries(k + 2, mA, eA);
+      lo_issue<EL, RELU>(pr, mA.off, eA, cnt - (k + 2) * LO_UN, col0, xA);
     }
     __builtin_amdgcn_sched_barrier(0);
-    multiply(mB, xB);
+    multiply(mB, eB, cnt - (k + 1) * LO_UN, xB);
   }
 }
 
-// One workgroup of sixteen waves per 128 x 128 tile of the lower triangle (per-head statistics: the diagonal tiles): wave (g, sub)
-// takes the list `sub` of row group g, then of column group g.
+// One workgroup of sixteen waves per 128 x 128 tile of the lower triangle (per-head statistics: the diagonal tiles; a head is one
+// tile, block == LO_TILE): wave (g, sub) takes the list `sub` of row group g, then of column group g.
+// A tile is a chain of memory round trips around a handful of products, and one workgroup fills a CU (132 KB of LDS), so the chain
+// is what a tile costs.  It is three long: (1) the launch's state words and, beside them, the lengths of the wave's two lists (which
+// also decide the early exit) and emax of the tile's rows and columns; (2) the heads of both lists -- and, issued before them, the
+// thread's 16 elements of sigma for the fold, whether or not they will be stored; (3) the first batch of partner rows of BOTH
+// passes.  The fold then has everything in registers.  (It used to be seven: state, the lengths, the lengths again, the two
+// heads one after the other, each pass's partners with emax, emax before the fold, sigma behind emax.)  No load leaves the
+// statistic's buffers: n is a multiple of LO_TILE, so every row and column of a tile exists; the elements above the diagonal of a
+// diagonal tile read sigma[0][0] instead.  Measured at the sigma_mlp shape, Gaussian columns, per launch
+// (profiles/lo_sparse_*_kernel_trace_bygrid.csv): 0.98 ms before, 0.69 - 0.71 with all of this; with every batch 16 slots wide (no short
+// last batch) 0.74; with the sigma loads behind the first partner loads instead of at entry (a wave's loads return in order, so at
+// entry the list heads wait for them, behind the partners only the second batches do) 0.72 -- entry it is.  Not built: two
+// workgroups of 128 x 64 per CU.
 constexpr int LO_THREADS = 1024;
 template <class EL, bool RELU>
 __global__ __launch_bounds__(LO_THREADS) void i8_lo_product_kernel(LoArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lo_acc[];     // [128][LO_PITCH]
-  if (a.state[EXACT_RAN] != 1 || a.state[EXACT_OVERFLOW] != 0 || a.state[EXACT_MODE] != 1) return;
   int p = 0;
   while (p + 1 < a.nprob && (int)blockIdx.x >= a.prob[p + 1].tile0[2]) p++;
-  if (a.route_flag[p] & 2) return;
   const LoProblem& pr = a.prob[p];
   const int t = blockIdx.x - pr.tile0[2];
   int bi, bj;
@@ -413,36 +462,50 @@ __global__ __launch_bounds__(LO_THREADS) void i8_lo_product_kernel(LoArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave & 3, sub = wave >> 2;
-  // anything to do?  (the lists of the tile's four row groups and four column groups)
-  int any = 0;
-  if (tid < 8 * LO_SUB) any = pr.rtotals[(tid < 4 * LO_SUB ? 4 * bi * LO_SUB : 4 * bj * LO_SUB - 4 * LO_SUB) + tid];
-  if (!__syncthreads_or(any)) return;
-  const LoFirst first_rows = lo_first(pr, 4 * bi + g, sub, lane), first_cols = lo_first(pr, 4 * bj + g, sub, lane);
-  for (int i = tid; i < LO_TILE * LO_PITCH; i += LO_THREADS) lo_acc[i] = 0.;
-  __syncthreads();
-  lo_events<EL, RELU, false>(pr, a.nch, 4 * bi + g, sub, bj * LO_TILE, g, lane, lo_acc, first_rows);
+  constexpr int PER = LO_TILE * LO_TILE / LO_THREADS, ROWS = LO_THREADS / LO_TILE;      // 16 elements per thread, 8 rows apart
+  // ---- round trip 1: the launch's state words and, beside them, the small loads of the tile (they lie in the workspace whatever
+  // the state says, and a workgroup that leaves at once has spent a few cached loads on them) ...
+  const int ran = a.state[EXACT_RAN], overflow = a.state[EXACT_OVERFLOW], mode = a.state[EXACT_MODE], flag = a.route_flag[p];
+  const int list_r = (4 * bi + g) * LO_SUB + sub, list_c = (4 * bj + g) * LO_SUB + sub;
+  const int len_r = pr.rtotals[list_r], len_c = pr.rtotals[list_c];
+  const int ea = pr.emax[bi * LO_TILE + 2 * lane], eb = pr.emax[bi * LO_TILE + 2 * lane + 1];      // rows 2 lane, 2 lane + 1 of the tile
+  const int c = tid % LO_TILE, col = bj * LO_TILE + c, row0 = bi * LO_TILE + tid / LO_TILE;
+  const int e_col = pr.emax[col];
+  __builtin_amdgcn_sched_barrier(0);
+  if (ran != 1 || overflow != 0 || mode != 1 || (flag & 2)) return;
+  // ... then sigma (128 KB per tile: only for a launch that runs), in flight until the fold
+  double* const sigma = pr.sigma;
+  const int64_t ld_sigma = pr.ld_sigma, at0 = (int64_t)row0 * ld_sigma + col - (pr.block ? bi * LO_TILE : 0);
+  double old[PER];
+#pragma unroll
+  for (int u = 0; u < PER; u++) {      // (every row of the tile exists; above the diagonal: offset 0, by a mask -- no branch around a load)
+    const int64_t at = at0 + (int64_t)u * ROWS * ld_sigma;
+    old[u] = sigma[at & -(int64_t)(col <= row0 + u * ROWS)];
+  }
+  for (int i = tid; i < LO_TILE * LO_PITCH; i += LO_THREADS) lo_acc[i] = 0.;      // (under the loads; the early exit's barrier is theirs too)
+  __builtin_amdgcn_sched_barrier(0);      // (all of the above is issued before the first of it is waited for)
+  // anything to do?  (the sixteen waves hold the lists of the tile's four row groups and four column groups between them)
+  const int cnt_r = __builtin_amdgcn_readfirstlane(len_r), cnt_c = __builtin_amdgcn_readfirstlane(len_c);
+  if (!__syncthreads_or(cnt_r | cnt_c)) return;
+  // ---- round trip 2: the heads of both lists;  3: their first batches of partner rows
+  const LoFirst first_rows = lo_first(pr, list_r, cnt_r, lane), first_cols = lo_first(pr, list_c, cnt_c, lane);
+  unsigned x_rows[LO_UN], x_cols[LO_UN];
+  if (cnt_r) lo_issue<EL, RELU>(pr, first_rows.m.off, 0, cnt_r, bj * LO_TILE + 2 * lane, x_rows);
+  if (cnt_c) lo_issue<EL, RELU>(pr, first_cols.m.off, 0, cnt_c, bi * LO_TILE + 2 * lane, x_cols);
+  __builtin_amdgcn_sched_barrier(0);
+  lo_events<EL, RELU, false>(pr, list_r, bj * LO_TILE, g, lane, lo_acc, first_rows, x_rows, 0, 0);
   __syncthreads();      // an accumulator changes owner between the two passes: the wave of its row, then the wave of its column
-  lo_events<EL, RELU, true>(pr, a.nch, 4 * bj + g, sub, bi * LO_TILE, g, lane, lo_acc, first_cols);
+  lo_events<EL, RELU, true>(pr, list_c, bi * LO_TILE, g, lane, lo_acc, first_cols, x_cols, ea, eb);
   __syncthreads();
-  // the tile's 16 elements of a thread: all their sigma loads first, then the additions and the stores (written as `*s += v` behind
-  // the tests, every element paid a memory round trip of its own: 16 in series per tile, most of the kernel's time on sparse lists)
-  constexpr int PER = LO_TILE * LO_TILE / LO_THREADS;
-  const int c = tid % LO_TILE, col = bj * LO_TILE + c;
-  const int e_col = col < pr.n ? pr.emax[col] : EMAX_COLUMN_OUT;
-  double* s[PER];
-  double old[PER], v[PER];
+  // the fold: sigma and emax are here already; the tests decide only the store (rows / columns of the fp64 column kernel are not ours)
+  const int e_rows = (wave & 2) ? eb : ea;      // the thread's rows tid / 128 + 8 u: all of one parity, row r in lane r / 2
 #pragma unroll
   for (int u = 0; u < PER; u++) {
-    const int r = tid / LO_TILE + u * (LO_THREADS / LO_TILE), row = bi * LO_TILE + r;
-    v[u] = lo_acc[lo_perm(r) * LO_PITCH + lo_perm(c)];
-    // (rows / columns of the fp64 column kernel are not ours)
-    const bool ours = col <= row && row < pr.n && v[u] != 0. && !((pr.emax[row] | e_col) & EMAX_COLUMN_OUT);
-    s[u] = ours ? pr.sigma + (int64_t)row * pr.ld_sigma + col - (pr.block ? row / pr.block * pr.block : 0) : nullptr;
-    old[u] = ours ? *s[u] : 0.;
+    const int r = tid / LO_TILE + u * ROWS, row = bi * LO_TILE + r;
+    const double v = lo_acc[lo_perm(r) * LO_PITCH + lo_perm(c)];
+    const int e_row = __builtin_amdgcn_readlane(e_rows, (wave >> 2) + u * (ROWS / 2));
+    if (col <= row && v != 0. && !((e_row | e_col) & EMAX_COLUMN_OUT)) sigma[at0 + (int64_t)u * ROWS * ld_sigma] = old[u] + v;
   }
-#pragma unroll
-  for (int u = 0; u < PER; u++)
-    if (s[u]) *s[u] = old[u] + v[u];
 }
 
 // The two remainder products.  One workgroup = the 16 columns of group G against a block of LW_BLOCK = 512 partner columns; wave w
