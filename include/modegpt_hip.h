@@ -49,7 +49,9 @@ extern "C" {
                                 unselected columns, see mdg_nystrom_down); no signature changed;
                              10: mdg_rope_gather_plan added (the rotary kernel's dispatch as a device-free function);
                                 added under 10: mdg_qk_rank_curve (what the Q/K pair selection costs the attention logits, per head and rank);
-                                added under 10: mdg_vo_bias (the v_proj / o_proj biases through the V/O truncation) */
+                                added under 10: mdg_vo_bias (the v_proj / o_proj biases through the V/O truncation);
+                                added under 10: mdg_col_sum_ws_bytes, mdg_col_sum_accum, mdg_cov_center, mdg_nystrom_intercept_ws_bytes,
+                                mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -404,6 +406,47 @@ int mdg_nystrom_down_overlapped(const double* C, int64_t n, int64_t ldc, const i
                                 int64_t d, int64_t ld_wd, int w_dtype, double eps, void* down_out, int64_t ld_out,
                                 double* down_f64, void* ws, size_t ws_bytes, void* side_stream, void* ev_fork, void* ev_join,
                                 void* stream);
+/* The mean-aware refit (added under ABI 10; not in the reference, whose refit is linear against the uncentred second moment).  With
+ * mu = E[h] over the calibration tokens (normalised as mdg_cov_finalize normalises C) and S = C - mu mu^T, minimising
+ * E|| W_d h + b_d - D h_k - b' ||^2 over (D, b') with the ridge on D alone gives
+ *     D  = W_d S[:,k] (S_kk + eps I)^-1        -- mdg_nystrom_down[_overlapped] called with S in place of C, nothing else
+ *     b' = b_d + W_d mu - D^ mu_k              -- D^ = the bf16 tensor that is STORED: the optimal intercept for exactly that tensor
+ * which is the least-squares fit on the augmented feature [h_k; 1] (Sherman-Morrison).  Three entry points supply what that needs.
+ *
+ * mdg_col_sum_accum:  sum[j] += sum_t f(x[t, j]), j < n, in fp64; x [n_tokens, n] of `dtype` (any MDG_* element type) with leading
+ * dimension ld >= n, f = identity or, with relu != 0, max(., 0) on load (OPT's fc1 statistic; a NaN stays a NaN).  One pass over x:
+ * a workgroup owns 128 tokens and 256 column slots, a slot being a 16-byte load of the row (8 / 4 / 2 columns) wherever the rows
+ * allow aligned ones -- ld a multiple of the vector; the columns in front of x's first 16-byte boundary and behind the last whole
+ * vector are single-column slots, as is every column when ld is no multiple of the vector -- so x need only be aligned to its
+ * element.  A thread adds its tokens in ascending order; the partial row of every 128-token chunk goes to the workspace, and a second
+ * kernel adds the partials in ascending chunk order and the total to sum[j].  No atomics: the same bits from run to run.  A column
+ * is only ever added to itself: a NaN or Inf stays in its column.  Nothing beyond column n of a row is read.
+ * ws: mdg_col_sum_ws_bytes(n_tokens, n) = 8 n ceil(n_tokens / 128) bytes, 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG for a null
+ * pointer, an unknown dtype, n_tokens or n < 1, ld < n, a misaligned pointer or a workspace that is too small. */
+size_t mdg_col_sum_ws_bytes(int64_t n_tokens, int64_t n);
+int mdg_col_sum_accum(const void* x, int dtype, int64_t n_tokens, int64_t n, int64_t ld, int relu, double* sum, void* ws,
+                      size_t ws_bytes, void* stream);
+/* S[i, j] = fma(-mu[i], mu[j], C[i, j]): one rounding per entry.  C [n, n] (ldc) is read at and below the diagonal only, S [n, n]
+ * (lds) is written in both triangles from the one value, so S equals its transpose bit for bit; the columns from n to ldc / lds are
+ * neither read nor written, and n need not be a multiple of the 64 x 64 tile.  C is not modified; C and S must not overlap.
+ * Only enqueues.  MDG_ERR_BAD_ARG for a null pointer, n < 1, ldc or lds < n. */
+int mdg_cov_center(const double* C, int64_t n, int64_t ldc, const double* mu, double* S, int64_t lds, void* stream);
+/* delta_i = sum_j W_d[i, j] mu[j] - sum_p D^[i, p] mu[idx[p]], i < d, in fp64, every product exact (fma).  W_d [d, n] (ld_wd) of
+ * w_dtype MDG_BF16 or MDG_F64, as mdg_nystrom_down takes it; down_hat = D^ [d, r] bf16 (ld_down), the tensor mdg_nystrom_down stored;
+ * idx [r] the selection it was called with; mu [n] fp64.
+ *     bias_f64[i] = b_d[i] + delta_i             (b_d [d] of b_dtype, any MDG_* element type; NULL: 0)
+ *     bias_out[i] = bias_f64[i] rounded once to out_dtype (the way torch's .to() rounds: through fp32 for the 16-bit types); may be NULL
+ *     norms[0] = sum_i delta_i^2 ,  norms[1] = sum_i (W_d mu)_i^2     (thread t adds rows t, t + 256, ... ascending, then a fixed tree)
+ * One read of both operands: a wave owns four rows, lanes go along the row (16-byte loads of eight bf16 where the pointer and the
+ * leading dimension allow), mu and mu[idx] are staged in LDS per 2048 columns; a lane adds its columns in ascending order, the wave
+ * reduces by butterfly.  No atomics: the same bits from run to run.  A NaN in row i of W_d or D^ reaches bias entry i alone (and
+ * both norms); an entry of idx outside 0 .. n-1 reads no memory and contributes NaN.
+ * ws: mdg_nystrom_intercept_ws_bytes(d) = 16 d bytes (delta and W_d mu per row), 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG
+ * for a null pointer, an unsupported dtype, d, n or r < 1, r > n, ld_wd < n, ld_down < r, or a workspace that is too small. */
+size_t mdg_nystrom_intercept_ws_bytes(int64_t d);
+int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64_t ld_wd, int w_dtype, const void* down_hat, int64_t r,
+                          int64_t ld_down, const int64_t* idx, const double* mu, const void* b_d, int b_dtype, void* bias_out,
+                          int out_dtype, double* bias_f64, double* norms, void* ws, size_t ws_bytes, void* stream);
 /* What that refit costs, at EVERY rank, from one factorisation (added under ABI 9; not in the reference, which reports nothing
  * about the objective compress_mlp.py:52-62 minimises).  With M = C + eps I, `order` = the columns in ascending ridge-score order
  * (ties: lower index first, NaN last -- torch.argsort(scores, stable=True) -- so that order[:r], sorted, is what

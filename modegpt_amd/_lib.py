@@ -76,6 +76,12 @@ SIGNATURES = {
                                  _ptr]),
     "mdg_nystrom_down_overlapped": (_i32, [_ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _i64, _i32, _f64, _ptr, _i64, _ptr, _ptr, _sz,
                                             _ptr, _ptr, _ptr, _ptr]),
+    "mdg_col_sum_ws_bytes": (_sz, [_i64, _i64]),
+    "mdg_col_sum_accum": (_i32, [_ptr, _i32, _i64, _i64, _i64, _i32, _ptr, _ptr, _sz, _ptr]),
+    "mdg_cov_center": (_i32, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr]),
+    "mdg_nystrom_intercept_ws_bytes": (_sz, [_i64]),
+    "mdg_nystrom_intercept": (_i32, [_ptr, _i64, _i64, _i64, _i32, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _ptr, _ptr,
+                                      _ptr, _sz, _ptr]),
     "mdg_nystrom_rank_curve_ws_bytes": (_sz, [_i64, _i64]),
     "mdg_nystrom_rank_curve": (_i32, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _i32, _f64, _ptr, _ptr, _sz, _ptr]),
     "mdg_mlp_output_error_ws_bytes": (_sz, [_i64, _i64]),

@@ -35,8 +35,11 @@ class LlamaAdapter(ModelAdapter):
         of its own, sigma_x + sigma_q + sigma_k in ONE persistent int8 launch (mdg_cov_accum_i8_multi), whose small problems'
         tiles fill what the large one's last round leaves idle; what the int8 planes cannot take, and everything in mode
         "f64", goes to the fp64 kernel in one launch (mdg_cov_accum_multi).  Nothing is copied; the parked tensors live until
-        the end of the layer's forward."""
+        the end of the layer's forward.  With MODEGPT_MLP_INTERCEPT=1 calibration leaves one fp64 vector per target layer on
+        self.mlp_sums, and the flush hands the sigma_mlp activation to ops.col_sum_accum as well (its column sums: the means of the
+        mean-aware refit); without the switch the list is None and nothing else is launched."""
         parked = {}
+        sums = getattr(self, "mlp_sums", None)
 
         def park(kind):
             @torch.no_grad()
@@ -52,6 +55,8 @@ class LlamaAdapter(ModelAdapter):
                 if t is not None:
                     items.append((lst[layer_idx], t, heads))
             ops.cov_accum_multi(items)
+            if sums is not None and sums[layer_idx] is not None:
+                ops.col_sum_accum(sums[layer_idx], input[0])
             return None
 
         handles.append(block.input_layernorm.register_forward_hook(park("x")))
@@ -61,11 +66,14 @@ class LlamaAdapter(ModelAdapter):
 
     # The reference's per-statistic hook factories, kept for adapters that register them one by one.
     @staticmethod
-    def _llama_pre_gate_hook(layer_idx, cov_mlp_list):
-        """sigma_mlp += H^T H, H = the input of down_proj (LlamaAdapter.py:127-136)."""
+    def _llama_pre_gate_hook(layer_idx, cov_mlp_list, sum_list=None):
+        """sigma_mlp += H^T H, H = the input of down_proj (LlamaAdapter.py:127-136).  sum_list (not upstream): one fp64 vector per
+        layer -- the column sums of H are added to sum_list[layer_idx] as well (ops.col_sum_accum)."""
         @torch.no_grad()
         def hook(module, input: Tuple[Tensor]):
             ops.cov_accum(cov_mlp_list[layer_idx], input[0])
+            if sum_list is not None and sum_list[layer_idx] is not None:
+                ops.col_sum_accum(sum_list[layer_idx], input[0])
             return None
         return hook
 

@@ -34,7 +34,8 @@ class OPTAdapter(ModelAdapter):
         return self.get_n_inner()
 
     def register_hooks(self, layer_idx, block, cov_mlp_list, cov_q_list, cov_k_list, cov_x_list, handles, logger):
-        handles.append(block.fc1.register_forward_hook(self._make_fc_hook(layer_idx, cov_mlp_list)))
+        handles.append(block.fc1.register_forward_hook(self._make_fc_hook(layer_idx, cov_mlp_list,
+                                                                            sum_list=getattr(self, "mlp_sums", None))))
         handles.append(block.self_attn.q_proj.register_forward_hook(
             self._make_proj_hook(layer_idx, cov_q_list, self.n_heads, self.head_dim, self.d_model)))
         handles.append(block.self_attn.k_proj.register_forward_hook(

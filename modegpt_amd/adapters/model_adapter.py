@@ -359,7 +359,8 @@ class ModelAdapter(ABC):
     def convert_model(self, saved_layers_dir: str = "./compressed_output/layers/", suffixes=("mlp", "qk", "vo"),
                       device: str = "cuda"):
         """Swap every layer's Linears for bf16 Linears built from the saved artefacts: bias-free (model_adapter.py:199-208), except
-        where the artefact carries a bias (`<name>_bias`: the compressors write them with MODEGPT_KEEP_BIAS=1 and for Qwen2)."""
+        where the artefact carries a bias (`<name>_bias`: the compressors write them with MODEGPT_KEEP_BIAS=1 and for Qwen2; down_bias
+        also with MODEGPT_MLP_INTERCEPT=1, the refit's intercept -- a key the reference's LlamaRebuild does not know)."""
         saved_layers_dir = os.path.expandvars(saved_layers_dir)
         self.flush_artifacts()
 
@@ -375,8 +376,14 @@ class ModelAdapter(ABC):
                 art = torch.load(os.path.join(saved_layers_dir, f"layer_{i}_{suffix}"), map_location=device)
                 if suffix == "mlp":
                     gate = art.get("gate")
+                    down_bias = art.get("down_bias")
+                    if down_bias is None and ops.mlp_intercept_enabled():
+                        # MODEGPT_MLP_INTERCEPT=1: the refitted layers store an intercept as down_bias; a layer whose artefact has
+                        # none (outside the target layers, or written without the switch) gets an exact zero, so that
+                        # projection_biases() is uniform over the layers and the checkpoint loads strictly
+                        down_bias = torch.zeros(art["down"].shape[0], dtype=torch.bfloat16, device=device)
                     self.replace_mlp_layers(i, new_up=linear_of(art["up"], art.get("up_bias")),
-                                            new_down=linear_of(art["down"], art.get("down_bias")),
+                                            new_down=linear_of(art["down"], down_bias),
                                             new_gate=None if gate is None else linear_of(gate, art.get("gate_bias")))
                 elif suffix == "qk":
                     self.replace_attn_layers(i, new_q=linear_of(art["q_proj"], art.get("q_bias")),
@@ -402,6 +409,31 @@ class ModelAdapter(ABC):
                 raise RuntimeError(f"layer {i} carries biases on {here}, earlier layers on {found}")
             found = here
         return found or []
+
+    # ---- the intercept of the mean-aware MLP refit (not upstream; MODEGPT_MLP_INTERCEPT=1) ----
+    def mlp_intercept(self, layer_idx: int, norms) -> None:
+        """compress_nystrom hands over ops.nystrom_intercept's norms (2 numbers, still on the device) for layer `layer_idx`."""
+        self.__dict__.setdefault("_mlp_intercepts", {})[int(layer_idx)] = norms
+
+    def report_mlp_intercepts(self, log=None) -> dict:
+        """Reads the recorded pairs (16 bytes per layer; call it where the host waits for the chains anyway) and writes
+        metrics["mlp_intercept"][str(layer)] = {"offset_norm2": ||delta||^2, "mean_output_norm2": ||W_d mu||^2, "relative": their
+        ratio}: delta = W_d mu - D^ mu_k is what the stored down_bias adds to the projection's own bias, W_d mu the mean output of the
+        uncompressed projection ("The MLP intercept").  Non-finite figures become None."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self.__dict__.pop("_mlp_intercepts", {})
+        report = {}
+        for layer in sorted(pending):
+            off2, mean2 = (float(x) for x in pending[layer].cpu().tolist())
+            ok = math.isfinite(off2) and math.isfinite(mean2)
+            report[layer] = {"offset_norm2": off2 if ok else None, "mean_output_norm2": mean2 if ok else None,
+                             "relative": off2 / mean2 if ok and mean2 > 0 else None}
+            log.info(f"[MLP] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            self.metrics.setdefault("mlp_intercept", {}).update({str(k): v for k, v in report.items()})
+        return report
 
     # ---- what the truncated v_proj cannot carry of a v bias where o_proj has no bias to fold it into (not upstream) ----
     def vo_bias_residual(self, layer_idx: int, resid) -> None:
@@ -573,13 +605,16 @@ class ModelAdapter(ABC):
 
     # ---- statistic hooks shared by adapters (model_adapter.py:546-567) ----
     @staticmethod
-    def _make_fc_hook(layer_idx, cov_mlp_list):
+    def _make_fc_hook(layer_idx, cov_mlp_list, sum_list=None):
         """sigma_mlp += ReLU(fc1 out)^T ReLU(fc1 out) -- ReLU fused into the kernel's load.  bf16 / fp16 activations of at least
         ops.FC_I8_MIN_FEATURES features (a multiple of 128) take the int8 digit planes with ReLU on load; everything else the fp64
-        kernel, as before (ops.cov_accum_fc_relu)."""
+        kernel, as before (ops.cov_accum_fc_relu).  sum_list (not upstream): one fp64 vector per layer -- the column sums of
+        ReLU(fc1 out) are added to sum_list[layer_idx] as well (ops.col_sum_accum, ReLU on load)."""
         @torch.no_grad()
         def hook(module, inp, out):
             ops.cov_accum_fc_relu(cov_mlp_list[layer_idx], out)
+            if sum_list is not None and sum_list[layer_idx] is not None:
+                ops.col_sum_accum(sum_list[layer_idx], out, relu=True)
         return hook
 
     @staticmethod

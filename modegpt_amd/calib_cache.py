@@ -7,6 +7,11 @@ One directory, one self-contained record per layer, so chunks of layers, target_
                                            entries 0..r at offset r(r+1)/2; ops.sym_pack_lower).  numpy alone reads one:
                                            full[np.tril_indices(n)] = np.fromfile(path, "<f8")
     layer_<i>_q.f64, layer_<i>_k.f64       raw little-endian fp64, full [heads, head_dim, head_dim]
+    layer_<i>_mlp_mean.f64                 only with MODEGPT_MLP_INTERCEPT=1: n_inner raw little-endian fp64, mu = E[h] of the sigma_mlp
+                                           activation under sigma_mlp's normaliser; np.fromfile(path, "<f8") reads it.  Its sidecar
+                                           entry files.mlp_mean holds the length, n and the bit pattern of its exact sum.  A run
+                                           with the switch refuses a record without the entry (it never recalibrates); a run without
+                                           ignores file and entry; records written without the switch are what they always were
     layer_<i>.json                         the sidecar, written LAST: the commit marker -- a layer without it does not exist
     bi_scores.json                         the Block-Influence scores of all layers, written by the rank that computed them
 
@@ -131,6 +136,58 @@ def read_data_file(directory: str, layer: int, kind: str, entry: dict, out: np.n
     if bits != entry["trace_bits"]:
         raise ValueError(f"calibration statistics, layer {layer}: field files.{kind}.trace_bits -- the trace of {path} has the bit "
                          f"pattern {bits}, the sidecar recorded {entry['trace_bits']}")
+
+
+# ------------------------------------------------------------------ host half: the activation mean (MODEGPT_MLP_INTERCEPT=1)
+MEAN_KIND = "mlp_mean"
+
+
+def sum_bits(values: np.ndarray) -> int:
+    """The bit pattern (as int64) of the exact sum of the vector, rounded once (math.fsum: no summation order)."""
+    return struct.unpack("<q", struct.pack("<d", math.fsum(np.asarray(values, dtype=np.float64).ravel().tolist())))[0]
+
+
+def write_mean_file(directory: str, layer: int, values: np.ndarray, n: int) -> dict:
+    """layer_<i>_mlp_mean.f64 from the n means; returns the sidecar's entry for it."""
+    values = np.ascontiguousarray(values, dtype="<f8").reshape(-1)
+    if values.size != n:
+        raise ValueError(f"layer {layer}: the activation mean has {values.size} entries, n_inner is {n}")
+    path = data_path(directory, layer, MEAN_KIND)
+    _replace_into(path, values.tofile)
+    return {"file": os.path.basename(path), "layout": "vector", "n": int(n), "bytes": int(n * 8), "sum_bits": sum_bits(values)}
+
+
+def validate_mean_entry(meta: dict, n: int, layer: int) -> dict:
+    """Metadata alone: the record must carry files.mlp_mean for n means.  Returns the entry."""
+    entry = meta.get("files", {}).get(MEAN_KIND)
+    if not isinstance(entry, dict):
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND} is missing -- the record was saved without "
+                         "MODEGPT_MLP_INTERCEPT=1 and this run has the switch on; save the statistics again with it (nothing is "
+                         "recalibrated on load)")
+    want = {"n": int(n), "bytes": 8 * int(n), "layout": "vector"}
+    for name, value in want.items():
+        if entry.get(name) != value:
+            _refuse(layer, f"files.{MEAN_KIND}.{name}", entry.get(name), value)
+    if not isinstance(entry.get("sum_bits"), int) or not isinstance(entry.get("file"), str):
+        _refuse(layer, f"files.{MEAN_KIND}.sum_bits", entry.get("sum_bits"), "an integer")
+    return entry
+
+
+def read_mean_file(directory: str, layer: int, entry: dict) -> np.ndarray:
+    """The n means of the file, checked against the length and the exact sum the sidecar holds."""
+    path = os.path.join(directory, entry["file"])
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"calibration statistics, layer {layer}: data file {path} (field files.{MEAN_KIND}.file) is missing")
+    size = os.path.getsize(path)
+    if size != entry["bytes"]:
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND}.bytes -- {path} holds {size} bytes, the "
+                         f"sidecar says {entry['bytes']}")
+    values = np.fromfile(path, dtype="<f8").astype(np.float64)
+    bits = sum_bits(values)
+    if bits != entry["sum_bits"]:
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND}.sum_bits -- the sum of {path} has the bit "
+                         f"pattern {bits}, the sidecar recorded {entry['sum_bits']}")
+    return values
 
 
 # ------------------------------------------------------------------ host half: the sidecar
@@ -342,9 +399,10 @@ def _staging_for(arch: dict, device) -> Staging:
 
 
 def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arch: dict, calibration: dict, model: str,
-                weights: dict, certificates: dict) -> dict:
+                weights: dict, certificates: dict, mean=None) -> dict:
     """One layer's record from its four device tensors ({"mlp", "x": [n, n]; "q", "k": [heads, hd, hd]}): data files first, the
-    sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file."""
+    sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  mean: the layer's
+    activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too."""
     import torch
     from . import ops
     os.makedirs(directory, exist_ok=True)
@@ -368,18 +426,23 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
             finish(waiting)
         waiting = (kind, n, batch, host, ev)
     finish(waiting)
+    if mean is not None:
+        files[MEAN_KIND] = write_mean_file(directory, layer, mean.detach().cpu().numpy(), arch["n_inner"])
     meta = make_sidecar(layer, arch, calibration, model, weights, files, certificates)
     write_sidecar(directory, meta)
     return meta
 
 
-def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict) -> dict:
+def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None) -> dict:
     """The inverse: checks the sidecar against `expect`, fills the four device tensors, returns the sidecar.  The file of a
-    statistic is read while the one before it is copied to the device and unpacked."""
+    statistic is read while the one before it is copied to the device and unpacked.  mean: an fp64 [n_inner] device tensor to fill
+    from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1); a record without the entry is refused before any data is read."""
     import torch
     from . import ops
     meta = read_sidecar(directory, layer)
     validate_sidecar(meta, expect, layer)
+    if mean is not None:
+        mean_entry = validate_mean_entry(meta, expect["arch"]["n_inner"], layer)
     for kind in KINDS:
         t = tensors[kind]
         entry = meta["files"][kind]
@@ -393,6 +456,8 @@ def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expe
             else:
                 t.view(-1).copy_(host, non_blocking=True)
             staging.mark(slot)
+    if mean is not None:
+        mean.copy_(torch.from_numpy(read_mean_file(directory, layer, mean_entry)))
     return meta
 
 
@@ -421,13 +486,17 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
                        "n_texts": int(sum(len(b) for b in adapter.calibs)), "n_tokens": int(adapter.calib_tokens)}
         certificates = certificates_in_force(adapter)
     nbytes = 0
+    from . import ops
+    means = getattr(adapter, "mlp_means", None) if ops.mlp_intercept_enabled() else None      # (switch off: today's record, bit for bit)
+    if ops.mlp_intercept_enabled() and targets and (means is None or any(means[i] is None for i in targets)):
+        raise RuntimeError("MODEGPT_MLP_INTERCEPT=1 but the adapter carries no activation means (adapter.mlp_means) to save")
     if targets:
         staging = _staging_for(arch, cov["mlp"][targets[0]].device)
         for i in targets:
             cal = calibration if loaded is None else loaded[i]["calibration"]
             cert = certificates if loaded is None else loaded[i]["certificates"]
             meta = write_layer(directory, i, {k: cov[k][i] for k in KINDS}, staging, arch, cal, model,
-                               weight_fingerprint(adapter, i), cert)
+                               weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i])
             nbytes += sum(e["bytes"] for e in meta["files"].values())
         torch.cuda.synchronize(staging.device)
     if bi_scores is not None and getattr(adapter, "calib_want_bi", True):
@@ -454,11 +523,13 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
         read_sidecar(directory, missing[0])      # raises, naming the layer
     sig = SigmaBuffers(adapter, targets)
     metas: Dict[int, dict] = {}
+    adapter.mlp_means = sig.mlp_sums           # (MODEGPT_MLP_INTERCEPT=1: filled below from the mean files; None without the switch)
     if targets:
         staging = _staging_for(expect["arch"], sig.lists["mlp"][targets[0]].device)
         for i in targets:
             metas[i] = read_layer(directory, i, {k: sig.lists[k][i] for k in KINDS}, staging,
-                                  dict(expect, weights=weight_fingerprint(adapter, i)))
+                                  dict(expect, weights=weight_fingerprint(adapter, i)),
+                                  mean=None if sig.mlp_sums is None else sig.mlp_sums[i])
         torch.cuda.synchronize(staging.device)
     adapter.bi_scores = bi_scores
     cert = merge_certificates([m["certificates"] for m in metas.values()])

@@ -45,6 +45,12 @@ class SigmaBuffers:
         for i in self.layers:
             for kind, shp in shapes.items():
                 self.lists[kind][i] = torch.zeros(*shp, dtype=dtype_p, device=device)
+        # the column sums of the sigma_mlp activation (MODEGPT_MLP_INTERCEPT=1: the means of the mean-aware refit); None without it
+        self.mlp_sums: Optional[List[Optional[torch.Tensor]]] = None
+        if ops.mlp_intercept_enabled():
+            self.mlp_sums = [None] * L
+            for i in self.layers:
+                self.mlp_sums[i] = torch.zeros(f, dtype=dtype_p, device=device)
 
     def finalize(self, n_texts: int) -> None:
         """sigma <- sigma / (n_texts * 2048), lower triangle mirrored into the upper (src/calibration.py:141-146)."""
@@ -52,6 +58,8 @@ class SigmaBuffers:
         for i in self.layers:
             for kind in self.KINDS:
                 ops.cov_finalize(self.lists[kind][i], scale)
+            if self.mlp_sums is not None:
+                self.mlp_sums[i].mul_(scale)                 # mu = E[h] under the normaliser sigma_mlp gets: one rounding per entry
 
 
 class BlockInfluence:
@@ -121,6 +129,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     bi = BlockInfluence(adapter.n_layers)
     blocks = adapter.get_transformer_blocks()
     handles: list = []
+    adapter.mlp_sums = sig.mlp_sums                      # (read by register_hooks; None without MODEGPT_MLP_INTERCEPT=1)
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -156,6 +165,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.bi_scores = bi_scores
     adapter.calib_tokens = n_tokens       # (how many tokens each statistic summed over: the fp64 route's rounding bound scales with it)
     sig.finalize(n_texts)
+    adapter.mlp_sums = None
+    adapter.mlp_means = sig.mlp_sums                     # per target layer mu = E[h] (None without the switch): compress_nystrom reads it
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

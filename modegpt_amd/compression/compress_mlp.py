@@ -64,7 +64,7 @@ def covariance_error_eps(adapter, n_features: int) -> float:
 @torch.no_grad()
 def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_idx: int, ridge_lambda: float,
                      margin_eps: float = None, margin_out: list = None, curve_out: list = None, error_out: list = None,
-                     bias_out: dict = None):
+                     bias_out: dict = None, intercept: Tensor = None, intercept_out: list = None, carry_bias: bool = True):
     """compress_mlp.py:28-64.  Returns (W_u'^T [d, r], W_d' [r, d], W_g'^T [d, r] or None, rank), bf16 --
     the same orientation the reference returns (transposed views of the saved layout).
     margin_eps / margin_out (not upstream): with both given, the certificate of the rank selection against an entry-wise relative
@@ -77,8 +77,17 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
     of the bf16 tensor this call RETURNS, not of the fp64 solution) are appended to it; the outputs are the same bits either way.
     bias_out (not upstream's save route, which drops every bias; its in-place slice_gate_dims keeps these three): a dict -- the biases
     the projections have go into it as "up_bias" / "gate_bias" (the entries at the selected columns, in their order) and "down_bias"
-    (unchanged: the refit has no intercept), bit copies in the bias's own dtype; the weights are the same bits either way."""
+    (unchanged without `intercept`: the linear refit has none), bit copies in the bias's own dtype; the weights are the same bits
+    either way.  carry_bias=False: bias_out receives nothing but the intercept below (the caller does not carry biases).
+    intercept (not upstream; DESIGN.md section 7, "The MLP intercept"): mu = E[h] [n] fp64, normalised as C is -- the refit is taken
+    on the centred statistic S = C - mu mu^T (ops.cov_center into a buffer of its own; C is not modified) and
+    bias_out["down_bias"] = b_d + W_d mu - D^ mu_k for the bf16 tensor D^ this call RETURNS (ops.nystrom_intercept; b_d = the
+    projection's bias with carry_bias, else 0; in the bias's dtype, else the weight's), so bias_out is required.  Scores, idx, up and
+    gate still come from C and are the same bits with and without it; the curve and the output error are taken on S, where they
+    are the affine map's.  intercept_out: a list -- the two norms (||delta||^2, ||W_d mu||^2, on the device) are appended to it."""
     C = C.to(dtype=dtype_p, device=local_device())
+    if intercept is not None and bias_out is None:
+        raise ValueError("compress_weights: intercept= needs bias_out= to leave the down_bias in")
     rank = int(C.shape[0] * keep_ratio)
     if margin_out is not None and margin_eps is not None:
         scores, sens = ops.ridge_scores(C, _fl32(ridge_lambda), want_sens=True)
@@ -94,6 +103,9 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         W_g = comps.gate_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
         gate = ops.gather_rows(W_g, idx)                              # W_g[topk, :]               (:50)
     W_d = comps.down_proj.weight.detach().to(device=local_device())              # bf16 as is; fp16/fp32 widen exactly to fp64
+    if intercept is not None:
+        mu = intercept.to(dtype=dtype_p, device=local_device())
+        C = ops.cov_center(C, mu)                                     # S: from here on the statistic of h - mu (selection is done)
     down = ops.nystrom_down(C, idx, W_d, eps=1e-6)                    # [d, r] bf16                (:52-62)
     if curve_out is not None and ops.rank_curve_enabled():
         # the selection is a prefix of the ridge-score order (ties: lower index first, NaN last, as select_smallest_sorted ranks them),
@@ -104,12 +116,19 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         q = ops.mlp_output_error(C, W_d, None, None)                  # the channel's energy: nothing subtracted
         e, unorm2 = ops.mlp_output_error(C, W_d, idx, down, want_unorm2=True)     # ... and what the tensor that is saved loses of it
         error_out.extend((q, e, unorm2))
-    if bias_out is not None:
+    if bias_out is not None and carry_bias:
         for name, proj, rows in (("up_bias", comps.up_proj, idx), ("gate_bias", comps.gate_proj, idx), ("down_bias", comps.down_proj, None)):
             b = getattr(proj, "bias", None)
             if b is not None:
                 b = b.detach().to(local_device())
                 bias_out[name] = b.clone() if rows is None else torch.index_select(b, 0, rows.to(torch.int64))
+    if intercept is not None:
+        b_d = getattr(comps.down_proj, "bias", None) if carry_bias else None
+        b_d = None if b_d is None else b_d.detach().to(local_device())
+        bias, _, norms = ops.nystrom_intercept(W_d, down, idx, mu, b_d=b_d)
+        bias_out["down_bias"] = bias
+        if intercept_out is not None:
+            intercept_out.append(norms)
     return up.T, down.T, (None if gate is None else gate.T), rank
 
 
@@ -126,21 +145,33 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
         curve = [] if callable(record_curve) else None               # (filled only with MODEGPT_RANK_CURVE=1)
         record_error = getattr(adapter, "output_error", None)        # (... and without this: no realised output error)
         error = [] if callable(record_error) else None               # (filled only with MODEGPT_OUTPUT_ERROR=1)
-        biases = {} if ops.keep_bias_enabled(getattr(adapter, "arch", None)) else None     # (MODEGPT_KEEP_BIAS=1, or Qwen2)
+        carry = ops.keep_bias_enabled(getattr(adapter, "arch", None))                      # (MODEGPT_KEEP_BIAS=1, or Qwen2)
+        more = {}
+        if ops.mlp_intercept_enabled():                                                     # (MODEGPT_MLP_INTERCEPT=1)
+            means = getattr(adapter, "mlp_means", None)
+            if means is None or means[layer_idx] is None:
+                raise RuntimeError(f"MODEGPT_MLP_INTERCEPT=1 but layer {layer_idx} has no activation mean (adapter.mlp_means): "
+                                   "the statistics were collected without the switch")
+            more = {"intercept": means[layer_idx], "intercept_out": [], "carry_bias": carry}
+        biases = {} if carry or more else None
         if record is None:
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
-                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error, bias_out=biases)
+                                      ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error, bias_out=biases,
+                                      **more)
         else:
             eps, margin = covariance_error_eps(adapter, cov[layer_idx].shape[0]), []
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
                                       ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve,
-                                      error_out=error, bias_out=biases)
+                                      error_out=error, bias_out=biases, **more)
             # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
             record(layer_idx, margin[0], eps)
         if curve:
             record_curve(layer_idx, curve[0], result[3])             # ... and so does the curve (report_rank_curves)
         if error:
             record_error(layer_idx, tuple(error), result[3])         # ... and the stored tensor's output error (report_output_errors)
+        record_intercept = getattr(adapter, "mlp_intercept", None)
+        if more and more["intercept_out"] and callable(record_intercept):
+            record_intercept(layer_idx, more["intercept_out"][0])    # ... and the intercept's two norms (report_mlp_intercepts)
         return result + (biases or {},)
 
     def retire(layer_idx, result):

@@ -66,13 +66,18 @@ def make_activation_batch(shape: dict, tokens: int, seed: int, device, scale_see
 def new_covs(shape: dict, device) -> Dict[str, torch.Tensor]:
     d, f, nh, nkv, hd = shape["d"], shape["d_ff"], shape["n_heads"], shape["n_kv_heads"], shape["head_dim"]
     z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=device)  # noqa: E731
-    return {"mlp": z(f, f), "x": z(d, d), "q": z(nh, hd, hd), "k": z(nkv, hd, hd)}
+    covs = {"mlp": z(f, f), "x": z(d, d), "q": z(nh, hd, hd), "k": z(nkv, hd, hd)}
+    if ops.mlp_intercept_enabled():
+        covs["mlp_sum"] = z(f)
+    return covs
 
 
 def accumulate(covs: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], shape: dict, mode: Optional[str] = None) -> None:
     """What the four hooks of one layer do for one calibration batch: one fused launch (the Llama / Qwen3 adapters
     defer sigma_x / sigma_q / sigma_k to the layer's last hook for exactly this); OPT's ReLU statistic stays separate.
     mode: None = ops.COV_MODE; "i8" routes sigma_mlp and sigma_x through the int8 digit-plane kernel."""
+    if covs.get("mlp_sum") is not None:           # (new_covs with MODEGPT_MLP_INTERCEPT=1: the column sums of the sigma_mlp activation)
+        ops.col_sum_accum(covs["mlp_sum"], batch["h"], relu=shape["arch"] == "opt")
     if shape["arch"] == "opt":
         ops.cov_accum_fc_relu(covs["mlp"], batch["h"], mode=mode)
         ops.cov_accum_multi([(covs["x"], batch["x"], 1), (covs["q"], batch["q"], shape["n_heads"]),
@@ -83,8 +88,11 @@ def accumulate(covs: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], sh
 
 
 def finalize(covs: Dict[str, torch.Tensor], n_texts: int) -> None:
-    for c in covs.values():
-        ops.cov_finalize(c, 1.0 / (n_texts * 2048))
+    for kind, c in covs.items():
+        if kind == "mlp_sum":
+            c.mul_(1.0 / (n_texts * 2048))
+        else:
+            ops.cov_finalize(c, 1.0 / (n_texts * 2048))
 
 
 class _W:
@@ -198,6 +206,7 @@ def compress_layer(adapter: TensorAdapter, layer_idx: int, covs: Dict[str, torch
     n = max(adapter.shape["n_layers"], layer_idx + 1)
     lst = lambda t: [t if i == layer_idx else None for i in range(n)]  # noqa: E731
     keep = [keep_ratio] * n
+    adapter.mlp_means = lst(covs["mlp_sum"]) if covs.get("mlp_sum") is not None else None
     # VO (one GEMM, a batched 128 x 128 eigensolve on 8 workgroups, skinny products: 8 ms of mostly latency) needs sigma_x only and
     # runs on a stream of its own beside the MLP chain, whose Cholesky steps leave most of the chip idle between their GEMMs
     dev = covs["x"].device

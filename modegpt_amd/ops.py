@@ -531,6 +531,64 @@ def cov_finalize(sigma: torch.Tensor, scale: float) -> None:
               "mdg_cov_finalize")
 
 
+# The mean-aware MLP refit ("The MLP intercept").  Opt-in: MODEGPT_MLP_INTERCEPT=1 makes calibration collect the
+# column sums of the sigma_mlp activation and compress_nystrom refit on the centred statistic and store an intercept as down_bias.
+def mlp_intercept_enabled() -> bool:
+    """MODEGPT_MLP_INTERCEPT as it stands when calibration or a compressor asks (per layer; not frozen at import)."""
+    return os.environ.get("MODEGPT_MLP_INTERCEPT", "0").lower() in ("1", "on", "true")
+
+
+COL_SUM_CHUNK = 128        # tokens per workgroup of mdg_col_sum_accum (one partial row each)
+COV_CENTER_TILE = 64       # tile edge of mdg_cov_center
+
+
+def col_sum_accum(sum_: torch.Tensor, x: torch.Tensor, relu: bool = False) -> None:
+    """sum_[j] += sum_t f(x[t, j]) in fp64 (mdg_col_sum_accum): x [..., n] of bf16 / fp16 / fp32 / fp64, read in place when its rows are
+    contiguous and equally spaced (any leading dimension, any element-aligned offset); f = ReLU with relu=True.  sum_: fp64 [n],
+    contiguous.  Deterministic, no atomics.  The call only enqueues."""
+    _need_gpu(sum_, x)
+    lib = _lib.load()
+    n = x.shape[-1]
+    if sum_.dtype != torch.float64 or sum_.dim() != 1 or sum_.numel() != n or not sum_.is_contiguous():
+        raise ValueError(f"col_sum_accum: sum must be a contiguous float64 vector of {n} entries")
+    if x.dtype not in _DT:
+        raise ValueError(f"col_sum_accum: unsupported dtype {x.dtype}")
+    x2 = x.detach()
+    if x2.dim() != 2:
+        x2 = x2.reshape(-1, n)              # (a view when the leading dimensions collapse, as the hooks' [batch, T, n] does)
+    if x2.shape[0] == 0:
+        return
+    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
+        x2 = x2.contiguous()
+    tokens = x2.shape[0]
+    ld = x2.stride(0) if tokens > 1 else n
+    nbytes = lib.mdg_col_sum_ws_bytes(tokens, n)
+    ws, wsp = _ws(nbytes, x2.device)
+    with torch.cuda.device(x2.device):
+        check(lib.mdg_col_sum_accum(x2.data_ptr(), _DT[x2.dtype], tokens, n, ld, int(bool(relu)), sum_.data_ptr(), wsp, nbytes,
+                                    _stream(x2)), "mdg_col_sum_accum")
+
+
+def cov_center(Cm: torch.Tensor, mu: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """S = C - mu mu^T, S_ij = fma(-mu_i, mu_j, C_ij) (mdg_cov_center): C fp64 [n, n] with contiguous rows (any row stride), read at
+    and below its diagonal; mu fp64 [n]; the result is written in both triangles from one value, symmetric bit for bit.  out: an fp64
+    [n, n] view with contiguous rows to write into (default: a new tensor); C itself is not modified.  The call only enqueues."""
+    _need_gpu(Cm, mu, out)
+    lib = _lib.load()
+    n, _, ldc, _ = _sym_view(Cm)
+    if Cm.dim() != 2 or mu.dtype != torch.float64 or mu.numel() != n:
+        raise ValueError(f"cov_center: C must be [n, n] and mu a float64 vector of {n} entries")
+    mu = mu.contiguous()
+    if out is None:
+        out = torch.empty(n, n, dtype=torch.float64, device=Cm.device)
+    n_o, _, lds, _ = _sym_view(out)
+    if out.dim() != 2 or n_o != n:
+        raise ValueError("cov_center: out must be [n, n] like C")
+    with torch.cuda.device(Cm.device):
+        check(lib.mdg_cov_center(Cm.data_ptr(), n, ldc, mu.data_ptr(), out.data_ptr(), lds, _stream(Cm)), "mdg_cov_center")
+    return out
+
+
 def _sym_view(full: torch.Tensor):
     """(n, batch, ld, batch stride) of a [n, n] or [batch, n, n] fp64 view whose rows are contiguous."""
     if full.dtype != torch.float64 or full.dim() not in (2, 3) or full.shape[-1] != full.shape[-2] or full.stride(-1) != 1:
@@ -797,6 +855,44 @@ def nystrom_down(Cm: torch.Tensor, idx: torch.Tensor, W_down: torch.Tensor, eps:
                                        W_down.stride(0), _DT[W_down.dtype], float(eps), out.data_ptr(), out.stride(0), _p(f64), wsp, nbytes,
                                        _stream(Cm)), "mdg_nystrom_down")
     return (out, f64) if want_f64 else out
+
+
+def nystrom_intercept(W_down: torch.Tensor, down_hat: torch.Tensor, idx: torch.Tensor, mu: torch.Tensor,
+                      b_d: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+    """The intercept of the mean-aware refit (mdg_nystrom_intercept): delta = W_down mu - down_hat mu[idx] in fp64 with exact products;
+    W_down [d, n] as nystrom_down takes it, down_hat [d, r] the bf16 tensor nystrom_down RETURNED for the selection idx, mu fp64 [n].
+    Returns (bias, bias_f64, norms): bias_f64 [d] = b_d + delta (b_d None: 0), bias = its one rounding to out_dtype (default: b_d's
+    dtype, else bf16 for a bf16 weight and W_down's own dtype otherwise), norms [2] = (||delta||^2, ||W_down mu||^2), fp64 ON THE
+    DEVICE.  The call only enqueues."""
+    _need_gpu(W_down, down_hat, idx, mu, b_d)
+    lib = _lib.load()
+    if out_dtype is None:
+        out_dtype = b_d.dtype if b_d is not None else W_down.dtype
+    W = _as_weight(W_down)
+    if down_hat.dtype != torch.bfloat16 or down_hat.dim() != 2 or down_hat.stride(1) != 1:
+        raise ValueError("nystrom_intercept: down_hat must be the stored bf16 [d, r] tensor with contiguous rows")
+    d, n = W.shape
+    r = idx.numel()
+    if down_hat.shape[0] != d or down_hat.shape[1] != r or mu.numel() != n or mu.dtype != torch.float64:
+        raise ValueError(f"nystrom_intercept: shapes disagree (W_down {tuple(W.shape)}, down_hat {tuple(down_hat.shape)}, "
+                         f"idx {r}, mu {mu.numel()} {mu.dtype})")
+    if out_dtype not in _DT or (b_d is not None and (b_d.dtype not in _DT or b_d.numel() != d)):
+        raise ValueError("nystrom_intercept: unsupported bias dtype or length")
+    idx = idx.to(torch.int64).contiguous()
+    mu = mu.contiguous()
+    bd = None if b_d is None else b_d.detach().contiguous()
+    dev = W.device
+    bias = torch.empty(d, dtype=out_dtype, device=dev)
+    bias_f64 = torch.empty(d, dtype=torch.float64, device=dev)
+    norms = torch.empty(2, dtype=torch.float64, device=dev)
+    nbytes = lib.mdg_nystrom_intercept_ws_bytes(d)
+    ws, wsp = _ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        check(lib.mdg_nystrom_intercept(W.data_ptr(), d, n, W.stride(0), _DT[W.dtype], down_hat.data_ptr(), r, down_hat.stride(0),
+                                        idx.data_ptr(), mu.data_ptr(), _p(bd), _DT[bd.dtype] if bd is not None else 0, bias.data_ptr(),
+                                        _DT[out_dtype], bias_f64.data_ptr(), norms.data_ptr(), wsp, nbytes, _stream(W)),
+              "mdg_nystrom_intercept")
+    return bias, bias_f64, norms
 
 
 # The Nystrom refit's error at every rank (mdg_nystrom_rank_curve).  Opt-in: MODEGPT_RANK_CURVE=1 makes compress_nystrom compute
