@@ -84,10 +84,24 @@ class ModelAdapter(ABC):
         that keeps results on the device (engine.TensorAdapter) collects the statuses and checks them later."""
         status.check()
 
+    # ---- the plumbing of the opt-in reports below: a compressor records device tensors per layer, report_xxx reads them ----
+    def _record(self, name: str, key, payload) -> None:
+        self.__dict__.setdefault(name, {})[key] = payload
+
+    def _take(self, name: str) -> dict:
+        return self.__dict__.pop(name, {})
+
+    def _merge_metrics(self, key: str, report: dict) -> None:
+        """metrics[key][str(layer)] = report[layer]; nothing for an empty report."""
+        if report:
+            if not isinstance(getattr(self, "metrics", None), dict):
+                self.metrics = {}
+            self.metrics.setdefault(key, {}).update({str(k): v for k, v in report.items()})
+
     # ---- the certificate of the MLP rank selections (not upstream; north_star: "rank selections bit-identical") ----
     def selection_margin(self, layer_idx: int, out8, eps: float) -> None:
         """compress_nystrom hands over ops.select_margin's 8 numbers (still on the device) for layer `layer_idx`."""
-        self.__dict__.setdefault("_selection_margins", {})[int(layer_idx)] = (out8, float(eps))
+        self._record("_selection_margins", int(layer_idx), (out8, float(eps)))
 
     def report_selection_margins(self, log=None) -> dict:
         """Reads the recorded certificates (one 64-byte copy per layer; call it where the host waits for the chains anyway), writes
@@ -96,7 +110,7 @@ class ModelAdapter(ABC):
         scores sit closer than the bound on what the route's sigma error can do to them, and another accumulation order / route /
         the reference's CPU arithmetic may select a different column set (compress_mlp.py:45-47)."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_selection_margins", {})
+        pending = self._take("_selection_margins")
         report = {}
         for layer in sorted(pending):
             out8, eps = pending[layer]
@@ -106,18 +120,14 @@ class ModelAdapter(ABC):
                 log.warning(f"[MLP] Layer {layer}: rank selection NOT certified -- threshold margin {m['margin']:.3e} against a score "
                             f"perturbation bound {m['score_bound']:.3e} (covariance error bound eps = {eps:.2e}); "
                             f"{m['scores_at_risk']} scores within reach of the threshold")
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            store = self.metrics.setdefault("mlp_selection", {})
-            store.update({str(k): v for k, v in report.items()})
+        self._merge_metrics("mlp_selection", report)
         return report
 
     # ---- what the MLP compression costs, at every rank (not upstream; MODEGPT_RANK_CURVE=1) ----
     def rank_curve(self, layer_idx: int, curve, rank: int) -> None:
         """compress_nystrom hands over ops.nystrom_rank_curve's n + 1 numbers (still on the device) for layer `layer_idx`, which it
         compressed to `rank`."""
-        self.__dict__.setdefault("_rank_curves", {})[int(layer_idx)] = (curve, int(rank))
+        self._record("_rank_curves", int(layer_idx), (curve, int(rank)))
 
     def report_rank_curves(self, log=None) -> dict:
         """Reads the recorded curves (8 (n + 1) bytes per layer; call it where the host waits for the chains anyway), keeps them as
@@ -126,12 +136,12 @@ class ModelAdapter(ABC):
         reaches 1e-1 / 1e-2 / 1e-3 -- under sigma_mlp + eps I and for the fp64 refit ("The error-versus-rank
         curve", says what that is not).  Logs one line per layer and the energy-weighted mean over the layers read by this call."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_rank_curves", {})
+        pending = self._take("_rank_curves")
         report = {}
         for layer in sorted(pending):
             curve, rank = pending[layer]
             host = curve.detach().cpu()
-            self.__dict__.setdefault("rank_curves", {})[layer] = host
+            self._record("rank_curves", layer, host)
             m = report[layer] = ops.decode_rank_curve(host.tolist(), rank)
             if m["rel_error"] is None:
                 log.warning(f"[MLP] Layer {layer}: rank curve has no usable energy (curve[0] = {m['energy']!r})")
@@ -139,11 +149,9 @@ class ModelAdapter(ABC):
             log.info(f"[MLP] Layer {layer}: rank {rank} of {m['n']}: relative output error {m['rel_error']:.3e}; "
                      f"rank for 1e-2: {m['rank_for_rel_error']['0.01']}")
         if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
             # (a NaN / Inf energy would be written as the non-standard NaN / Infinity by json.dump: None there, as the relative fields)
             finite = lambda m: m if math.isfinite(m["energy"]) else {**m, "energy": None}      # noqa: E731
-            self.metrics.setdefault("mlp_rank_curve", {}).update({str(k): finite(v) for k, v in report.items()})
+            self._merge_metrics("mlp_rank_curve", {k: finite(v) for k, v in report.items()})
             usable = [m for m in report.values() if m["rel_error"] is not None]
             energy = sum(m["energy"] for m in usable)
             if usable and energy > 0:
@@ -155,7 +163,7 @@ class ModelAdapter(ABC):
     def output_error(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_nystrom hands over (q, e, unorm2) of ops.mlp_output_error (d numbers each, still on the device) for layer
         `layer_idx`, which it compressed to `rank`."""
-        self.__dict__.setdefault("_output_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+        self._record("_output_errors", int(layer_idx), (tuple(tensors), int(rank)))
 
     def report_output_errors(self, log=None) -> dict:
         """Reads the recorded tensors (24 d bytes per layer; call it where the host waits for the chains anyway), keeps them as CPU
@@ -165,13 +173,13 @@ class ModelAdapter(ABC):
         the distance from the best possible refit ("The realised output error of the stored MLP weights", says
         what that is not).  Logs one line per layer."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_output_errors", {})
+        pending = self._take("_output_errors")
         curves = self.__dict__.get("rank_curves", {})
         report = {}
         for layer in sorted(pending):
             (q, e, unorm2), rank = pending[layer]
             host = tuple(t.detach().cpu() for t in (q, e, unorm2))
-            self.__dict__.setdefault("output_errors", {})[layer] = host
+            self._record("output_errors", layer, host)
             curve = curves.get(layer)
             m = report[layer] = ops.decode_output_error(host[1].tolist(), host[0].tolist(), host[2].tolist(), ops.NYSTROM_EPS, rank,
                                                         curve=None if curve is None else curve.tolist())
@@ -182,17 +190,14 @@ class ModelAdapter(ABC):
             log.info(f"[MLP] Layer {layer}: rank {rank}: stored weights lose {m['relative_error']:.3e} of the output energy; "
                      f"worst channel {m['worst_channel']} loses {m['worst_channel_relative_error']:.3e}"
                      + ("" if excess is None else f"; {excess:.3e} of the energy above the best refit"))
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            self.metrics.setdefault("mlp_output_error", {}).update({str(k): v for k, v in report.items()})
+        self._merge_metrics("mlp_output_error", report)
         return report
 
     # ---- what the STORED v_proj / o_proj lose of the attention output (not upstream; MODEGPT_VO_ERROR=1) ----
     def vo_error(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_vo hands over (q, e, dnorm2, curve) -- ops.vo_output_error's [n_heads, d] tensors and
         ops.vo_compress(want_curve=True)'s [n_kv, hd + 1], still on the device -- for layer `layer_idx`, truncated to `rank` per head."""
-        self.__dict__.setdefault("_vo_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+        self._record("_vo_errors", int(layer_idx), (tuple(tensors), int(rank)))
 
     def report_vo_errors(self, log=None) -> dict:
         """Reads the recorded tensors (24 n_heads d + 8 n_kv (hd + 1) bytes per layer; call it where the host waits for the chains
@@ -202,12 +207,12 @@ class ModelAdapter(ABC):
         head and channel, and the distance from the fp64 truncation's curve ("The realised output error of the
         stored V/O factors", says what that is not).  Logs one line per layer."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_vo_errors", {})
+        pending = self._take("_vo_errors")
         report = {}
         for layer in sorted(pending):
             tensors, rank = pending[layer]
             host = tuple(t.detach().cpu() for t in tensors)
-            self.__dict__.setdefault("vo_errors", {})[layer] = host
+            self._record("vo_errors", layer, host)
             q, e, dnorm2, curve = host
             m = report[layer] = ops.decode_vo_output_error(e.tolist(), q.tolist(), dnorm2.tolist(), self.config.ridge_vo, rank,
                                                            curve.shape[0], curve=curve.tolist())
@@ -218,18 +223,15 @@ class ModelAdapter(ABC):
             log.info(f"[VO] Layer {layer}: rank {rank}: stored factors lose {m['relative_error']:.3e} of the output energy; "
                      f"worst head {m['worst_head']} loses {m['worst_head_relative_error']:.3e}"
                      + ("" if excess is None else f"; {excess:.3e} of the energy above the fp64 truncation"))
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            # (decode_vo_output_error maps every non-finite sum to None, so json.dump never meets a NaN)
-            self.metrics.setdefault("vo_output_error", {}).update({str(k): v for k, v in report.items()})
+        # (decode_vo_output_error maps every non-finite sum to None, so json.dump never meets a NaN)
+        self._merge_metrics("vo_output_error", report)
         return report
 
     # ---- what the Q/K pair selection loses of the attention logits (not upstream; MODEGPT_QK_ERROR=1) ----
     def qk_error(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_qk hands over ops.qk_rank_curve's (curve_h, curve, terms, scale, greedy_curve, greedy_order) and the order they
         were taken along, still on the device, for layer `layer_idx`, whose heads keep `rank` columns."""
-        self.__dict__.setdefault("_qk_errors", {})[int(layer_idx)] = (tuple(tensors), int(rank))
+        self._record("_qk_errors", int(layer_idx), (tuple(tensors), int(rank)))
 
     def report_qk_errors(self, log=None) -> dict:
         """Reads the recorded tensors (about 8 (n_heads + 4 n_kv) (ns + 1) bytes per layer; call it where the host waits for the
@@ -239,12 +241,12 @@ class ModelAdapter(ABC):
         layer, what the diagonal rule believed it would lose, and what a greedy order on the full objective loses at the same rank
         ("What the Q/K selection costs the attention logits", says what that is not).  Logs one line per layer."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_qk_errors", {})
+        pending = self._take("_qk_errors")
         report = {}
         for layer in sorted(pending):
             tensors, rank = pending[layer]
             host = tuple(None if t is None else t.detach().cpu() for t in tensors)
-            self.__dict__.setdefault("qk_errors", {})[layer] = host
+            self._record("qk_errors", layer, host)
             curve_h, curve, terms, scale, g_curve = host[:5]
             cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
             m = report[layer] = ops.decode_qk_logit_error(curve_h.tolist(), curve.tolist(), rank, cols, terms=terms.tolist(),
@@ -257,11 +259,8 @@ class ModelAdapter(ABC):
                      + ("" if diag is None else f"; the diagonal rule's estimate is {diag:.3g} x that")
                      + ("" if greedy is None else f"; a greedy order on the full objective loses {greedy:.3e}")
                      + ("; NOT monotone in the rank" if m["non_monotone"] else ""))
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            # (decode_qk_logit_error maps every non-finite figure to None, so json.dump never meets a NaN)
-            self.metrics.setdefault("qk_logit_error", {}).update({str(k): v for k, v in report.items()})
+        # (decode_qk_logit_error maps every non-finite figure to None, so json.dump never meets a NaN)
+        self._merge_metrics("qk_logit_error", report)
         return report
 
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
@@ -270,7 +269,7 @@ class ModelAdapter(ABC):
         ops.vo_compress(want_spectrum=True)'s [n_kv, 8], eps = (eps,)) hand their device tensors over for layer `layer_idx`."""
         if kind not in ("qk", "vo"):
             raise ValueError(f"attention_margin: kind must be 'qk' or 'vo', got {kind!r}")
-        self.__dict__.setdefault("_attention_margins", {})[(kind, int(layer_idx))] = (tensor, tuple(float(e) for e in eps))
+        self._record("_attention_margins", (kind, int(layer_idx)), (tensor, tuple(float(e) for e in eps)))
 
     def report_attention_margins(self, log=None) -> dict:
         """Reads the recorded attention certificates (64 bytes per kv head; call it where the host waits for the chains anyway) and
@@ -281,7 +280,7 @@ class ModelAdapter(ABC):
         (compress_qk.py:366-367) -- and once per grouped VO layer in which some head's sigma_r and sigma_r+1 are not separated
         (compress_vo.py:130-146: the kept subspace is then not determined by the data)."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_attention_margins", {})
+        pending = self._take("_attention_margins")
         report = {"qk": {}, "vo": {}}
         for kind, layer in sorted(pending):
             tensor, eps = pending[(kind, layer)]
@@ -304,12 +303,8 @@ class ModelAdapter(ABC):
                                 f"{w['gap']:.3e} between sigma_r and sigma_r+1 (lambda_r - lambda_r+1 = "
                                 f"{w['lambda_r'] - w['lambda_next']:.3e} against twice the bound {w['bound']:.3e}, eps = {eps[0]:.2e})")
             report[kind][layer] = m
-        if pending:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            for kind, key in (("qk", "qk_selection"), ("vo", "vo_spectrum")):
-                if report[kind]:
-                    self.metrics.setdefault(key, {}).update({str(k): v for k, v in report[kind].items()})
+        for kind, key in (("qk", "qk_selection"), ("vo", "vo_spectrum")):       # (only the non-empty kinds)
+            self._merge_metrics(key, report[kind])
         return report
 
     # ---- reconstruction: per-(layer, stage) artefacts and the final swap (model_adapter.py:184-237) ----
@@ -413,7 +408,7 @@ class ModelAdapter(ABC):
     # ---- the intercept of the mean-aware MLP refit (not upstream; MODEGPT_MLP_INTERCEPT=1) ----
     def mlp_intercept(self, layer_idx: int, norms) -> None:
         """compress_nystrom hands over ops.nystrom_intercept's norms (2 numbers, still on the device) for layer `layer_idx`."""
-        self.__dict__.setdefault("_mlp_intercepts", {})[int(layer_idx)] = norms
+        self._record("_mlp_intercepts", int(layer_idx), norms)
 
     def report_mlp_intercepts(self, log=None) -> dict:
         """Reads the recorded pairs (16 bytes per layer; call it where the host waits for the chains anyway) and writes
@@ -421,7 +416,7 @@ class ModelAdapter(ABC):
         ratio}: delta = W_d mu - D^ mu_k is what the stored down_bias adds to the projection's own bias, W_d mu the mean output of the
         uncompressed projection ("The MLP intercept").  Non-finite figures become None."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_mlp_intercepts", {})
+        pending = self._take("_mlp_intercepts")
         report = {}
         for layer in sorted(pending):
             off2, mean2 = (float(x) for x in pending[layer].cpu().tolist())
@@ -429,16 +424,13 @@ class ModelAdapter(ABC):
             report[layer] = {"offset_norm2": off2 if ok else None, "mean_output_norm2": mean2 if ok else None,
                              "relative": off2 / mean2 if ok and mean2 > 0 else None}
             log.info(f"[MLP] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            self.metrics.setdefault("mlp_intercept", {}).update({str(k): v for k, v in report.items()})
+        self._merge_metrics("mlp_intercept", report)
         return report
 
     # ---- what the truncated v_proj cannot carry of a v bias where o_proj has no bias to fold it into (not upstream) ----
     def vo_bias_residual(self, layer_idx: int, resid) -> None:
         """compress_vo hands over ops.vo_bias's resid (2 numbers, still on the device) for layer `layer_idx`."""
-        self.__dict__.setdefault("_vo_bias_residuals", {})[int(layer_idx)] = resid
+        self._record("_vo_bias_residuals", int(layer_idx), resid)
 
     def report_vo_bias_residuals(self, log=None) -> dict:
         """Reads the recorded pairs (16 bytes per layer; call it where the host waits for the chains anyway) and writes
@@ -446,7 +438,7 @@ class ModelAdapter(ABC):
         "relative": their ratio}: rho = sum_h W_o,h (I - Pi_g) b_v,kv(h) is the part of the constant a v bias adds to the attention
         output that the rank-r v_proj cannot represent ("Projection biases").  Non-finite figures become None."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self.__dict__.pop("_vo_bias_residuals", {})
+        pending = self._take("_vo_bias_residuals")
         report = {}
         for layer in sorted(pending):
             rho2, const2 = (float(x) for x in pending[layer].cpu().tolist())
@@ -454,10 +446,7 @@ class ModelAdapter(ABC):
             report[layer] = {"residual_norm2": rho2 if ok else None, "constant_norm2": const2 if ok else None,
                              "relative": rho2 / const2 if ok and const2 > 0 else None}
             log.info(f"[VO] Layer {layer}: the truncated v_proj loses {rho2:.3e} of the v bias's output constant {const2:.3e} (squared norms)")
-        if report:
-            if not isinstance(getattr(self, "metrics", None), dict):
-                self.metrics = {}
-            self.metrics.setdefault("vo_bias_residual", {}).update({str(k): v for k, v in report.items()})
+        self._merge_metrics("vo_bias_residual", report)
         return report
 
     # ---- in-place slicing (model_adapter.py:394-542; upstream's call sites are commented out in favour of the

@@ -5,17 +5,8 @@
 // read from the LOWER triangle of C alone.  sum_k e_k is the E_D of the sandwich in DESIGN.md section 7 ("The error-versus-rank
 // curve"): E_D + eps ||U||^2 - eps ||W_S||^2 <= curve[r] <= E_D + eps ||U||^2 -- here for ANY down tensor, the bf16 artefact included.
 //
-// Tile scheme (the shared 128 x 128 / 4-wave / LDS-fp64-panel core of common.hpp).  A workgroup owns a 128-row block of U and one
-// 128-wide tile COLUMN J of C and walks the tiles (I, J), I = J .. T-1, of the lower triangle down that column:
-//   P[128, 128] = sum_{I >= J} U[:, I] C[I, J]     (v_mfma_f64_16x16x4_f64; the diagonal tile C_JJ masked to its STRICT lower part
-//                                                   while staging, so what lies on or above the diagonal of C is never loaded)
-// -- one accumulator for the whole column, so the epilogue runs once per workgroup and the partial sums are d * T numbers, not
-// d * T (T + 1) / 2.  U is formed in the A-operand staging: the weight and the down entry are widened exactly to fp64 and subtracted
-// there (a bf16 - bf16 difference is exact in fp64); `pos` [n] int32 is the inverse index map (-1: not kept).  Epilogue, per entry
-// (k, j) of the tile:  u_kj (2 P_kj + C_jj u_kj)  -- the factor 2 on the strict lower part, the diagonal term without it -- and
-// u_kj^2, summed along the tile's 128 columns (4 in the lane, 16 lanes by shuffles in a fixed tree, the two wave columns through
-// LDS).  P is never written to memory.  A second small kernel adds each row's T partials in ascending tile order.  No atomics:
-// two runs are bit-identical.  Tile columns are handed out longest first (J ascending): T - J tiles each.
+// Tile scheme, epilogue and reduction: quad_form.hpp (a workgroup = a 128-row block of U x one tile column of C; U is formed in the
+// A-operand staging, a bf16 - bf16 difference being exact in fp64; `pos` [n] int32 is the inverse index map, -1: not kept).
 //
 // Work: d n (n + 1) flop (half of the full product U C), 0.84 TFLOP at n = 14336, d = 4096.  Workspace: the inverse map + two planes
 // of partials, 4 n + 16 d ceil(n / 128) bytes (7.4 MB there; the route through a materialised U, a mirrored C and U C needs 2.6 GB).
@@ -23,6 +14,7 @@
 // Non-finite input: a NaN in row k of W_d or down stays in row k of U, of P and of the sums -- e[k] alone is NaN; a NaN in the lower
 // triangle of C reaches every row.  Out-of-range rows / columns are never loaded (selects, not multiplications by zero).
 #include "common.hpp"
+#include "quad_form.hpp"
 
 namespace mdg {
 
@@ -62,141 +54,33 @@ struct OutErrArgs {
   int tiles_d;
 };
 
+// row k of U: W_d[k, col], minus down[k, pos[col]] where the column is kept (pos looked up once per column)
 template <int WDT, int DDT>
-__device__ __forceinline__ double oe_u(const OutErrArgs& g, int64_t row, int64_t col, int p) {
-  double u = load_f64<WDT>(g.W, row * g.ldw + col);
-  if (p >= 0) u -= load_f64<DDT>(g.down, row * g.sd_row + (int64_t)p * g.sd_col);
-  return u;
-}
+struct OutErrRows {
+  typedef int64_t Idx;
+  typedef int Col;
+  const OutErrArgs g;   // (a copy, as in vo_err.hip: through a reference the kernel compiles to more code)
+  __device__ __forceinline__ Col prepare(int64_t col) const { return g.pos ? g.pos[col] : -1; }
+  __device__ __forceinline__ double at(int64_t row, int64_t col, Col p) const {
+    double u = load_f64<WDT>(g.W, row * g.ldw + col);
+    if (p >= 0) u -= load_f64<DDT>(g.down, row * g.sd_row + (int64_t)p * g.sd_col);
+    return u;
+  }
+};
 
 template <int WDT, int DDT>
 __global__ __launch_bounds__(256, 2) void out_err_kernel(OutErrArgs g) {
   __shared__ double lds[4 * PANEL];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
+  const int tid = threadIdx.x;
   const int bj = blockIdx.x / g.tiles_d, bi = blockIdx.x % g.tiles_d;     // tile column of C (longest first), row block of U
-  const int64_t i0 = (int64_t)bi * TILE, j0 = (int64_t)bj * TILE;
-  const int64_t n_stage = (g.n - j0 + BK - 1) / BK;                       // k runs over the columns j0 .. n-1 of U (>= 1 stage)
-
-  // A panel: element (x = row of U, k); W_d is k-contiguous, so consecutive threads walk k: a thread keeps one k and 8 rows
-  const int ak = tid & 15, ax = tid >> 4;
-  // B panel: element (k = row of C, y = column of C); C is y-contiguous: a thread keeps one column and 8 rows
-  const int bk = tid >> 7, by = tid & 127;
-  const int64_t gcb = j0 + by;
-  double rg[8];  // one panel's prefetch at a time: A rides under the first half of a stage, B under the second (gemm.hip)
-
-  auto load_a = [&](int64_t k0) {
-    const int64_t col = k0 + ak;
-    const bool ok = col < g.n;
-    const int p = (ok && g.pos) ? g.pos[col] : -1;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int64_t row = i0 + ax + 16 * q;
-      rg[q] = (ok && row < g.d) ? oe_u<WDT, DDT>(g, row, col, p) : 0.;
-    }
-  };
-  auto store_a = [&](double* panel) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) panel[ak * PITCH + ax + 16 * q] = rg[q];
-  };
-  auto load_b = [&](int64_t k0) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int64_t gr = k0 + bk + 2 * q;
-      rg[q] = (gr < g.n && gr > gcb) ? g.C[gr * g.ldc + gcb] : 0.;       // strictly below the diagonal only (gcb < gr < n)
-    }
-  };
-  auto store_b = [&](double* panel) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) panel[(bk + 2 * q) * PITCH + by] = rg[q];
-  };
-
-  Acc acc;
-  acc_zero(acc);
-  load_a(j0);
-  store_a(lds);
-  load_b(j0);
-  store_b(lds + 2 * PANEL);
-  __syncthreads();
-  for (int64_t s = 0; s < n_stage; s++) {
-    const int cur = (int)(s & 1);
-    const bool more = s + 1 < n_stage;
-    const int64_t k0 = j0 + (s + 1) * BK;
-    const double* As = lds + cur * PANEL;
-    const double* Bs = lds + (2 + cur) * PANEL;
-    if (more) load_a(k0);
-    mma_steps<0, BK / 8>(As, Bs, wr, wc, lane, acc);
-    if (more) {
-      store_a(lds + (cur ^ 1) * PANEL);
-      load_b(k0);
-    }
-    mma_steps<BK / 8, BK / 4>(As, Bs, wr, wc, lane, acc);
-    if (more) store_b(lds + (2 + (cur ^ 1)) * PANEL);
-    __syncthreads();
-  }
-
-  // epilogue: sum_j u_kj (2 P_kj + C_jj u_kj) and sum_j u_kj^2 over the tile's columns
-  double* red_e = lds;                 // [2][TILE]  (the panels are dead: the loop ended with a barrier)
-  double* red_u = lds + 2 * TILE;      // [2][TILE]
-  const int64_t gc0 = j0 + acc_col(wc, lane, 0);
-  bool cok[4];
-  int pj[4];
-  double cd[4];
-#pragma unroll
-  for (int sb = 0; sb < 4; sb++) {
-    const int64_t col = gc0 + sb;
-    cok[sb] = col < g.n;
-    pj[sb] = (cok[sb] && g.pos) ? g.pos[col] : -1;
-    cd[sb] = cok[sb] ? g.C[col * g.ldc + col] : 0.;
-  }
-#pragma unroll
-  for (int sa = 0; sa < 4; sa++) {
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int lr = acc_row(wr, lane, sa, reg);
-      const int64_t row = i0 + lr;
-      double se = 0., su = 0.;
-      if (row < g.d) {
-#pragma unroll
-        for (int sb = 0; sb < 4; sb++) {
-          if (!cok[sb]) continue;
-          const double u = oe_u<WDT, DDT>(g, row, gc0 + sb, pj[sb]);
-          se += u * (2. * acc.v[sa][sb][reg] + cd[sb] * u);
-          su += u * u;
-        }
-      }
-      // the 16 lanes that share (lane >> 4) hold this row's other columns: a fixed butterfly, the same value in all of them
-#pragma unroll
-      for (int m = 1; m < 16; m <<= 1) {
-        se += __shfl_xor(se, m);
-        su += __shfl_xor(su, m);
-      }
-      if ((lane & 15) == 0) {
-        red_e[wc * TILE + lr] = se;
-        red_u[wc * TILE + lr] = su;
-      }
-    }
-  }
-  __syncthreads();
+  const int64_t i0 = (int64_t)bi * TILE;
+  double se, su;
+  quad_form_tile_column<true>(OutErrRows<WDT, DDT>{g}, g.C, g.ldc, g.n, g.d, i0, (int64_t)bj * TILE, lds, se, su);
   if (tid < TILE && i0 + tid < g.d) {
     const int64_t o = (int64_t)bj * g.d + i0 + tid;
-    g.part_e[o] = red_e[tid] + red_e[TILE + tid];
-    g.part_u[o] = red_u[tid] + red_u[TILE + tid];
+    g.part_e[o] = se;
+    g.part_u[o] = su;
   }
-}
-
-// e[k] = sum_J part_e[J][k] in ascending J (and unorm2 likewise): one thread per output channel, coalesced along k
-__global__ __launch_bounds__(256) void oe_reduce_kernel(const double* part_e, const double* part_u, int64_t d, int tiles_n, double* e,
-                                                        double* unorm2) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= d) return;
-  double se = 0., su = 0.;
-  for (int t = 0; t < tiles_n; t++) {
-    se += part_e[(int64_t)t * d + k];
-    su += part_u[(int64_t)t * d + k];
-  }
-  e[k] = se;
-  if (unorm2) unorm2[k] = su;
 }
 
 static size_t oe_pos_bytes(int64_t n) { return align_up((size_t)n * sizeof(int), 16); }
@@ -251,7 +135,8 @@ extern "C" int mdg_mlp_output_error(const double* C, int64_t n, int64_t ldc, con
   else if (!d64) hipLaunchKernelGGL((out_err_kernel<MDG_F64, MDG_BF16>), grid, dim3(256), 0, st, g);
   else hipLaunchKernelGGL((out_err_kernel<MDG_F64, MDG_F64>), grid, dim3(256), 0, st, g);
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(oe_reduce_kernel, dim3((unsigned)ceil_div(d, 256)), dim3(256), 0, st, part_e, part_u, d, (int)tiles_n, e, unorm2);
+  // (part_u starts tiles_n * d behind part_e: the two plane sets of quad_reduce_kernel)
+  hipLaunchKernelGGL(quad_reduce_kernel, dim3((unsigned)ceil_div(d, 256)), dim3(256), 0, st, part_e, d, (int)tiles_n, e, unorm2);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

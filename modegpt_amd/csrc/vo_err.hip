@@ -13,8 +13,9 @@
 //                          P = sum_{I >= J} y[:, I] G[I, J] on v_mfma_f64_16x16x4_f64 with the diagonal tile masked to its STRICT lower
 //                          part while staging (the Gram's upper triangle is never loaded), y stitched from W_o,h and o'_h in the
 //                          A-operand staging (both widened exactly); epilogue y_kj (2 P_kj + G_jj y_kj) summed along the tile's
-//                          columns in a fixed tree (out_err.hip).  P is never written.  grid = (row blocks, Gram x J, heads).
-//   vo_quad_reduce_kernel  adds the (at most two) tile-column partials of a channel in ascending J.
+//                          columns in a fixed tree.  P is never written.  grid = (row blocks, Gram x J, heads).
+//                          Tile scheme, epilogue and reduction: quad_form.hpp.
+//   quad_reduce_kernel     adds the (at most two) tile-column partials of a channel in ascending J.
 // No atomics: two runs are bit-identical.  e is accurate relative to a[h][k] = (|y| |V_g|) |C| (|y| |V_g|)^T, not to itself.
 //
 // mdg_vo_rank_curve: from the eigen-decomposition (lambda_i, v_i) the last mdg_vo_compress left in its workspace,
@@ -28,6 +29,7 @@
 // head's W_v or v' reaches that group's Grams, i.e. every channel of that group's heads, and no other group; a NaN in C reaches
 // everything.  Out-of-range rows / columns are never loaded (selects, not multiplications by zero).
 #include "common.hpp"
+#include "quad_form.hpp"
 #include "vo_ws.hpp"
 
 namespace mdg {
@@ -49,127 +51,29 @@ struct VoQuadArgs {
 
 // y_{h,k}[col]: W_o,h for col < hd, o'_h behind it
 template <int WDT, int NDT>
-__device__ __forceinline__ double vo_y(const VoQuadArgs& g, int h, int64_t row, int col) {
-  return col < g.hd ? load_f64<WDT>(g.Wo, row * g.ld_wo + (int64_t)h * g.hd + col)
-                    : load_f64<NDT>(g.o_new, row * g.ld_o + (int64_t)h * g.r + (col - g.hd));
-}
+struct VoQuadRows {
+  typedef int Idx;
+  struct Col {};        // (nothing to look up per column)
+  const VoQuadArgs g;   // (a copy: through a reference the kernel compiles to branches where this gives selects, a third more code)
+  int h;
+  __device__ __forceinline__ Col prepare(int) const { return {}; }
+  __device__ __forceinline__ double at(int64_t row, int col, Col) const {
+    return col < g.hd ? load_f64<WDT>(g.Wo, row * g.ld_wo + (int64_t)h * g.hd + col)
+                      : load_f64<NDT>(g.o_new, row * g.ld_o + (int64_t)h * g.r + (col - g.hd));
+  }
+};
 
 template <int WDT, int NDT>
 __global__ __launch_bounds__(256, 2) void vo_quad_kernel(VoQuadArgs g) {
   __shared__ double lds[4 * PANEL];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
+  const int tid = threadIdx.x;
   const int bi = blockIdx.x, plane = blockIdx.y / g.tiles_n, bj = blockIdx.y % g.tiles_n, h = blockIdx.z;
-  const int n = g.n;
   const int64_t i0 = (int64_t)bi * TILE;
-  const int j0 = bj * TILE;
-  const int n_stage = (n - j0 + BK - 1) / BK;                              // k runs over the columns j0 .. n-1 of y (>= 1 stage)
-  const double* G = g.gram + ((size_t)plane * g.n_kv + (size_t)(h / g.group)) * (size_t)n * n;
-
-  // A panel: element (x = output channel, k); both sources of y are k-contiguous: a thread keeps one k and 8 rows
-  const int ak = tid & 15, ax = tid >> 4;
-  // B panel: element (k = row of G, y = column of G); G is column-contiguous: a thread keeps one column and 8 rows
-  const int bk = tid >> 7, by = tid & 127;
-  const int gcb = j0 + by;
-  double rg[8];  // one panel's prefetch at a time: A rides under the first half of a stage, B under the second (gemm.hip)
-
-  auto load_a = [&](int k0) {
-    const int col = k0 + ak;
-    const bool ok = col < n;
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int64_t row = i0 + ax + 16 * q;
-      rg[q] = (ok && row < g.d) ? vo_y<WDT, NDT>(g, h, row, col) : 0.;
-    }
-  };
-  auto store_a = [&](double* panel) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) panel[ak * PITCH + ax + 16 * q] = rg[q];
-  };
-  auto load_b = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int gr = k0 + bk + 2 * q;
-      rg[q] = (gr < n && gr > gcb) ? G[(size_t)gr * n + gcb] : 0.;        // strictly below the diagonal only (gcb < gr < n)
-    }
-  };
-  auto store_b = [&](double* panel) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) panel[(bk + 2 * q) * PITCH + by] = rg[q];
-  };
-
-  Acc acc;
-  acc_zero(acc);
-  load_a(j0);
-  store_a(lds);
-  load_b(j0);
-  store_b(lds + 2 * PANEL);
-  __syncthreads();
-  for (int s = 0; s < n_stage; s++) {
-    const int cur = s & 1;
-    const bool more = s + 1 < n_stage;
-    const int k0 = j0 + (s + 1) * BK;
-    const double* As = lds + cur * PANEL;
-    const double* Bs = lds + (2 + cur) * PANEL;
-    if (more) load_a(k0);
-    mma_steps<0, BK / 8>(As, Bs, wr, wc, lane, acc);
-    if (more) {
-      store_a(lds + (cur ^ 1) * PANEL);
-      load_b(k0);
-    }
-    mma_steps<BK / 8, BK / 4>(As, Bs, wr, wc, lane, acc);
-    if (more) store_b(lds + (2 + (cur ^ 1)) * PANEL);
-    __syncthreads();
-  }
-
-  // epilogue: sum_j y_kj (2 P_kj + G_jj y_kj) over the tile's columns
-  double* red = lds;                   // [2][TILE]  (the panels are dead: the loop ended with a barrier)
-  const int gc0 = j0 + acc_col(wc, lane, 0);
-  bool cok[4];
-  double gd[4];
-#pragma unroll
-  for (int sb = 0; sb < 4; sb++) {
-    const int col = gc0 + sb;
-    cok[sb] = col < n;
-    gd[sb] = cok[sb] ? G[(size_t)col * n + col] : 0.;
-  }
-#pragma unroll
-  for (int sa = 0; sa < 4; sa++) {
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int lr = acc_row(wr, lane, sa, reg);
-      const int64_t row = i0 + lr;
-      double se = 0.;
-      if (row < g.d) {
-#pragma unroll
-        for (int sb = 0; sb < 4; sb++) {
-          if (!cok[sb]) continue;
-          const double y = vo_y<WDT, NDT>(g, h, row, gc0 + sb);
-          se += y * (2. * acc.v[sa][sb][reg] + gd[sb] * y);
-        }
-      }
-      // the 16 lanes that share (lane >> 4) hold this row's other columns: a fixed butterfly, the same value in all of them
-#pragma unroll
-      for (int m = 1; m < 16; m <<= 1) se += __shfl_xor(se, m);
-      if ((lane & 15) == 0) red[wc * TILE + lr] = se;
-    }
-  }
-  __syncthreads();
+  const double* G = g.gram + ((size_t)plane * g.n_kv + (size_t)(h / g.group)) * (size_t)g.n * g.n;
+  double se, unused;
+  quad_form_tile_column<false>(VoQuadRows<WDT, NDT>{g, h}, G, g.n, g.n, g.d, i0, bj * TILE, lds, se, unused);
   if (tid < TILE && i0 + tid < g.d)
-    g.part[(((size_t)plane * g.tiles_n + bj) * g.n_heads + h) * (size_t)g.d + i0 + tid] = red[tid] + red[TILE + tid];
-}
-
-// e[h][k] = sum_J part[0][J][h][k] in ascending J, dnorm2 from plane 1 likewise: one thread per (head, channel)
-__global__ __launch_bounds__(256) void vo_quad_reduce_kernel(const double* part, int64_t total, int tiles_n, double* e, double* dnorm2) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  double se = 0., sn = 0.;
-  for (int t = 0; t < tiles_n; t++) {
-    se += part[(size_t)t * total + i];
-    if (dnorm2) sn += part[(size_t)(tiles_n + t) * total + i];
-  }
-  e[i] = se;
-  if (dnorm2) dnorm2[i] = sn;
+    g.part[(((size_t)plane * g.tiles_n + bj) * g.n_heads + h) * (size_t)g.d + i0 + tid] = se;
 }
 
 struct VoErrWs {
@@ -321,7 +225,7 @@ extern "C" int mdg_vo_output_error(const double* cov_x, int64_t d, int64_t ldc, 
   MDG_LAUNCH_CHECK();
   const int64_t total = (int64_t)n_heads * d;
   // (the partials are laid out [plane][J][head][d]: plane 1 starts tiles_n * total behind plane 0)
-  hipLaunchKernelGGL(vo_quad_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, w.part, total, g.tiles_n, e, dnorm2);
+  hipLaunchKernelGGL(quad_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, w.part, total, g.tiles_n, e, dnorm2);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

@@ -7,7 +7,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-import math
 import os
 import threading
 from typing import NamedTuple, Optional, Sequence, Tuple
@@ -16,6 +15,11 @@ import torch
 
 from . import _lib
 from ._lib import check
+# the host side of the reports (switches, constants, decoders) lives in reports.py; every name stays reachable as ops.<name>
+from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_MARGIN_FIELDS, RANK_CURVE_KEEP,  # noqa: F401
+                      RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
+                      decode_qk_margin, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
+                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, rank_curve_enabled, vo_error_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
        torch.float64: _lib.MDG_F64}
@@ -531,13 +535,6 @@ def cov_finalize(sigma: torch.Tensor, scale: float) -> None:
               "mdg_cov_finalize")
 
 
-# The mean-aware MLP refit ("The MLP intercept").  Opt-in: MODEGPT_MLP_INTERCEPT=1 makes calibration collect the
-# column sums of the sigma_mlp activation and compress_nystrom refit on the centred statistic and store an intercept as down_bias.
-def mlp_intercept_enabled() -> bool:
-    """MODEGPT_MLP_INTERCEPT as it stands when calibration or a compressor asks (per layer; not frozen at import)."""
-    return os.environ.get("MODEGPT_MLP_INTERCEPT", "0").lower() in ("1", "on", "true")
-
-
 COL_SUM_CHUNK = 128        # tokens per workgroup of mdg_col_sum_accum (one partial row each)
 COV_CENTER_TILE = 64       # tile edge of mdg_cov_center
 
@@ -775,10 +772,6 @@ def select_smallest_sorted(scores: torch.Tensor, k: int) -> torch.Tensor:
     return idx
 
 
-MARGIN_FIELDS = ("s_selected_max", "s_unselected_min", "selected_upper", "unselected_lower", "sens_selected_max", "sens_unselected_max",
-                 "scores_at_risk", "certified")
-
-
 def select_margin(scores: torch.Tensor, sens: torch.Tensor, idx: torch.Tensor, eps: float) -> torch.Tensor:
     """The certificate of a k-smallest selection (mdg_select_margin): 8 fp64 numbers ON THE DEVICE (MARGIN_FIELDS), enqueued only --
     read them when the stream is waited for anyway (decode_margin)."""
@@ -792,19 +785,6 @@ def select_margin(scores: torch.Tensor, sens: torch.Tensor, idx: torch.Tensor, e
         check(lib.mdg_select_margin(s.data_ptr(), b.data_ptr(), idx.data_ptr() if idx.numel() else None, s.numel(), idx.numel(),
                                     float(eps), out.data_ptr(), _stream(s)), "mdg_select_margin")
     return out
-
-
-def decode_margin(out8, eps: float) -> dict:
-    """Host-side reading of select_margin's 8 numbers (a list / CPU tensor): the relative margin of the selection threshold, the
-    bound on what a perturbation of relative size eps can do to a score there, and whether the selected set is certified."""
-    v = [float(x) for x in out8]
-    s_k, s_k1 = v[0], v[1]
-    finite = s_k > float("-inf") and s_k1 < float("inf")
-    margin = (s_k1 - s_k) / abs(s_k) if finite and s_k != 0 else float("inf")
-    spread = v[4] + v[5]
-    return {"margin": margin, "score_bound": eps * max(v[4], v[5]) / abs(s_k) if finite and s_k != 0 else 0.0,
-            "eps": eps, "eps_certifiable": (s_k1 - s_k) / spread if finite and spread > 0 else float("inf"),
-            "scores_at_risk": int(v[6]), "certified": bool(v[7] == 1.0), **{k: x for k, x in zip(MARGIN_FIELDS[:4], v[:4])}}
 
 
 def gather_rows(W: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
@@ -895,13 +875,6 @@ def nystrom_intercept(W_down: torch.Tensor, down_hat: torch.Tensor, idx: torch.T
     return bias, bias_f64, norms
 
 
-# The Nystrom refit's error at every rank (mdg_nystrom_rank_curve).  Opt-in: MODEGPT_RANK_CURVE=1 makes compress_nystrom compute
-# it for every layer (one more factorisation of sigma_mlp and a triangular product per layer; DESIGN.md section 7, "The error-versus-rank curve").
-def rank_curve_enabled() -> bool:
-    """MODEGPT_RANK_CURVE as it stands when compress_nystrom asks (per layer; not frozen at import)."""
-    return os.environ.get("MODEGPT_RANK_CURVE", "0").lower() in ("1", "on", "true")
-
-
 def nystrom_rank_curve(Cm: torch.Tensor, order: torch.Tensor, W_down: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     """curve [n + 1] fp64 ON THE DEVICE: curve[r] = tr(W (M - M[:, S] M_SS^-1 M[S, :]) W^T), M = C + eps I, S = order[:r] -- the
     residual energy of the Nystrom refit that keeps the first r columns of `order`, for every r from one factorisation.  `order`:
@@ -925,49 +898,6 @@ def nystrom_rank_curve(Cm: torch.Tensor, order: torch.Tensor, W_down: torch.Tens
                                          _DT[W_down.dtype], float(eps), curve.data_ptr(), wsp, nbytes, _stream(Cm)),
               "mdg_nystrom_rank_curve")
     return curve
-
-
-RANK_CURVE_KEEP = tuple(k / 100 for k in range(5, 101, 5))          # 0.05, 0.10, ..., 1.00
-RANK_CURVE_TARGETS = (1e-1, 1e-2, 1e-3)
-
-
-def decode_rank_curve(curve, rank: int) -> dict:
-    """Host-side reading of a rank curve (a list / CPU tensor of n + 1 numbers) for a layer compressed to `rank`:
-    n, rank, energy = curve[0] (the output energy tr(W (C + eps I) W^T) of the uncompressed MLP), rel_error = curve[rank] / energy,
-    keep = RANK_CURVE_KEEP with rel_error_at_keep = the relative error at rank int(n * keep) (compress_weights' rounding), and
-    rank_for_rel_error = {target: the smallest rank whose relative error is at or under it} for RANK_CURVE_TARGETS.  A zero or
-    non-finite energy gives None in every relative field."""
-    v = [float(x) for x in curve]
-    n, rank, energy = len(v) - 1, int(rank), v[0]
-    if n < 0 or not 0 <= rank <= n:
-        raise ValueError(f"decode_rank_curve: rank {rank} outside 0 .. {n}")
-    ok = energy > 0 and energy < float("inf")         # (False for NaN)
-    rel = (lambda r: v[r] / energy) if ok else (lambda r: None)
-
-    def smallest_rank(target):       # the curve is non-increasing: the first rank at or under the target
-        if not ok:
-            return None
-        lo, hi = 0, n                # invariant: rel(hi) <= target (rel(n) = 0)
-        if not v[n] / energy <= target:
-            return None
-        while lo < hi:
-            mid = (lo + hi) // 2
-            if v[mid] / energy <= target:
-                hi = mid
-            else:
-                lo = mid + 1
-        return hi
-    return {"n": n, "rank": rank, "energy": energy, "rel_error": rel(rank), "keep": list(RANK_CURVE_KEEP),
-            "rel_error_at_keep": [rel(int(n * k)) for k in RANK_CURVE_KEEP],
-            "rank_for_rel_error": {"%g" % t: smallest_rank(t) for t in RANK_CURVE_TARGETS}}
-
-
-# The realised output error of the STORED down projection (mdg_mlp_output_error).  Opt-in: MODEGPT_OUTPUT_ERROR=1 makes
-# compress_nystrom compute it for every layer from the bf16 tensor it saves (two launches of d n (n + 1) flop per layer; DESIGN.md
-# section 7, "The realised output error of the stored MLP weights").
-def output_error_enabled() -> bool:
-    """MODEGPT_OUTPUT_ERROR as it stands when compress_nystrom asks (per layer; not frozen at import)."""
-    return os.environ.get("MODEGPT_OUTPUT_ERROR", "0").lower() in ("1", "on", "true")
 
 
 def mlp_output_error(Cm: torch.Tensor, W_down: torch.Tensor, idx: Optional[torch.Tensor], down: Optional[torch.Tensor],
@@ -1006,42 +936,7 @@ def mlp_output_error(Cm: torch.Tensor, W_down: torch.Tensor, idx: Optional[torch
     return (e, u2) if want_unorm2 else e
 
 
-OUTPUT_ERROR_LEVELS = (1e-1, 1e-2, 1e-3)
 NYSTROM_EPS = 1e-6          # the ridge of the refit compress_weights computes (compress_mlp.py:52,56): the eps of `objective`
-
-
-def decode_output_error(e, q, unorm2, eps: float, rank: int, curve=None) -> dict:
-    """Host-side reading of a layer's output error (lists / CPU tensors of d numbers each: e and unorm2 of the stored tensor, q of
-    the uncompressed weights; eps: the ridge of the refit; rank: the columns kept):
-    rank, energy = sum q, error = sum e, relative_error = error / energy, objective = error + eps sum unorm2 (what the refit
-    minimises, compress_mlp.py:52-62), worst_channel = the channel with the largest e_k / q_k among those with q_k > 0 and
-    worst_channel_relative_error that ratio, channels_above = {level: how many such channels exceed it} for OUTPUT_ERROR_LEVELS.
-    With the layer's rank curve (n + 1 numbers): predicted_objective = curve[rank], the minimum of the objective over all refits,
-    and excess_over_optimum = (objective - curve[rank]) / curve[0] -- what rounding to bf16 and solving with C[S, :] instead of
-    M[S, :] cost beyond the best refit.  A non-finite sum gives None in the fields derived from it."""
-    ev, qv, uv = ([float(x) for x in t] for t in (e, q, unorm2))
-    if not len(ev) == len(qv) == len(uv):
-        raise ValueError("decode_output_error: e, q and unorm2 must have one entry per output channel")
-    fin = lambda x: x if math.isfinite(x) else None                    # noqa: E731
-    total = lambda v: math.fsum(v) if all(map(math.isfinite, v)) else float("nan")      # noqa: E731
-    energy, error, u2 = total(qv), total(ev), total(uv)
-    objective = error + float(eps) * u2
-    ratios = [(ek / qk, k) for k, (ek, qk) in enumerate(zip(ev, qv)) if qk > 0 and math.isfinite(qk) and math.isfinite(ek)]
-    worst = max(ratios, key=lambda t: (t[0], -t[1])) if ratios and math.isfinite(error) and math.isfinite(energy) else None
-    out = {"rank": int(rank), "energy": fin(energy), "error": fin(error),
-           "relative_error": error / energy if math.isfinite(error) and math.isfinite(energy) and energy > 0 else None,
-           "objective": fin(objective),
-           "worst_channel": None if worst is None else worst[1],
-           "worst_channel_relative_error": None if worst is None else worst[0],
-           "channels_above": {"%g" % t: (None if worst is None else sum(1 for x, _ in ratios if x > t)) for t in OUTPUT_ERROR_LEVELS}}
-    if curve is not None:
-        cv = [float(x) for x in curve]
-        if not 0 <= int(rank) < len(cv):
-            raise ValueError(f"decode_output_error: rank {rank} outside the curve's 0 .. {len(cv) - 1}")
-        ok = math.isfinite(cv[int(rank)]) and math.isfinite(cv[0]) and cv[0] > 0
-        out["predicted_objective"] = cv[int(rank)] if ok else None
-        out["excess_over_optimum"] = (objective - cv[int(rank)]) / cv[0] if ok and math.isfinite(objective) else None
-    return out
 
 
 # ------------------------------------------------------------------ QK / VO
@@ -1064,10 +959,6 @@ def qk_select(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: int, ri
     return mask, q_rows, k_rows
 
 
-QK_MARGIN_FIELDS = ("s_selected_min", "s_unselected_max", "selected_lower", "unselected_upper", "score_halfwidth", "units_at_risk",
-                    "order_at_risk", "certified")
-
-
 def qk_select_margin(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: int, ridge_q: float, ridge_k: float,
                      mask: torch.Tensor, eps_rel: float, eps_abs: float) -> torch.Tensor:
     """The certificate of a qk_select selection (mdg_qk_select_margin): [n_kv, 8] fp64 ON THE DEVICE (QK_MARGIN_FIELDS), enqueued
@@ -1088,37 +979,6 @@ def qk_select_margin(cov_q: torch.Tensor, cov_k: torch.Tensor, rank: int, mode: 
                                        mask.data_ptr(), float(eps_rel), float(eps_abs), out.data_ptr(), _stream(cq)),
               "mdg_qk_select_margin")
     return out
-
-
-def decode_qk_margin(rows, eps_rel: float, eps_abs: float) -> dict:
-    """Host-side reading of qk_select_margin's [n_kv, 8] numbers (nested list / CPU tensor).  Per kv head: the relative margin
-    between the weakest selected and the strongest unselected unit, the relative half-width a score can move within the error
-    model, how many units sit within reach of the threshold, how many neighbours of the selected order could swap, and whether set
-    and order are certified.  Layer summary: the weakest head (smallest margin among the uncertified heads, else among all), its
-    margin and half-width, and whether every head is certified."""
-    heads = []
-    for row in rows:
-        v = [float(x) for x in row]
-        s_sel, s_unsel = v[0], v[1]
-        separable = s_unsel > float("-inf") and s_sel < float("inf")
-        margin = (s_sel - s_unsel) / s_sel if separable and s_sel > 0 else (float("inf") if not separable else float("-inf"))
-        certified = v[7] == 1.0
-        heads.append({"margin": margin, "score_halfwidth": v[4], "units_at_risk": int(v[5]), "order_at_risk": int(v[6]),
-                      "certified": certified, "order_certified": certified and v[6] == 0.0,
-                      **{k: x for k, x in zip(QK_MARGIN_FIELDS[:4], v[:4])}})
-    weakest = min(range(len(heads)), key=lambda i: (heads[i]["certified"], heads[i]["margin"])) if heads else None
-    return {"heads": heads, "eps_rel": float(eps_rel), "eps_abs": float(eps_abs), "weakest_head": weakest,
-            "margin": heads[weakest]["margin"] if heads else float("inf"),
-            "score_halfwidth": heads[weakest]["score_halfwidth"] if heads else 0.0,
-            "certified": all(h["certified"] for h in heads), "order_certified": all(h["order_certified"] for h in heads)}
-
-
-# What the Q/K selection costs the attention logits on the calibration statistic, per query head and at every rank
-# (mdg_qk_rank_curve).  Opt-in: MODEGPT_QK_ERROR=1 makes compress_qk compute it for every layer from the statistics it holds anyway
-# (DESIGN.md section 7, "What the Q/K selection costs the attention logits").
-def qk_error_enabled() -> bool:
-    """MODEGPT_QK_ERROR as it stands when compress_qk asks (per layer; not frozen at import)."""
-    return os.environ.get("MODEGPT_QK_ERROR", "0").lower() in ("1", "on", "true")
 
 
 def qk_units(mode: int, hd: int):
@@ -1160,89 +1020,6 @@ def qk_rank_curve(cov_q: torch.Tensor, cov_k: torch.Tensor, mode: int, ridge_q: 
                                     order.data_ptr(), float(tq), float(tk), curve_h.data_ptr(), curve.data_ptr(), terms.data_ptr(),
                                     scale.data_ptr(), _p(g_curve), _p(g_order), _stream(cq)), "mdg_qk_rank_curve")
     return curve_h, curve, terms, scale, g_curve, g_order
-
-
-QK_ERROR_TARGETS = (1e-1, 1e-2, 1e-3)
-
-
-def decode_qk_logit_error(curve_h, curve, rank: int, cols_per_unit: int, terms=None, scale=None, greedy_curve=None) -> dict:
-    """Host-side reading of qk_rank_curve's numbers (nested lists / CPU tensors: curve_h [n_heads][ns + 1], curve and greedy_curve
-    [n_kv][ns + 1], terms [n_kv][ns], scale [n_kv]); rank: the columns kept per head, cols_per_unit: 2 for the RoPE modes, 1 for OPT.
-    With m = rank / cols_per_unit units kept, per kv head under "heads":
-    energy = curve[0] (the mean-square logit of the group's heads), error = curve[m], relative_error = error / energy;
-    diagonal_estimate = sum_{i >= m} terms[i] (what the reference's rule believes the cost is) and diagonal_ratio = diagonal_estimate /
-    error (far from 1: the off-diagonal correlations the rule ignores matter); greedy_relative_error = greedy_curve[m] / energy;
-    rank_for_rel_error = {"selection" / "greedy": {target: the fewest columns per head at which the curve is at or under target x
-    energy}} for QK_ERROR_TARGETS (the curve need not be monotone: the FIRST such rank; None without a usable energy);
-    head_relative_error = [curve_h[h][m] / curve_h[h][0]] over the group's query heads; noise_floor = (g hd^2 + 2) 2^-53 scale / energy,
-    below which a relative value says nothing; non_monotone = some curve[i + 1] > curve[i] by more than that floor.
-    The layer: the sums over the kv heads (energy-weighted), non_monotone = any head's.  Values are reported raw, never clamped; a
-    non-finite figure, or one derived from an unusable energy, is None."""
-    ch = [[float(x) for x in row] for row in curve_h]
-    cv = [[float(x) for x in row] for row in curve]
-    n_heads, n_kv, rank, cols = len(ch), len(cv), int(rank), int(cols_per_unit)
-    if n_kv <= 0 or n_heads % n_kv or cols not in (1, 2) or any(len(row) != len(cv[0]) for row in cv + ch) or len(cv[0]) < 1:
-        raise ValueError("decode_qk_logit_error: curve_h must be [n_heads][ns + 1] and curve [n_kv][ns + 1], n_heads a multiple of n_kv")
-    ns, group = len(cv[0]) - 1, n_heads // n_kv
-    if rank % cols or not 0 <= rank // cols <= ns:
-        raise ValueError(f"decode_qk_logit_error: rank {rank} is not a whole number of units within 0 .. {ns * cols}")
-    m, hd = rank // cols, ns * cols
-    opt = lambda t, width: None if t is None else [[float(x) for x in row] for row in t] if width else [float(x) for x in t]  # noqa: E731
-    tv, gv, sv = opt(terms, ns), opt(greedy_curve, ns + 1), opt(scale, 0)
-    if (tv is not None and (len(tv) != n_kv or any(len(r) != ns for r in tv))) or (sv is not None and len(sv) != n_kv) or \
-            (gv is not None and (len(gv) != n_kv or any(len(r) != ns + 1 for r in gv))):
-        raise ValueError(f"decode_qk_logit_error: terms must be [{n_kv}][{ns}], scale [{n_kv}] and greedy_curve [{n_kv}][{ns + 1}]")
-    fin = lambda x: x if x is not None and math.isfinite(x) else None                    # noqa: E731
-    ratio = lambda a, b: a / b if fin(a) is not None and fin(b) is not None and b > 0 else None   # noqa: E731
-    unit = (group * hd * hd + 2) * 2.0 ** -53
-
-    def first_under(c, energy):
-        if fin(energy) is None or energy <= 0 or not all(map(math.isfinite, c)):
-            return {"%g" % t: None for t in QK_ERROR_TARGETS}
-        return {"%g" % t: next((i * cols for i, x in enumerate(c) if x <= t * energy), None) for t in QK_ERROR_TARGETS}
-
-    heads = []
-    for g in range(n_kv):
-        c = cv[g]
-        energy, error = c[0], c[m]
-        floor_abs = unit * sv[g] if sv is not None and fin(sv[g]) is not None else None
-        diag = None
-        if tv is not None:
-            diag = math.fsum(tv[g][m:]) if all(map(math.isfinite, tv[g][m:])) else float("nan")
-        h = {"energy": fin(energy), "error": fin(error), "relative_error": ratio(error, energy),
-             "diagonal_estimate": fin(diag), "diagonal_ratio": ratio(diag, error),
-             "greedy_relative_error": None if gv is None else ratio(gv[g][m], energy),
-             "rank_for_rel_error": {"selection": first_under(c, energy), "greedy": None if gv is None else first_under(gv[g], energy)},
-             "head_relative_error": [ratio(ch[q][m], ch[q][0]) for q in range(g * group, (g + 1) * group)],
-             "noise_floor": ratio(floor_abs, energy),
-             "non_monotone": (any(b > a + (floor_abs or 0.0) for a, b in zip(c, c[1:])) if all(map(math.isfinite, c)) else None)}
-        heads.append(h)
-
-    def total(key, source=None):
-        vals = [h[key] for h in heads] if source is None else source
-        return math.fsum(vals) if all(v is not None and math.isfinite(v) for v in vals) else None
-
-    energy, error, diag = total("energy"), total("error"), total("diagonal_estimate")
-    greedy = None if gv is None else total(None, [gv[g][m] for g in range(n_kv)])
-    floors = None if sv is None else total(None, [unit * s for s in sv])
-    flags = [h["non_monotone"] for h in heads]
-    return {"rank": rank, "units_kept": m, "n_kv": n_kv, "head_dim": hd, "energy": energy, "error": error,
-            "relative_error": ratio(error, energy), "diagonal_estimate": diag, "diagonal_ratio": ratio(diag, error),
-            "greedy_relative_error": ratio(greedy, energy), "noise_floor": ratio(floors, energy),
-            "non_monotone": None if any(f is None for f in flags) else any(flags), "heads": heads}
-
-
-VO_SPECTRUM_FIELDS = ("lambda_r", "lambda_next", "gap", "energy", "bound", "separated", "lambda_max", "lambda_min")
-
-
-def keep_bias_enabled(arch: Optional[str] = None) -> bool:
-    """Whether the compressors carry the projection biases into the artefacts ("Projection biases"): always
-    for Qwen2 / Qwen2.5 (model_type "qwen2": nothing of the reference's to preserve, and dropping q/k/v biases is never right),
-    otherwise MODEGPT_KEEP_BIAS as it stands when a compressor asks (per layer; not frozen at import).  Off: the reference's
-    behaviour, every rebuilt Linear bias-free (model_adapter.py:199-208)."""
-    if arch == "qwen2":
-        return True
-    return os.environ.get("MODEGPT_KEEP_BIAS", "0").lower() in ("1", "on", "true")
 
 
 def vo_bias(ws: torch.Tensor, W_o: torch.Tensor, b_v: torch.Tensor, b_o: Optional[torch.Tensor], n_heads: int, n_kv: int, hd: int,
@@ -1328,31 +1105,6 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
     return out + (carried,) if bias is not None else out
 
 
-def decode_vo_spectrum(rows, eps: float) -> dict:
-    """Host-side reading of vo_compress(want_spectrum=True)'s [n_kv, 8] numbers.  Per kv head VO_SPECTRUM_FIELDS ("separated": True /
-    False for the grouped variant, None for the two-SVD MHA variant, whose second spectrum has no bound here).  Layer summary: the
-    head with the smallest relative gap, that gap, the smallest retained energy, and "separated" (False as soon as one grouped head
-    is not; None for MHA)."""
-    heads = []
-    for row in rows:
-        v = [float(x) for x in row]
-        sep = None if v[5] != v[5] else v[5] == 1.0
-        heads.append({**{k: x for k, x in zip(VO_SPECTRUM_FIELDS, v)}, "bound": None if v[4] != v[4] else v[4], "separated": sep})
-    weakest = min(range(len(heads)), key=lambda i: heads[i]["gap"]) if heads else None
-    seps = [h["separated"] for h in heads]
-    return {"heads": heads, "eps": float(eps), "weakest_head": weakest, "gap": heads[weakest]["gap"] if heads else float("inf"),
-            "energy_min": min((h["energy"] for h in heads), default=1.0),
-            "separated": None if (not seps or any(x is None for x in seps)) else all(seps)}
-
-
-# The realised output error of the STORED v_proj / o_proj (mdg_vo_output_error) and the truncation's cost at every rank
-# (mdg_vo_rank_curve).  Opt-in: MODEGPT_VO_ERROR=1 makes compress_vo compute both for every layer from the bf16 tensors it saves
-# (DESIGN.md section 7, "The realised output error of the stored V/O factors").
-def vo_error_enabled() -> bool:
-    """MODEGPT_VO_ERROR as it stands when compress_vo asks (per layer; not frozen at import)."""
-    return os.environ.get("MODEGPT_VO_ERROR", "0").lower() in ("1", "on", "true")
-
-
 def vo_output_error(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
                     v_new: Optional[torch.Tensor], o_new: Optional[torch.Tensor], want_dnorm2: bool = False):
     """e [n_heads, d] fp64 ON THE DEVICE: e[h][k] = delta C delta^T, delta = W_o,h[k, :] W_v,g - o'_h[k, :] v'_g -- what output
@@ -1390,86 +1142,6 @@ def vo_output_error(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n
                                       on.data_ptr() if r else None, on.stride(0) if r else 0, _DT[vn.dtype] if r else _lib.MDG_BF16,
                                       e.data_ptr(), _p(dn), wsp, nbytes, _stream(cov_x)), "mdg_vo_output_error")
     return (e, dn) if want_dnorm2 else e
-
-
-VO_ERROR_TARGETS = (1e-1, 1e-2, 1e-3)
-
-
-def decode_vo_output_error(e, q, dnorm2, ridge: float, rank: int, n_kv: int, curve=None, hd: Optional[int] = None) -> dict:
-    """Host-side reading of a layer's V/O output error (nested lists / CPU tensors [n_heads][d]: e and dnorm2 of the stored factors, q
-    of the uncompressed weights; ridge: the ridge vo_compress was called with; rank: the components kept per head).  Layer and, under
-    "heads", per kv head (a kv head's numbers are the sums over its group's query heads):
-    energy = sum q, error = sum e, relative_error = error / energy, objective = error + ridge sum dnorm2 (what the truncation is
-    judged by under C + ridge I), noise_floor = 64 (d + hd + rank) 2^-53 energy -- e is accurate relative to a scale a >= q, not to
-    itself, so an error below the floor (of either sign) says nothing; hd is taken from the curve, else from `hd`, else as rank.
-    worst_head = the QUERY head with the largest error / energy, worst_head_relative_error, and worst_channel /
-    worst_channel_relative_error = the channel of that head with the largest e / q among those with q > 0.
-    With the layer's curve ([n_kv][hd + 1], vo_compress(want_curve=True)), per kv head: predicted_objective = curve[g][rank],
-    excess_over_curve = (objective - curve[g][rank]) / curve[g][0] (what rounding the factors to bf16 costs beyond the fp64
-    truncation; rounding noise of either sign for fp64 factors), relative_curve = curve[g][r] / curve[g][0] for every r, and
-    rank_for_rel_error = {target: the smallest rank at or under it} for VO_ERROR_TARGETS; the layer gets predicted_objective and
-    excess_over_curve of the sums.  A zero or non-finite sum gives None in the fields derived from it."""
-    ev, qv, nv = ([[float(x) for x in row] for row in t] for t in (e, q, dnorm2))
-    n_heads, rank, n_kv = len(ev), int(rank), int(n_kv)
-    if not (len(qv) == len(nv) == n_heads) or n_kv <= 0 or n_heads % n_kv or any(len(a) != len(b) or len(a) != len(c)
-                                                                                 for a, b, c in zip(ev, qv, nv)):
-        raise ValueError("decode_vo_output_error: e, q and dnorm2 must be [n_heads][d] with n_heads a multiple of n_kv")
-    group, d = n_heads // n_kv, (len(ev[0]) if n_heads else 0)
-    cv = None
-    if curve is not None:
-        cv = [[float(x) for x in row] for row in curve]
-        if len(cv) != n_kv or any(len(row) != len(cv[0]) or not 0 <= rank < len(row) for row in cv):
-            raise ValueError(f"decode_vo_output_error: the curve must be [{n_kv}][hd + 1] with rank {rank} <= hd")
-        hd = len(cv[0]) - 1
-    hd = rank if hd is None else int(hd)
-    unit = 64.0 * (d + hd + rank) * 2.0 ** -53
-    fin = lambda x: x if math.isfinite(x) else None                    # noqa: E731
-    total = lambda rows: math.fsum(x for row in rows for x in row) if all(math.isfinite(x) for row in rows for x in row) \
-        else float("nan")                                              # noqa: E731
-
-    def summary(heads_of, curves):
-        energy, error, n2 = (total([t[h] for h in heads_of]) for t in (qv, ev, nv))
-        objective = error + float(ridge) * n2
-        usable = math.isfinite(energy) and energy > 0
-        out = {"energy": fin(energy), "error": fin(error), "objective": fin(objective),
-               "relative_error": error / energy if usable and math.isfinite(error) else None,
-               "noise_floor": unit * energy if usable else None}
-        if curves is not None:
-            at, top = math.fsum(c[rank] for c in curves), math.fsum(c[0] for c in curves)
-            ok = math.isfinite(at) and math.isfinite(top) and top > 0
-            out["predicted_objective"] = at if ok else None
-            out["excess_over_curve"] = (objective - at) / top if ok and math.isfinite(objective) else None
-        return out
-
-    heads = []
-    for g in range(n_kv):
-        m = summary(range(g * group, (g + 1) * group), None if cv is None else [cv[g]])
-        if cv is not None:
-            c = cv[g]
-            ok = math.isfinite(c[0]) and c[0] > 0 and all(math.isfinite(x) for x in c)
-            m["relative_curve"] = [x / c[0] for x in c] if ok else None
-            # (non-increasing: the first rank at or under the target)
-            m["rank_for_rel_error"] = {"%g" % t: (next(r for r, x in enumerate(c) if x / c[0] <= t) if ok else None)
-                                       for t in VO_ERROR_TARGETS}
-        heads.append(m)
-    out = {"rank": rank, "n_kv": n_kv, **summary(range(n_heads), cv), "heads": heads}
-    ratios = []
-    for h in range(n_heads):
-        eh, qh = math.fsum(ev[h]) if all(map(math.isfinite, ev[h])) else float("nan"), \
-            math.fsum(qv[h]) if all(map(math.isfinite, qv[h])) else float("nan")
-        if math.isfinite(eh) and math.isfinite(qh) and qh > 0:
-            ratios.append((eh / qh, -h))
-    worst = max(ratios) if ratios and out["relative_error"] is not None else None
-    out["worst_head"] = None if worst is None else -worst[1]
-    out["worst_head_relative_error"] = None if worst is None else worst[0]
-    chan = None
-    if worst is not None:
-        h = -worst[1]
-        per = [(ek / qk, -k) for k, (ek, qk) in enumerate(zip(ev[h], qv[h])) if qk > 0]
-        chan = max(per) if per else None
-    out["worst_channel"] = None if chan is None else -chan[1]
-    out["worst_channel_relative_error"] = None if chan is None else chan[0]
-    return out
 
 
 ROPE_PLAN_FIELDS = ("route", "hpt", "vec", "norm", "half_even", "iters", "one_shot", "cs_vec16", "nw_vec16", "tt", "wi", "wo",
