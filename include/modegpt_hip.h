@@ -51,7 +51,8 @@ extern "C" {
                                 added under 10: mdg_qk_rank_curve (what the Q/K pair selection costs the attention logits, per head and rank);
                                 added under 10: mdg_vo_bias (the v_proj / o_proj biases through the V/O truncation);
                                 added under 10: mdg_col_sum_ws_bytes, mdg_col_sum_accum, mdg_cov_center, mdg_nystrom_intercept_ws_bytes,
-                                mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept) */
+                                mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept);
+                                added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -639,6 +640,37 @@ int mdg_vo_spectrum(const void* ws, size_t ws_bytes, const double* cov_x, int64_
  * or 2 (n_kv hd + d) > n_kv hd d (no room for the scratch). */
 int mdg_vo_bias(void* ws, size_t ws_bytes, const void* Wo, int64_t ld_wo, int w_dtype, int64_t d, const void* b_v, const void* b_o,
                 int b_dtype, int n_heads, int n_kv, int hd, int rank, double* o_bias, double* v_bias, double* resid, void* stream);
+/* The intercept of the mean-aware V/O truncation (added under ABI 10; not in the reference: compress_vo.py:112-223 looks at no first
+ * moment and truncates the spectrum of the UNCENTRED second moment).  Softmax rows sum to one, so with mu = E[x] (x the post-norm
+ * hidden state, normalised as mdg_cov_finalize normalises sigma_x) the mean reaches the attention output as the constant
+ * sum_h W_o,h (W_v,kv(h) mu + b_v,kv(h)), whatever the attention weights are; the truncation then runs on S = sigma_x - mu mu^T
+ * (mdg_cov_center, then mdg_vo_compress unchanged) and this call computes the optimal intercept for exactly the tensors that are STORED:
+ *     a_g  = W_v,g mu + b_v,g   [hd]    per kv head   (b_v NULL: 0)
+ *     a'_g = v^_g mu            [rank]  per kv head   (v^_g = rows g rank .. of v_new)
+ *     delta_i = sum_h ( W_o,h[i, :] a_kv(h) - o^_h[i, :] a'_kv(h) )        i < d   (o^_h = columns h rank .. of o_new)
+ *     bias_f64[i] = b_o[i] + delta_i             (b_o NULL: 0)
+ *     bias_out[i] = bias_f64[i] rounded once to out_dtype (the way torch's .to() rounds: through fp32 for the 16-bit types); may be NULL
+ *     norms[0] = sum_i delta_i^2 ,  norms[1] = sum_i (sum_h W_o,h[i, :] a_kv(h))^2    (the constant the uncompressed attention adds)
+ * Wv [n_kv hd, d] (ld_wv) and Wo [d, n_heads hd] (ld_wo) of w_dtype, v_new [n_kv rank, d] (ld_v) and o_new [d, n_heads rank] (ld_o) of
+ * new_dtype, each MDG_BF16 or MDG_F64 as mdg_vo_output_error takes them (the stored bf16 tensors or mdg_vo_compress's v_f64 / o_f64);
+ * mu [d] fp64; b_v [n_kv hd] and b_o [d] of b_dtype (any MDG_* element type).  Head layouts as mdg_vo_compress (grouped, and MHA with
+ * n_kv == n_heads); 0 <= rank <= hd, and at rank 0 the factors are not read (they may be NULL) and delta is the whole constant.
+ * Two launches and the norm tree.  Head stage: the n_kv (hd + rank) rows of W_v and v^ against mu; row stage: the d rows of
+ * [W_o | o^] against a and a', expanded to the query heads' columns in LDS.  In both a wave owns four rows, lanes go along the row
+ * (16-byte loads of eight bf16 where the pointer and the leading dimension allow, single elements otherwise), the vector is staged in
+ * LDS per 2048 columns; every product enters through fma, a lane adds its columns in ascending order, the wave reduces by butterfly;
+ * norms: thread t adds rows t, t + 256, ... ascending, then a fixed tree.  One read of each operand, no atomics: the same bits from
+ * run to run.  A NaN in row i of W_o or o_new reaches bias entry i alone (and the norms); a NaN in one kv head's W_v, v_new or b_v
+ * reaches every bias entry (every row sums over all heads) and the norms.
+ * ws: mdg_vo_intercept_ws_bytes(d, n_kv, hd, rank) = 8 (n_kv (hd + rank) + 2 d) bytes (a, a', delta and the constant per row), 8-byte
+ * aligned, its own (not mdg_vo_compress's: the call also serves factors from elsewhere).  Only enqueues.  MDG_ERR_BAD_ARG for a null
+ * required pointer, an unsupported dtype or head layout, a rank outside the range, ld_wv or ld_v < d, ld_wo < n_heads hd,
+ * ld_o < n_heads rank, a workspace that is too small, or rank > 0 without v_new / o_new. */
+size_t mdg_vo_intercept_ws_bytes(int64_t d, int n_kv, int hd, int rank);
+int mdg_vo_intercept(const void* Wv, int64_t ld_wv, const void* Wo, int64_t ld_wo, int w_dtype, const void* v_new, int64_t ld_v,
+                     const void* o_new, int64_t ld_o, int new_dtype, int64_t d, int n_heads, int n_kv, int hd, int rank,
+                     const double* mu, const void* b_v, const void* b_o, int b_dtype, void* bias_out, int out_dtype, double* bias_f64,
+                     double* norms, void* ws, size_t ws_bytes, void* stream);
 
 /* What the STORED V/O factors lose of the attention output on the calibration statistic, per query head and output channel (added
  * under ABI 9; not in the reference: compress_vo.py:112-223 cuts its SVD at `rank` and reports nothing about the product).  Field [3]

@@ -95,6 +95,9 @@ SIGNATURES = {
                                 _ptr, _i64, _ptr, _ptr, _ptr, _sz, _ptr]),
     "mdg_vo_spectrum": (_i32, [_ptr, _sz, _ptr, _i64, _i64, _ptr, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _ptr, _ptr]),
     "mdg_vo_bias": (_i32, [_ptr, _sz, _ptr, _i64, _i32, _i64, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "mdg_vo_intercept_ws_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "mdg_vo_intercept": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _ptr, _i64, _ptr, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _ptr,
+                                 _i32, _ptr, _i32, _ptr, _ptr, _ptr, _sz, _ptr]),
     "mdg_vo_output_error_ws_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
     "mdg_vo_output_error": (_i32, [_ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _i32, _i32, _ptr, _i64, _ptr, _i64, _i32,
                                     _ptr, _ptr, _ptr, _sz, _ptr]),

@@ -37,9 +37,11 @@ class LlamaAdapter(ModelAdapter):
         "f64", goes to the fp64 kernel in one launch (mdg_cov_accum_multi).  Nothing is copied; the parked tensors live until
         the end of the layer's forward.  With MODEGPT_MLP_INTERCEPT=1 calibration leaves one fp64 vector per target layer on
         self.mlp_sums, and the flush hands the sigma_mlp activation to ops.col_sum_accum as well (its column sums: the means of the
-        mean-aware refit); without the switch the list is None and nothing else is launched."""
+        mean-aware refit); without the switch the list is None and nothing else is launched.  MODEGPT_VO_INTERCEPT=1 does the same
+        for x on self.x_sums (the means of the mean-aware V/O truncation); the covariance launches are the same either way."""
         parked = {}
         sums = getattr(self, "mlp_sums", None)
+        x_sums = getattr(self, "x_sums", None)
 
         def park(kind):
             @torch.no_grad()
@@ -50,13 +52,17 @@ class LlamaAdapter(ModelAdapter):
         @torch.no_grad()
         def flush(module, input):
             items = [(cov_mlp_list[layer_idx], input[0], 1)]
+            x = None
             for kind, lst, heads in (("x", cov_x_list, 1), ("q", cov_q_list, self.n_heads), ("k", cov_k_list, self.n_kv_heads)):
                 t = parked.pop(kind, None)
                 if t is not None:
                     items.append((lst[layer_idx], t, heads))
+                    x = t if kind == "x" else x
             ops.cov_accum_multi(items)
             if sums is not None and sums[layer_idx] is not None:
                 ops.col_sum_accum(sums[layer_idx], input[0])
+            if x_sums is not None and x_sums[layer_idx] is not None and x is not None:
+                ops.col_sum_accum(x_sums[layer_idx], x)
             return None
 
         handles.append(block.input_layernorm.register_forward_hook(park("x")))
@@ -88,11 +94,14 @@ class LlamaAdapter(ModelAdapter):
         return hook
 
     @staticmethod
-    def _input_hook(layer_idx, cov_list):
-        """sigma_x += sum_b X_b^T X_b, X = input_layernorm's output (LlamaAdapter.py:138-147)."""
+    def _input_hook(layer_idx, cov_list, sum_list=None):
+        """sigma_x += sum_b X_b^T X_b, X = input_layernorm's output (LlamaAdapter.py:138-147).  sum_list (not upstream): one fp64
+        vector per layer -- the column sums of X are added to sum_list[layer_idx] as well (ops.col_sum_accum)."""
         @torch.no_grad()
         def hook(module, inp, out):
             ops.cov_accum(cov_list[layer_idx], out)
+            if sum_list is not None and sum_list[layer_idx] is not None:
+                ops.col_sum_accum(sum_list[layer_idx], out)
         return hook
 
     def compute_layer_energy(self, layer_idx: int, Ca: Optional[Tensor] = None) -> MLPTensors:

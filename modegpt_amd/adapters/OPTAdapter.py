@@ -42,13 +42,18 @@ class OPTAdapter(ModelAdapter):
             self._make_proj_hook(layer_idx, cov_k_list, self.n_heads, self.head_dim, self.d_model)))
         # the reference's on_batch_end_step (OPTAdapter.py:54-55) is never called; the statistic it meant is the
         # input of the attention block, i.e. self_attn_layer_norm's output
-        handles.append(block.self_attn_layer_norm.register_forward_hook(self._x_hook(layer_idx, cov_x_list)))
+        handles.append(block.self_attn_layer_norm.register_forward_hook(self._x_hook(layer_idx, cov_x_list,
+                                                                                      sum_list=getattr(self, "x_sums", None))))
 
     @staticmethod
-    def _x_hook(layer_idx, cov_x_list):
+    def _x_hook(layer_idx, cov_x_list, sum_list=None):
+        """sigma_x += X^T X.  sum_list (not upstream; MODEGPT_VO_INTERCEPT=1): one fp64 vector per layer -- the column sums of X are
+        added to sum_list[layer_idx] as well (ops.col_sum_accum)."""
         @torch.no_grad()
         def hook(module, inp, out):
             ops.cov_accum(cov_x_list[layer_idx], out)
+            if sum_list is not None and sum_list[layer_idx] is not None:
+                ops.col_sum_accum(sum_list[layer_idx], out)
         return hook
 
     def on_batch_end_step(self, layer_idx, x_in, cov_x_list):

@@ -194,10 +194,11 @@ class ModelAdapter(ABC):
         return report
 
     # ---- what the STORED v_proj / o_proj lose of the attention output (not upstream; MODEGPT_VO_ERROR=1) ----
-    def vo_error(self, layer_idx: int, tensors, rank: int) -> None:
+    def vo_error(self, layer_idx: int, tensors, rank: int, centred: bool = False) -> None:
         """compress_vo hands over (q, e, dnorm2, curve) -- ops.vo_output_error's [n_heads, d] tensors and
-        ops.vo_compress(want_curve=True)'s [n_kv, hd + 1], still on the device -- for layer `layer_idx`, truncated to `rank` per head."""
-        self._record("_vo_errors", int(layer_idx), (tuple(tensors), int(rank)))
+        ops.vo_compress(want_curve=True)'s [n_kv, hd + 1], still on the device -- for layer `layer_idx`, truncated to `rank` per head.
+        centred: they were taken on S = C - mu mu^T (MODEGPT_VO_INTERCEPT=1); the layer's entry then says "centred": true."""
+        self._record("_vo_errors", int(layer_idx), (tuple(tensors), int(rank), bool(centred)))
 
     def report_vo_errors(self, log=None) -> dict:
         """Reads the recorded tensors (24 n_heads d + 8 n_kv (hd + 1) bytes per layer; call it where the host waits for the chains
@@ -210,12 +211,14 @@ class ModelAdapter(ABC):
         pending = self._take("_vo_errors")
         report = {}
         for layer in sorted(pending):
-            tensors, rank = pending[layer]
+            tensors, rank, centred = pending[layer]
             host = tuple(t.detach().cpu() for t in tensors)
             self._record("vo_errors", layer, host)
             q, e, dnorm2, curve = host
             m = report[layer] = ops.decode_vo_output_error(e.tolist(), q.tolist(), dnorm2.tolist(), self.config.ridge_vo, rank,
                                                            curve.shape[0], curve=curve.tolist())
+            if centred:
+                m["centred"] = True                   # (the figures are the affine map's: the statistic was S = C - mu mu^T)
             if m["relative_error"] is None:
                 log.warning(f"[VO] Layer {layer}: output error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
                 continue
@@ -355,7 +358,8 @@ class ModelAdapter(ABC):
                       device: str = "cuda"):
         """Swap every layer's Linears for bf16 Linears built from the saved artefacts: bias-free (model_adapter.py:199-208), except
         where the artefact carries a bias (`<name>_bias`: the compressors write them with MODEGPT_KEEP_BIAS=1 and for Qwen2; down_bias
-        also with MODEGPT_MLP_INTERCEPT=1, the refit's intercept -- a key the reference's LlamaRebuild does not know)."""
+        also with MODEGPT_MLP_INTERCEPT=1, the refit's intercept, and o_bias with MODEGPT_VO_INTERCEPT=1, the truncation's -- keys the
+        reference's LlamaRebuild does not know)."""
         saved_layers_dir = os.path.expandvars(saved_layers_dir)
         self.flush_artifacts()
 
@@ -384,8 +388,19 @@ class ModelAdapter(ABC):
                     self.replace_attn_layers(i, new_q=linear_of(art["q_proj"], art.get("q_bias")),
                                              new_k=linear_of(art["k_proj"], art.get("k_bias")), new_v=None, new_o=None)
                 elif suffix == "vo":
+                    o_bias = art.get("o_bias")
+                    if ops.vo_intercept_enabled():
+                        # MODEGPT_VO_INTERCEPT=1: the truncated layers store an intercept as o_bias and no v_bias (the v bias is part
+                        # of the intercept); a layer whose artefact has no o_bias (outside the target layers, or written without the
+                        # switch) gets an exact zero, as down_bias above.  A v_bias cannot stand beside it: projection_biases() would
+                        # differ between the layers and the checkpoint would not load strictly
+                        if art.get("v_bias") is not None:
+                            raise RuntimeError(f"MODEGPT_VO_INTERCEPT=1 but the vo artefact of layer {i} carries a v_bias: it was written "
+                                               "without the switch (MODEGPT_KEEP_BIAS=1 / Qwen2); compress the layer again with the switch on")
+                        if o_bias is None:
+                            o_bias = torch.zeros(art["o_proj"].shape[0], dtype=torch.bfloat16, device=device)
                     self.replace_attn_layers(i, new_q=None, new_k=None, new_v=linear_of(art["v_proj"], art.get("v_bias")),
-                                             new_o=linear_of(art["o_proj"], art.get("o_bias")))
+                                             new_o=linear_of(art["o_proj"], o_bias))
 
     # ---- which projections of the converted model carry a bias (not upstream; patch_config records it) ----
     BIAS_SLOTS = ("up", "gate", "down", "q", "k", "v", "o")
@@ -425,6 +440,29 @@ class ModelAdapter(ABC):
                              "relative": off2 / mean2 if ok and mean2 > 0 else None}
             log.info(f"[MLP] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
         self._merge_metrics("mlp_intercept", report)
+        return report
+
+    # ---- the intercept of the mean-aware V/O truncation (not upstream; MODEGPT_VO_INTERCEPT=1) ----
+    def vo_intercept(self, layer_idx: int, norms) -> None:
+        """compress_vo hands over ops.vo_intercept's norms (2 numbers, still on the device) for layer `layer_idx`."""
+        self._record("_vo_intercepts", int(layer_idx), norms)
+
+    def report_vo_intercepts(self, log=None) -> dict:
+        """Reads the recorded pairs (16 bytes per layer; call it where the host waits for the chains anyway) and writes
+        metrics["vo_intercept"][str(layer)] = {"offset_norm2": ||delta||^2, "mean_output_norm2": ||sum_h W_o,h a_kv(h)||^2, "relative":
+        their ratio}: a_g = W_v,g mu + b_v,g, the second figure is the constant the uncompressed attention adds to its output, delta what
+        the stored o_bias adds to the projection's own bias -- the part of that constant the stored factors do not carry (DESIGN.md
+        section 7, "The V/O intercept").  Non-finite figures become None."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self._take("_vo_intercepts")
+        report = {}
+        for layer in sorted(pending):
+            off2, mean2 = (float(x) for x in pending[layer].cpu().tolist())
+            ok = math.isfinite(off2) and math.isfinite(mean2)
+            report[layer] = {"offset_norm2": off2 if ok else None, "mean_output_norm2": mean2 if ok else None,
+                             "relative": off2 / mean2 if ok and mean2 > 0 else None}
+            log.info(f"[VO] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
+        self._merge_metrics("vo_intercept", report)
         return report
 
     # ---- what the truncated v_proj cannot carry of a v bias where o_proj has no bias to fold it into (not upstream) ----

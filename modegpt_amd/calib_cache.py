@@ -12,6 +12,9 @@ One directory, one self-contained record per layer, so chunks of layers, target_
                                            entry files.mlp_mean holds the length, n and the bit pattern of its exact sum.  A run
                                            with the switch refuses a record without the entry (it never recalibrates); a run without
                                            ignores file and entry; records written without the switch are what they always were
+    layer_<i>_x_mean.f64                   only with MODEGPT_VO_INTERCEPT=1: d_model raw little-endian fp64, mu = E[x] of the sigma_x
+                                           activation under sigma_x's normaliser; the same format, sidecar entry (files.x_mean) and
+                                           rules as layer_<i>_mlp_mean.f64, under its own switch
     layer_<i>.json                         the sidecar, written LAST: the commit marker -- a layer without it does not exist
     bi_scores.json                         the Block-Influence scores of all layers, written by the rank that computed them
 
@@ -138,8 +141,11 @@ def read_data_file(directory: str, layer: int, kind: str, entry: dict, out: np.n
                          f"pattern {bits}, the sidecar recorded {entry['trace_bits']}")
 
 
-# ------------------------------------------------------------------ host half: the activation mean (MODEGPT_MLP_INTERCEPT=1)
+# ------------------------------------------------------------------ host half: the activation means (MODEGPT_MLP_INTERCEPT=1 / MODEGPT_VO_INTERCEPT=1)
 MEAN_KIND = "mlp_mean"
+X_MEAN_KIND = "x_mean"
+# per kind of mean: the switch that writes and demands it, and the arch field that is its length
+MEAN_KINDS = {MEAN_KIND: ("MODEGPT_MLP_INTERCEPT", "n_inner"), X_MEAN_KIND: ("MODEGPT_VO_INTERCEPT", "d_model")}
 
 
 def sum_bits(values: np.ndarray) -> int:
@@ -147,45 +153,45 @@ def sum_bits(values: np.ndarray) -> int:
     return struct.unpack("<q", struct.pack("<d", math.fsum(np.asarray(values, dtype=np.float64).ravel().tolist())))[0]
 
 
-def write_mean_file(directory: str, layer: int, values: np.ndarray, n: int) -> dict:
-    """layer_<i>_mlp_mean.f64 from the n means; returns the sidecar's entry for it."""
+def write_mean_file(directory: str, layer: int, values: np.ndarray, n: int, kind: str = MEAN_KIND) -> dict:
+    """layer_<i>_<kind>.f64 from the n means; returns the sidecar's entry for it."""
     values = np.ascontiguousarray(values, dtype="<f8").reshape(-1)
     if values.size != n:
-        raise ValueError(f"layer {layer}: the activation mean has {values.size} entries, n_inner is {n}")
-    path = data_path(directory, layer, MEAN_KIND)
+        raise ValueError(f"layer {layer}: the activation mean has {values.size} entries, {MEAN_KINDS[kind][1]} is {n}")
+    path = data_path(directory, layer, kind)
     _replace_into(path, values.tofile)
     return {"file": os.path.basename(path), "layout": "vector", "n": int(n), "bytes": int(n * 8), "sum_bits": sum_bits(values)}
 
 
-def validate_mean_entry(meta: dict, n: int, layer: int) -> dict:
-    """Metadata alone: the record must carry files.mlp_mean for n means.  Returns the entry."""
-    entry = meta.get("files", {}).get(MEAN_KIND)
+def validate_mean_entry(meta: dict, n: int, layer: int, kind: str = MEAN_KIND) -> dict:
+    """Metadata alone: the record must carry files.<kind> for n means.  Returns the entry."""
+    entry = meta.get("files", {}).get(kind)
     if not isinstance(entry, dict):
-        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND} is missing -- the record was saved without "
-                         "MODEGPT_MLP_INTERCEPT=1 and this run has the switch on; save the statistics again with it (nothing is "
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{kind} is missing -- the record was saved without "
+                         f"{MEAN_KINDS[kind][0]}=1 and this run has the switch on; save the statistics again with it (nothing is "
                          "recalibrated on load)")
     want = {"n": int(n), "bytes": 8 * int(n), "layout": "vector"}
     for name, value in want.items():
         if entry.get(name) != value:
-            _refuse(layer, f"files.{MEAN_KIND}.{name}", entry.get(name), value)
+            _refuse(layer, f"files.{kind}.{name}", entry.get(name), value)
     if not isinstance(entry.get("sum_bits"), int) or not isinstance(entry.get("file"), str):
-        _refuse(layer, f"files.{MEAN_KIND}.sum_bits", entry.get("sum_bits"), "an integer")
+        _refuse(layer, f"files.{kind}.sum_bits", entry.get("sum_bits"), "an integer")
     return entry
 
 
-def read_mean_file(directory: str, layer: int, entry: dict) -> np.ndarray:
+def read_mean_file(directory: str, layer: int, entry: dict, kind: str = MEAN_KIND) -> np.ndarray:
     """The n means of the file, checked against the length and the exact sum the sidecar holds."""
     path = os.path.join(directory, entry["file"])
     if not os.path.exists(path):
-        raise FileNotFoundError(f"calibration statistics, layer {layer}: data file {path} (field files.{MEAN_KIND}.file) is missing")
+        raise FileNotFoundError(f"calibration statistics, layer {layer}: data file {path} (field files.{kind}.file) is missing")
     size = os.path.getsize(path)
     if size != entry["bytes"]:
-        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND}.bytes -- {path} holds {size} bytes, the "
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{kind}.bytes -- {path} holds {size} bytes, the "
                          f"sidecar says {entry['bytes']}")
     values = np.fromfile(path, dtype="<f8").astype(np.float64)
     bits = sum_bits(values)
     if bits != entry["sum_bits"]:
-        raise ValueError(f"calibration statistics, layer {layer}: field files.{MEAN_KIND}.sum_bits -- the sum of {path} has the bit "
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{kind}.sum_bits -- the sum of {path} has the bit "
                          f"pattern {bits}, the sidecar recorded {entry['sum_bits']}")
     return values
 
@@ -399,10 +405,11 @@ def _staging_for(arch: dict, device) -> Staging:
 
 
 def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arch: dict, calibration: dict, model: str,
-                weights: dict, certificates: dict, mean=None) -> dict:
+                weights: dict, certificates: dict, mean=None, x_mean=None) -> dict:
     """One layer's record from its four device tensors ({"mlp", "x": [n, n]; "q", "k": [heads, hd, hd]}): data files first, the
     sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  mean: the layer's
-    activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too."""
+    activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too; x_mean: the
+    mean of x (fp64 [d_model], MODEGPT_VO_INTERCEPT=1) -- likewise, files.x_mean."""
     import torch
     from . import ops
     os.makedirs(directory, exist_ok=True)
@@ -428,21 +435,26 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
     finish(waiting)
     if mean is not None:
         files[MEAN_KIND] = write_mean_file(directory, layer, mean.detach().cpu().numpy(), arch["n_inner"])
+    if x_mean is not None:
+        files[X_MEAN_KIND] = write_mean_file(directory, layer, x_mean.detach().cpu().numpy(), arch["d_model"], kind=X_MEAN_KIND)
     meta = make_sidecar(layer, arch, calibration, model, weights, files, certificates)
     write_sidecar(directory, meta)
     return meta
 
 
-def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None) -> dict:
+def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None, x_mean=None) -> dict:
     """The inverse: checks the sidecar against `expect`, fills the four device tensors, returns the sidecar.  The file of a
     statistic is read while the one before it is copied to the device and unpacked.  mean: an fp64 [n_inner] device tensor to fill
-    from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1); a record without the entry is refused before any data is read."""
+    from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1), x_mean: an fp64 [d_model] one to fill from layer_<i>_x_mean.f64
+    (MODEGPT_VO_INTERCEPT=1); a record without the entry is refused before any data is read."""
     import torch
     from . import ops
     meta = read_sidecar(directory, layer)
     validate_sidecar(meta, expect, layer)
     if mean is not None:
         mean_entry = validate_mean_entry(meta, expect["arch"]["n_inner"], layer)
+    if x_mean is not None:
+        x_mean_entry = validate_mean_entry(meta, expect["arch"]["d_model"], layer, kind=X_MEAN_KIND)
     for kind in KINDS:
         t = tensors[kind]
         entry = meta["files"][kind]
@@ -458,6 +470,8 @@ def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expe
             staging.mark(slot)
     if mean is not None:
         mean.copy_(torch.from_numpy(read_mean_file(directory, layer, mean_entry)))
+    if x_mean is not None:
+        x_mean.copy_(torch.from_numpy(read_mean_file(directory, layer, x_mean_entry, kind=X_MEAN_KIND)))
     return meta
 
 
@@ -490,13 +504,17 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
     means = getattr(adapter, "mlp_means", None) if ops.mlp_intercept_enabled() else None      # (switch off: today's record, bit for bit)
     if ops.mlp_intercept_enabled() and targets and (means is None or any(means[i] is None for i in targets)):
         raise RuntimeError("MODEGPT_MLP_INTERCEPT=1 but the adapter carries no activation means (adapter.mlp_means) to save")
+    x_means = getattr(adapter, "x_means", None) if ops.vo_intercept_enabled() else None         # (likewise)
+    if ops.vo_intercept_enabled() and targets and (x_means is None or any(x_means[i] is None for i in targets)):
+        raise RuntimeError("MODEGPT_VO_INTERCEPT=1 but the adapter carries no input means (adapter.x_means) to save")
     if targets:
         staging = _staging_for(arch, cov["mlp"][targets[0]].device)
         for i in targets:
             cal = calibration if loaded is None else loaded[i]["calibration"]
             cert = certificates if loaded is None else loaded[i]["certificates"]
             meta = write_layer(directory, i, {k: cov[k][i] for k in KINDS}, staging, arch, cal, model,
-                               weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i])
+                               weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i],
+                               x_mean=None if x_means is None else x_means[i])
             nbytes += sum(e["bytes"] for e in meta["files"].values())
         torch.cuda.synchronize(staging.device)
     if bi_scores is not None and getattr(adapter, "calib_want_bi", True):
@@ -524,12 +542,14 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
     sig = SigmaBuffers(adapter, targets)
     metas: Dict[int, dict] = {}
     adapter.mlp_means = sig.mlp_sums           # (MODEGPT_MLP_INTERCEPT=1: filled below from the mean files; None without the switch)
+    adapter.x_means = sig.x_sums               # (MODEGPT_VO_INTERCEPT=1: likewise)
     if targets:
         staging = _staging_for(expect["arch"], sig.lists["mlp"][targets[0]].device)
         for i in targets:
             metas[i] = read_layer(directory, i, {k: sig.lists[k][i] for k in KINDS}, staging,
                                   dict(expect, weights=weight_fingerprint(adapter, i)),
-                                  mean=None if sig.mlp_sums is None else sig.mlp_sums[i])
+                                  mean=None if sig.mlp_sums is None else sig.mlp_sums[i],
+                                  x_mean=None if sig.x_sums is None else sig.x_sums[i])
         torch.cuda.synchronize(staging.device)
     adapter.bi_scores = bi_scores
     cert = merge_certificates([m["certificates"] for m in metas.values()])

@@ -51,6 +51,12 @@ class SigmaBuffers:
             self.mlp_sums = [None] * L
             for i in self.layers:
                 self.mlp_sums[i] = torch.zeros(f, dtype=dtype_p, device=device)
+        # ... and of x, the post-norm hidden state (MODEGPT_VO_INTERCEPT=1: the means of the mean-aware V/O truncation); None without it
+        self.x_sums: Optional[List[Optional[torch.Tensor]]] = None
+        if ops.vo_intercept_enabled():
+            self.x_sums = [None] * L
+            for i in self.layers:
+                self.x_sums[i] = torch.zeros(d, dtype=dtype_p, device=device)
 
     def finalize(self, n_texts: int) -> None:
         """sigma <- sigma / (n_texts * 2048), lower triangle mirrored into the upper (src/calibration.py:141-146)."""
@@ -60,6 +66,8 @@ class SigmaBuffers:
                 ops.cov_finalize(self.lists[kind][i], scale)
             if self.mlp_sums is not None:
                 self.mlp_sums[i].mul_(scale)                 # mu = E[h] under the normaliser sigma_mlp gets: one rounding per entry
+            if self.x_sums is not None:
+                self.x_sums[i].mul_(scale)                   # mu = E[x] under sigma_x's normaliser, likewise
 
 
 class BlockInfluence:
@@ -130,6 +138,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     blocks = adapter.get_transformer_blocks()
     handles: list = []
     adapter.mlp_sums = sig.mlp_sums                      # (read by register_hooks; None without MODEGPT_MLP_INTERCEPT=1)
+    adapter.x_sums = sig.x_sums                          # (likewise; None without MODEGPT_VO_INTERCEPT=1)
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -167,6 +176,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     sig.finalize(n_texts)
     adapter.mlp_sums = None
     adapter.mlp_means = sig.mlp_sums                     # per target layer mu = E[h] (None without the switch): compress_nystrom reads it
+    adapter.x_sums = None
+    adapter.x_means = sig.x_sums                         # per target layer mu = E[x] (None without the switch): compress_vo reads it
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

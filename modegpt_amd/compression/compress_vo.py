@@ -93,7 +93,12 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
     """compress_vo.py:13-109.  Grouped (GQA) and two-SVD (MHA) variants are chosen by n_kv_heads != n_heads, as
     upstream; both run inside mdg_vo_compress on the head-sized Gram matrix.  Saves {"v_proj": [n_kv*r, d],
     "o_proj": [d, n_heads*r]} bf16 -- and, with the biases carried (ops.keep_bias_enabled), "o_bias" [d] (b_o + sum_h W_o,h b_v,kv(h):
-    v_proj becomes bias-free) or, where o_proj has no bias, "v_bias" [n_kv*r] (P_g b_v,g), in the bias's own dtype."""
+    v_proj becomes bias-free) or, where o_proj has no bias, "v_bias" [n_kv*r] (P_g b_v,g), in the bias's own dtype.
+    With MODEGPT_VO_INTERCEPT=1 (not upstream; DESIGN.md section 7, "The V/O intercept") the truncation is taken on the centred
+    statistic S = C - mu mu^T, mu = adapter.x_means[layer], and "o_bias" [d] = b_o + delta is saved for every layer (ops.vo_intercept
+    on the stored bf16 factors; b_v / b_o enter only where the biases are carried) and no "v_bias".  The spectrum report's Weyl bound
+    still reads the diagonal of the UNCENTRED C: |E_ab| <= eps sqrt(c_aa c_bb) bounds the error of S as well, up to the fp64
+    rounding of mu, so the bound stays a bound; the output-error report and the rank curve are evaluated on S."""
     if target_layers is None:
         target_layers = list(range(adapter.n_layers))
     n_heads, head_dim, arch, n_kv = adapter.n_heads, adapter.head_dim, adapter.arch, adapter.n_kv_heads
@@ -121,10 +126,30 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
             b_v, b_o = getattr(comps.v_proj, "bias", None), getattr(comps.o_proj, "bias", None)
             b_v = None if b_v is None else b_v.detach().to(local_device())
             b_o = None if b_o is None else b_o.detach().to(local_device())
+        # the mean-aware truncation (MODEGPT_VO_INTERCEPT=1; DESIGN.md section 7, "The V/O intercept"): the statistic is centred, the
+        # factorisation runs on S unchanged (the ridge acts on S), and the mean -- v bias included -- goes into o_bias for exactly the
+        # bf16 tensors that are stored.  The spectrum's Weyl bound keeps reading the diagonal of the uncentred C (ops.vo_compress)
+        mu, more = None, {"bias": None if b_v is None else (b_v, b_o)}
+        if ops.vo_intercept_enabled():
+            means = getattr(adapter, "x_means", None)
+            if means is None or means[layer] is None:
+                raise RuntimeError(f"MODEGPT_VO_INTERCEPT=1 but layer {layer} has no input mean (adapter.x_means): "
+                                   "the statistics were collected without the switch")
+            mu = means[layer].to(device=local_device(), dtype=dtype_p)
+            more = {"spectrum_cov": C}
+            C = ops.cov_center(C, mu)                            # S: from here on the statistic of x - mu (cov[layer] is not modified)
         out = ops.vo_compress(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, adapter.config.ridge_vo, want_spectrum=record is not None,
-                              spectrum_eps=eps, want_curve=record_error is not None, bias=None if b_v is None else (b_v, b_o))
+                              spectrum_eps=eps, want_curve=record_error is not None, **more)
         biases = {}
-        if b_v is not None:
+        if mu is not None:
+            # b_o + delta, in o_proj's bias dtype where it has one (and biases are carried), else the weight's; no v_bias: the v bias
+            # is part of a_g and folded exactly at every rank, so mdg_vo_bias is not called and nothing is left for vo_bias_residual
+            o_bias, _, norms = ops.vo_intercept(Wv_d, Wo_d, out[0], out[1], mu, n_heads, n_kv, head_dim, rank_i, b_v=b_v, b_o=b_o)
+            biases["o_bias"] = o_bias
+            record_intercept = getattr(adapter, "vo_intercept", None)
+            if callable(record_intercept):
+                record_intercept(layer, norms)                   # stays on the device until report_vo_intercepts
+        elif b_v is not None:
             (o_bias, v_bias, resid), out = out[-1], out[:-1]
             if o_bias is not None:
                 biases["o_bias"] = o_bias.to(b_o.dtype)          # (one rounding of the fp64 sum)
@@ -143,7 +168,8 @@ def compress_vo(adapter: ModelAdapter, cov: List[Tensor], keep_ratios=None, slic
             # only, read by report_vo_errors
             q = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, 0, None, None)
             e, dnorm2 = ops.vo_output_error(C, Wv_d, Wo_d, n_heads, n_kv, head_dim, rank_i, V_heads, O_heads, want_dnorm2=True)
-            record_error(layer, (q, e, dnorm2, out[-1]), rank_i)
+            # (with the intercept C is S here: report and curve are the affine map's, and sum(e + rho dnorm2) = curve[r] holds on S)
+            record_error(layer, (q, e, dnorm2, out[-1]), rank_i, **({"centred": True} if mu is not None else {}))
         return V_heads, O_heads, biases
 
     def retire(layer, result):

@@ -69,6 +69,8 @@ def new_covs(shape: dict, device) -> Dict[str, torch.Tensor]:
     covs = {"mlp": z(f, f), "x": z(d, d), "q": z(nh, hd, hd), "k": z(nkv, hd, hd)}
     if ops.mlp_intercept_enabled():
         covs["mlp_sum"] = z(f)
+    if ops.vo_intercept_enabled():
+        covs["x_sum"] = z(d)
     return covs
 
 
@@ -78,6 +80,8 @@ def accumulate(covs: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], sh
     mode: None = ops.COV_MODE; "i8" routes sigma_mlp and sigma_x through the int8 digit-plane kernel."""
     if covs.get("mlp_sum") is not None:           # (new_covs with MODEGPT_MLP_INTERCEPT=1: the column sums of the sigma_mlp activation)
         ops.col_sum_accum(covs["mlp_sum"], batch["h"], relu=shape["arch"] == "opt")
+    if covs.get("x_sum") is not None:             # (... with MODEGPT_VO_INTERCEPT=1: the column sums of x)
+        ops.col_sum_accum(covs["x_sum"], batch["x"])
     if shape["arch"] == "opt":
         ops.cov_accum_fc_relu(covs["mlp"], batch["h"], mode=mode)
         ops.cov_accum_multi([(covs["x"], batch["x"], 1), (covs["q"], batch["q"], shape["n_heads"]),
@@ -89,7 +93,7 @@ def accumulate(covs: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], sh
 
 def finalize(covs: Dict[str, torch.Tensor], n_texts: int) -> None:
     for kind, c in covs.items():
-        if kind == "mlp_sum":
+        if kind in ("mlp_sum", "x_sum"):
             c.mul_(1.0 / (n_texts * 2048))
         else:
             ops.cov_finalize(c, 1.0 / (n_texts * 2048))
@@ -207,6 +211,7 @@ def compress_layer(adapter: TensorAdapter, layer_idx: int, covs: Dict[str, torch
     lst = lambda t: [t if i == layer_idx else None for i in range(n)]  # noqa: E731
     keep = [keep_ratio] * n
     adapter.mlp_means = lst(covs["mlp_sum"]) if covs.get("mlp_sum") is not None else None
+    adapter.x_means = lst(covs["x_sum"]) if covs.get("x_sum") is not None else None
     # VO (one GEMM, a batched 128 x 128 eigensolve on 8 workgroups, skinny products: 8 ms of mostly latency) needs sigma_x only and
     # runs on a stream of its own beside the MLP chain, whose Cholesky steps leave most of the chip idle between their GEMMs
     dev = covs["x"].device

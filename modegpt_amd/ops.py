@@ -19,7 +19,8 @@ from ._lib import check
 from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_MARGIN_FIELDS, RANK_CURVE_KEEP,  # noqa: F401
                       RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
                       decode_qk_margin, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
-                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, rank_curve_enabled, vo_error_enabled)
+                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, rank_curve_enabled, vo_error_enabled,
+                      vo_intercept_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
        torch.float64: _lib.MDG_F64}
@@ -1055,10 +1056,65 @@ def vo_bias(ws: torch.Tensor, W_o: torch.Tensor, b_v: torch.Tensor, b_o: Optiona
     return o_bias, v_bias, resid
 
 
+def vo_intercept(W_v: torch.Tensor, W_o: torch.Tensor, v_new: Optional[torch.Tensor], o_new: Optional[torch.Tensor], mu: torch.Tensor,
+                 n_heads: int, n_kv: int, hd: int, rank: int, b_v: Optional[torch.Tensor] = None, b_o: Optional[torch.Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None):
+    """The intercept of the mean-aware V/O truncation (mdg_vo_intercept): delta = sum_h (W_o,h a_kv(h) - o^_h a'_kv(h)) in fp64 with
+    exact products, a_g = W_v,g mu + b_v,g, a'_g = v^_g mu.  W_v [n_kv*hd, d] / W_o [d, n_heads*hd] as vo_compress takes them, v_new
+    [n_kv*rank, d] / o_new [d, n_heads*rank] the stored bf16 tensors vo_compress RETURNED or its v_f64 / o_f64 (row-strided views are
+    taken as they are; any other dtype is widened exactly to fp64); mu fp64 [d]; rank 0 (or v_new None): nothing is subtracted.
+    Returns (bias, bias_f64, norms): bias_f64 [d] = b_o + delta (b_o None: 0), bias = its one rounding to out_dtype (default: b_o's
+    dtype, else the dtype of W_o), norms [2] = (||delta||^2, ||sum_h W_o,h a_kv(h)||^2), fp64 ON THE DEVICE.  The call only enqueues."""
+    _need_gpu(W_v, W_o, v_new, o_new, mu, b_v, b_o)
+    lib = _lib.load()
+    if out_dtype is None:
+        out_dtype = b_o.dtype if b_o is not None else W_o.dtype
+    Wv, Wo = _as_weight(W_v), _as_weight(W_o)
+    if Wv.dtype != Wo.dtype:
+        Wv, Wo = Wv.to(torch.float64), Wo.to(torch.float64)
+    d = Wv.shape[1]
+    if Wv.dim() != 2 or Wo.dim() != 2 or tuple(Wv.shape) != (n_kv * hd, d) or tuple(Wo.shape) != (d, n_heads * hd):
+        raise ValueError(f"vo_intercept: W_v must be [{n_kv * hd}, d] and W_o [d, {n_heads * hd}], got {tuple(Wv.shape)} and {tuple(Wo.shape)}")
+    if mu.dtype != torch.float64 or mu.numel() != d:
+        raise ValueError(f"vo_intercept: mu must be a float64 vector of {d} entries")
+    r = 0 if (v_new is None or o_new is None) else int(rank)
+    vn = on = None
+    if r:
+        if tuple(v_new.shape) != (n_kv * r, d) or tuple(o_new.shape) != (d, n_heads * r):
+            raise ValueError(f"vo_intercept: v_new must be [{n_kv * r}, {d}] and o_new [{d}, {n_heads * r}], got "
+                             f"{tuple(v_new.shape)} and {tuple(o_new.shape)}")
+        vn, on = _as_weight(v_new), _as_weight(o_new)
+        if vn.dtype != on.dtype:
+            vn, on = vn.to(torch.float64), on.to(torch.float64)
+    bv = None if b_v is None else b_v.detach().contiguous()
+    bo = None if b_o is None else b_o.detach().contiguous()
+    if bv is not None and bo is not None and bv.dtype != bo.dtype:        # (one b_dtype for both: widen exactly)
+        bv, bo = bv.to(torch.float64), bo.to(torch.float64)
+    bdt = bv.dtype if bv is not None else (bo.dtype if bo is not None else torch.float64)
+    if out_dtype not in _DT or bdt not in _DT or (bv is not None and bv.numel() != n_kv * hd) or (bo is not None and bo.numel() != d):
+        raise ValueError(f"vo_intercept: unsupported bias dtype, or b_v does not hold {n_kv * hd} entries / b_o {d}")
+    mu = mu.contiguous()
+    dev = Wv.device
+    bias = torch.empty(d, dtype=out_dtype, device=dev)
+    bias_f64 = torch.empty(d, dtype=torch.float64, device=dev)
+    norms = torch.empty(2, dtype=torch.float64, device=dev)
+    nbytes = lib.mdg_vo_intercept_ws_bytes(d, n_kv, hd, r)
+    ws, wsp = _ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        check(lib.mdg_vo_intercept(Wv.data_ptr(), Wv.stride(0), Wo.data_ptr(), Wo.stride(0), _DT[Wv.dtype], _p(vn),
+                                   vn.stride(0) if r else 0, _p(on), on.stride(0) if r else 0, _DT[vn.dtype] if r else _lib.MDG_BF16, d,
+                                   n_heads, n_kv, hd, r, mu.data_ptr(), _p(bv), _p(bo), _DT[bdt], bias.data_ptr(), _DT[out_dtype],
+                                   bias_f64.data_ptr(), norms.data_ptr(), wsp, nbytes, _stream(Wv)), "mdg_vo_intercept")
+    return bias, bias_f64, norms
+
+
 def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_heads: int, n_kv: int, hd: int, rank: int,
                 ridge: float, want_f64: bool = False, want_spectrum: bool = False, spectrum_eps: Optional[float] = None,
-                want_curve: bool = False, bias=None):
+                want_curve: bool = False, bias=None, spectrum_cov: Optional[torch.Tensor] = None):
     """Returns (v_proj [n_kv*rank, d] bf16, o_proj [d, n_heads*rank] bf16[, v_f64, o_f64][, spectrum][, curve][, bias]).
+    spectrum_cov: the statistic whose DIAGONAL mdg_vo_spectrum's Weyl bound reads (default: cov_x).  The mean-aware truncation passes
+    the centred S = C - mu mu^T as cov_x and the uncentred C here: S was computed from C, so an entry-wise relative error eps of C
+    leaves |E_ab| <= eps sqrt(c_aa c_bb) in S as well (up to the fp64 rounding of mu), and c_aa >= s_aa -- the bound stays a bound.
     bias: (b_v, b_o or None) -- vo_bias's (o_bias, v_bias, resid) for this truncation comes last in the tuple, enqueued behind
     everything else while the workspace is alive; the factors are the same bits with or without it.
     want_curve: what the truncation costs the attention output at every rank (mdg_vo_rank_curve: [n_kv, hd + 1] fp64 ON THE DEVICE;
@@ -1088,7 +1144,12 @@ def vo_compress(cov_x: torch.Tensor, W_v: torch.Tensor, W_o: torch.Tensor, n_hea
                                   v_out.stride(0), o_out.data_ptr(), o_out.stride(0), _p(v64), _p(o64), wsp, nbytes,
                                   _stream(Cx)), "mdg_vo_compress")
         if want_spectrum:
-            check(lib.mdg_vo_spectrum(wsp, nbytes, Cx.data_ptr(), d, Cx.stride(0), Wv.data_ptr(), Wv.stride(0), _DT[Wv.dtype],
+            Cd = Cx
+            if spectrum_cov is not None:
+                Cd = spectrum_cov
+                if Cd.dtype != torch.float64 or Cd.dim() != 2 or Cd.stride(1) != 1 or tuple(Cd.shape) != (d, d) or Cd.device != dev:
+                    raise ValueError(f"vo_compress: spectrum_cov must be a float64 [{d}, {d}] matrix with unit column stride beside cov_x")
+            check(lib.mdg_vo_spectrum(wsp, nbytes, Cd.data_ptr(), d, Cd.stride(0), Wv.data_ptr(), Wv.stride(0), _DT[Wv.dtype],
                                       n_heads, n_kv, hd, rank, float(ridge), float(spectrum_eps or 0.0), spectrum.data_ptr(),
                                       _stream(Cx)), "mdg_vo_spectrum")
         if want_curve:

@@ -25,6 +25,13 @@ def mlp_intercept_enabled() -> bool:
     return _switch("MODEGPT_MLP_INTERCEPT")
 
 
+# The mean-aware V/O truncation ("The V/O intercept").  Opt-in: MODEGPT_VO_INTERCEPT=1 makes calibration collect the
+# column sums of x (the post-norm hidden state) and compress_vo truncate on the centred statistic and store an intercept as o_bias.
+def vo_intercept_enabled() -> bool:
+    """MODEGPT_VO_INTERCEPT as it stands when calibration or a compressor asks (per layer; not frozen at import)."""
+    return _switch("MODEGPT_VO_INTERCEPT")
+
+
 # The Nystrom refit's error at every rank (mdg_nystrom_rank_curve).  Opt-in: MODEGPT_RANK_CURVE=1 makes compress_nystrom compute
 # it for every layer (one more factorisation of sigma_mlp and a triangular product per layer; DESIGN.md section 7, "The error-versus-rank curve").
 def rank_curve_enabled() -> bool:

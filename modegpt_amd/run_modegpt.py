@@ -125,6 +125,9 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
     report = getattr(adapter, "report_mlp_intercepts", None)
     if report is not None:
         report(logger)                          # ... what the refit's intercepts carry (MODEGPT_MLP_INTERCEPT=1) -> metrics["mlp_intercept"]
+    report = getattr(adapter, "report_vo_intercepts", None)
+    if report is not None:
+        report(logger)                          # ... what the V/O truncation's intercepts carry (MODEGPT_VO_INTERCEPT=1) -> metrics["vo_intercept"]
     report = getattr(adapter, "report_vo_errors", None)
     if report is not None:
         report(logger)                          # ... what the stored v_proj / o_proj lose (MODEGPT_VO_ERROR=1) -> metrics["vo_output_error"]
