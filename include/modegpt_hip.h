@@ -52,7 +52,8 @@ extern "C" {
                                 added under 10: mdg_vo_bias (the v_proj / o_proj biases through the V/O truncation);
                                 added under 10: mdg_col_sum_ws_bytes, mdg_col_sum_accum, mdg_cov_center, mdg_nystrom_intercept_ws_bytes,
                                 mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept);
-                                added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation) */
+                                added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation);
+                                added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -791,6 +792,25 @@ int mdg_rope_gather(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T
 int mdg_rope_gather_plan(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int n_kv, int r, int hd,
                          const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
                          const void* norm_w, double eps, void* out, void* stream, int64_t* plan);
+
+/* ------------------------------------------------------------------ post-RoPE rows for the calibration statistics
+ * Rotary embedding of a projection output in its own layout: the rows q', k' the model's attention really multiplies
+ * (apply_rotary_pos_emb), for sigma_q' / sigma_k'.  Stands for the post-RoPE hook variant the reference carries but disabled:
+ * src/adapters/LlamaAdapter.py:46-69 (patched_attn_forward) and 305-325 (_attn_hook).  Additive entry, ABI version unchanged.
+ *   x    [B*T, n_heads*hd] rows of pitch ld_x elements, last dimension contiguous, dtype bf16 / f16 / f32
+ *   cos, sin  [Bc, T, hd] same dtype, FULL width (the two halves need not be equal); cs_batch_stride elements between batches,
+ *        0 = one table shared by every batch
+ *   out  [B*T, n_heads*hd] rows of pitch ld_out elements, same dtype; elements of a row beyond n_heads*hd are not written
+ *   out[t, h, c] = dt( dt(x[t, h, c] * cos[t, c]) + dt(r[t, h, c] * sin[t, c]) ),  r[c] = -x[c + hd/2] for c < hd/2, x[c - hd/2] otherwise
+ * Every product and the sum are formed in fp32 and rounded to the element dtype one op at a time, without FMA contraction, as
+ * torch's eager expression does: the result is bit-identical to it.  Each element of x is read once and each element of out
+ * written once; 16-byte loads and stores when x, out, cos, sin are 16-byte aligned, ld_x, ld_out and cs_batch_stride are
+ * multiples of 16 bytes of elements and hd/2 is one too, element-wise otherwise.  No atomics, no dependence on launch order.
+ * MDG_ERR_BAD_ARG (with a message, before any device work): unknown dtype, negative extent, n_heads <= 0, hd odd, < 2 or > 256,
+ * ld_x or ld_out < n_heads*hd, a batch stride in (0, T*hd), a NULL operand of a non-empty call, and an out whose byte range
+ * (pitch included) intersects that of x -- the model still needs x.  B == 0 or T == 0 launches nothing. */
+int mdg_rope_rows(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int hd, const void* cos,
+                  const void* sin, int64_t cs_batch_stride, void* out, int64_t ld_out, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

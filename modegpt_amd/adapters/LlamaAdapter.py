@@ -1,6 +1,6 @@
 """Llama adapter (reference: src/adapters/LlamaAdapter.py).  Hook sites as the reference registers them
 (LlamaAdapter.py:71-100): pre-hook on mlp.down_proj, forward hooks on input_layernorm, q_proj, k_proj
-(pre-RoPE statistics; the post-RoPE variant is disabled upstream)."""
+(pre-RoPE statistics; the post-RoPE variant is disabled upstream and opt-in here: MODEGPT_QK_ROPE=1)."""
 from __future__ import annotations
 
 import copy
@@ -38,10 +38,18 @@ class LlamaAdapter(ModelAdapter):
         the end of the layer's forward.  With MODEGPT_MLP_INTERCEPT=1 calibration leaves one fp64 vector per target layer on
         self.mlp_sums, and the flush hands the sigma_mlp activation to ops.col_sum_accum as well (its column sums: the means of the
         mean-aware refit); without the switch the list is None and nothing else is launched.  MODEGPT_VO_INTERCEPT=1 does the same
-        for x on self.x_sums (the means of the mean-aware V/O truncation); the covariance launches are the same either way."""
+        for x on self.x_sums (the means of the mean-aware V/O truncation); the covariance launches are the same either way.
+        With MODEGPT_QK_ROPE=1 (Llama, Qwen2) calibration leaves the (sigma_q', sigma_k') lists on self.qk_rope_sums: a forward
+        pre-hook on self_attn parks the rotary tables the module is called with, and after the launches above the flush rotates the
+        parked q and k (ops.rope_rows) and accumulates their per-head Grams in one separate ops.cov_accum_multi call (the reference's
+        disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); the launches above are the same either way."""
         parked = {}
         sums = getattr(self, "mlp_sums", None)
         x_sums = getattr(self, "x_sums", None)
+        rope = getattr(self, "qk_rope_sums", None)       # (sigma_q', sigma_k') lists with MODEGPT_QK_ROPE=1 on a rotary model, else None
+        if rope is not None and rope[0][layer_idx] is None:
+            rope = None
+        head_dim = self.head_dim
 
         def park(kind):
             @torch.no_grad()
@@ -49,22 +57,48 @@ class LlamaAdapter(ModelAdapter):
                 parked[kind] = out
             return hook
 
+        def park_position_embeddings(module, args, kwargs):
+            """The (cos, sin) the attention module is about to rotate q and k with: [1 or B, T, head_dim] in the model dtype."""
+            pe = kwargs.get("position_embeddings")
+            if not isinstance(pe, (tuple, list)) or len(pe) != 2:
+                raise RuntimeError(f"MODEGPT_QK_ROPE=1: layer {layer_idx}'s attention module was called without the keyword argument "
+                                   "position_embeddings = (cos, sin); the post-RoPE statistics need the tables the model rotates with")
+            cos, sin = pe
+            if cos.shape[-1] != head_dim or sin.shape[-1] != head_dim:
+                raise RuntimeError(f"MODEGPT_QK_ROPE=1: layer {layer_idx}'s rotary tables are {cos.shape[-1]} wide, head_dim is "
+                                   f"{head_dim} (partial rotary embeddings are not supported)")
+            parked["pos"] = (cos, sin)
+            return None
+
         @torch.no_grad()
         def flush(module, input):
             items = [(cov_mlp_list[layer_idx], input[0], 1)]
-            x = None
+            got = {}
             for kind, lst, heads in (("x", cov_x_list, 1), ("q", cov_q_list, self.n_heads), ("k", cov_k_list, self.n_kv_heads)):
                 t = parked.pop(kind, None)
                 if t is not None:
                     items.append((lst[layer_idx], t, heads))
-                    x = t if kind == "x" else x
+                    got[kind] = t
+            x = got.get("x")
             ops.cov_accum_multi(items)
             if sums is not None and sums[layer_idx] is not None:
                 ops.col_sum_accum(sums[layer_idx], input[0])
             if x_sums is not None and x_sums[layer_idx] is not None and x is not None:
                 ops.col_sum_accum(x_sums[layer_idx], x)
+            pos = parked.pop("pos", None)
+            if rope is not None and "q" in got and "k" in got:
+                if pos is None:
+                    raise RuntimeError(f"MODEGPT_QK_ROPE=1: layer {layer_idx} reached its MLP without rotary tables parked")
+                # q', k' as the model computes them, into two scratch buffers reused across layers and batches, then ONE launch of
+                # their own: beside no plane the two per-head statistics take the fp64 kernel, and the layer's plan above is untouched
+                q, k = (t if t.dim() == 3 else t.reshape(-1, t.shape[-2], t.shape[-1]) for t in (got["q"], got["k"]))
+                rq = ops.rope_rows(q, pos[0], pos[1], self.n_heads, head_dim, out=ops.rope_scratch(q, "q"))
+                rk = ops.rope_rows(k, pos[0], pos[1], self.n_kv_heads, head_dim, out=ops.rope_scratch(k, "k"))
+                ops.cov_accum_multi([(rope[0][layer_idx], rq, self.n_heads), (rope[1][layer_idx], rk, self.n_kv_heads)])
             return None
 
+        if rope is not None:
+            handles.append(block.self_attn.register_forward_pre_hook(park_position_embeddings, with_kwargs=True))
         handles.append(block.input_layernorm.register_forward_hook(park("x")))
         handles.append(block.self_attn.k_proj.register_forward_hook(park("k")))
         handles.append(block.self_attn.q_proj.register_forward_hook(park("q")))

@@ -264,7 +264,36 @@ class ModelAdapter(ABC):
                      + ("; NOT monotone in the rank" if m["non_monotone"] else ""))
         # (decode_qk_logit_error maps every non-finite figure to None, so json.dump never meets a NaN)
         self._merge_metrics("qk_logit_error", report)
+        # the same curves on the post-RoPE statistics, where compress_qk had them (MODEGPT_QK_ROPE=1): the same decoder, the same
+        # order, under metrics["qk_logit_error_rope"] with the pre-RoPE figure beside it
+        pending_rope = self._take("_qk_errors_rope")
+        rope_report = {}
+        for layer in sorted(pending_rope):
+            tensors, rank = pending_rope[layer]
+            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
+            self._record("qk_errors_rope", layer, host)
+            curve_h, curve, terms, scale, g_curve = host[:5]
+            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
+            m = ops.decode_qk_logit_error(curve_h.tolist(), curve.tolist(), rank, cols, terms=terms.tolist(), scale=scale.tolist(),
+                                          greedy_curve=None if g_curve is None else g_curve.tolist())
+            pre = report.get(layer, {}).get("relative_error")
+            m["statistic"], m["pre_rope_relative_error"] = "post_rope", pre
+            rope_report[layer] = m
+            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
+            log.info(f"[QK] Layer {layer}: rank {rank}: of the post-RoPE logit energy the kept columns lose {show(m['relative_error'])} "
+                     f"(exact for a rotary model); the pre-RoPE statistic said {show(pre)}")
+        self._merge_metrics("qk_logit_error_rope", rope_report)
         return report
+
+    def qk_error_rope(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_qk hands over ops.qk_rank_curve's outputs on the post-RoPE statistics (sigma_q', sigma_k') and the order -- the one
+        of qk_error's tensors -- for layer `layer_idx`; report_qk_errors reads them into metrics["qk_logit_error_rope"]."""
+        self._record("_qk_errors_rope", int(layer_idx), (tuple(tensors), int(rank)))
+
+    def qk_selection_statistic(self, layer_idx: int, statistic: str) -> None:
+        """compress_qk says which statistic the layer's pair selection was scored on ("pre_rope" / "post_rope") when the run carries
+        post-RoPE statistics; report_attention_margins writes it to metrics["qk_selection"][layer]["statistic"]."""
+        self._record("_qk_selection_statistics", int(layer_idx), str(statistic))
 
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
     def attention_margin(self, layer_idx: int, kind: str, tensor, *eps: float) -> None:
@@ -284,12 +313,15 @@ class ModelAdapter(ABC):
         (compress_vo.py:130-146: the kept subspace is then not determined by the data)."""
         log = log or logging.getLogger("MoDeGPT")
         pending = self._take("_attention_margins")
+        statistics = self._take("_qk_selection_statistics")
         report = {"qk": {}, "vo": {}}
         for kind, layer in sorted(pending):
             tensor, eps = pending[(kind, layer)]
             rows = tensor.cpu().tolist()
             if kind == "qk":
                 m = ops.decode_qk_margin(rows, *eps)
+                if layer in statistics:               # (only a run that carries post-RoPE statistics says which one it scored on)
+                    m["statistic"] = statistics[layer]
                 if not m["certified"]:
                     flagged = [i for i, h in enumerate(m["heads"]) if not h["certified"]]
                     log.warning(f"[QK] Layer {layer}: pair selection NOT certified -- kv head {m['weakest_head']}: threshold margin "

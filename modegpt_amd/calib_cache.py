@@ -15,6 +15,10 @@ One directory, one self-contained record per layer, so chunks of layers, target_
     layer_<i>_x_mean.f64                   only with MODEGPT_VO_INTERCEPT=1: d_model raw little-endian fp64, mu = E[x] of the sigma_x
                                            activation under sigma_x's normaliser; the same format, sidecar entry (files.x_mean) and
                                            rules as layer_<i>_mlp_mean.f64, under its own switch
+    layer_<i>_q_rope.f64, _k_rope.f64      only with MODEGPT_QK_ROPE=1 on a rotary model (Llama, Qwen2): the per-head Grams of the post-RoPE
+                                           rows, raw little-endian fp64, full [heads, head_dim, head_dim] -- the format and sidecar entry
+                                           fields of layer_<i>_q.f64 / _k.f64 (files.q_rope, files.k_rope), under the rules of the means:
+                                           written only with the switch, demanded by a run with it, ignored by a run without
     layer_<i>.json                         the sidecar, written LAST: the commit marker -- a layer without it does not exist
     bi_scores.json                         the Block-Influence scores of all layers, written by the rank that computed them
 
@@ -49,6 +53,7 @@ FORMAT_VERSION = 1
 PACKED_KINDS = ("mlp", "x")      # 2-D statistics: packed lower triangle
 FULL_KINDS = ("q", "k")          # per-head statistics: full (tiny)
 KINDS = PACKED_KINDS + FULL_KINDS
+ROPE_KINDS = {"q_rope": "q", "k_rope": "k"}      # MODEGPT_QK_ROPE=1: post-RoPE statistic -> the statistic whose shape and layout it has
 ARCH_FIELDS = ("arch", "d_model", "n_inner", "n_heads", "n_kv_heads", "head_dim", "n_layers", "dtype")
 BI_FILE = "bi_scores.json"
 
@@ -194,6 +199,25 @@ def read_mean_file(directory: str, layer: int, entry: dict, kind: str = MEAN_KIN
         raise ValueError(f"calibration statistics, layer {layer}: field files.{kind}.sum_bits -- the sum of {path} has the bit "
                          f"pattern {bits}, the sidecar recorded {entry['sum_bits']}")
     return values
+
+
+# ------------------------------------------------------------------ host half: the post-RoPE statistics (MODEGPT_QK_ROPE=1)
+def validate_rope_entry(meta: dict, arch: dict, layer: int, kind: str) -> dict:
+    """Metadata alone: the record must carry files.<kind> (kind "q_rope" / "k_rope") with the shape of files.q / files.k.  Returns
+    the entry."""
+    entry = meta.get("files", {}).get(kind)
+    if not isinstance(entry, dict):
+        raise ValueError(f"calibration statistics, layer {layer}: field files.{kind} is missing -- the record was saved without "
+                         "MODEGPT_QK_ROPE=1 and this run has the switch on; save the statistics again with it (nothing is "
+                         "recalibrated on load)")
+    n, batch = stat_shapes(arch)[ROPE_KINDS[kind]]
+    want = {"n": n, "batch": batch, "bytes": 8 * stat_numel(kind, n, batch), "layout": "full"}
+    for name, value in want.items():
+        if entry.get(name) != value:
+            _refuse(layer, f"files.{kind}.{name}", entry.get(name), value)
+    if not isinstance(entry.get("trace_bits"), int) or not isinstance(entry.get("file"), str):
+        _refuse(layer, f"files.{kind}.trace_bits", entry.get("trace_bits"), "an integer")
+    return entry
 
 
 # ------------------------------------------------------------------ host half: the sidecar
@@ -405,22 +429,24 @@ def _staging_for(arch: dict, device) -> Staging:
 
 
 def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arch: dict, calibration: dict, model: str,
-                weights: dict, certificates: dict, mean=None, x_mean=None) -> dict:
+                weights: dict, certificates: dict, mean=None, x_mean=None, rope=None) -> dict:
     """One layer's record from its four device tensors ({"mlp", "x": [n, n]; "q", "k": [heads, hd, hd]}): data files first, the
     sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  mean: the layer's
     activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too; x_mean: the
-    mean of x (fp64 [d_model], MODEGPT_VO_INTERCEPT=1) -- likewise, files.x_mean."""
+    mean of x (fp64 [d_model], MODEGPT_VO_INTERCEPT=1) -- likewise, files.x_mean; rope: {"q_rope", "k_rope": [heads, hd, hd]}, the
+    post-RoPE statistics (MODEGPT_QK_ROPE=1) -- their files and entries follow those of the four, through the same staging."""
     import torch
     from . import ops
     os.makedirs(directory, exist_ok=True)
     files, waiting = {}, None
+    tensors = dict(tensors, **(rope or {}))
 
     def finish(item):
         kind, n, batch, host, ev = item
         ev.synchronize()
         files[kind] = write_data_file(directory, layer, kind, host.numpy(), n, batch)
 
-    for kind in KINDS:
+    for kind in KINDS + tuple(k for k in ROPE_KINDS if rope):
         t = tensors[kind]
         n, batch = t.shape[-1], (1 if t.dim() == 2 else t.shape[0])
         numel = stat_numel(kind, n, batch)
@@ -442,11 +468,12 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
     return meta
 
 
-def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None, x_mean=None) -> dict:
+def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None, x_mean=None, rope=None) -> dict:
     """The inverse: checks the sidecar against `expect`, fills the four device tensors, returns the sidecar.  The file of a
     statistic is read while the one before it is copied to the device and unpacked.  mean: an fp64 [n_inner] device tensor to fill
     from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1), x_mean: an fp64 [d_model] one to fill from layer_<i>_x_mean.f64
-    (MODEGPT_VO_INTERCEPT=1); a record without the entry is refused before any data is read."""
+    (MODEGPT_VO_INTERCEPT=1), rope: {"q_rope", "k_rope": fp64 [heads, hd, hd] device tensors} to fill from layer_<i>_q_rope.f64 /
+    _k_rope.f64 (MODEGPT_QK_ROPE=1); a record without the entry is refused before any data is read."""
     import torch
     from . import ops
     meta = read_sidecar(directory, layer)
@@ -455,7 +482,10 @@ def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expe
         mean_entry = validate_mean_entry(meta, expect["arch"]["n_inner"], layer)
     if x_mean is not None:
         x_mean_entry = validate_mean_entry(meta, expect["arch"]["d_model"], layer, kind=X_MEAN_KIND)
-    for kind in KINDS:
+    for kind in ROPE_KINDS if rope else ():
+        validate_rope_entry(meta, expect["arch"], layer, kind)
+    tensors = dict(tensors, **(rope or {}))
+    for kind in KINDS + tuple(k for k in ROPE_KINDS if rope):
         t = tensors[kind]
         entry = meta["files"][kind]
         numel = stat_numel(kind, entry["n"], entry["batch"])
@@ -507,6 +537,10 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
     x_means = getattr(adapter, "x_means", None) if ops.vo_intercept_enabled() else None         # (likewise)
     if ops.vo_intercept_enabled() and targets and (x_means is None or any(x_means[i] is None for i in targets)):
         raise RuntimeError("MODEGPT_VO_INTERCEPT=1 but the adapter carries no input means (adapter.x_means) to save")
+    from .calibration import qk_rope_collected
+    rope = getattr(adapter, "qk_rope_stats", None) if qk_rope_collected(adapter) else None       # (likewise)
+    if qk_rope_collected(adapter) and targets and (rope is None or any(rope[0][i] is None or rope[1][i] is None for i in targets)):
+        raise RuntimeError("MODEGPT_QK_ROPE=1 but the adapter carries no post-RoPE statistics (adapter.qk_rope_stats) to save")
     if targets:
         staging = _staging_for(arch, cov["mlp"][targets[0]].device)
         for i in targets:
@@ -514,7 +548,8 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
             cert = certificates if loaded is None else loaded[i]["certificates"]
             meta = write_layer(directory, i, {k: cov[k][i] for k in KINDS}, staging, arch, cal, model,
                                weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i],
-                               x_mean=None if x_means is None else x_means[i])
+                               x_mean=None if x_means is None else x_means[i],
+                               rope=None if rope is None else {"q_rope": rope[0][i], "k_rope": rope[1][i]})
             nbytes += sum(e["bytes"] for e in meta["files"].values())
         torch.cuda.synchronize(staging.device)
     if bi_scores is not None and getattr(adapter, "calib_want_bi", True):
@@ -543,13 +578,15 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
     metas: Dict[int, dict] = {}
     adapter.mlp_means = sig.mlp_sums           # (MODEGPT_MLP_INTERCEPT=1: filled below from the mean files; None without the switch)
     adapter.x_means = sig.x_sums               # (MODEGPT_VO_INTERCEPT=1: likewise)
+    adapter.qk_rope_stats = sig.qk_rope        # (MODEGPT_QK_ROPE=1 on a rotary model: likewise, from the q_rope / k_rope files)
     if targets:
         staging = _staging_for(expect["arch"], sig.lists["mlp"][targets[0]].device)
         for i in targets:
             metas[i] = read_layer(directory, i, {k: sig.lists[k][i] for k in KINDS}, staging,
                                   dict(expect, weights=weight_fingerprint(adapter, i)),
                                   mean=None if sig.mlp_sums is None else sig.mlp_sums[i],
-                                  x_mean=None if sig.x_sums is None else sig.x_sums[i])
+                                  x_mean=None if sig.x_sums is None else sig.x_sums[i],
+                                  rope=None if sig.q_rope is None else {"q_rope": sig.q_rope[i], "k_rope": sig.k_rope[i]})
         torch.cuda.synchronize(staging.device)
     adapter.bi_scores = bi_scores
     cert = merge_certificates([m["certificates"] for m in metas.values()])

@@ -30,10 +30,32 @@ random.seed(1234)
 TOKENS_PER_TEXT_NORMALISER = 2048
 
 
+QK_ROPE_ARCHS = ("llama", "qwen2")      # rotary models whose compressed attention keeps the dropped-column identity
+
+
+def qk_rope_collected(adapter: ModelAdapter, log=None) -> bool:
+    """Whether this run collects (or loads) the post-RoPE statistics sigma_q', sigma_k': MODEGPT_QK_ROPE=1 on a Llama / Qwen2
+    adapter.  With the switch on any other architecture nothing is collected and, given a logger, one line says why."""
+    if not ops.qk_rope_enabled():
+        return False
+    arch = adapter.arch
+    if arch in QK_ROPE_ARCHS:
+        return True
+    if log is not None:
+        if "qwen" in arch:
+            log.warning(f"MODEGPT_QK_ROPE=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
+                        "RMSNorm), so the dropped-column identity of the post-RoPE statistic does not hold; nothing is collected")
+        else:
+            log.info(f"MODEGPT_QK_ROPE=1: {arch} has no rotary embedding, the pre-RoPE statistic is already the exact one; nothing "
+                     "more is collected")
+    return False
+
+
 class SigmaBuffers:
     """The four statistic families of the target layers (shapes: src/calibration.py:82-96)."""
 
     KINDS = ("mlp", "q", "k", "x")
+    ROPE_KINDS = ("q_rope", "k_rope")
 
     def __init__(self, adapter: ModelAdapter, target_layers: Sequence[int], device=None):
         L = adapter.n_layers
@@ -57,6 +79,19 @@ class SigmaBuffers:
             self.x_sums = [None] * L
             for i in self.layers:
                 self.x_sums[i] = torch.zeros(d, dtype=dtype_p, device=device)
+        # the per-head Grams of the post-RoPE rows q', k' (MODEGPT_QK_ROPE=1 on a rotary model): the shapes of q / k; None without it
+        self.q_rope: Optional[List[Optional[torch.Tensor]]] = None
+        self.k_rope: Optional[List[Optional[torch.Tensor]]] = None
+        if qk_rope_collected(adapter, logger):
+            self.q_rope, self.k_rope = [None] * L, [None] * L
+            for i in self.layers:
+                self.q_rope[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
+                self.k_rope[i] = torch.zeros(*shapes["k"], dtype=dtype_p, device=device)
+
+    @property
+    def qk_rope(self):
+        """(q_rope, k_rope), or None without the switch."""
+        return None if self.q_rope is None else (self.q_rope, self.k_rope)
 
     def finalize(self, n_texts: int) -> None:
         """sigma <- sigma / (n_texts * 2048), lower triangle mirrored into the upper (src/calibration.py:141-146)."""
@@ -68,6 +103,9 @@ class SigmaBuffers:
                 self.mlp_sums[i].mul_(scale)                 # mu = E[h] under the normaliser sigma_mlp gets: one rounding per entry
             if self.x_sums is not None:
                 self.x_sums[i].mul_(scale)                   # mu = E[x] under sigma_x's normaliser, likewise
+            if self.q_rope is not None:
+                ops.cov_finalize(self.q_rope[i], scale)      # the same mirror + normaliser as sigma_q / sigma_k
+                ops.cov_finalize(self.k_rope[i], scale)
 
 
 class BlockInfluence:
@@ -139,6 +177,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     handles: list = []
     adapter.mlp_sums = sig.mlp_sums                      # (read by register_hooks; None without MODEGPT_MLP_INTERCEPT=1)
     adapter.x_sums = sig.x_sums                          # (likewise; None without MODEGPT_VO_INTERCEPT=1)
+    adapter.qk_rope_sums = sig.qk_rope                   # (likewise; None without MODEGPT_QK_ROPE=1 on a rotary model)
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -178,6 +217,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.mlp_means = sig.mlp_sums                     # per target layer mu = E[h] (None without the switch): compress_nystrom reads it
     adapter.x_sums = None
     adapter.x_means = sig.x_sums                         # per target layer mu = E[x] (None without the switch): compress_vo reads it
+    adapter.qk_rope_sums = None
+    adapter.qk_rope_stats = sig.qk_rope                  # (sigma_q', sigma_k') lists (None without the switch): compress_qk reads them
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

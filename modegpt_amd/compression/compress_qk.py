@@ -76,21 +76,40 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     mode, ridge_q, ridge_k = qk_mode_and_ridges(arch, n_kv != n_heads, adapter.config.ridge_qk)
     cq = cov_q_list.to(device=local_device(), dtype=dtype_p)
     ck = cov_k_list.to(device=local_device(), dtype=dtype_p)
-    mask, q_rows, k_rows = ops.qk_select(cq, ck, rank, mode, ridge_q, ridge_k)
+    # the post-RoPE statistics of the layer (MODEGPT_QK_ROPE=1 at calibration or in the loaded record), or None
+    rope = getattr(adapter, "qk_rope_stats", None)
+    rope = None if rope is None or rope[0][layer_idx] is None or rope[1][layer_idx] is None else \
+        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in rope)
+    # MODEGPT_QK_ROPE_SELECT=1: the selection, its certificate and the report's order take (sigma_q', sigma_k') instead of the
+    # reference's pre-RoPE pair, same mode and ridges; everything downstream of the mask is unchanged
+    by_rope = ops.qk_rope_select_enabled()
+    if by_rope and rope is None:
+        raise RuntimeError(f"MODEGPT_QK_ROPE_SELECT=1 but layer {layer_idx} has no post-RoPE statistics (adapter.qk_rope_stats): "
+                           "calibrate, or load a record saved, with MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
+    sq, sk = rope if by_rope else (cq, ck)
+    mask, q_rows, k_rows = ops.qk_select(sq, sk, rank, mode, ridge_q, ridge_k)
     record = getattr(adapter, "attention_margin", None)           # (a duck-typed adapter without it: no certificate)
     if record is not None:
         # the selection's certificate stays on the device until the adapter next waits for the stream (report_attention_margins)
         eps_rel = attention_error_eps(adapter)
-        record(layer_idx, "qk", ops.qk_select_margin(cq, ck, rank, mode, ridge_q, ridge_k, mask, eps_rel, EIGH_ROUTE_EPS_ABS),
+        record(layer_idx, "qk", ops.qk_select_margin(sq, sk, rank, mode, ridge_q, ridge_k, mask, eps_rel, EIGH_ROUTE_EPS_ABS),
                eps_rel, EIGH_ROUTE_EPS_ABS)
+        note = getattr(adapter, "qk_selection_statistic", None)
+        if rope is not None and note is not None:     # (a run without post-RoPE statistics: the entry is what it always was)
+            note(layer_idx, "post_rope" if by_rope else "pre_rope")
     record_error = getattr(adapter, "qk_error", None) if ops.qk_error_enabled() else None      # (... without this: no logit error)
     if record_error is not None:
         # what the selection loses of the logits, at every rank: the order of ALL units from one more scoring call (the mask above is
         # its prefix), then the curves on the RAW statistics (ridges 0: the stored rows are bit copies, so this is the artefact's
         # error) with the diagonal terms under the ridges the scores really use.  Enqueued only, read by report_qk_errors.
         ns, _ = ops.qk_units(mode, head_dim)
-        order = ops.qk_select(cq, ck, head_dim, mode, ridge_q, ridge_k)[0][:, :ns].contiguous()
+        order = ops.qk_select(sq, sk, head_dim, mode, ridge_q, ridge_k)[0][:, :ns].contiguous()
         record_error(layer_idx, ops.qk_rank_curve(cq, ck, mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,), rank)
+        record_rope = getattr(adapter, "qk_error_rope", None)
+        if rope is not None and record_rope is not None:
+            # the same curves along the SAME order on (sigma_q', sigma_k'): for a rotary model the exact mean-square logit change
+            record_rope(layer_idx, ops.qk_rank_curve(rope[0], rope[1], mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,),
+                        rank)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

@@ -19,8 +19,8 @@ from ._lib import check
 from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_MARGIN_FIELDS, RANK_CURVE_KEEP,  # noqa: F401
                       RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
                       decode_qk_margin, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
-                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, rank_curve_enabled, vo_error_enabled,
-                      vo_intercept_enabled)
+                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled,
+                      rank_curve_enabled, vo_error_enabled, vo_intercept_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
        torch.float64: _lib.MDG_F64}
@@ -1276,6 +1276,53 @@ def rope_gather_plan(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask
     x, cos, sin, mask, norm_weight, out, (B, T, r) = _rope_operands(x, cos, sin, mask, n_heads, n_kv, head_dim, norm_weight, out)
     return rope_plan_at(x.dtype, B, T, n_heads, n_kv, r, head_dim, x.stride(1), x.data_ptr(), cos.data_ptr(), sin.data_ptr(),
                         0 if cos.shape[0] == 1 else T * head_dim, _p(mask), _p(norm_weight), out.data_ptr())
+
+
+def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: int, head_dim: int,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rotary embedding of a projection output in its own layout (mdg_rope_rows): x [B, T, n_heads*head_dim] (bf16 / f16 / f32,
+    last dim contiguous, rows of one pitch) -> x's shape, bit-identical to torch's eager x * cos + rotate_half(x) * sin.  cos, sin:
+    [B or 1, T, head_dim], full width.  `out`: a caller-owned tensor of x's shape and dtype with a contiguous last dim and rows of one
+    pitch (it is returned); it must not overlap x -- the model still needs x."""
+    _need_gpu(x, cos, sin, out)
+    lib = _lib.load()
+    if x.dim() != 3 or x.shape[2] != n_heads * head_dim:
+        raise ValueError(f"rope_rows: x must be [B, T, n_heads*head_dim = {n_heads * head_dim}], got {tuple(x.shape)}")
+    B, T, width = x.shape
+    x = x.detach()
+    if x.stride(2) != 1 or (B > 1 and x.stride(0) != T * x.stride(1)):
+        x = x.contiguous()
+    cos = cos.detach().to(x.dtype).contiguous()
+    sin = sin.detach().to(x.dtype).contiguous()
+    if cos.dim() != 3 or cos.shape != sin.shape or tuple(cos.shape[-2:]) != (T, head_dim) or cos.shape[0] not in (1, B):
+        raise ValueError(f"rope_rows: cos/sin {tuple(cos.shape)} / {tuple(sin.shape)} do not fit [B or 1, {T}, {head_dim}]")
+    if out is None:
+        out = torch.empty(B, T, width, dtype=x.dtype, device=x.device)
+    elif (tuple(out.shape) != (B, T, width) or out.dtype != x.dtype or out.device != x.device or out.stride(2) != 1
+          or (B > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"rope_rows: out must be a {x.dtype} [{B}, {T}, {width}] on {x.device} with a contiguous last dim and rows of "
+                         f"one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    if x.numel() == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(lib.mdg_rope_rows(x.data_ptr(), _DT[x.dtype], x.stride(1), B, T, n_heads, head_dim, cos.data_ptr(), sin.data_ptr(),
+                                0 if cos.shape[0] == 1 else T * head_dim, out.data_ptr(), out.stride(1), _stream(x)), "mdg_rope_rows")
+    return out
+
+
+_ROPE_SCRATCH = {}
+
+
+def rope_scratch(like: torch.Tensor, slot: str) -> torch.Tensor:
+    """A scratch tensor of `like`'s shape and dtype on its device for the rotated rows of a calibration batch (slot "q" / "k"):
+    one flat buffer per (device, slot), grown on demand and reused across layers and batches.  Reuse is ordered by the caller's
+    stream: whoever reads the scratch enqueues on the stream the next rope_rows call into it is enqueued on."""
+    key = (_device_index(like.device), slot)
+    need = like.numel() * like.element_size()
+    buf = _ROPE_SCRATCH.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _ROPE_SCRATCH[key] = torch.empty(need, dtype=torch.uint8, device=like.device)
+    return buf[:need].view(like.dtype).view(like.shape)
 
 
 def cast_transpose(x: torch.Tensor) -> torch.Tensor:

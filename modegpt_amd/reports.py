@@ -63,6 +63,21 @@ def vo_error_enabled() -> bool:
     return _switch("MODEGPT_VO_ERROR")
 
 
+# The post-RoPE Q/K statistics ("Post-RoPE Q/K statistics").  Opt-in: MODEGPT_QK_ROPE=1 makes calibration of a
+# rotary model (Llama, Qwen2) rotate the parked q / k rows (mdg_rope_rows) and accumulate sigma_q', sigma_k' beside the pre-RoPE
+# pair; with MODEGPT_QK_ERROR=1 compress_qk then reports the logit error on them, which is exact for a rotary model.
+def qk_rope_enabled() -> bool:
+    """MODEGPT_QK_ROPE as it stands when calibration, the cache or compress_qk asks (not frozen at import)."""
+    return _switch("MODEGPT_QK_ROPE")
+
+
+# Opt-in: MODEGPT_QK_ROPE_SELECT=1 makes compress_qk score, certify and order the pair selection on the post-RoPE statistics instead
+# of the reference's pre-RoPE pair.  Needs the statistics (MODEGPT_QK_ROPE=1 at calibration or in the loaded record).
+def qk_rope_select_enabled() -> bool:
+    """MODEGPT_QK_ROPE_SELECT as it stands when compress_qk asks (per layer; not frozen at import)."""
+    return _switch("MODEGPT_QK_ROPE_SELECT")
+
+
 def keep_bias_enabled(arch=None) -> bool:
     """Whether the compressors carry the projection biases into the artefacts ("Projection biases"): always
     for Qwen2 / Qwen2.5 (model_type "qwen2": nothing of the reference's to preserve, and dropping q/k/v biases is never right),
