@@ -53,7 +53,8 @@ extern "C" {
                                 added under 10: mdg_col_sum_ws_bytes, mdg_col_sum_accum, mdg_cov_center, mdg_nystrom_intercept_ws_bytes,
                                 mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept);
                                 added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation);
-                                added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics) */
+                                added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics);
+                                added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -811,6 +812,39 @@ int mdg_rope_gather_plan(const void* x, int dtype, int64_t ld_x, int64_t B, int6
  * (pitch included) intersects that of x -- the model still needs x.  B == 0 or T == 0 launches nothing. */
 int mdg_rope_rows(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, int n_heads, int hd, const void* cos,
                   const void* sin, int64_t cs_batch_stride, void* out, int64_t ld_out, void* stream);
+
+/* ------------------------------------------------------------------ within-sequence, shift-invariant Q/K statistic
+ * Softmax ignores any part of a logit that depends on the query alone.  Dropping the columns D of a head changes logit (i, j)
+ * by e_ij = q'_iD . k'_jD; what the attention probabilities of query i see is the VARIANCE of e_ij over the keys j of i's own
+ * sequence, and summed over the queries of the calibration set that is 1^T P_h[D,D] 1 with, per query head h,
+ *   P_h = sum over sequences s of  G^q_{s,h} (.) ( G^k_{s,kv} - m m^T / T ),   G^q = Q'^T Q', G^k = K'^T K', m = K'^T 1
+ * ((.): entry-wise product; kv = h / (n_heads / n_kv)).  P_h is positive semidefinite.  Additive entries, ABI version unchanged.
+ *   q  [B*T, n_heads*hd] rows of pitch ld_q elements, k [B*T, n_kv*hd] rows of pitch ld_k, last dimension contiguous, dtype
+ *      bf16 / f16 / f32 (widened to fp64 exactly on load): the layouts mdg_rope_rows writes.  Rows b*T .. b*T+T-1 are sequence b.
+ *   pair, pair_raw  [n_heads, hd, hd] fp64 contiguous, ACCUMULATED INTO; pair_raw may be NULL.  For b = 0 .. B-1 in ascending
+ *      order   pair[h] += G^q_{b,h} (.) (G^k_{b,kv} - m m^T / T),   pair_raw[h] += G^q_{b,h} (.) G^k_{b,kv};  nothing is normalised.
+ *   ws  mdg_qk_pair_ws_bytes(B, n_heads, hd, pair_raw != NULL) = 8 B n_heads hd^2 (twice that with pair_raw) bytes, 8-byte aligned.
+ * hd <= 128: one workgroup per (sequence, query head) holds both 128x128 Grams in accumulator registers, on
+ * v_mfma_f64_16x16x4_f64; a second kernel adds the per-sequence products onto pair, one addition per sequence in ascending b.
+ * So one call over B sequences gives the bits of B single-sequence calls in that order, and every run gives the same bits: no
+ * atomics, every sum in a fixed order.  Both triangles of every output matrix are written and are equal to the bit.  16-byte
+ * loads when q (k) is 16-byte aligned and ld_q (ld_k) and hd are multiples of 16 bytes of elements, element-wise otherwise.
+ * A non-finite element of q in head h reaches pair[h] and pair_raw[h] only; one of k in kv head v reaches the heads of group v only.
+ * At T == 1 the centred term is exactly zero, so pair receives +0.
+ * Accuracy (u = 2^-53; no overflow or underflow).  Products of two bf16, f16 or f32 values are exact in fp64, so per sequence:
+ * a Gram entry is a chain of T additions, |err G_ab| <= T u sqrt(G_aa G_bb); a column sum m_a is a chain of at most T additions,
+ * and with |m_a| <= sqrt(T G^k_aa) the product, the division by T and the chain errors give |err (m_a m_b / T)| <= (2T + 2) u K_ab,
+ * K_ab = sqrt(G^k_aa G^k_bb); the subtraction adds u K_ab (|S_ab| <= K_ab), so |err S_ab| <= (3T + 3) u K_ab; the Hadamard
+ * product adds the query Gram's T u and one rounding: (4T + 4) u sqrt(G^q_aa G^q_bb) K_ab per sequence.  The fold onto a pair
+ * that held zero rounds B - 1 times a running sum of at most sum_s sqrt(G^q_aa G^q_bb) K_ab.  With the second-order terms,
+ *   | pair[h][a,b] - exact | <= (4T + B + 8) u  sum_s sqrt(G^q_{s,aa} G^q_{s,bb}) sqrt(G^k_{s,aa} G^k_{s,bb}),
+ * and the same bound holds for pair_raw.  A pair that held p on entry adds B u |p[a,b]|.
+ * Only enqueues.  MDG_ERR_BAD_ARG (with a message, before any device work): unknown dtype, hd < 1 or > 128, n_heads <= 0,
+ * n_kv <= 0 or n_heads % n_kv != 0, negative extent, ld_q < n_heads*hd or ld_k < n_kv*hd, a NULL q, k, pair or ws of a non-empty
+ * call, ws_bytes below mdg_qk_pair_ws_bytes.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
+size_t mdg_qk_pair_ws_bytes(int64_t B, int n_heads, int hd, int want_raw);
+int mdg_qk_pair_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, int dtype, int64_t B, int64_t T, int n_heads,
+                      int n_kv, int hd, double* pair, double* pair_raw, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -42,13 +42,18 @@ class LlamaAdapter(ModelAdapter):
         With MODEGPT_QK_ROPE=1 (Llama, Qwen2) calibration leaves the (sigma_q', sigma_k') lists on self.qk_rope_sums: a forward
         pre-hook on self_attn parks the rotary tables the module is called with, and after the launches above the flush rotates the
         parked q and k (ops.rope_rows) and accumulates their per-head Grams in one separate ops.cov_accum_multi call (the reference's
-        disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); the launches above are the same either way."""
+        disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); the launches above are the same either way.  With
+        MODEGPT_QK_SEQ=1 beside it the (P, P_raw) lists are on self.qk_pair_sums and the rotated rows also go to ops.qk_pair_accum,
+        one call per layer and batch (the within-sequence Q/K statistic); every other launch is the same either way."""
         parked = {}
         sums = getattr(self, "mlp_sums", None)
         x_sums = getattr(self, "x_sums", None)
         rope = getattr(self, "qk_rope_sums", None)       # (sigma_q', sigma_k') lists with MODEGPT_QK_ROPE=1 on a rotary model, else None
         if rope is not None and rope[0][layer_idx] is None:
             rope = None
+        pairs = getattr(self, "qk_pair_sums", None)      # (P, P_raw) lists with MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1, else None
+        if pairs is not None and (rope is None or pairs[0][layer_idx] is None):
+            pairs = None
         head_dim = self.head_dim
 
         def park(kind):
@@ -94,6 +99,10 @@ class LlamaAdapter(ModelAdapter):
                 q, k = (t if t.dim() == 3 else t.reshape(-1, t.shape[-2], t.shape[-1]) for t in (got["q"], got["k"]))
                 rq = ops.rope_rows(q, pos[0], pos[1], self.n_heads, head_dim, out=ops.rope_scratch(q, "q"))
                 rk = ops.rope_rows(k, pos[0], pos[1], self.n_kv_heads, head_dim, out=ops.rope_scratch(k, "k"))
+                if pairs is not None:
+                    # the within-sequence statistic of the batch's B sequences of T rows, from the same scratch rows
+                    ops.qk_pair_accum(pairs[0][layer_idx], pairs[1][layer_idx], rq, rk, q.shape[0], q.shape[1], self.n_heads,
+                                      self.n_kv_heads, head_dim)
                 ops.cov_accum_multi([(rope[0][layer_idx], rq, self.n_heads), (rope[1][layer_idx], rk, self.n_kv_heads)])
             return None
 

@@ -283,7 +283,32 @@ class ModelAdapter(ABC):
             log.info(f"[QK] Layer {layer}: rank {rank}: of the post-RoPE logit energy the kept columns lose {show(m['relative_error'])} "
                      f"(exact for a rotary model); the pre-RoPE statistic said {show(pre)}")
         self._merge_metrics("qk_logit_error_rope", rope_report)
+        # ... and on the within-sequence statistic, where compress_qk had it (MODEGPT_QK_SEQ=1): the same order, under
+        # metrics["qk_logit_error_seq"], with the error on the uncentred statistic and the share of it softmax cannot see
+        pending_seq = self._take("_qk_errors_seq")
+        seq_report = {}
+        for layer in sorted(pending_seq):
+            tensors, rank = pending_seq[layer]
+            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
+            self._record("qk_errors_seq", layer, host)
+            curve_h, curve, terms, scale, g_curve = host[:5]
+            raw_curve = host[7]
+            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
+            m = ops.decode_qk_seq_error(curve_h.tolist(), curve.tolist(), raw_curve.tolist(), rank, cols, terms=terms.tolist(),
+                                        scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist())
+            m["statistic"] = "within_sequence"
+            seq_report[layer] = m
+            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
+            log.info(f"[QK] Layer {layer}: rank {rank}: within-sequence, shift-invariant logit error {show(m['error'])} "
+                     f"({show(m['relative_error'])} of its energy); {show(m['shift_share'])} of the uncentred change is invisible to softmax")
+        self._merge_metrics("qk_logit_error_seq", seq_report)
         return report
+
+    def qk_error_seq(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_qk hands over ops.qk_rank_curve's outputs on the within-sequence statistic (P, ones), the order -- the one of
+        qk_error's tensors -- and the kv-head curve on the uncentred P_raw, for layer `layer_idx`; report_qk_errors reads them into
+        metrics["qk_logit_error_seq"]."""
+        self._record("_qk_errors_seq", int(layer_idx), (tuple(tensors), int(rank)))
 
     def qk_error_rope(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_qk hands over ops.qk_rank_curve's outputs on the post-RoPE statistics (sigma_q', sigma_k') and the order -- the one
@@ -292,7 +317,8 @@ class ModelAdapter(ABC):
 
     def qk_selection_statistic(self, layer_idx: int, statistic: str) -> None:
         """compress_qk says which statistic the layer's pair selection was scored on ("pre_rope" / "post_rope") when the run carries
-        post-RoPE statistics; report_attention_margins writes it to metrics["qk_selection"][layer]["statistic"]."""
+        post-RoPE statistics, or "within_sequence" under MODEGPT_QK_SEQ_SELECT=1; report_attention_margins writes it to
+        metrics["qk_selection"][layer]["statistic"]."""
         self._record("_qk_selection_statistics", int(layer_idx), str(statistic))
 
     # ---- the certificates of the attention half: QK pair selection, VO spectral gap (not upstream) ----
@@ -338,6 +364,12 @@ class ModelAdapter(ABC):
                                 f"{w['gap']:.3e} between sigma_r and sigma_r+1 (lambda_r - lambda_r+1 = "
                                 f"{w['lambda_r'] - w['lambda_next']:.3e} against twice the bound {w['bound']:.3e}, eps = {eps[0]:.2e})")
             report[kind][layer] = m
+        for layer in sorted(statistics):
+            if statistics[layer] == "within_sequence" and layer not in report["qk"]:
+                # MODEGPT_QK_SEQ_SELECT=1: no certificate is computed for this selection; the entry says so instead of carrying one
+                # computed on an error model that does not cover the centring's cancellation
+                report["qk"][layer] = {"statistic": "within_sequence", "certificate": None, "certified": None, "order_certified": None,
+                                       "reason": "no certificate is issued for a selection on the within-sequence statistic"}
         for kind, key in (("qk", "qk_selection"), ("vo", "vo_spectrum")):       # (only the non-empty kinds)
             self._merge_metrics(key, report[kind])
         return report

@@ -51,6 +51,31 @@ def qk_rope_collected(adapter: ModelAdapter, log=None) -> bool:
     return False
 
 
+def qk_seq_collected(adapter: ModelAdapter, log=None) -> bool:
+    """Whether this run collects (or loads) the within-sequence Q/K statistic P, P_raw: MODEGPT_QK_SEQ=1 on a Llama / Qwen2 adapter
+    that collects the post-RoPE statistics too -- the statistic is taken on the rotated rows the post-RoPE flush produces, so
+    MODEGPT_QK_SEQ=1 without MODEGPT_QK_ROPE=1 raises there.  On any other architecture nothing is collected and, given a logger,
+    one line says why."""
+    if not ops.qk_seq_enabled():
+        return False
+    arch = adapter.arch
+    if arch in QK_ROPE_ARCHS:
+        if not ops.qk_rope_enabled():
+            raise RuntimeError("MODEGPT_QK_SEQ=1 needs MODEGPT_QK_ROPE=1: the within-sequence Q/K statistic is accumulated from the "
+                               "post-RoPE rows, which are only produced when the post-RoPE statistics are collected")
+        if adapter.head_dim > 128:
+            raise RuntimeError(f"MODEGPT_QK_SEQ=1: head_dim {adapter.head_dim} > 128 is not supported by mdg_qk_pair_accum")
+        return True
+    if log is not None:
+        if "qwen" in arch:
+            log.warning(f"MODEGPT_QK_SEQ=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
+                        "RMSNorm), so the dropped-column identity of the within-sequence statistic does not hold; nothing is collected")
+        else:
+            log.info(f"MODEGPT_QK_SEQ=1: {arch} has no rotary embedding and separate q / k hooks; the within-sequence statistic is "
+                     "not collected for it")
+    return False
+
+
 class SigmaBuffers:
     """The four statistic families of the target layers (shapes: src/calibration.py:82-96)."""
 
@@ -88,6 +113,21 @@ class SigmaBuffers:
                 self.q_rope[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
                 self.k_rope[i] = torch.zeros(*shapes["k"], dtype=dtype_p, device=device)
 
+        # the within-sequence Q/K statistic and its uncentred twin (MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1 on a rotary model): per
+        # layer [n_heads, hd, hd], both triangles; None without it
+        self.qk_pair: Optional[List[Optional[torch.Tensor]]] = None
+        self.qk_pair_raw: Optional[List[Optional[torch.Tensor]]] = None
+        if qk_seq_collected(adapter, logger):
+            self.qk_pair, self.qk_pair_raw = [None] * L, [None] * L
+            for i in self.layers:
+                self.qk_pair[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
+                self.qk_pair_raw[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
+
+    @property
+    def qk_pairs(self):
+        """(qk_pair, qk_pair_raw), or None without the switch."""
+        return None if self.qk_pair is None else (self.qk_pair, self.qk_pair_raw)
+
     @property
     def qk_rope(self):
         """(q_rope, k_rope), or None without the switch."""
@@ -106,6 +146,12 @@ class SigmaBuffers:
             if self.q_rope is not None:
                 ops.cov_finalize(self.q_rope[i], scale)      # the same mirror + normaliser as sigma_q / sigma_k
                 ops.cov_finalize(self.k_rope[i], scale)
+            if self.qk_pair is not None:
+                # the token normaliser squared: the mean over the within-sequence pairs in the unit of <sigma_q', sigma_k'> (one
+                # rounding per entry, the same for both triangles)
+                pair_scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER ** 2)
+                self.qk_pair[i].mul_(pair_scale)
+                self.qk_pair_raw[i].mul_(pair_scale)
 
 
 class BlockInfluence:
@@ -178,6 +224,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.mlp_sums = sig.mlp_sums                      # (read by register_hooks; None without MODEGPT_MLP_INTERCEPT=1)
     adapter.x_sums = sig.x_sums                          # (likewise; None without MODEGPT_VO_INTERCEPT=1)
     adapter.qk_rope_sums = sig.qk_rope                   # (likewise; None without MODEGPT_QK_ROPE=1 on a rotary model)
+    adapter.qk_pair_sums = sig.qk_pairs                  # (likewise; None without MODEGPT_QK_SEQ=1 beside it)
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -219,6 +266,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.x_means = sig.x_sums                         # per target layer mu = E[x] (None without the switch): compress_vo reads it
     adapter.qk_rope_sums = None
     adapter.qk_rope_stats = sig.qk_rope                  # (sigma_q', sigma_k') lists (None without the switch): compress_qk reads them
+    adapter.qk_pair_sums = None
+    adapter.qk_pair_stats = sig.qk_pairs                 # (P, P_raw) lists (None without the switch): compress_qk reads them
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

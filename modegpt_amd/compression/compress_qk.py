@@ -86,10 +86,31 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     if by_rope and rope is None:
         raise RuntimeError(f"MODEGPT_QK_ROPE_SELECT=1 but layer {layer_idx} has no post-RoPE statistics (adapter.qk_rope_stats): "
                            "calibrate, or load a record saved, with MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
-    sq, sk = rope if by_rope else (cq, ck)
-    mask, q_rows, k_rows = ops.qk_select(sq, sk, rank, mode, ridge_q, ridge_k)
+    # the within-sequence statistic of the layer (MODEGPT_QK_SEQ=1 at calibration or in the loaded record): (P, P_raw), or None
+    pair = getattr(adapter, "qk_pair_stats", None)
+    pair = None if pair is None or pair[0][layer_idx] is None or pair[1][layer_idx] is None else \
+        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in pair)
+    # MODEGPT_QK_SEQ_SELECT=1: the selection and the report's order take (P, ones) with ridges 0 -- a unit's score is then the
+    # diagonal of the within-sequence objective 1^T P[D,D] 1, summed over the group.  No certificate: mdg_qk_select_margin's error
+    # model does not cover the cancellation in the centring.  Everything downstream of the mask is unchanged.
+    by_seq = ops.qk_seq_select_enabled()
+    if by_seq and by_rope:
+        raise RuntimeError("MODEGPT_QK_SEQ_SELECT=1 and MODEGPT_QK_ROPE_SELECT=1 are both set: the pair selection takes one statistic")
+    if by_seq and pair is None:
+        raise RuntimeError(f"MODEGPT_QK_SEQ_SELECT=1 but layer {layer_idx} has no within-sequence statistic (adapter.qk_pair_stats): "
+                           "calibrate, or load a record saved, with MODEGPT_QK_SEQ=1 and MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
+    ones = torch.ones(n_kv, head_dim, head_dim, dtype=dtype_p, device=local_device()) if pair is not None else None
+    if by_seq:
+        sq, sk, sel_ridges = pair[0], ones, (0.0, 0.0)
+    else:
+        (sq, sk), sel_ridges = (rope if by_rope else (cq, ck)), (ridge_q, ridge_k)
+    mask, q_rows, k_rows = ops.qk_select(sq, sk, rank, mode, *sel_ridges)
     record = getattr(adapter, "attention_margin", None)           # (a duck-typed adapter without it: no certificate)
-    if record is not None:
+    if by_seq:
+        note = getattr(adapter, "qk_selection_statistic", None)
+        if note is not None:                          # (report_attention_margins writes the entry, with the certificate's absence)
+            note(layer_idx, "within_sequence")
+    elif record is not None:
         # the selection's certificate stays on the device until the adapter next waits for the stream (report_attention_margins)
         eps_rel = attention_error_eps(adapter)
         record(layer_idx, "qk", ops.qk_select_margin(sq, sk, rank, mode, ridge_q, ridge_k, mask, eps_rel, EIGH_ROUTE_EPS_ABS),
@@ -103,13 +124,20 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
         # its prefix), then the curves on the RAW statistics (ridges 0: the stored rows are bit copies, so this is the artefact's
         # error) with the diagonal terms under the ridges the scores really use.  Enqueued only, read by report_qk_errors.
         ns, _ = ops.qk_units(mode, head_dim)
-        order = ops.qk_select(sq, sk, head_dim, mode, ridge_q, ridge_k)[0][:, :ns].contiguous()
+        order = ops.qk_select(sq, sk, head_dim, mode, *sel_ridges)[0][:, :ns].contiguous()
         record_error(layer_idx, ops.qk_rank_curve(cq, ck, mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,), rank)
         record_rope = getattr(adapter, "qk_error_rope", None)
         if rope is not None and record_rope is not None:
             # the same curves along the SAME order on (sigma_q', sigma_k'): for a rotary model the exact mean-square logit change
             record_rope(layer_idx, ops.qk_rank_curve(rope[0], rope[1], mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,),
                         rank)
+        record_seq = getattr(adapter, "qk_error_seq", None)
+        if pair is not None and record_seq is not None:
+            # ... and on the within-sequence statistic: cov_q = P (then P_raw), cov_k = ones -- a product with 1.0 is exact, so the
+            # curve is 1^T P[D,D] 1 over the dropped columns D, the part of the logit change softmax can see (then the whole of it)
+            seq = ops.qk_rank_curve(pair[0], ones, mode, 0.0, 0.0, order)
+            raw_curve = ops.qk_rank_curve(pair[1], ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
+            record_seq(layer_idx, seq + (order, raw_curve), rank)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

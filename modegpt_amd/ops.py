@@ -18,9 +18,9 @@ from ._lib import check
 # the host side of the reports (switches, constants, decoders) lives in reports.py; every name stays reachable as ops.<name>
 from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_MARGIN_FIELDS, RANK_CURVE_KEEP,  # noqa: F401
                       RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
-                      decode_qk_margin, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
-                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled,
-                      rank_curve_enabled, vo_error_enabled, vo_intercept_enabled)
+                      decode_qk_margin, decode_qk_seq_error, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
+                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled, qk_seq_enabled,
+                      qk_seq_select_enabled,                      rank_curve_enabled, vo_error_enabled, vo_intercept_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
        torch.float64: _lib.MDG_F64}
@@ -1308,6 +1308,53 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
         check(lib.mdg_rope_rows(x.data_ptr(), _DT[x.dtype], x.stride(1), B, T, n_heads, head_dim, cos.data_ptr(), sin.data_ptr(),
                                 0 if cos.shape[0] == 1 else T * head_dim, out.data_ptr(), out.stride(1), _stream(x)), "mdg_rope_rows")
     return out
+
+
+def qk_pair_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: torch.Tensor, k_rows: torch.Tensor, B: int, T: int,
+                  n_heads: int, n_kv: int, head_dim: int) -> None:
+    """The within-sequence Q/K statistic of one calibration batch (mdg_qk_pair_accum), enqueued only: for the B sequences of T rows
+    each in q_rows [B*T, n_heads*head_dim] and k_rows [B*T, n_kv*head_dim] (bf16 / f16 / f32, one dtype, last dim contiguous, rows
+    of one pitch; [B, T, width] views of such rows are taken too -- the rows rope_rows writes), in ascending order,
+    pair[h] += G^q (.) (G^k - m m^T / T) and, unless pair_raw is None, pair_raw[h] += G^q (.) G^k.  pair, pair_raw: fp64
+    [n_heads, head_dim, head_dim], contiguous, accumulated into."""
+    _need_gpu(pair, pair_raw, q_rows, k_rows)
+    lib = _lib.load()
+    B, T, n_heads, n_kv, head_dim = int(B), int(T), int(n_heads), int(n_kv), int(head_dim)
+    if B < 0 or T < 0:
+        raise ValueError(f"qk_pair_accum: negative extent (B={B}, T={T})")
+    if n_heads <= 0 or n_kv <= 0 or n_heads % n_kv:
+        raise ValueError(f"qk_pair_accum: n_heads={n_heads} must be a positive multiple of n_kv={n_kv}")
+    if not 1 <= head_dim <= 128:
+        raise ValueError(f"qk_pair_accum: head_dim={head_dim} must be within 1 .. 128")
+    rows = []
+    for name, x, width in (("q_rows", q_rows, n_heads * head_dim), ("k_rows", k_rows, n_kv * head_dim)):
+        x = x.detach()
+        if x.dim() == 3 and tuple(x.shape) == (B, T, width) and (B <= 1 or T == 0 or x.stride(0) == T * x.stride(1)):
+            x = x.as_strided((B * T, width), (x.stride(1), x.stride(2)), x.storage_offset()) if B * T else x.reshape(0, width)
+        if x.dim() != 2 or tuple(x.shape) != (B * T, width):
+            raise ValueError(f"qk_pair_accum: {name} must be [B*T = {B * T}, {width}] (or [B, T, {width}] rows of one pitch), got "
+                             f"{tuple(x.shape)}")
+        if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"qk_pair_accum: {name} must be bf16, f16 or f32, got {x.dtype}")
+        if B * T and x.stride(1) != 1:
+            raise ValueError(f"qk_pair_accum: {name} needs a contiguous last dim, got strides {x.stride()}")
+        rows.append(x)
+    q2, k2 = rows
+    if q2.dtype != k2.dtype or q2.device != k2.device:
+        raise ValueError(f"qk_pair_accum: q_rows and k_rows differ in dtype or device ({q2.dtype} on {q2.device}, {k2.dtype} on {k2.device})")
+    for name, p in (("pair", pair), ("pair_raw", pair_raw)):
+        if p is None and name == "pair_raw":
+            continue
+        if (p is None or p.dtype != torch.float64 or tuple(p.shape) != (n_heads, head_dim, head_dim) or not p.is_contiguous()
+                or p.device != q2.device):
+            raise ValueError(f"qk_pair_accum: {name} must be a contiguous fp64 [{n_heads}, {head_dim}, {head_dim}] on {q2.device}")
+    if B * T == 0:
+        return
+    need = lib.mdg_qk_pair_ws_bytes(B, n_heads, head_dim, int(pair_raw is not None))
+    ws, wsp = _ws(need, q2.device)
+    with torch.cuda.device(q2.device):
+        check(lib.mdg_qk_pair_accum(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
+                                    head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_qk_pair_accum")
 
 
 _ROPE_SCRATCH = {}

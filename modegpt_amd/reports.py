@@ -78,6 +78,22 @@ def qk_rope_select_enabled() -> bool:
     return _switch("MODEGPT_QK_ROPE_SELECT")
 
 
+# The within-sequence, shift-invariant Q/K statistic ("The within-sequence Q/K statistic").  Opt-in:
+# MODEGPT_QK_SEQ=1 makes calibration of a rotary model (Llama, Qwen2) that collects the post-RoPE statistics (MODEGPT_QK_ROPE=1)
+# also accumulate P_h = sum_s G^q_s (.) (G^k_s - m m^T / T) and its uncentred twin per layer (mdg_qk_pair_accum); with
+# MODEGPT_QK_ERROR=1 compress_qk then reports metrics["qk_logit_error_seq"].
+def qk_seq_enabled() -> bool:
+    """MODEGPT_QK_SEQ as it stands when calibration, the cache or compress_qk asks (not frozen at import)."""
+    return _switch("MODEGPT_QK_SEQ")
+
+
+# Opt-in: MODEGPT_QK_SEQ_SELECT=1 makes compress_qk score and order the pair selection on the within-sequence statistic.  Needs the
+# statistic (MODEGPT_QK_SEQ=1 at calibration or in the loaded record); excludes MODEGPT_QK_ROPE_SELECT; no certificate is issued.
+def qk_seq_select_enabled() -> bool:
+    """MODEGPT_QK_SEQ_SELECT as it stands when compress_qk asks (per layer; not frozen at import)."""
+    return _switch("MODEGPT_QK_SEQ_SELECT")
+
+
 def keep_bias_enabled(arch=None) -> bool:
     """Whether the compressors carry the projection biases into the artefacts ("Projection biases"): always
     for Qwen2 / Qwen2.5 (model_type "qwen2": nothing of the reference's to preserve, and dropping q/k/v biases is never right),
@@ -264,6 +280,30 @@ def decode_qk_logit_error(curve_h, curve, rank: int, cols_per_unit: int, terms=N
             "relative_error": _ratio(error, energy), "diagonal_estimate": diag, "diagonal_ratio": _ratio(diag, error),
             "greedy_relative_error": _ratio(greedy, energy), "noise_floor": _ratio(floors, energy),
             "non_monotone": None if any(f is None for f in flags) else any(flags), "heads": heads}
+
+
+def decode_qk_seq_error(curve_h, curve, raw_curve, rank: int, cols_per_unit: int, terms=None, scale=None, greedy_curve=None) -> dict:
+    """decode_qk_logit_error of the curves taken on the within-sequence statistic P, plus the same error on the uncentred P_raw
+    (raw_curve [n_kv][ns + 1], same order): per kv head and for the layer, raw_error = raw_curve[m] and
+    shift_share = 1 - error / raw_error, the share of the within-sequence logit change at the kept rank that depends on the query
+    alone and that softmax therefore cannot see (None where raw_error is not a usable positive number)."""
+    out = decode_qk_logit_error(curve_h, curve, rank, cols_per_unit, terms=terms, scale=scale, greedy_curve=greedy_curve)
+    rv = _mat(raw_curve)
+    if len(rv) != out["n_kv"] or any(len(r) != len(rv[0]) for r in rv) or len(rv[0]) != out["head_dim"] // int(cols_per_unit) + 1:
+        raise ValueError("decode_qk_seq_error: raw_curve must have curve's shape")
+    m = out["units_kept"]
+
+    def share(error, raw):
+        r = _ratio(error, raw)
+        return None if r is None or raw <= 0 else 1.0 - r
+
+    for g, h in enumerate(out["heads"]):
+        h["raw_error"] = _fin(rv[g][m])
+        h["shift_share"] = share(h["error"], rv[g][m])
+    raw = _fin(_total([rv[g][m] for g in range(out["n_kv"])]))
+    out["raw_error"] = raw
+    out["shift_share"] = None if raw is None else share(out["error"], raw)
+    return out
 
 
 # ------------------------------------------------------------------ V/O
