@@ -361,7 +361,7 @@ size_t mdg_ridge_scores_ws_bytes(int64_t n);
 int mdg_ridge_scores(const double* C, int64_t n, int64_t ldc, double ridge, double* scores, double* sens, void* ws,
                      size_t ws_bytes, void* stream);
 /* idx[0..k) = indices of the k smallest scores, ascending index order (topk(largest=False) + sort,
- * compress_mlp.py:45-47).  Ties: lower index first.  NaN ranks as largest. */
+ * compress_mlp.py:45-47).  Ties: lower index first.  NaN ranks as largest.  k == 0: nothing is written, idx may be NULL. */
 int mdg_select_smallest_sorted(const double* scores, int64_t n, int64_t k, int64_t* idx, void* stream);
 /* The certificate of that selection ("rank selections bit-identical" made checkable): with every score known only up to
  * eps * sens[j] (mdg_ridge_scores), can the selected SET differ?  idx [k]: the selection (ascending); out8 (DEVICE, 8 doubles):
@@ -509,7 +509,8 @@ int mdg_mlp_output_error(const double* C, int64_t n, int64_t ldc, const void* Wd
  * mask [n_kv, rank] (int64, score-descending, NOT sorted: compress_qk.py:366-367,418-419,464),
  * q_rows [n_heads*rank] / k_rows [n_kv*rank]: absolute row indices into W_q / W_k for mdg_gather_rows_16.
  * cov_q [n_heads, hd, hd], cov_k [n_kv, hd, hd] fp64.  Scores use ||col_j(sqrt(C + rho I))||^2 = C_jj + rho
- * (exact for symmetric PSD C; DESIGN.md section "Identities").  ROPE modes need even rank. */
+ * (exact for symmetric PSD C; DESIGN.md section "Identities"), clamped at 0; a NaN diagonal entry stays NaN, and a NaN score ranks
+ * first (torch.topk).  Ties: lower index first.  ROPE modes need even rank. */
 int mdg_qk_select(const double* cov_q, const double* cov_k, int n_heads, int n_kv, int hd, double ridge_q,
                   double ridge_k, int rank, int mode, int64_t* mask, int64_t* q_rows, int64_t* k_rows,
                   void* stream);

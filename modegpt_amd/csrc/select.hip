@@ -123,6 +123,10 @@ __global__ __launch_bounds__(256) void gather_rows16_kernel(const unsigned short
   }
 }
 
+// A squared column norm max(C_jj + rho, 0).  NaN stays NaN (fmax would hand back the 0): a NaN diagonal makes a NaN score, which
+// ranks first in qk_select_kernel and leaves the head uncertified in qk_select_margin_kernel.
+__device__ __forceinline__ double clamp0(double x) { return x > 0. ? x : (x != x ? x : 0.); }
+
 // One workgroup per kv head.  Scores from the diagonal identity, then rank-by-count for a score-descending,
 // lower-index-first order (torch.topk).
 __global__ __launch_bounds__(128) void qk_select_kernel(const double* cov_q, const double* cov_k, int n_heads, int n_kv,
@@ -139,15 +143,15 @@ __global__ __launch_bounds__(128) void qk_select_kernel(const double* cov_q, con
     double sc;
     if (mode == MDG_QK_OPT) {
       const double* Cq = cov_q + (int64_t)h * hd * hd;
-      double nq2 = fmax(Cq[tid * hd + tid] + ridge_q, 0.), nk2 = fmax(Ck[tid * hd + tid] + ridge_k, 0.);
+      double nq2 = clamp0(Cq[tid * hd + tid] + ridge_q), nk2 = clamp0(Ck[tid * hd + tid] + ridge_k);
       sc = sqrt(nq2) * sqrt(nk2);  // compress_qk.py:458-461
     } else {
       const int j1 = tid, j2 = tid + hd / 2;
-      double nk1 = fmax(Ck[j1 * hd + j1] + ridge_k, 0.), nk2 = fmax(Ck[j2 * hd + j2] + ridge_k, 0.);
+      double nk1 = clamp0(Ck[j1 * hd + j1] + ridge_k), nk2 = clamp0(Ck[j2 * hd + j2] + ridge_k);
       double acc = 0.;
       for (int q = 0; q < g; q++) {
         const double* Cq = cov_q + (int64_t)(h * g + q) * hd * hd;
-        double nq1 = fmax(Cq[j1 * hd + j1] + ridge_q, 0.), nq2 = fmax(Cq[j2 * hd + j2] + ridge_q, 0.);
+        double nq1 = clamp0(Cq[j1 * hd + j1] + ridge_q), nq2 = clamp0(Cq[j2 * hd + j2] + ridge_q);
         acc += nq1 * nk1 + nq2 * nk2;  // compress_qk.py:360-362 / :414-416
       }
       sc = (mode == MDG_QK_ROPE_GROUPED) ? sqrt(acc) : acc;  // :364
@@ -230,9 +234,9 @@ __device__ __forceinline__ double block_norm_inf(const double* C, int hd, int ve
 // delta = eps_rel |C_jj| + eps_abs (||C||_inf + rho): v[0] centre (the expression qk_select_kernel evaluates), v[1] low, v[2] high.
 __device__ __forceinline__ void norm2_interval(double c, double ridge, double norm, double eps_rel, double eps_abs, double v[3]) {
   const double delta = eps_rel * fabs(c) + eps_abs * (norm + ridge);
-  v[0] = fmax(c + ridge, 0.);
-  v[1] = fmax(c - delta + ridge, 0.);
-  v[2] = fmax(c + delta + ridge, 0.);
+  v[0] = clamp0(c + ridge);
+  v[1] = clamp0(c - delta + ridge);
+  v[2] = clamp0(c + delta + ridge);
 }
 
 // The certificate of qk_select_kernel's selection (mask: what that kernel wrote) against an uncertainty of every diagonal entry of
@@ -355,7 +359,7 @@ using namespace mdg;
 
 extern "C" int mdg_select_smallest_sorted(const double* scores, int64_t n, int64_t k, int64_t* idx, void* stream) {
   MDG_CLEAR();
-  MDG_CHECK_ARG(scores && idx && n > 0 && k >= 0 && k <= n, "mdg_select_smallest_sorted: bad arguments (n=%lld k=%lld)",
+  MDG_CHECK_ARG(scores && (idx || k == 0) && n > 0 && k >= 0 && k <= n, "mdg_select_smallest_sorted: bad arguments (n=%lld k=%lld)",
                 (long long)n, (long long)k);
   if (k == 0) return MDG_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -439,9 +443,9 @@ extern "C" int mdg_qk_select_margin(const double* cov_q, const double* cov_k, in
 extern "C" int mdg_cast_transpose_f64_bf16(const double* in, int64_t rows, int64_t cols, int64_t ld_in, void* out,
                                            int64_t ld_out, void* stream) {
   MDG_CLEAR();
-  MDG_CHECK_ARG(in && out && rows > 0 && cols > 0 && ld_in >= cols && ld_out >= rows, "mdg_cast_transpose: bad arguments");
+  MDG_CHECK_ARG(in && out && rows > 0 && cols > 0 && ld_in >= cols && ld_out >= rows, "mdg_cast_transpose_f64_bf16: bad arguments");
   dim3 grid((unsigned)ceil_div(cols, 32), (unsigned)ceil_div(rows, 32));
-  MDG_CHECK_ARG(grid.y < 65536, "mdg_cast_transpose: too many rows");
+  MDG_CHECK_ARG(grid.y < 65536, "mdg_cast_transpose_f64_bf16: too many rows");
   hipLaunchKernelGGL(cast_transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, rows, cols, ld_in,
                      (bf16_t*)out, ld_out);
   MDG_LAUNCH_CHECK();
