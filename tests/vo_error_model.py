@@ -9,6 +9,8 @@ tests/output_error_model.py.
 errors_fp64 restates the kernel's route -- T = V_g C, the Grams, their lower triangles with the factor 2 -- in plain fp64.
 curve: the eigen-decomposition of G_g = W_v,g (C + rho I) W_v,g^T by tests/eig_ref.jacobi_eigh (long double, or fp64 for the e_cpu of
 the criterion), grouped c_i = max(lambda_i, 0) sum_h ||W_o,h v_i||^2, MHA c_i = max(lambda2_i, 0) from the second decomposition.
+whitening_error, head_map_error, signed_factor_error, mha_gram_error, weyl_bound: the metrics tests/test_gpu_vo_factors.py holds the
+device's own factors and mdg_vo_spectrum's bound to, against `factors(spectra(...))` in long double.
 Nothing here imports the package or needs a GPU."""
 import numpy as np
 
@@ -105,10 +107,11 @@ def factors(spec, Wv, Wo, n_heads, n_kv, hd, r, dtype=LD):
     vs, os_ = [], [None] * n_heads
     for g, (lam, V, lam2, Up) in enumerate(spec):
         S = np.sqrt(np.maximum(lam, 0))
+        VoverS = np.divide(V, S, out=np.zeros_like(V), where=S > 0)          # (a zero eigenvalue's component is dropped, as in vo.hip)
         if lam2 is None:
-            P, Q = (V[:, :r] / S[:r]).T, V[:, :r] * S[:r]
+            P, Q = VoverS[:, :r].T, V[:, :r] * S[:r]
         else:
-            P, Q = Up[:, :r].T @ (V / S).T, (V * S) @ Up[:, :r]
+            P, Q = Up[:, :r].T @ VoverS.T, (V * S) @ Up[:, :r]
         vs.append(P @ Wvl[g * hd:(g + 1) * hd])
         for h in range(g * group, (g + 1) * group):
             os_[h] = Wol[:, h * hd:(h + 1) * hd] @ Q
@@ -119,6 +122,70 @@ def min_relative_gap(lam):
     """min_i (lam_i - lam_i+1) / lam_i of a descending positive spectrum."""
     lam = np.asarray(lam)
     return float(((lam[:-1] - lam[1:]) / lam[:-1]).min())
+
+
+# ---------------------------------------------------------------- the metrics of the factors themselves (tests/test_gpu_vo_factors.py)
+def _heads(v, o, n_heads, n_kv, r):
+    """[(g, h, v_g [r, d], o_h [d, r])] in long double."""
+    v, o = wide(v), wide(o)
+    group = n_heads // n_kv
+    return [(h // group, h, v[h // group * r:(h // group + 1) * r], o[:, h * r:(h + 1) * r]) for h in range(n_heads)]
+
+
+def whitening_error(C, ridge, v, n_kv, r, keep=None):
+    """W: max_g max |v_g M v_g^T - I|, M = C + ridge I in long double.  keep: the components (of every kv head) that count."""
+    M = wide(C) + LD(np.float64(ridge)) * np.eye(C.shape[0], dtype=LD)
+    v = wide(v)
+    keep = np.arange(r) if keep is None else np.asarray(keep)
+    worst = 0.0
+    for g in range(n_kv):
+        vg = v[g * r:(g + 1) * r][keep]
+        worst = max(worst, float(np.abs(vg @ M @ vg.T - np.eye(len(keep), dtype=LD)).max()))
+    return worst
+
+
+def head_map_error(v, o, tv, to, n_heads, n_kv, r):
+    """P: max_h max |o_h v_g - to_h tv_g| / max |to_h tv_g|: the per-head map, which no choice of signs or of a basis inside the kept
+    subspace changes."""
+    worst = 0.0
+    for (g, h, vg, oh), (_, _, tvg, toh) in zip(_heads(v, o, n_heads, n_kv, r), _heads(tv, to, n_heads, n_kv, r)):
+        want = toh @ tvg
+        worst = max(worst, float(np.abs(oh @ vg - want).max() / np.abs(want).max()))
+    return worst
+
+
+def signed_factor_error(v, o, tv, to, n_heads, n_kv, r):
+    """F: component a of kv head g gets the sign of <v_g[a], tv_g[a]>, the same sign on column a of every o_h of the group; then
+    max_a max |s_a v_g[a] - tv_g[a]| / max |tv_g[a]| over the rows of v and likewise over the columns of o."""
+    worst = 0.0
+    for (g, h, vg, oh), (_, _, tvg, toh) in zip(_heads(v, o, n_heads, n_kv, r), _heads(tv, to, n_heads, n_kv, r)):
+        sgn = np.sign((vg * tvg).sum(axis=1))
+        sgn[sgn == 0] = 1
+        ev = np.abs(sgn[:, None] * vg - tvg).max(axis=1) / np.abs(tvg).max(axis=1)
+        eo = np.abs(oh * sgn - toh).max(axis=0) / np.abs(toh).max(axis=0)
+        worst = max(worst, float(ev.max()), float(eo.max()))
+    return worst
+
+
+def mha_gram_error(o, spec, n_heads, r):
+    """L (MHA): max_h max |o_h^T o_h - diag(lam2[:r])| / lam2[0]."""
+    o, worst = wide(o), 0.0
+    for h in range(n_heads):
+        oh, lam2 = o[:, h * r:(h + 1) * r], spec[h][2]
+        worst = max(worst, float(np.abs(oh.T @ oh - np.diag(lam2[:r])).max() / lam2[0]))
+    return worst
+
+
+def relative_gap_at(lam, r):
+    """(lam_r - lam_r+1) / lam_r, 1-based; r = len(lam) needs no gap: inf."""
+    return float("inf") if r >= len(lam) else float((lam[r - 1] - lam[r]) / lam[r - 1])
+
+
+def weyl_bound(C, Wv, n_kv, hd, eps):
+    """mdg_vo_spectrum's out[4] per kv head in long double: eps || |W_v,g| sqrt(diag C) ||_2^2."""
+    s = np.sqrt(np.maximum(np.diagonal(wide(C)), 0))
+    W = np.abs(wide(Wv))
+    return np.array([LD(np.float64(eps)) * (((W[g * hd:(g + 1) * hd] @ s) ** 2).sum()) for g in range(n_kv)], dtype=LD)
 
 
 def weights(d, n_heads, n_kv, hd, wdt, seed=0, grade=1.0):
