@@ -54,7 +54,8 @@ extern "C" {
                                 mdg_nystrom_intercept (first moments of the MLP statistic, the centred refit and its intercept);
                                 added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation);
                                 added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics);
-                                added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic) */
+                                added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic);
+                                added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -476,6 +477,44 @@ size_t mdg_nystrom_rank_curve_ws_bytes(int64_t n, int64_t d);
 int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, const int64_t* order, const void* Wd, int64_t d,
                            int64_t ld_wd, int w_dtype, double eps, double* curve /* [n + 1] */, void* ws,
                            size_t ws_bytes, void* stream);
+
+/* MLP column selection by block-greedy descent on the objective the Nystrom refit minimises (added under ABI 10; not in the
+ * reference, whose ridge-leverage rule never looks at W_d; DESIGN.md section 7, "Greedy MLP selection").
+ * Inputs: C [n, n] fp64 (ldc; only the lower triangle is read -- NaN above the diagonal is harmless -- and C is not modified);
+ * W = W_d [d, n] (ld_wd), MDG_BF16 or MDG_F64 as in mdg_nystrom_down; eps; the rank r, 0 <= r <= n; rounds = T >= 1 (T > r counts as r).
+ * State: M = C + eps I (eps added in fp64, one rounding per diagonal entry, as mdg_nystrom_down adds it); S = {}, R = M, B = W R
+ * [d, n]; J = sum_ij B_ij W_ij = tr(W R W^T), the value mdg_nystrom_rank_curve reports.
+ * Round t = 0 .. T-1 takes m_t = floor(r (t + 1) / T) - floor(r t / T) columns:
+ *   gain         g_j = (sum_i B_ij^2) / R_jj -- the exact drop of J if j alone joined S;
+ *   eligibility  j not in S, R_jj > n 2^-52 M_jj (the accumulated rounding of at most n non-negative downdates of a diagonal
+ *                entry: a condition, not a knob) and g_j finite;
+ *   pick         the m_t eligible columns of largest gain, ties to the lower index; if fewer are eligible, the round is filled with
+ *                unselected ineligible columns in ascending index order -- "dead picks", which join S with no downdate and are counted;
+ *   downdate     with the eligible picks P: K = R[P, P], X = K^-1 R[P, :] by Cholesky of K, R <- R - R[:, P] X, B <- B - B[:, P] X;
+ *   record       objective[t + 1] = sum B o W.
+ * Outputs (DEVICE): order int64 [r], round by round and ascending index within a round (dead picks included); objective fp64
+ * [rounds + 1], objective[0] = tr(W M W^T) -- a round that takes nothing (t >= r) repeats the previous entry; cut fp64
+ * [rounds][2] (optional), per round the smallest picked gain and the largest eligible gain not picked, NaN where there is none
+ * (both NaN for a round that takes nothing); n_dead int64 [1] (optional), the number of dead picks.  T = r is exact forward greedy
+ * selection (orthogonal least squares), T = 1 a one-shot weighted score.
+ * R is never formed: Yt [|S|, n] with R = M - Yt^T Yt, diag(R) as a vector, one panel R[P, :] per round (its product split over K
+ * and summed in split order where a round's picks are few), B downdated right-looking -- about n r^2 + 2 d n r + 2 d n^2 flops in the fp64 GEMM.  Every round is ordinary launches on one stream; no
+ * atomics, every sum in a fixed order: bit-identical from run to run.
+ * r == 0 writes objective[0 .. rounds] = J_0 and nothing else (order may then be NULL).  Non-finite input: order is still r
+ * distinct indices in 0 .. n-1, objectives may be NaN, the status may be MDG_ERR_NOT_PD, nothing is written out of bounds.
+ * ws: mdg_nystrom_greedy_ws_bytes(n, d, r, rounds) bytes, 16-byte aligned: about 8 n' (d + r + max(m, min(n, 2048))) for B, Yt and
+ * the panel, 8 m' (2.25 m + 2 d + r) for K, its inverse and the picked columns (m = ceil(r / T); n', m' rounded up to 16) and
+ * 8 n' (38 + ceil(n / 1024) / 2) for the vectors and the pick's counts, and for T > 1 min(8 m n', 2^24) doubles for the K-split
+ * partial panels: 2.0 GB at n = 14336, d = 4096, r = 10035, T = 32.  0 for arguments the call refuses.
+ * Status: follows the deferred-status convention.  Between mdg_deferred_status_begin / _end the call only enqueues and merges each
+ * round's pivot word into the device status; outside, it SYNCHRONISES once per round and returns MDG_ERR_NOT_PD after the last
+ * round if a pivot of some K failed.  MDG_ERR_BAD_ARG, with a message and before any device work: a null required pointer,
+ * n < 1, d < 1, r < 0, r > n, rounds < 1, ldc < n, ld_wd < n, an unsupported dtype, a workspace that is too small. */
+size_t mdg_nystrom_greedy_ws_bytes(int64_t n, int64_t d, int64_t r, int64_t rounds);
+int mdg_nystrom_greedy_select(const double* C, int64_t n, int64_t ldc, const void* Wd, int64_t d, int64_t ld_wd, int w_dtype,
+                              double eps, int64_t r, int64_t rounds, int64_t* order /* [r] */, double* objective /* [rounds + 1] */,
+                              double* cut /* [rounds][2], optional */, int64_t* n_dead /* device, optional */, void* ws,
+                              size_t ws_bytes, void* stream);
 
 /* What a STORED down projection lost, per output channel, on the calibration statistic (added under ABI 9; not in the reference:
  * compress_mlp.py:52-62 computes the refit and reports nothing about it).  The rank curve above belongs to the fp64 minimiser under

@@ -84,6 +84,8 @@ SIGNATURES = {
                                       _ptr, _sz, _ptr]),
     "mdg_nystrom_rank_curve_ws_bytes": (_sz, [_i64, _i64]),
     "mdg_nystrom_rank_curve": (_i32, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _i32, _f64, _ptr, _ptr, _sz, _ptr]),
+    "mdg_nystrom_greedy_ws_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "mdg_nystrom_greedy_select": (_i32, [_ptr, _i64, _i64, _ptr, _i64, _i64, _i32, _f64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     "mdg_mlp_output_error_ws_bytes": (_sz, [_i64, _i64]),
     "mdg_mlp_output_error": (_i32, [_ptr, _i64, _i64, _ptr, _i64, _i64, _i32, _ptr, _i64, _ptr, _i64, _i64, _i32, _ptr, _ptr, _ptr, _sz,
                                      _ptr]),

@@ -159,6 +159,44 @@ class ModelAdapter(ABC):
                 log.info(f"[MLP] rank curves of {len(usable)} layers: energy-weighted mean relative output error {mean:.3e}")
         return report
 
+    # ---- the greedy MLP selection's own numbers (not upstream; MODEGPT_MLP_GREEDY=T) ----
+    def mlp_greedy(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_nystrom hands over (objective, cut, n_dead, ridge_at_rank, greedy_at_rank) of the layer's greedy selection --
+        ops.nystrom_greedy_select's outputs and, with MODEGPT_RANK_CURVE=1, the two rank curves' values at `rank` (else None) --
+        still on the device."""
+        self._record("_mlp_greedy", int(layer_idx), (tuple(tensors), int(rank)))
+
+    def report_mlp_greedy(self, log=None) -> dict:
+        """Reads the recorded tensors (8 (3 rounds + 4) bytes per layer; call it where the host waits for the chains anyway) and
+        writes metrics["mlp_greedy"][str(layer)] = ops.decode_mlp_greedy(...): the objective before the first round and after
+        each, its last value over the first, the dead picks, the narrowest cut, and the ridge rule's residual energy at the same
+        rank beside this selection's where the rank curve ran.  metrics["mlp_selection"][str(layer)] says that the selection
+        carries no certificate.  WARNS once per layer where the ridge rule's value is the smaller one: more rounds are needed
+        ("Greedy MLP selection")."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self._take("_mlp_greedy")
+        report, selection = {}, {}
+        for layer in sorted(pending):
+            tensors, rank = pending[layer]
+            objective, cut, n_dead, ridge, greedy = (None if t is None else t.detach().cpu() for t in tensors)
+            m = report[layer] = ops.decode_mlp_greedy(objective.tolist(), cut.tolist(), int(n_dead), rank,
+                                                      ridge_at_rank=None if ridge is None else float(ridge),
+                                                      greedy_at_rank=None if greedy is None else float(greedy))
+            selection[layer] = {"statistic": "greedy", "certificate": None, "certified": None,
+                                "reason": "no certificate is issued for a selection by greedy descent on the refit's objective"}
+            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
+            log.info(f"[MLP] Layer {layer}: greedy selection, {m['rounds']} rounds to rank {rank}: objective over total "
+                     f"{show(m['objective_over_total'])}, {m['dead_picks']} dead picks, narrowest cut {show(m['min_cut_gap'])}"
+                     + ("" if m.get("greedy_over_ridge") is None else f"; {m['greedy_over_ridge']:.3g} x the ridge rule's residual"))
+            over = m.get("greedy_over_ridge")
+            if over is not None and over > 1.0:
+                log.warning(f"[MLP] Layer {layer}: the ridge rule's residual energy {m['ridge_at_rank']:.3e} is below the greedy "
+                            f"selection's {m['greedy_at_rank']:.3e} at rank {rank}: {m['rounds']} rounds take correlated columns "
+                            f"together -- more rounds are needed (MODEGPT_MLP_GREEDY)")
+        self._merge_metrics("mlp_greedy", report)
+        self._merge_metrics("mlp_selection", selection)
+        return report
+
     # ---- what the STORED MLP weights lose of the layer's output (not upstream; MODEGPT_OUTPUT_ERROR=1) ----
     def output_error(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_nystrom hands over (q, e, unorm2) of ops.mlp_output_error (d numbers each, still on the device) for layer

@@ -64,7 +64,8 @@ def covariance_error_eps(adapter, n_features: int) -> float:
 @torch.no_grad()
 def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_idx: int, ridge_lambda: float,
                      margin_eps: float = None, margin_out: list = None, curve_out: list = None, error_out: list = None,
-                     bias_out: dict = None, intercept: Tensor = None, intercept_out: list = None, carry_bias: bool = True):
+                     bias_out: dict = None, intercept: Tensor = None, intercept_out: list = None, carry_bias: bool = True,
+                     greedy_out: list = None):
     """compress_mlp.py:28-64.  Returns (W_u'^T [d, r], W_d' [r, d], W_g'^T [d, r] or None, rank), bf16 --
     the same orientation the reference returns (transposed views of the saved layout).
     margin_eps / margin_out (not upstream): with both given, the certificate of the rank selection against an entry-wise relative
@@ -84,12 +85,25 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
     bias_out["down_bias"] = b_d + W_d mu - D^ mu_k for the bf16 tensor D^ this call RETURNS (ops.nystrom_intercept; b_d = the
     projection's bias with carry_bias, else 0; in the bias's dtype, else the weight's), so bias_out is required.  Scores, idx, up and
     gate still come from C and are the same bits with and without it; the curve and the output error are taken on S, where they
-    are the affine map's.  intercept_out: a list -- the two norms (||delta||^2, ||W_d mu||^2, on the device) are appended to it."""
+    are the affine map's.  intercept_out: a list -- the two norms (||delta||^2, ||W_d mu||^2, on the device) are appended to it.
+    MODEGPT_MLP_GREEDY=T (not upstream; DESIGN.md section 7, "Greedy MLP selection"): idx = the sorted picks of T rounds of
+    block-greedy descent on the refit's objective (ops.nystrom_greedy_select on the uncentred C, eps = 1e-6) instead of the ridge
+    rule; up, gate, the refit, the biases and the intercept run on that idx as before.  The ridge scores are then computed only
+    for the rank curve, which runs along the greedy order followed by the unselected columns in ridge-score order; no certificate
+    is computed (margin_out stays empty).  greedy_out: a list -- (objective, cut, n_dead, ridge_at_rank, greedy_at_rank), on the
+    device, are appended to it; the last two are the ridge order's and this order's curve at `rank`, None without the curve."""
     C = C.to(dtype=dtype_p, device=local_device())
     if intercept is not None and bias_out is None:
         raise ValueError("compress_weights: intercept= needs bias_out= to leave the down_bias in")
     rank = int(C.shape[0] * keep_ratio)
-    if margin_out is not None and margin_eps is not None:
+    greedy_rounds = ops.mlp_greedy_rounds()                           # (MODEGPT_MLP_GREEDY: 0 = off, the reference's rule below)
+    scores = greedy = None
+    if greedy_rounds:
+        # block-greedy descent on the refit's own objective, on the uncentred C with the refit's eps; no ridge scores, no certificate
+        W_sel = comps.down_proj.weight.detach().to(device=local_device())
+        greedy = ops.nystrom_greedy_select(C, W_sel, rank, greedy_rounds, eps=1e-6)
+        idx = torch.sort(greedy[0]).values
+    elif margin_out is not None and margin_eps is not None:
         scores, sens = ops.ridge_scores(C, _fl32(ridge_lambda), want_sens=True)
         idx = ops.select_smallest_sorted(scores, rank)
         margin_out.append(ops.select_margin(scores, sens, idx, margin_eps))
@@ -103,15 +117,31 @@ def compress_weights(comps: MLPComponents, C: Tensor, keep_ratio: float, layer_i
         W_g = comps.gate_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
         gate = ops.gather_rows(W_g, idx)                              # W_g[topk, :]               (:50)
     W_d = comps.down_proj.weight.detach().to(device=local_device())              # bf16 as is; fp16/fp32 widen exactly to fp64
+    C_sel = C                                                         # (the statistic every selection is taken on)
     if intercept is not None:
         mu = intercept.to(dtype=dtype_p, device=local_device())
-        C = ops.cov_center(C, mu)                                     # S: from here on the statistic of h - mu (selection is done)
+        C = ops.cov_center(C, mu)                                    # S: from here on the statistic of h - mu (selection is done)
     down = ops.nystrom_down(C, idx, W_d, eps=1e-6)                    # [d, r] bf16                (:52-62)
+    at_rank = (None, None)
     if curve_out is not None and ops.rank_curve_enabled():
         # the selection is a prefix of the ridge-score order (ties: lower index first, NaN last, as select_smallest_sorted ranks them),
         # so the factor of sigma_mlp in that order holds the refit's residual energy at every rank, this layer's included
+        if scores is None:                                            # (the greedy selection skipped them)
+            scores = get_ridge_scores(C_sel, layer_idx=layer_idx, ridge_lambda=ridge_lambda)
         order = torch.argsort(scores, stable=True)
+        if greedy is not None:
+            # the curve runs along the greedy order, then the unselected columns in ridge-score order (a stable sort on "unselected"
+            # keeps that order: no host round trip); the curve along the plain ridge order gives the rule's value at this rank
+            ridge_curve = ops.nystrom_rank_curve(C, order, W_d, eps=1e-6)
+            unselected = torch.ones(C.shape[0], dtype=torch.int64, device=C.device)
+            unselected[greedy[0]] = 0
+            rest = order[torch.argsort(unselected[order], stable=True)][rank:]
+            order = torch.cat((greedy[0], rest))
         curve_out.append(ops.nystrom_rank_curve(C, order, W_d, eps=1e-6))
+        if greedy is not None:
+            at_rank = (ridge_curve[rank], curve_out[-1][rank])
+    if greedy is not None and greedy_out is not None:
+        greedy_out.append(greedy[1:] + at_rank)                      # (objective, cut, n_dead, ridge_at_rank, greedy_at_rank)
     if error_out is not None and ops.output_error_enabled():
         q = ops.mlp_output_error(C, W_d, None, None)                  # the channel's energy: nothing subtracted
         e, unorm2 = ops.mlp_output_error(C, W_d, idx, down, want_unorm2=True)     # ... and what the tensor that is saved loses of it
@@ -154,6 +184,9 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
                                    "the statistics were collected without the switch")
             more = {"intercept": means[layer_idx], "intercept_out": [], "carry_bias": carry}
         biases = {} if carry or more else None
+        record_greedy = getattr(adapter, "mlp_greedy", None)         # (... and without this: the greedy selection reports nothing)
+        if ops.mlp_greedy_rounds():                                  # (MODEGPT_MLP_GREEDY=T; unset: no list, nothing recorded)
+            more["greedy_out"] = []
         if record is None:
             result = compress_weights(comps, cov[layer_idx], keep_ratios[layer_idx], layer_idx=layer_idx,
                                       ridge_lambda=adapter.config.nystrom_ridge, curve_out=curve, error_out=error, bias_out=biases,
@@ -164,13 +197,16 @@ def compress_nystrom(adapter: ModelAdapter, cov, keep_ratios, target_layers, rid
                                       ridge_lambda=adapter.config.nystrom_ridge, margin_eps=eps, margin_out=margin, curve_out=curve,
                                       error_out=error, bias_out=biases, **more)
             # the selection's certificate stays on the device until the adapter next waits for the chain (report_selection_margins)
-            record(layer_idx, margin[0], eps)
+            if margin:                                               # (empty under the greedy selection: it has no certificate)
+                record(layer_idx, margin[0], eps)
+        if more.get("greedy_out") and callable(record_greedy):
+            record_greedy(layer_idx, more["greedy_out"][0], result[3])       # ... and the descent's numbers (report_mlp_greedy)
         if curve:
             record_curve(layer_idx, curve[0], result[3])             # ... and so does the curve (report_rank_curves)
         if error:
             record_error(layer_idx, tuple(error), result[3])         # ... and the stored tensor's output error (report_output_errors)
         record_intercept = getattr(adapter, "mlp_intercept", None)
-        if more and more["intercept_out"] and callable(record_intercept):
+        if more.get("intercept_out") and callable(record_intercept):
             record_intercept(layer_idx, more["intercept_out"][0])    # ... and the intercept's two norms (report_mlp_intercepts)
         return result + (biases or {},)
 

@@ -18,8 +18,8 @@ from ._lib import check
 # the host side of the reports (switches, constants, decoders) lives in reports.py; every name stays reachable as ops.<name>
 from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_MARGIN_FIELDS, RANK_CURVE_KEEP,  # noqa: F401
                       RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
-                      decode_qk_margin, decode_qk_seq_error, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum, keep_bias_enabled,
-                      mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled, qk_seq_enabled,
+                      decode_mlp_greedy, decode_qk_margin, decode_qk_seq_error, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum,
+                      greedy_partition, keep_bias_enabled, mlp_greedy_rounds, mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled, qk_seq_enabled,
                       qk_seq_select_enabled,                      rank_curve_enabled, vo_error_enabled, vo_intercept_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
@@ -899,6 +899,38 @@ def nystrom_rank_curve(Cm: torch.Tensor, order: torch.Tensor, W_down: torch.Tens
                                          _DT[W_down.dtype], float(eps), curve.data_ptr(), wsp, nbytes, _stream(Cm)),
               "mdg_nystrom_rank_curve")
     return curve
+
+
+def nystrom_greedy_select(Cm: torch.Tensor, W_down: torch.Tensor, r: int, rounds: int, eps: float = 1e-6):
+    """(order [r] int64, objective [rounds + 1] fp64, cut [rounds, 2] fp64, n_dead [1] int64), all ON THE DEVICE: the r columns that
+    `rounds` rounds of block-greedy descent on tr(W (M - M[:, S] M_SS^-1 M[S, :]) W^T), M = C + eps I, select
+    (mdg_nystrom_greedy_select; include/modegpt_hip.h states the algorithm) -- order round by round and ascending within a round,
+    the objective before the first round and after each, per round the smallest picked and the largest unpicked eligible gain,
+    and the number of dead picks.  W_down [d, n] as in nystrom_down; only the lower triangle of C is read.  Inside an
+    ops.DeferredStatus the call only enqueues; outside it raises torch.linalg.LinAlgError when a round's pivot block is not
+    positive definite.  Read the numbers with decode_mlp_greedy."""
+    _need_gpu(Cm, W_down)
+    lib = _lib.load()
+    if Cm.dtype != torch.float64 or Cm.dim() != 2 or Cm.shape[0] != Cm.shape[1] or Cm.stride(1) != 1:
+        raise ValueError("C must be a square float64 matrix with unit column stride")
+    W_down = _as_weight(W_down)
+    n, d, r, rounds = Cm.shape[0], W_down.shape[0], int(r), int(rounds)
+    if W_down.dim() != 2 or W_down.shape[1] != n:
+        raise ValueError(f"nystrom_greedy_select: W_down needs {n} columns")
+    if not 0 <= r <= n or rounds < 1:
+        raise ValueError(f"nystrom_greedy_select: need 0 <= r <= {n} and rounds >= 1, got r = {r}, rounds = {rounds}")
+    dev = Cm.device
+    order = torch.empty(r, dtype=torch.int64, device=dev)
+    objective = torch.empty(rounds + 1, dtype=torch.float64, device=dev)
+    cut = torch.full((rounds, 2), float("nan"), dtype=torch.float64, device=dev)
+    n_dead = torch.zeros(1, dtype=torch.int64, device=dev)
+    nbytes = lib.mdg_nystrom_greedy_ws_bytes(n, d, r, rounds)
+    ws, wsp = _ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        check(lib.mdg_nystrom_greedy_select(Cm.data_ptr(), n, Cm.stride(0), W_down.data_ptr(), d, W_down.stride(0), _DT[W_down.dtype],
+                                            float(eps), r, rounds, order.data_ptr() if r else None, objective.data_ptr(), cut.data_ptr(),
+                                            n_dead.data_ptr(), wsp, nbytes, _stream(Cm)), "mdg_nystrom_greedy_select")
+    return order, objective, cut, n_dead
 
 
 def mlp_output_error(Cm: torch.Tensor, W_down: torch.Tensor, idx: Optional[torch.Tensor], down: Optional[torch.Tensor],

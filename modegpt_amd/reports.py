@@ -94,6 +94,31 @@ def qk_seq_select_enabled() -> bool:
     return _switch("MODEGPT_QK_SEQ_SELECT")
 
 
+# Greedy MLP selection (mdg_nystrom_greedy_select; DESIGN.md section 7, "Greedy MLP selection").  Opt-in: MODEGPT_MLP_GREEDY=T makes
+# compress_nystrom select each layer's columns by T rounds of block-greedy descent on the objective the refit minimises, instead of
+# the reference's ridge-leverage rule.  No certificate is issued for that selection.
+def mlp_greedy_rounds() -> int:
+    """MODEGPT_MLP_GREEDY as it stands when compress_nystrom asks (per layer; not frozen at import): 0 (off) when unset or "0",
+    the number of rounds for a positive integer, ValueError for anything else."""
+    raw = os.environ.get("MODEGPT_MLP_GREEDY")
+    if raw is None:
+        return 0
+    rounds = int(raw) if raw.strip().isdigit() else -1
+    if rounds < 0:
+        raise ValueError(f"MODEGPT_MLP_GREEDY must be unset, 0 or a positive number of rounds, got {raw!r}")
+    return rounds
+
+
+def greedy_partition(r: int, rounds: int) -> list:
+    """The picks per round of mdg_nystrom_greedy_select: m_t = floor(r (t + 1) / T) - floor(r t / T) with T = min(rounds, r), then
+    zeros for the rounds beyond r.  Sums to r."""
+    r, rounds = int(r), int(rounds)
+    if r < 0 or rounds < 1:
+        raise ValueError(f"greedy_partition: need r >= 0 and rounds >= 1, got {r}, {rounds}")
+    T = min(rounds, r)
+    return [r * (t + 1) // T - r * t // T for t in range(T)] + [0] * (rounds - T)
+
+
 def keep_bias_enabled(arch=None) -> bool:
     """Whether the compressors carry the projection biases into the artefacts ("Projection biases"): always
     for Qwen2 / Qwen2.5 (model_type "qwen2": nothing of the reference's to preserve, and dropping q/k/v biases is never right),
@@ -167,6 +192,33 @@ def decode_rank_curve(curve, rank: int) -> dict:
     return {"n": n, "rank": rank, "energy": energy, "rel_error": rel(rank), "keep": list(RANK_CURVE_KEEP),
             "rel_error_at_keep": [rel(int(n * k)) for k in RANK_CURVE_KEEP],
             "rank_for_rel_error": {"%g" % t: smallest_rank(t) for t in RANK_CURVE_TARGETS}}
+
+
+def decode_mlp_greedy(objective, cut, n_dead, rank: int, ridge_at_rank=None, greedy_at_rank=None) -> dict:
+    """Host-side reading of nystrom_greedy_select's numbers (lists / CPU tensors: objective [rounds + 1], cut [rounds][2] or None,
+    n_dead a number) for a layer that keeps `rank` columns:
+    rounds, rank, objective (a non-finite entry as None), objective_over_total = objective[-1] / objective[0], dead_picks,
+    min_cut_gap = the smallest (picked - unpicked) / picked over the rounds that have both sides of their cut -- how far the weakest
+    pick stood above the strongest column left behind (None without such a round).  With the rank curves' two values at `rank`
+    (MODEGPT_RANK_CURVE=1): ridge_at_rank (the ridge-leverage rule's residual energy), greedy_at_rank (this selection's, by the
+    rank curve's independent route) and greedy_over_ridge, their ratio.  Non-finite figures become None."""
+    obj = _vec(objective)
+    if len(obj) < 2:
+        raise ValueError("decode_mlp_greedy: objective needs rounds + 1 >= 2 entries")
+    gaps = []
+    for row in ([] if cut is None else _mat(cut)):
+        lo, hi = _fin(row[0]), _fin(row[1])
+        if lo is not None and hi is not None and lo > 0:
+            gaps.append((lo - hi) / lo)
+    out = {"rounds": len(obj) - 1, "rank": int(rank), "objective": [_fin(x) for x in obj],
+           "objective_over_total": _ratio(obj[-1], obj[0]) if _fin(obj[-1]) is not None and obj[-1] >= 0 else None,
+           "dead_picks": int(n_dead), "min_cut_gap": min(gaps) if gaps else None}
+    if ridge_at_rank is not None or greedy_at_rank is not None:
+        ridge = None if ridge_at_rank is None else float(ridge_at_rank)
+        greedy = None if greedy_at_rank is None else float(greedy_at_rank)
+        out.update({"ridge_at_rank": _fin(ridge), "greedy_at_rank": _fin(greedy),
+                    "greedy_over_ridge": _ratio(greedy, ridge) if greedy is not None and greedy >= 0 else None})
+    return out
 
 
 def decode_output_error(e, q, unorm2, eps: float, rank: int, curve=None) -> dict:

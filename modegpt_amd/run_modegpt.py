@@ -116,6 +116,9 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
     report = getattr(adapter, "report_selection_margins", None)     # (a duck-typed adapter has none)
     if report is not None:
         report(logger)                          # certificates of this chunk's MLP rank selections -> metrics["mlp_selection"], warnings
+    report = getattr(adapter, "report_mlp_greedy", None)
+    if report is not None:
+        report(logger)                          # ... the greedy selections' own numbers (MODEGPT_MLP_GREEDY=T) -> metrics["mlp_greedy"], "no certificate" entries
     report = getattr(adapter, "report_rank_curves", None)
     if report is not None:
         report(logger)                          # ... what each of them costs at every rank (MODEGPT_RANK_CURVE=1) -> metrics["mlp_rank_curve"]
