@@ -785,7 +785,26 @@ size_t mdg_sqrt_psd_small_ws_bytes(int64_t n, int64_t batch);
  * clamps never bind on a PSD input; an input it cannot certify (indefinite) falls through to the eigen route.
  * Otherwise: two-sided block Jacobi on 64-wide blocks -- 128x128 pair sub-problems through the LDS Jacobi kernel,
  * rotations applied by batched fp64-MFMA GEMMs, blocks rotated round-robin; evals_out [n], UNSORTED (pre-ridge).
- * Not used by this engine's own VO stage (DESIGN.md "Identities").  SYNCHRONISES once per step / sweep. */
+ * Once ||off||_F <= 1e-13 ||A||_F the accumulated V takes one Newton-Schulz step towards its polar factor,
+ * V (3 I - V^T V) / 2 (orthogonality defect delta -> delta^2), V^T M V is formed afresh and the sweeps go on until the threshold
+ * is met a second time -- the one confirming sweep -- so the result does not carry the drift of the earlier sweeps.  If that
+ * does not happen within 30 sweeps in all: MDG_ERR_NO_CONVERGE.
+ * Not used by this engine's own VO stage (DESIGN.md "Identities").  SYNCHRONISES once per step / sweep.
+ * Only the lower triangle of M is read (ld >= n, any alignment); M is not written; ws may hold anything.  Calls are
+ * bit-reproducible: every sum that steers a route (||A||_F^2, the Newton-Schulz residual, the off-norm) is formed in a fixed
+ * order, no floating-point atomics -- the same input gives the same bits of root, inv_root and evals_out on every call and stream.
+ * A NaN or Inf in the lower triangle is found by the load pass of either route: MDG_ERR_NO_CONVERGE with the message
+ * "mdg_sqrt_psd_large: the input holds non-finite values (NaN or Inf)" (as mdg_sqrt_psd_small's), root, inv_root and evals_out
+ * all NaN.  Block Jacobi then runs no sweep; the Newton-Schulz route reads the flag with its first residual, after one GEMM
+ * and one shift pass, and does not go on to the eigen route.  MDG_ERR_BAD_ARG (nothing launched, outputs untouched) for a null M / root / ws, n <= 0, ld < n,
+ * or ws_bytes < mdg_sqrt_psd_large_ws_bytes(n) -- query it: it holds the per-row partial sums too.
+ * Accuracy (tests/test_gpu_sqrt_large.py, against long double): both routes within max(4 e_ref, n 2^-52) of the truth in the
+ * relative Frobenius norm, e_ref the larger fp64 CPU error of LAPACK's eigh formula and of the route's own algorithm.
+ * That is what was measured.  The CONTRACT of the eigen route is what its stopping rule implies: it returns the function of a
+ * matrix B with ||A - B||_F <= 4 tau ||A||_F, tau = 1e-13 (the off-norm at the stop, and a factor 4 for the rounding of the
+ * rebuild), and for PSD A, B  ||A^1/2 - B^1/2||_F <= ||A - B||_F / (lambda_min(A)^1/2 + lambda_min(B)^1/2), hence
+ *     ||root - truth||_F <= 4 tau ||A||_F / (2 sqrt(max(lambda_min, 0) + ridge))      (ridge times lambda_max if scaled),
+ * also asserted by that test on every eigen-route case (largest share seen: DESIGN.md "Eigensolver accuracy"). */
 size_t mdg_sqrt_psd_large_ws_bytes(int64_t n);
 int mdg_sqrt_psd_large(const double* M, int64_t n, int64_t ld, double ridge, int scaled, double* root,
                        double* inv_root, double* evals_out, void* ws, size_t ws_bytes, void* stream);

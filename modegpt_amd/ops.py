@@ -723,7 +723,9 @@ def sqrt_psd_small(M: torch.Tensor, ridge: float, scaled: bool, want_inverse: bo
 def sqrt_psd_large(M: torch.Tensor, ridge: float, scaled: bool, want_inverse: bool, want_evals: bool = True):
     """sqrt_M for one symmetric matrix of any size: returns (root, inv_root or None, evals unsorted or None).
     With want_evals=False and scaled=False the library takes the GEMM-only Newton-Schulz route for sqrt(M + ridge I)
-    (falling back to block Jacobi by itself when the input is not positive definite); eigenvalues need block Jacobi."""
+    (falling back to block Jacobi by itself when the input is not positive definite); eigenvalues need block Jacobi.
+    Only the lower triangle is read; the same input gives the same bits on every call; a NaN or Inf there raises with the
+    non-finite-input message (include/modegpt_hip.h)."""
     _need_gpu(M)
     lib = _lib.load()
     if M.dim() != 2 or M.shape[0] != M.shape[1]:

@@ -286,7 +286,7 @@ def test_vo_compress_reports_a_poisoned_statistic(ops, dev, n_heads, n_kv, defer
 def test_sqrt_psd_large_rejects_nan(ops, dev, want_evals):
     M = R.wishart(130).copy()
     M[70, 3] = M[3, 70] = NAN
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="non-finite"):          # (return code and NaN-filled outputs: test_gpu_sqrt_large.py)
         ops.sqrt_psd_large(torch.from_numpy(M).to(dev), 1e-5, False, True, want_evals=want_evals)
 
 
