@@ -55,7 +55,8 @@ extern "C" {
                                 added under 10: mdg_vo_intercept_ws_bytes, mdg_vo_intercept (the intercept of the mean-aware V/O truncation);
                                 added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics);
                                 added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic);
-                                added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective) */
+                                added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective);
+                                added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -904,6 +905,58 @@ int mdg_rope_rows(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, 
 size_t mdg_qk_pair_ws_bytes(int64_t B, int n_heads, int hd, int want_raw);
 int mdg_qk_pair_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, int dtype, int64_t B, int64_t T, int n_heads,
                       int n_kv, int hd, double* pair, double* pair_raw, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ causal Q/K statistic
+ * In a causal decoder query i of a sequence multiplies the keys j <= i only, and its softmax normalises over n_i = i + 1 of them.
+ * Dropping the columns D of a head changes logit (i, j) by e_ij = q'_iD . k'_jD; what the attention probabilities of query i see is
+ * the variance of e_ij over the keys j <= i.  Summed over the queries that is 1^T P^c_h[D,D] 1 with, per query head h,
+ *   K_i = sum_{j<=i} k'_j k'_j^T,   m_i = sum_{j<=i} k'_j,   C_i = K_i / n_i - m_i m_i^T / n_i^2,
+ *   P^c_h     = sum over sequences s, tokens i of  (q'_i q'_i^T) (.) C_i          1^T P^c_h[D,D] 1     = sum_s sum_i Var_{j<=i}(e_ij)
+ *   P^c_raw,h = sum over sequences s, tokens i of  (q'_i q'_i^T) (.) K_i / n_i    1^T P^c_raw,h[D,D] 1 = sum_s sum_i mean_{j<=i}(e_ij^2)
+ * ((.): entry-wise product; k' of kv head h / (n_heads / n_kv)).  P^c_h is positive semidefinite.  Additive entries, ABI version
+ * unchanged.  Arguments as mdg_qk_pair_accum:
+ *   q  [B*T, n_heads*hd] rows of pitch ld_q elements, k [B*T, n_kv*hd] rows of pitch ld_k, last dimension contiguous, dtype
+ *      bf16 / f16 / f32 (widened to fp64 exactly on load): the layouts mdg_rope_rows writes.  Rows b*T .. b*T+T-1 are sequence b,
+ *      row b*T its position 0.
+ *   pair, pair_raw  [n_heads, hd, hd] fp64 contiguous, ACCUMULATED INTO; pair_raw may be NULL.  For b = 0 .. B-1 in ascending order
+ *      pair[h] += (sequence b's sum over i of the first expression), pair_raw[h] += (the second); nothing is normalised.
+ *   ws  mdg_qk_causal_ws_bytes(B, n_heads, hd, pair_raw != NULL) = 8 B n_heads hd^2 (twice that with pair_raw) bytes, 8-byte aligned.
+ * The expression evaluated, per sequence, for i = 0 .. T-1 in ascending order, per entry (a, b), in fp64 (fma: one rounding):
+ *   m_i[a] = m_{i-1}[a] + k_i[a]           r = 1.0 / (double)n_i  (correctly rounded)
+ *   K = fma(k_i[a], k_i[b], K)             w = (q_i[a] * q_i[b]) * r                      t = fma(-(m_i[a] * m_i[b]), r, K)
+ *   S = fma(w, t, S)                       S_raw = fma(w, K, S_raw)
+ * from K = S = S_raw = 0, m_{-1} = 0: S accumulates q_a q_b (K - m_a m_b r) r.  Then pair[h][a,b] += S, pair_raw[h][a,b] += S_raw.
+ * hd <= 128: one workgroup per (sequence, query head) keeps K, S and S_raw in registers on the vector ALU (the recurrence is
+ * serial in the token and element-wise in the entry); a second kernel adds the per-sequence sums onto pair, one addition per
+ * sequence in ascending b.  So one call over B sequences gives the bits of B single-sequence calls in that order, and every run
+ * gives the same bits: no atomics, every sum in a fixed order.  Every operation above is symmetric in (a, b), so both triangles
+ * of every output matrix are written and are equal to the bit.  16-byte loads when q (k) is 16-byte aligned and ld_q (ld_k) and hd
+ * are multiples of 16 bytes of elements, element-wise otherwise.  A non-finite element of q in head h reaches pair[h] and
+ * pair_raw[h] only; one of k in kv head v reaches the heads of group v only.  At T == 1, t = fma(-k_a k_b, 1, k_a k_b) = 0, so
+ * pair receives +0.
+ * Accuracy (u = 2^-53; no overflow or underflow; (4T + B + 8) u < 2^-20).  Write kappa_i = sqrt(K_i[a,a] K_i[b,b]) for the exact
+ * prefix Gram, and   A_h[a,b] = sum_s sum_i |q'_ia q'_ib| kappa_i / n_i.   Products of two bf16, f16 or f32 values are exact in
+ * fp64.  To first order in u, at token i with n = n_i:
+ *   K       a chain of n fused additions of exact products, sum_j |k_ja k_jb| <= kappa_i:        |err K|  <=  n u kappa_i
+ *   m_a     a chain of n additions, |m_a| <= sum_j |k_ja| <= sqrt(n K_i[a,a]):                   |err m_a| <= n u sqrt(n K_i[a,a])
+ *   mm      two such factors and one rounding:                                                    |err mm| <= (2n + 1) u n kappa_i
+ *   t       exact value K - m_a m_b / n = n C_i[a,b], |n C_i[a,b]| <= kappa_i (C_i is a covariance with n C_i[a,a] <= K_i[a,a]);
+ *           err K, err mm / n, r's rounding on |m_a m_b| / n <= kappa_i, and the fma's own:      |err t|  <= (3n + 3) u kappa_i
+ *   w       q_a q_b exact, r and the product round:                                               |err w|  <= 2 u |q_a q_b| / n
+ *   w t     |err| <= (3n + 5) u |q_a q_b| kappa_i / n;      w K:  |err| <= (n + 2) u |q_a q_b| kappa_i / n
+ * Summed over the T tokens of a sequence these give (3T + 5) u A_s; each of the T fused accumulations rounds a partial sum of
+ * magnitude <= A_s, T u A_s more: (4T + 5) u A_s per sequence for pair, (2T + 2) u A_s for pair_raw.  The fold onto a pair that
+ * held zero rounds B - 1 times a running sum of at most A.  With the second-order terms (a factor 1 + 2^-19 under the condition
+ * above, inside the constant),
+ *   | pair[h][a,b] - exact |  <=  (4T + B + 8) u A_h[a,b],        c = 4, c' = 8,
+ * and the same bound holds for pair_raw.  The scale is sqrt(K_aa K_bb), not |C_ab|: the centring cancels.  A pair that held p on
+ * entry adds B u |p[a,b]|.
+ * Only enqueues.  MDG_ERR_BAD_ARG (with a message, before any device work): unknown dtype, hd < 1 or > 128, n_heads <= 0,
+ * n_kv <= 0 or n_heads % n_kv != 0, negative extent, ld_q < n_heads*hd or ld_k < n_kv*hd, a NULL q, k, pair or ws of a non-empty
+ * call, ws_bytes below mdg_qk_causal_ws_bytes.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
+size_t mdg_qk_causal_ws_bytes(int64_t B, int n_heads, int hd, int want_raw);
+int mdg_qk_causal_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, int dtype, int64_t B, int64_t T, int n_heads,
+                        int n_kv, int hd, double* pair, double* pair_raw, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

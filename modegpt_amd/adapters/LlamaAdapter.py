@@ -44,7 +44,9 @@ class LlamaAdapter(ModelAdapter):
         parked q and k (ops.rope_rows) and accumulates their per-head Grams in one separate ops.cov_accum_multi call (the reference's
         disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); the launches above are the same either way.  With
         MODEGPT_QK_SEQ=1 beside it the (P, P_raw) lists are on self.qk_pair_sums and the rotated rows also go to ops.qk_pair_accum,
-        one call per layer and batch (the within-sequence Q/K statistic); every other launch is the same either way."""
+        one call per layer and batch (the within-sequence Q/K statistic); every other launch is the same either way.  With
+        MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 the (P^c, P^c_raw) lists are on self.qk_causal_sums and the rotated rows go to
+        ops.qk_causal_accum, likewise (the causal Q/K statistic)."""
         parked = {}
         sums = getattr(self, "mlp_sums", None)
         x_sums = getattr(self, "x_sums", None)
@@ -54,6 +56,9 @@ class LlamaAdapter(ModelAdapter):
         pairs = getattr(self, "qk_pair_sums", None)      # (P, P_raw) lists with MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1, else None
         if pairs is not None and (rope is None or pairs[0][layer_idx] is None):
             pairs = None
+        causals = getattr(self, "qk_causal_sums", None)  # (P^c, P^c_raw) lists with MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1, else None
+        if causals is not None and (rope is None or causals[0][layer_idx] is None):
+            causals = None
         head_dim = self.head_dim
 
         def park(kind):
@@ -99,6 +104,10 @@ class LlamaAdapter(ModelAdapter):
                 q, k = (t if t.dim() == 3 else t.reshape(-1, t.shape[-2], t.shape[-1]) for t in (got["q"], got["k"]))
                 rq = ops.rope_rows(q, pos[0], pos[1], self.n_heads, head_dim, out=ops.rope_scratch(q, "q"))
                 rk = ops.rope_rows(k, pos[0], pos[1], self.n_kv_heads, head_dim, out=ops.rope_scratch(k, "k"))
+                if causals is not None:
+                    # the causal statistic of the batch's B sequences of T rows (each starting at position 0), from the same rows
+                    ops.qk_causal_accum(causals[0][layer_idx], causals[1][layer_idx], rq, rk, q.shape[0], q.shape[1], self.n_heads,
+                                        self.n_kv_heads, head_dim)
                 if pairs is not None:
                     # the within-sequence statistic of the batch's B sequences of T rows, from the same scratch rows
                     ops.qk_pair_accum(pairs[0][layer_idx], pairs[1][layer_idx], rq, rk, q.shape[0], q.shape[1], self.n_heads,

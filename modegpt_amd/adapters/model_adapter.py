@@ -340,7 +340,34 @@ class ModelAdapter(ABC):
             log.info(f"[QK] Layer {layer}: rank {rank}: within-sequence, shift-invariant logit error {show(m['error'])} "
                      f"({show(m['relative_error'])} of its energy); {show(m['shift_share'])} of the uncentred change is invisible to softmax")
         self._merge_metrics("qk_logit_error_seq", seq_report)
+        # ... and on the causal statistic, where compress_qk had it (MODEGPT_QK_CAUSAL=1): the same order, under
+        # metrics["qk_logit_error_causal"], the seq entry's fields plus over_full against the layer's seq entry where there is one
+        pending_causal = self._take("_qk_errors_causal")
+        causal_report = {}
+        for layer in sorted(pending_causal):
+            tensors, rank = pending_causal[layer]
+            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
+            self._record("qk_errors_causal", layer, host)
+            curve_h, curve, terms, scale, g_curve = host[:5]
+            raw_curve = host[7]
+            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
+            m = ops.decode_qk_causal_error(curve_h.tolist(), curve.tolist(), raw_curve.tolist(), rank, cols, terms=terms.tolist(),
+                                           scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist(),
+                                           seq=seq_report.get(layer))
+            m["statistic"] = "within_sequence_causal"
+            causal_report[layer] = m
+            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
+            log.info(f"[QK] Layer {layer}: rank {rank}: causal within-sequence logit error {show(m['error'])} "
+                     f"({show(m['relative_error'])} of its energy); {show(m['shift_share'])} of the uncentred change is invisible to softmax"
+                     + (f"; {show(m['over_full'])} x the figure without the causal mask" if "over_full" in m else ""))
+        self._merge_metrics("qk_logit_error_causal", causal_report)
         return report
+
+    def qk_error_causal(self, layer_idx: int, tensors, rank: int) -> None:
+        """compress_qk hands over ops.qk_rank_curve's outputs on the causal statistic (P^c, ones), the order -- the one of qk_error's
+        tensors -- and the kv-head curve on the uncentred P^c_raw, for layer `layer_idx`; report_qk_errors reads them into
+        metrics["qk_logit_error_causal"]."""
+        self._record("_qk_errors_causal", int(layer_idx), (tuple(tensors), int(rank)))
 
     def qk_error_seq(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_qk hands over ops.qk_rank_curve's outputs on the within-sequence statistic (P, ones), the order -- the one of
@@ -355,7 +382,8 @@ class ModelAdapter(ABC):
 
     def qk_selection_statistic(self, layer_idx: int, statistic: str) -> None:
         """compress_qk says which statistic the layer's pair selection was scored on ("pre_rope" / "post_rope") when the run carries
-        post-RoPE statistics, or "within_sequence" under MODEGPT_QK_SEQ_SELECT=1; report_attention_margins writes it to
+        post-RoPE statistics, "within_sequence" under MODEGPT_QK_SEQ_SELECT=1 or "within_sequence_causal" under
+        MODEGPT_QK_CAUSAL_SELECT=1; report_attention_margins writes it to
         metrics["qk_selection"][layer]["statistic"]."""
         self._record("_qk_selection_statistics", int(layer_idx), str(statistic))
 
@@ -408,6 +436,10 @@ class ModelAdapter(ABC):
                 # computed on an error model that does not cover the centring's cancellation
                 report["qk"][layer] = {"statistic": "within_sequence", "certificate": None, "certified": None, "order_certified": None,
                                        "reason": "no certificate is issued for a selection on the within-sequence statistic"}
+            elif statistics[layer] == "within_sequence_causal" and layer not in report["qk"]:         # MODEGPT_QK_CAUSAL_SELECT=1: likewise
+                report["qk"][layer] = {"statistic": "within_sequence_causal", "certificate": None, "certified": None,
+                                       "order_certified": None,
+                                       "reason": "no certificate is issued for a selection on the causal within-sequence statistic"}
         for kind, key in (("qk", "qk_selection"), ("vo", "vo_spectrum")):       # (only the non-empty kinds)
             self._merge_metrics(key, report[kind])
         return report

@@ -23,6 +23,8 @@ One directory, one self-contained record per layer, so chunks of layers, target_
                                            Q/K statistic P and its uncentred twin, raw little-endian fp64, full [n_heads, head_dim,
                                            head_dim] -- the format and sidecar entry fields of layer_<i>_q.f64 (files.qk_pair,
                                            files.qk_pair_raw), under the rules of the post-RoPE files, with their own switch
+    layer_<i>_qk_causal.f64, _qk_causal_raw.f64  only with MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 on a rotary model: the causal
+                                           Q/K statistic P^c and its uncentred twin, likewise (files.qk_causal, files.qk_causal_raw)
     layer_<i>.json                         the sidecar, written LAST: the commit marker -- a layer without it does not exist
     bi_scores.json                         the Block-Influence scores of all layers, written by the rank that computed them
 
@@ -59,8 +61,10 @@ FULL_KINDS = ("q", "k")          # per-head statistics: full (tiny)
 KINDS = PACKED_KINDS + FULL_KINDS
 ROPE_KINDS = {"q_rope": "q", "k_rope": "k"}      # MODEGPT_QK_ROPE=1: post-RoPE statistic -> the statistic whose shape and layout it has
 PAIR_KINDS = {"qk_pair": "q", "qk_pair_raw": "q"}   # MODEGPT_QK_SEQ=1: the within-sequence Q/K statistic and its uncentred twin, likewise
-EXTRA_KINDS = {**ROPE_KINDS, **PAIR_KINDS}
-EXTRA_SWITCH = {**{k: "MODEGPT_QK_ROPE=1" for k in ROPE_KINDS}, **{k: "MODEGPT_QK_SEQ=1" for k in PAIR_KINDS}}
+CAUSAL_KINDS = {"qk_causal": "q", "qk_causal_raw": "q"}   # MODEGPT_QK_CAUSAL=1: the causal Q/K statistic and its uncentred twin, likewise
+EXTRA_KINDS = {**ROPE_KINDS, **PAIR_KINDS, **CAUSAL_KINDS}
+EXTRA_SWITCH = {**{k: "MODEGPT_QK_ROPE=1" for k in ROPE_KINDS}, **{k: "MODEGPT_QK_SEQ=1" for k in PAIR_KINDS},
+                **{k: "MODEGPT_QK_CAUSAL=1" for k in CAUSAL_KINDS}}
 ARCH_FIELDS = ("arch", "d_model", "n_inner", "n_heads", "n_kv_heads", "head_dim", "n_layers", "dtype")
 BI_FILE = "bi_scores.json"
 
@@ -210,7 +214,7 @@ def read_mean_file(directory: str, layer: int, entry: dict, kind: str = MEAN_KIN
 
 # ------------------------------------------------------------------ host half: the post-RoPE statistics (MODEGPT_QK_ROPE=1)
 def validate_rope_entry(meta: dict, arch: dict, layer: int, kind: str) -> dict:
-    """Metadata alone: the record must carry files.<kind> (kind "q_rope" / "k_rope", or "qk_pair" / "qk_pair_raw") with the shape of
+    """Metadata alone: the record must carry files.<kind> (kind "q_rope" / "k_rope", "qk_pair" / "qk_pair_raw" or "qk_causal" / "qk_causal_raw") with the shape of
     files.q / files.k.  Returns the entry."""
     entry = meta.get("files", {}).get(kind)
     if not isinstance(entry, dict):
@@ -436,18 +440,19 @@ def _staging_for(arch: dict, device) -> Staging:
 
 
 def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arch: dict, calibration: dict, model: str,
-                weights: dict, certificates: dict, mean=None, x_mean=None, rope=None, pair=None) -> dict:
+                weights: dict, certificates: dict, mean=None, x_mean=None, rope=None, pair=None, causal=None) -> dict:
     """One layer's record from its four device tensors ({"mlp", "x": [n, n]; "q", "k": [heads, hd, hd]}): data files first, the
     sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  mean: the layer's
     activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too; x_mean: the
     mean of x (fp64 [d_model], MODEGPT_VO_INTERCEPT=1) -- likewise, files.x_mean; rope: {"q_rope", "k_rope": [heads, hd, hd]}, the
     post-RoPE statistics (MODEGPT_QK_ROPE=1) -- their files and entries follow those of the four, through the same staging; pair:
-    {"qk_pair", "qk_pair_raw": [n_heads, hd, hd]}, the within-sequence Q/K statistic (MODEGPT_QK_SEQ=1) -- likewise."""
+    {"qk_pair", "qk_pair_raw": [n_heads, hd, hd]}, the within-sequence Q/K statistic (MODEGPT_QK_SEQ=1) -- likewise; causal:
+    {"qk_causal", "qk_causal_raw": [n_heads, hd, hd]}, the causal Q/K statistic (MODEGPT_QK_CAUSAL=1) -- likewise."""
     import torch
     from . import ops
     os.makedirs(directory, exist_ok=True)
     files, waiting = {}, None
-    extra = dict(rope or {}, **(pair or {}))
+    extra = dict(rope or {}, **(pair or {}), **(causal or {}))
     tensors = dict(tensors, **extra)
 
     def finish(item):
@@ -478,13 +483,14 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
 
 
 def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None, x_mean=None, rope=None,
-               pair=None) -> dict:
+               pair=None, causal=None) -> dict:
     """The inverse: checks the sidecar against `expect`, fills the four device tensors, returns the sidecar.  The file of a
     statistic is read while the one before it is copied to the device and unpacked.  mean: an fp64 [n_inner] device tensor to fill
     from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1), x_mean: an fp64 [d_model] one to fill from layer_<i>_x_mean.f64
     (MODEGPT_VO_INTERCEPT=1), rope: {"q_rope", "k_rope": fp64 [heads, hd, hd] device tensors} to fill from layer_<i>_q_rope.f64 /
     _k_rope.f64 (MODEGPT_QK_ROPE=1), pair: {"qk_pair", "qk_pair_raw": fp64 [n_heads, hd, hd] device tensors} to fill from
-    layer_<i>_qk_pair.f64 / _qk_pair_raw.f64 (MODEGPT_QK_SEQ=1); a record without the entry is refused before any data is read."""
+    layer_<i>_qk_pair.f64 / _qk_pair_raw.f64 (MODEGPT_QK_SEQ=1), causal: {"qk_causal", "qk_causal_raw": likewise} to fill from
+    layer_<i>_qk_causal.f64 / _qk_causal_raw.f64 (MODEGPT_QK_CAUSAL=1); a record without the entry is refused before any data is read."""
     import torch
     from . import ops
     meta = read_sidecar(directory, layer)
@@ -493,7 +499,7 @@ def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expe
         mean_entry = validate_mean_entry(meta, expect["arch"]["n_inner"], layer)
     if x_mean is not None:
         x_mean_entry = validate_mean_entry(meta, expect["arch"]["d_model"], layer, kind=X_MEAN_KIND)
-    extra = dict(rope or {}, **(pair or {}))
+    extra = dict(rope or {}, **(pair or {}), **(causal or {}))
     for kind in extra:
         validate_rope_entry(meta, expect["arch"], layer, kind)
     tensors = dict(tensors, **extra)
@@ -549,13 +555,17 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
     x_means = getattr(adapter, "x_means", None) if ops.vo_intercept_enabled() else None         # (likewise)
     if ops.vo_intercept_enabled() and targets and (x_means is None or any(x_means[i] is None for i in targets)):
         raise RuntimeError("MODEGPT_VO_INTERCEPT=1 but the adapter carries no input means (adapter.x_means) to save")
-    from .calibration import qk_rope_collected, qk_seq_collected
+    from .calibration import qk_causal_collected, qk_rope_collected, qk_seq_collected
     rope = getattr(adapter, "qk_rope_stats", None) if qk_rope_collected(adapter) else None       # (likewise)
     if qk_rope_collected(adapter) and targets and (rope is None or any(rope[0][i] is None or rope[1][i] is None for i in targets)):
         raise RuntimeError("MODEGPT_QK_ROPE=1 but the adapter carries no post-RoPE statistics (adapter.qk_rope_stats) to save")
     pairs = getattr(adapter, "qk_pair_stats", None) if qk_seq_collected(adapter) else None       # (likewise)
     if qk_seq_collected(adapter) and targets and (pairs is None or any(pairs[0][i] is None or pairs[1][i] is None for i in targets)):
         raise RuntimeError("MODEGPT_QK_SEQ=1 but the adapter carries no within-sequence statistic (adapter.qk_pair_stats) to save")
+    causals = getattr(adapter, "qk_causal_stats", None) if qk_causal_collected(adapter) else None   # (likewise)
+    if qk_causal_collected(adapter) and targets and (causals is None or
+                                                     any(causals[0][i] is None or causals[1][i] is None for i in targets)):
+        raise RuntimeError("MODEGPT_QK_CAUSAL=1 but the adapter carries no causal statistic (adapter.qk_causal_stats) to save")
     if targets:
         staging = _staging_for(arch, cov["mlp"][targets[0]].device)
         for i in targets:
@@ -565,7 +575,8 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
                                weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i],
                                x_mean=None if x_means is None else x_means[i],
                                rope=None if rope is None else {"q_rope": rope[0][i], "k_rope": rope[1][i]},
-                               pair=None if pairs is None else {"qk_pair": pairs[0][i], "qk_pair_raw": pairs[1][i]})
+                               pair=None if pairs is None else {"qk_pair": pairs[0][i], "qk_pair_raw": pairs[1][i]},
+                               causal=None if causals is None else {"qk_causal": causals[0][i], "qk_causal_raw": causals[1][i]})
             nbytes += sum(e["bytes"] for e in meta["files"].values())
         torch.cuda.synchronize(staging.device)
     if bi_scores is not None and getattr(adapter, "calib_want_bi", True):
@@ -596,6 +607,7 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
     adapter.x_means = sig.x_sums               # (MODEGPT_VO_INTERCEPT=1: likewise)
     adapter.qk_rope_stats = sig.qk_rope        # (MODEGPT_QK_ROPE=1 on a rotary model: likewise, from the q_rope / k_rope files)
     adapter.qk_pair_stats = sig.qk_pairs       # (MODEGPT_QK_SEQ=1 beside it: likewise, from the qk_pair / qk_pair_raw files)
+    adapter.qk_causal_stats = sig.qk_causals   # (MODEGPT_QK_CAUSAL=1 beside it: likewise, from the qk_causal / qk_causal_raw files)
     if targets:
         staging = _staging_for(expect["arch"], sig.lists["mlp"][targets[0]].device)
         for i in targets:
@@ -604,7 +616,9 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
                                   mean=None if sig.mlp_sums is None else sig.mlp_sums[i],
                                   x_mean=None if sig.x_sums is None else sig.x_sums[i],
                                   rope=None if sig.q_rope is None else {"q_rope": sig.q_rope[i], "k_rope": sig.k_rope[i]},
-                                  pair=None if sig.qk_pair is None else {"qk_pair": sig.qk_pair[i], "qk_pair_raw": sig.qk_pair_raw[i]})
+                                  pair=None if sig.qk_pair is None else {"qk_pair": sig.qk_pair[i], "qk_pair_raw": sig.qk_pair_raw[i]},
+                                  causal=None if sig.qk_causal is None else {"qk_causal": sig.qk_causal[i],
+                                                                             "qk_causal_raw": sig.qk_causal_raw[i]})
         torch.cuda.synchronize(staging.device)
     adapter.bi_scores = bi_scores
     cert = merge_certificates([m["certificates"] for m in metas.values()])

@@ -76,6 +76,31 @@ def qk_seq_collected(adapter: ModelAdapter, log=None) -> bool:
     return False
 
 
+def qk_causal_collected(adapter: ModelAdapter, log=None) -> bool:
+    """Whether this run collects (or loads) the causal Q/K statistic P^c, P^c_raw: MODEGPT_QK_CAUSAL=1 on a Llama / Qwen2 adapter
+    that collects the post-RoPE statistics too -- the statistic is taken on the rotated rows the post-RoPE flush produces, so
+    MODEGPT_QK_CAUSAL=1 without MODEGPT_QK_ROPE=1 raises there.  Independent of MODEGPT_QK_SEQ.  On any other architecture nothing
+    is collected and, given a logger, one line says why."""
+    if not ops.qk_causal_enabled():
+        return False
+    arch = adapter.arch
+    if arch in QK_ROPE_ARCHS:
+        if not ops.qk_rope_enabled():
+            raise RuntimeError("MODEGPT_QK_CAUSAL=1 needs MODEGPT_QK_ROPE=1: the causal Q/K statistic is accumulated from the "
+                               "post-RoPE rows, which are only produced when the post-RoPE statistics are collected")
+        if adapter.head_dim > 128:
+            raise RuntimeError(f"MODEGPT_QK_CAUSAL=1: head_dim {adapter.head_dim} > 128 is not supported by mdg_qk_causal_accum")
+        return True
+    if log is not None:
+        if "qwen" in arch:
+            log.warning(f"MODEGPT_QK_CAUSAL=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
+                        "RMSNorm), so the dropped-column identity of the causal statistic does not hold; nothing is collected")
+        else:
+            log.info(f"MODEGPT_QK_CAUSAL=1: {arch} has no rotary embedding and separate q / k hooks; the causal statistic is "
+                     "not collected for it")
+    return False
+
+
 class SigmaBuffers:
     """The four statistic families of the target layers (shapes: src/calibration.py:82-96)."""
 
@@ -123,6 +148,21 @@ class SigmaBuffers:
                 self.qk_pair[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
                 self.qk_pair_raw[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
 
+        # the causal Q/K statistic and its uncentred twin (MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 on a rotary model): per layer
+        # [n_heads, hd, hd], both triangles; None without it
+        self.qk_causal: Optional[List[Optional[torch.Tensor]]] = None
+        self.qk_causal_raw: Optional[List[Optional[torch.Tensor]]] = None
+        if qk_causal_collected(adapter, logger):
+            self.qk_causal, self.qk_causal_raw = [None] * L, [None] * L
+            for i in self.layers:
+                self.qk_causal[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
+                self.qk_causal_raw[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
+
+    @property
+    def qk_causals(self):
+        """(qk_causal, qk_causal_raw), or None without the switch."""
+        return None if self.qk_causal is None else (self.qk_causal, self.qk_causal_raw)
+
     @property
     def qk_pairs(self):
         """(qk_pair, qk_pair_raw), or None without the switch."""
@@ -152,6 +192,12 @@ class SigmaBuffers:
                 pair_scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER ** 2)
                 self.qk_pair[i].mul_(pair_scale)
                 self.qk_pair_raw[i].mul_(pair_scale)
+            if self.qk_causal is not None:
+                # every query row carries a mean over its keys already, so ONE token normaliser: the mean over the queries of the
+                # variance over the keys each can see, in the unit of the within-sequence figure (one rounding per entry)
+                causal_scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER)
+                self.qk_causal[i].mul_(causal_scale)
+                self.qk_causal_raw[i].mul_(causal_scale)
 
 
 class BlockInfluence:
@@ -225,6 +271,7 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.x_sums = sig.x_sums                          # (likewise; None without MODEGPT_VO_INTERCEPT=1)
     adapter.qk_rope_sums = sig.qk_rope                   # (likewise; None without MODEGPT_QK_ROPE=1 on a rotary model)
     adapter.qk_pair_sums = sig.qk_pairs                  # (likewise; None without MODEGPT_QK_SEQ=1 beside it)
+    adapter.qk_causal_sums = sig.qk_causals              # (likewise; None without MODEGPT_QK_CAUSAL=1 beside it)
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -268,6 +315,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.qk_rope_stats = sig.qk_rope                  # (sigma_q', sigma_k') lists (None without the switch): compress_qk reads them
     adapter.qk_pair_sums = None
     adapter.qk_pair_stats = sig.qk_pairs                 # (P, P_raw) lists (None without the switch): compress_qk reads them
+    adapter.qk_causal_sums = None
+    adapter.qk_causal_stats = sig.qk_causals             # (P^c, P^c_raw) lists (None without the switch): compress_qk reads them
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

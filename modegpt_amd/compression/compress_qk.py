@@ -82,7 +82,9 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
         tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in rope)
     # MODEGPT_QK_ROPE_SELECT=1: the selection, its certificate and the report's order take (sigma_q', sigma_k') instead of the
     # reference's pre-RoPE pair, same mode and ridges; everything downstream of the mask is unchanged
-    by_rope = ops.qk_rope_select_enabled()
+    # (which statistic the selection is scored on; two select switches set together are refused here, before anything else)
+    statistic = ops.qk_select_statistic()
+    by_rope = statistic == "rope"
     if by_rope and rope is None:
         raise RuntimeError(f"MODEGPT_QK_ROPE_SELECT=1 but layer {layer_idx} has no post-RoPE statistics (adapter.qk_rope_stats): "
                            "calibrate, or load a record saved, with MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
@@ -93,23 +95,34 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     # MODEGPT_QK_SEQ_SELECT=1: the selection and the report's order take (P, ones) with ridges 0 -- a unit's score is then the
     # diagonal of the within-sequence objective 1^T P[D,D] 1, summed over the group.  No certificate: mdg_qk_select_margin's error
     # model does not cover the cancellation in the centring.  Everything downstream of the mask is unchanged.
-    by_seq = ops.qk_seq_select_enabled()
-    if by_seq and by_rope:
-        raise RuntimeError("MODEGPT_QK_SEQ_SELECT=1 and MODEGPT_QK_ROPE_SELECT=1 are both set: the pair selection takes one statistic")
+    by_seq = statistic == "seq"
     if by_seq and pair is None:
         raise RuntimeError(f"MODEGPT_QK_SEQ_SELECT=1 but layer {layer_idx} has no within-sequence statistic (adapter.qk_pair_stats): "
                            "calibrate, or load a record saved, with MODEGPT_QK_SEQ=1 and MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
-    ones = torch.ones(n_kv, head_dim, head_dim, dtype=dtype_p, device=local_device()) if pair is not None else None
-    if by_seq:
+    # the causal statistic of the layer (MODEGPT_QK_CAUSAL=1 at calibration or in the loaded record): (P^c, P^c_raw), or None
+    causal = getattr(adapter, "qk_causal_stats", None)
+    causal = None if causal is None or causal[0][layer_idx] is None or causal[1][layer_idx] is None else \
+        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in causal)
+    # MODEGPT_QK_CAUSAL_SELECT=1: the selection and the report's order take (P^c, ones) with ridges 0, as under MODEGPT_QK_SEQ_SELECT
+    # -- a unit's score is the diagonal of the causal objective 1^T P^c[D,D] 1, summed over the group.  No certificate either.
+    by_causal = statistic == "causal"
+    if by_causal and causal is None:
+        raise RuntimeError(f"MODEGPT_QK_CAUSAL_SELECT=1 but layer {layer_idx} has no causal statistic (adapter.qk_causal_stats): "
+                           "calibrate, or load a record saved, with MODEGPT_QK_CAUSAL=1 and MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
+    ones = torch.ones(n_kv, head_dim, head_dim, dtype=dtype_p, device=local_device()) if pair is not None or causal is not None \
+        else None
+    if by_causal:
+        sq, sk, sel_ridges = causal[0], ones, (0.0, 0.0)
+    elif by_seq:
         sq, sk, sel_ridges = pair[0], ones, (0.0, 0.0)
     else:
         (sq, sk), sel_ridges = (rope if by_rope else (cq, ck)), (ridge_q, ridge_k)
     mask, q_rows, k_rows = ops.qk_select(sq, sk, rank, mode, *sel_ridges)
     record = getattr(adapter, "attention_margin", None)           # (a duck-typed adapter without it: no certificate)
-    if by_seq:
+    if by_seq or by_causal:
         note = getattr(adapter, "qk_selection_statistic", None)
         if note is not None:                          # (report_attention_margins writes the entry, with the certificate's absence)
-            note(layer_idx, "within_sequence")
+            note(layer_idx, "within_sequence_causal" if by_causal else "within_sequence")
     elif record is not None:
         # the selection's certificate stays on the device until the adapter next waits for the stream (report_attention_margins)
         eps_rel = attention_error_eps(adapter)
@@ -138,6 +151,13 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
             seq = ops.qk_rank_curve(pair[0], ones, mode, 0.0, 0.0, order)
             raw_curve = ops.qk_rank_curve(pair[1], ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
             record_seq(layer_idx, seq + (order, raw_curve), rank)
+        record_causal = getattr(adapter, "qk_error_causal", None)
+        if causal is not None and record_causal is not None:
+            # ... and on the causal statistic, the same way: 1^T P^c[D,D] 1 is the variance of the logit change over the keys each
+            # query can see, summed over the queries (then, on P^c_raw, the mean square over them)
+            cau = ops.qk_rank_curve(causal[0], ones, mode, 0.0, 0.0, order)
+            raw_curve = ops.qk_rank_curve(causal[1], ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
+            record_causal(layer_idx, cau + (order, raw_curve), rank)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

@@ -20,6 +20,7 @@ from .reports import (MARGIN_FIELDS, OUTPUT_ERROR_LEVELS, QK_ERROR_TARGETS, QK_M
                       RANK_CURVE_TARGETS, VO_ERROR_TARGETS, VO_SPECTRUM_FIELDS, decode_margin, decode_output_error, decode_qk_logit_error,
                       decode_mlp_greedy, decode_qk_margin, decode_qk_seq_error, decode_rank_curve, decode_vo_output_error, decode_vo_spectrum,
                       greedy_partition, keep_bias_enabled, mlp_greedy_rounds, mlp_intercept_enabled, output_error_enabled, qk_error_enabled, qk_rope_enabled, qk_rope_select_enabled, qk_seq_enabled,
+                      qk_causal_enabled, qk_causal_select_enabled, qk_select_statistic, decode_qk_causal_error,
                       qk_seq_select_enabled,                      rank_curve_enabled, vo_error_enabled, vo_intercept_enabled)
 
 _DT = {torch.bfloat16: _lib.MDG_BF16, torch.float16: _lib.MDG_F16, torch.float32: _lib.MDG_F32,
@@ -1344,6 +1345,42 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
     return out
 
 
+def _qk_seq_rows(fn: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim):
+    """The argument checks qk_pair_accum and qk_causal_accum share (messages under the caller's name `fn`); returns the two row
+    matrices as [B*T, width] views and the extents as ints."""
+    _need_gpu(pair, pair_raw, q_rows, k_rows)
+    B, T, n_heads, n_kv, head_dim = int(B), int(T), int(n_heads), int(n_kv), int(head_dim)
+    if B < 0 or T < 0:
+        raise ValueError(f"{fn}: negative extent (B={B}, T={T})")
+    if n_heads <= 0 or n_kv <= 0 or n_heads % n_kv:
+        raise ValueError(f"{fn}: n_heads={n_heads} must be a positive multiple of n_kv={n_kv}")
+    if not 1 <= head_dim <= 128:
+        raise ValueError(f"{fn}: head_dim={head_dim} must be within 1 .. 128")
+    rows = []
+    for name, x, width in (("q_rows", q_rows, n_heads * head_dim), ("k_rows", k_rows, n_kv * head_dim)):
+        x = x.detach()
+        if x.dim() == 3 and tuple(x.shape) == (B, T, width) and (B <= 1 or T == 0 or x.stride(0) == T * x.stride(1)):
+            x = x.as_strided((B * T, width), (x.stride(1), x.stride(2)), x.storage_offset()) if B * T else x.reshape(0, width)
+        if x.dim() != 2 or tuple(x.shape) != (B * T, width):
+            raise ValueError(f"{fn}: {name} must be [B*T = {B * T}, {width}] (or [B, T, {width}] rows of one pitch), got "
+                             f"{tuple(x.shape)}")
+        if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"{fn}: {name} must be bf16, f16 or f32, got {x.dtype}")
+        if B * T and x.stride(1) != 1:
+            raise ValueError(f"{fn}: {name} needs a contiguous last dim, got strides {x.stride()}")
+        rows.append(x)
+    q2, k2 = rows
+    if q2.dtype != k2.dtype or q2.device != k2.device:
+        raise ValueError(f"{fn}: q_rows and k_rows differ in dtype or device ({q2.dtype} on {q2.device}, {k2.dtype} on {k2.device})")
+    for name, p in (("pair", pair), ("pair_raw", pair_raw)):
+        if p is None and name == "pair_raw":
+            continue
+        if (p is None or p.dtype != torch.float64 or tuple(p.shape) != (n_heads, head_dim, head_dim) or not p.is_contiguous()
+                or p.device != q2.device):
+            raise ValueError(f"{fn}: {name} must be a contiguous fp64 [{n_heads}, {head_dim}, {head_dim}] on {q2.device}")
+    return q2, k2, B, T, n_heads, n_kv, head_dim
+
+
 def qk_pair_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: torch.Tensor, k_rows: torch.Tensor, B: int, T: int,
                   n_heads: int, n_kv: int, head_dim: int) -> None:
     """The within-sequence Q/K statistic of one calibration batch (mdg_qk_pair_accum), enqueued only: for the B sequences of T rows
@@ -1351,44 +1388,33 @@ def qk_pair_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: 
     of one pitch; [B, T, width] views of such rows are taken too -- the rows rope_rows writes), in ascending order,
     pair[h] += G^q (.) (G^k - m m^T / T) and, unless pair_raw is None, pair_raw[h] += G^q (.) G^k.  pair, pair_raw: fp64
     [n_heads, head_dim, head_dim], contiguous, accumulated into."""
-    _need_gpu(pair, pair_raw, q_rows, k_rows)
-    lib = _lib.load()
-    B, T, n_heads, n_kv, head_dim = int(B), int(T), int(n_heads), int(n_kv), int(head_dim)
-    if B < 0 or T < 0:
-        raise ValueError(f"qk_pair_accum: negative extent (B={B}, T={T})")
-    if n_heads <= 0 or n_kv <= 0 or n_heads % n_kv:
-        raise ValueError(f"qk_pair_accum: n_heads={n_heads} must be a positive multiple of n_kv={n_kv}")
-    if not 1 <= head_dim <= 128:
-        raise ValueError(f"qk_pair_accum: head_dim={head_dim} must be within 1 .. 128")
-    rows = []
-    for name, x, width in (("q_rows", q_rows, n_heads * head_dim), ("k_rows", k_rows, n_kv * head_dim)):
-        x = x.detach()
-        if x.dim() == 3 and tuple(x.shape) == (B, T, width) and (B <= 1 or T == 0 or x.stride(0) == T * x.stride(1)):
-            x = x.as_strided((B * T, width), (x.stride(1), x.stride(2)), x.storage_offset()) if B * T else x.reshape(0, width)
-        if x.dim() != 2 or tuple(x.shape) != (B * T, width):
-            raise ValueError(f"qk_pair_accum: {name} must be [B*T = {B * T}, {width}] (or [B, T, {width}] rows of one pitch), got "
-                             f"{tuple(x.shape)}")
-        if x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise ValueError(f"qk_pair_accum: {name} must be bf16, f16 or f32, got {x.dtype}")
-        if B * T and x.stride(1) != 1:
-            raise ValueError(f"qk_pair_accum: {name} needs a contiguous last dim, got strides {x.stride()}")
-        rows.append(x)
-    q2, k2 = rows
-    if q2.dtype != k2.dtype or q2.device != k2.device:
-        raise ValueError(f"qk_pair_accum: q_rows and k_rows differ in dtype or device ({q2.dtype} on {q2.device}, {k2.dtype} on {k2.device})")
-    for name, p in (("pair", pair), ("pair_raw", pair_raw)):
-        if p is None and name == "pair_raw":
-            continue
-        if (p is None or p.dtype != torch.float64 or tuple(p.shape) != (n_heads, head_dim, head_dim) or not p.is_contiguous()
-                or p.device != q2.device):
-            raise ValueError(f"qk_pair_accum: {name} must be a contiguous fp64 [{n_heads}, {head_dim}, {head_dim}] on {q2.device}")
+    q2, k2, B, T, n_heads, n_kv, head_dim = _qk_seq_rows("qk_pair_accum", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
     if B * T == 0:
         return
+    lib = _lib.load()
     need = lib.mdg_qk_pair_ws_bytes(B, n_heads, head_dim, int(pair_raw is not None))
     ws, wsp = _ws(need, q2.device)
     with torch.cuda.device(q2.device):
         check(lib.mdg_qk_pair_accum(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
                                     head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_qk_pair_accum")
+
+
+def qk_causal_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: torch.Tensor, k_rows: torch.Tensor, B: int, T: int,
+                    n_heads: int, n_kv: int, head_dim: int) -> None:
+    """The causal Q/K statistic of one calibration batch (mdg_qk_causal_accum), enqueued only: for the B sequences of T rows each,
+    starting at position 0, in q_rows and k_rows (the layouts of qk_pair_accum), in ascending order,
+    pair[h] += sum_i (q_i q_i^T) (.) (K_i - m_i m_i^T / n_i) / n_i with the prefix sums K_i, m_i over the keys j <= i, n_i = i + 1,
+    and, unless pair_raw is None, pair_raw[h] += sum_i (q_i q_i^T) (.) K_i / n_i.  pair, pair_raw: fp64 [n_heads, head_dim,
+    head_dim], contiguous, accumulated into."""
+    q2, k2, B, T, n_heads, n_kv, head_dim = _qk_seq_rows("qk_causal_accum", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
+    if B * T == 0:
+        return
+    lib = _lib.load()
+    need = lib.mdg_qk_causal_ws_bytes(B, n_heads, head_dim, int(pair_raw is not None))
+    ws, wsp = _ws(need, q2.device)
+    with torch.cuda.device(q2.device):
+        check(lib.mdg_qk_causal_accum(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
+                                      head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_qk_causal_accum")
 
 
 _ROPE_SCRATCH = {}

@@ -94,6 +94,37 @@ def qk_seq_select_enabled() -> bool:
     return _switch("MODEGPT_QK_SEQ_SELECT")
 
 
+# The causal Q/K statistic ("The causal Q/K statistic").  Opt-in: MODEGPT_QK_CAUSAL=1 makes calibration of a
+# rotary model (Llama, Qwen2) that collects the post-RoPE statistics (MODEGPT_QK_ROPE=1) also accumulate, per layer,
+# P^c_h = sum_s sum_i (q_i q_i^T) (.) (K_i / n_i - m_i m_i^T / n_i^2) over the keys j <= i each query can see, and its uncentred
+# twin (mdg_qk_causal_accum); with MODEGPT_QK_ERROR=1 compress_qk then reports metrics["qk_logit_error_causal"].  Independent of
+# MODEGPT_QK_SEQ.
+def qk_causal_enabled() -> bool:
+    """MODEGPT_QK_CAUSAL as it stands when calibration, the cache or compress_qk asks (not frozen at import)."""
+    return _switch("MODEGPT_QK_CAUSAL")
+
+
+# Opt-in: MODEGPT_QK_CAUSAL_SELECT=1 makes compress_qk score and order the pair selection on the causal statistic.  Needs the
+# statistic (MODEGPT_QK_CAUSAL=1 at calibration or in the loaded record); excludes MODEGPT_QK_SEQ_SELECT and MODEGPT_QK_ROPE_SELECT;
+# no certificate is issued.
+def qk_causal_select_enabled() -> bool:
+    """MODEGPT_QK_CAUSAL_SELECT as it stands when compress_qk asks (per layer; not frozen at import)."""
+    return _switch("MODEGPT_QK_CAUSAL_SELECT")
+
+
+def qk_select_statistic() -> str:
+    """Which statistic the pair selection is scored on, from the three select switches as they stand: "causal", "seq", "rope" or
+    "default".  At most one of MODEGPT_QK_CAUSAL_SELECT, MODEGPT_QK_SEQ_SELECT, MODEGPT_QK_ROPE_SELECT may be set: the selection
+    takes one statistic."""
+    on = [(name, kind) for name, kind, fn in (("MODEGPT_QK_CAUSAL_SELECT", "causal", qk_causal_select_enabled),
+                                              ("MODEGPT_QK_SEQ_SELECT", "seq", qk_seq_select_enabled),
+                                              ("MODEGPT_QK_ROPE_SELECT", "rope", qk_rope_select_enabled)) if fn()]
+    if len(on) > 1:
+        raise RuntimeError(" and ".join(f"{name}=1" for name, _ in on) + (" are both set" if len(on) == 2 else " are all set") +
+                           ": the pair selection takes one statistic")
+    return on[0][1] if on else "default"
+
+
 # Greedy MLP selection (mdg_nystrom_greedy_select; DESIGN.md section 7, "Greedy MLP selection").  Opt-in: MODEGPT_MLP_GREEDY=T makes
 # compress_nystrom select each layer's columns by T rounds of block-greedy descent on the objective the refit minimises, instead of
 # the reference's ridge-leverage rule.  No certificate is issued for that selection.
@@ -355,6 +386,23 @@ def decode_qk_seq_error(curve_h, curve, raw_curve, rank: int, cols_per_unit: int
     raw = _fin(_total([rv[g][m] for g in range(out["n_kv"])]))
     out["raw_error"] = raw
     out["shift_share"] = None if raw is None else share(out["error"], raw)
+    return out
+
+
+def decode_qk_causal_error(curve_h, curve, raw_curve, rank: int, cols_per_unit: int, terms=None, scale=None, greedy_curve=None,
+                           seq=None) -> dict:
+    """decode_qk_seq_error of the curves taken on the causal statistic P^c and its uncentred twin: error is then the mean over the
+    queries of the variance of the logit change over the keys each query can see, raw_error the mean square over them, shift_share
+    the share of raw_error that softmax cannot see.  seq: the layer's metrics["qk_logit_error_seq"] entry at the same rank, or None;
+    with it, per kv head and for the layer, over_full = error / (seq error), what the causal mask makes of the figure that pairs every
+    query with every key of its sequence (None where the seq error is not a usable positive number)."""
+    out = decode_qk_seq_error(curve_h, curve, raw_curve, rank, cols_per_unit, terms=terms, scale=scale, greedy_curve=greedy_curve)
+    if seq is not None:
+        if seq.get("rank") != out["rank"] or len(seq.get("heads", ())) != out["n_kv"]:
+            raise ValueError("decode_qk_causal_error: seq must be the within-sequence entry of the same layer at the same rank")
+        for h, hs in zip(out["heads"], seq["heads"]):
+            h["over_full"] = _ratio(h["error"], hs.get("error"))
+        out["over_full"] = _ratio(out["error"], seq.get("error"))
     return out
 
 
