@@ -11,6 +11,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import ops
+from ..calib_stats import layer_value
 from .model_adapter import (AttentionComponents, MLPComponents, MLPTensors, ModelAdapter, QKComponents, QKTensors,
                             VOComponents, VOTensors)
 
@@ -35,30 +36,16 @@ class LlamaAdapter(ModelAdapter):
         of its own, sigma_x + sigma_q + sigma_k in ONE persistent int8 launch (mdg_cov_accum_i8_multi), whose small problems'
         tiles fill what the large one's last round leaves idle; what the int8 planes cannot take, and everything in mode
         "f64", goes to the fp64 kernel in one launch (mdg_cov_accum_multi).  Nothing is copied; the parked tensors live until
-        the end of the layer's forward.  With MODEGPT_MLP_INTERCEPT=1 calibration leaves one fp64 vector per target layer on
-        self.mlp_sums, and the flush hands the sigma_mlp activation to ops.col_sum_accum as well (its column sums: the means of the
-        mean-aware refit); without the switch the list is None and nothing else is launched.  MODEGPT_VO_INTERCEPT=1 does the same
-        for x on self.x_sums (the means of the mean-aware V/O truncation); the covariance launches are the same either way.
-        With MODEGPT_QK_ROPE=1 (Llama, Qwen2) calibration leaves the (sigma_q', sigma_k') lists on self.qk_rope_sums: a forward
-        pre-hook on self_attn parks the rotary tables the module is called with, and after the launches above the flush rotates the
-        parked q and k (ops.rope_rows) and accumulates their per-head Grams in one separate ops.cov_accum_multi call (the reference's
-        disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); the launches above are the same either way.  With
-        MODEGPT_QK_SEQ=1 beside it the (P, P_raw) lists are on self.qk_pair_sums and the rotated rows also go to ops.qk_pair_accum,
-        one call per layer and batch (the within-sequence Q/K statistic); every other launch is the same either way.  With
-        MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 the (P^c, P^c_raw) lists are on self.qk_causal_sums and the rotated rows go to
-        ops.qk_causal_accum, likewise (the causal Q/K statistic)."""
+        the end of the layer's forward.  Calibration leaves the buffers of the optional statistics it collects on this adapter
+        (calib_stats.STATS, under each record's sums_attr; None without the switch, and then nothing else is launched).  The means:
+        the flush hands the sigma_mlp activation, and x, to ops.col_sum_accum as well.  The post-RoPE statistics: a forward pre-hook
+        on self_attn parks the rotary tables the module is called with, and after the launches above the flush rotates the parked q
+        and k (ops.rope_rows) and accumulates their per-head Grams in one separate ops.cov_accum_multi call (the reference's
+        disabled post-RoPE variant, LlamaAdapter.py:46-69, 305-325); beside them the rotated rows also go to ops.qk_causal_accum
+        and ops.qk_pair_accum, one call per layer and batch.  The launches above are the same either way."""
         parked = {}
-        sums = getattr(self, "mlp_sums", None)
-        x_sums = getattr(self, "x_sums", None)
-        rope = getattr(self, "qk_rope_sums", None)       # (sigma_q', sigma_k') lists with MODEGPT_QK_ROPE=1 on a rotary model, else None
-        if rope is not None and rope[0][layer_idx] is None:
-            rope = None
-        pairs = getattr(self, "qk_pair_sums", None)      # (P, P_raw) lists with MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1, else None
-        if pairs is not None and (rope is None or pairs[0][layer_idx] is None):
-            pairs = None
-        causals = getattr(self, "qk_causal_sums", None)  # (P^c, P^c_raw) lists with MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1, else None
-        if causals is not None and (rope is None or causals[0][layer_idx] is None):
-            causals = None
+        sums, x_sums, rope, pairs, causals = (layer_value(self, name, layer_idx, "sums_attr") for name in
+                                              ("mlp_mean", "x_mean", "qk_rope", "qk_pair", "qk_causal"))
         head_dim = self.head_dim
 
         def park(kind):
@@ -91,10 +78,10 @@ class LlamaAdapter(ModelAdapter):
                     got[kind] = t
             x = got.get("x")
             ops.cov_accum_multi(items)
-            if sums is not None and sums[layer_idx] is not None:
-                ops.col_sum_accum(sums[layer_idx], input[0])
-            if x_sums is not None and x_sums[layer_idx] is not None and x is not None:
-                ops.col_sum_accum(x_sums[layer_idx], x)
+            if sums is not None:
+                ops.col_sum_accum(sums, input[0])
+            if x_sums is not None and x is not None:
+                ops.col_sum_accum(x_sums, x)
             pos = parked.pop("pos", None)
             if rope is not None and "q" in got and "k" in got:
                 if pos is None:
@@ -106,13 +93,11 @@ class LlamaAdapter(ModelAdapter):
                 rk = ops.rope_rows(k, pos[0], pos[1], self.n_kv_heads, head_dim, out=ops.rope_scratch(k, "k"))
                 if causals is not None:
                     # the causal statistic of the batch's B sequences of T rows (each starting at position 0), from the same rows
-                    ops.qk_causal_accum(causals[0][layer_idx], causals[1][layer_idx], rq, rk, q.shape[0], q.shape[1], self.n_heads,
-                                        self.n_kv_heads, head_dim)
+                    ops.qk_causal_accum(causals[0], causals[1], rq, rk, q.shape[0], q.shape[1], self.n_heads, self.n_kv_heads, head_dim)
                 if pairs is not None:
                     # the within-sequence statistic of the batch's B sequences of T rows, from the same scratch rows
-                    ops.qk_pair_accum(pairs[0][layer_idx], pairs[1][layer_idx], rq, rk, q.shape[0], q.shape[1], self.n_heads,
-                                      self.n_kv_heads, head_dim)
-                ops.cov_accum_multi([(rope[0][layer_idx], rq, self.n_heads), (rope[1][layer_idx], rk, self.n_kv_heads)])
+                    ops.qk_pair_accum(pairs[0], pairs[1], rq, rk, q.shape[0], q.shape[1], self.n_heads, self.n_kv_heads, head_dim)
+                ops.cov_accum_multi([(rope[0], rq, self.n_heads), (rope[1], rk, self.n_kv_heads)])
             return None
 
         if rope is not None:

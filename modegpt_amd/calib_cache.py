@@ -7,24 +7,13 @@ One directory, one self-contained record per layer, so chunks of layers, target_
                                            entries 0..r at offset r(r+1)/2; ops.sym_pack_lower).  numpy alone reads one:
                                            full[np.tril_indices(n)] = np.fromfile(path, "<f8")
     layer_<i>_q.f64, layer_<i>_k.f64       raw little-endian fp64, full [heads, head_dim, head_dim]
-    layer_<i>_mlp_mean.f64                 only with MODEGPT_MLP_INTERCEPT=1: n_inner raw little-endian fp64, mu = E[h] of the sigma_mlp
-                                           activation under sigma_mlp's normaliser; np.fromfile(path, "<f8") reads it.  Its sidecar
-                                           entry files.mlp_mean holds the length, n and the bit pattern of its exact sum.  A run
-                                           with the switch refuses a record without the entry (it never recalibrates); a run without
-                                           ignores file and entry; records written without the switch are what they always were
-    layer_<i>_x_mean.f64                   only with MODEGPT_VO_INTERCEPT=1: d_model raw little-endian fp64, mu = E[x] of the sigma_x
-                                           activation under sigma_x's normaliser; the same format, sidecar entry (files.x_mean) and
-                                           rules as layer_<i>_mlp_mean.f64, under its own switch
-    layer_<i>_q_rope.f64, _k_rope.f64      only with MODEGPT_QK_ROPE=1 on a rotary model (Llama, Qwen2): the per-head Grams of the post-RoPE
-                                           rows, raw little-endian fp64, full [heads, head_dim, head_dim] -- the format and sidecar entry
-                                           fields of layer_<i>_q.f64 / _k.f64 (files.q_rope, files.k_rope), under the rules of the means:
-                                           written only with the switch, demanded by a run with it, ignored by a run without
-    layer_<i>_qk_pair.f64, _qk_pair_raw.f64  only with MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1 on a rotary model: the within-sequence
-                                           Q/K statistic P and its uncentred twin, raw little-endian fp64, full [n_heads, head_dim,
-                                           head_dim] -- the format and sidecar entry fields of layer_<i>_q.f64 (files.qk_pair,
-                                           files.qk_pair_raw), under the rules of the post-RoPE files, with their own switch
-    layer_<i>_qk_causal.f64, _qk_causal_raw.f64  only with MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 on a rotary model: the causal
-                                           Q/K statistic P^c and its uncentred twin, likewise (files.qk_causal, files.qk_causal_raw)
+    layer_<i>_<kind>.f64                   one per member of every optional statistic this run collects (calib_stats.STATS: which
+                                           kinds, under which switch, of which shape).  Layout "vector" (the means): n raw
+                                           little-endian fp64, np.fromfile(path, "<f8") reads it; its sidecar entry files.<kind> holds
+                                           the length, n and the bit pattern of its exact sum.  Layout "full" (the Q/K statistics):
+                                           the format and sidecar entry fields of layer_<i>_q.f64 / _k.f64.  A run with the switch
+                                           refuses a record without the entry (it never recalibrates); a run without ignores file
+                                           and entry; records written without the switch are what they always were
     layer_<i>.json                         the sidecar, written LAST: the commit marker -- a layer without it does not exist
     bi_scores.json                         the Block-Influence scores of all layers, written by the rank that computed them
 
@@ -53,18 +42,20 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .calib_stats import BY_NAME, KIND_SHAPE, KIND_STAT, STATS
+
 logger = logging.getLogger("MoDeGPT")
 
 FORMAT_VERSION = 1
 PACKED_KINDS = ("mlp", "x")      # 2-D statistics: packed lower triangle
 FULL_KINDS = ("q", "k")          # per-head statistics: full (tiny)
 KINDS = PACKED_KINDS + FULL_KINDS
-ROPE_KINDS = {"q_rope": "q", "k_rope": "k"}      # MODEGPT_QK_ROPE=1: post-RoPE statistic -> the statistic whose shape and layout it has
-PAIR_KINDS = {"qk_pair": "q", "qk_pair_raw": "q"}   # MODEGPT_QK_SEQ=1: the within-sequence Q/K statistic and its uncentred twin, likewise
-CAUSAL_KINDS = {"qk_causal": "q", "qk_causal_raw": "q"}   # MODEGPT_QK_CAUSAL=1: the causal Q/K statistic and its uncentred twin, likewise
-EXTRA_KINDS = {**ROPE_KINDS, **PAIR_KINDS, **CAUSAL_KINDS}
-EXTRA_SWITCH = {**{k: "MODEGPT_QK_ROPE=1" for k in ROPE_KINDS}, **{k: "MODEGPT_QK_SEQ=1" for k in PAIR_KINDS},
-                **{k: "MODEGPT_QK_CAUSAL=1" for k in CAUSAL_KINDS}}
+# the optional statistics (calib_stats.STATS), in table order.  Layout "full": file kind -> the statistic whose shape and layout it has
+ROPE_KINDS, PAIR_KINDS, CAUSAL_KINDS = (dict(BY_NAME[name].members) for name in ("qk_rope", "qk_pair", "qk_causal"))
+EXTRA_KINDS = {kind: shape for kind, shape in KIND_SHAPE.items() if KIND_STAT[kind].layout == "full"}
+# ... layout "vector" (the activation means): file kind -> the arch field that is its length
+VECTOR_KINDS = {kind: shape for kind, shape in KIND_SHAPE.items() if KIND_STAT[kind].layout == "vector"}
+MEAN_KIND, X_MEAN_KIND = VECTOR_KINDS
 ARCH_FIELDS = ("arch", "d_model", "n_inner", "n_heads", "n_kv_heads", "head_dim", "n_layers", "dtype")
 BI_FILE = "bi_scores.json"
 
@@ -157,13 +148,7 @@ def read_data_file(directory: str, layer: int, kind: str, entry: dict, out: np.n
                          f"pattern {bits}, the sidecar recorded {entry['trace_bits']}")
 
 
-# ------------------------------------------------------------------ host half: the activation means (MODEGPT_MLP_INTERCEPT=1 / MODEGPT_VO_INTERCEPT=1)
-MEAN_KIND = "mlp_mean"
-X_MEAN_KIND = "x_mean"
-# per kind of mean: the switch that writes and demands it, and the arch field that is its length
-MEAN_KINDS = {MEAN_KIND: ("MODEGPT_MLP_INTERCEPT", "n_inner"), X_MEAN_KIND: ("MODEGPT_VO_INTERCEPT", "d_model")}
-
-
+# ------------------------------------------------------------------ host half: the optional statistics (calib_stats.STATS)
 def sum_bits(values: np.ndarray) -> int:
     """The bit pattern (as int64) of the exact sum of the vector, rounded once (math.fsum: no summation order)."""
     return struct.unpack("<q", struct.pack("<d", math.fsum(np.asarray(values, dtype=np.float64).ravel().tolist())))[0]
@@ -173,25 +158,31 @@ def write_mean_file(directory: str, layer: int, values: np.ndarray, n: int, kind
     """layer_<i>_<kind>.f64 from the n means; returns the sidecar's entry for it."""
     values = np.ascontiguousarray(values, dtype="<f8").reshape(-1)
     if values.size != n:
-        raise ValueError(f"layer {layer}: the activation mean has {values.size} entries, {MEAN_KINDS[kind][1]} is {n}")
+        raise ValueError(f"layer {layer}: the activation mean has {values.size} entries, {VECTOR_KINDS[kind]} is {n}")
     path = data_path(directory, layer, kind)
     _replace_into(path, values.tofile)
     return {"file": os.path.basename(path), "layout": "vector", "n": int(n), "bytes": int(n * 8), "sum_bits": sum_bits(values)}
 
 
-def validate_mean_entry(meta: dict, n: int, layer: int, kind: str = MEAN_KIND) -> dict:
-    """Metadata alone: the record must carry files.<kind> for n means.  Returns the entry."""
+def validate_extra_entry(meta: dict, arch: dict, layer: int, kind: str) -> dict:
+    """Metadata alone: the record must carry files.<kind> for a member of an optional statistic, with the shape `arch` gives it -- a
+    vector of the arch field it names, or the shape of files.q / files.k.  Returns the entry."""
     entry = meta.get("files", {}).get(kind)
     if not isinstance(entry, dict):
         raise ValueError(f"calibration statistics, layer {layer}: field files.{kind} is missing -- the record was saved without "
-                         f"{MEAN_KINDS[kind][0]}=1 and this run has the switch on; save the statistics again with it (nothing is "
+                         f"{KIND_STAT[kind].switch}=1 and this run has the switch on; save the statistics again with it (nothing is "
                          "recalibrated on load)")
-    want = {"n": int(n), "bytes": 8 * int(n), "layout": "vector"}
+    if kind in VECTOR_KINDS:
+        n = int(arch[VECTOR_KINDS[kind]])
+        want, bits = {"n": n, "bytes": 8 * n, "layout": "vector"}, "sum_bits"
+    else:
+        n, batch = stat_shapes(arch)[EXTRA_KINDS[kind]]
+        want, bits = {"n": n, "batch": batch, "bytes": 8 * stat_numel(kind, n, batch), "layout": "full"}, "trace_bits"
     for name, value in want.items():
         if entry.get(name) != value:
             _refuse(layer, f"files.{kind}.{name}", entry.get(name), value)
-    if not isinstance(entry.get("sum_bits"), int) or not isinstance(entry.get("file"), str):
-        _refuse(layer, f"files.{kind}.sum_bits", entry.get("sum_bits"), "an integer")
+    if not isinstance(entry.get(bits), int) or not isinstance(entry.get("file"), str):
+        _refuse(layer, f"files.{kind}.{bits}", entry.get(bits), "an integer")
     return entry
 
 
@@ -210,25 +201,6 @@ def read_mean_file(directory: str, layer: int, entry: dict, kind: str = MEAN_KIN
         raise ValueError(f"calibration statistics, layer {layer}: field files.{kind}.sum_bits -- the sum of {path} has the bit "
                          f"pattern {bits}, the sidecar recorded {entry['sum_bits']}")
     return values
-
-
-# ------------------------------------------------------------------ host half: the post-RoPE statistics (MODEGPT_QK_ROPE=1)
-def validate_rope_entry(meta: dict, arch: dict, layer: int, kind: str) -> dict:
-    """Metadata alone: the record must carry files.<kind> (kind "q_rope" / "k_rope", "qk_pair" / "qk_pair_raw" or "qk_causal" / "qk_causal_raw") with the shape of
-    files.q / files.k.  Returns the entry."""
-    entry = meta.get("files", {}).get(kind)
-    if not isinstance(entry, dict):
-        raise ValueError(f"calibration statistics, layer {layer}: field files.{kind} is missing -- the record was saved without "
-                         f"{EXTRA_SWITCH[kind]} and this run has the switch on; save the statistics again with it (nothing is "
-                         "recalibrated on load)")
-    n, batch = stat_shapes(arch)[EXTRA_KINDS[kind]]
-    want = {"n": n, "batch": batch, "bytes": 8 * stat_numel(kind, n, batch), "layout": "full"}
-    for name, value in want.items():
-        if entry.get(name) != value:
-            _refuse(layer, f"files.{kind}.{name}", entry.get(name), value)
-    if not isinstance(entry.get("trace_bits"), int) or not isinstance(entry.get("file"), str):
-        _refuse(layer, f"files.{kind}.trace_bits", entry.get("trace_bits"), "an integer")
-    return entry
 
 
 # ------------------------------------------------------------------ host half: the sidecar
@@ -440,19 +412,17 @@ def _staging_for(arch: dict, device) -> Staging:
 
 
 def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arch: dict, calibration: dict, model: str,
-                weights: dict, certificates: dict, mean=None, x_mean=None, rope=None, pair=None, causal=None) -> dict:
+                weights: dict, certificates: dict, extra: Optional[dict] = None) -> dict:
     """One layer's record from its four device tensors ({"mlp", "x": [n, n]; "q", "k": [heads, hd, hd]}): data files first, the
-    sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  mean: the layer's
-    activation mean (fp64 [n_inner], MODEGPT_MLP_INTERCEPT=1) -- its file and the entry files.mlp_mean are written too; x_mean: the
-    mean of x (fp64 [d_model], MODEGPT_VO_INTERCEPT=1) -- likewise, files.x_mean; rope: {"q_rope", "k_rope": [heads, hd, hd]}, the
-    post-RoPE statistics (MODEGPT_QK_ROPE=1) -- their files and entries follow those of the four, through the same staging; pair:
-    {"qk_pair", "qk_pair_raw": [n_heads, hd, hd]}, the within-sequence Q/K statistic (MODEGPT_QK_SEQ=1) -- likewise; causal:
-    {"qk_causal", "qk_causal_raw": [n_heads, hd, hd]}, the causal Q/K statistic (MODEGPT_QK_CAUSAL=1) -- likewise."""
+    sidecar last.  The device -> host copy of a statistic runs while the one before it is written to its file.  extra: file kind ->
+    the layer's device tensor, for the members of the optional statistics the record is to hold (calib_stats.STATS) -- the files and
+    entries of the "full" ones follow those of the four through the same staging, in table order, then the vectors."""
     import torch
     from . import ops
     os.makedirs(directory, exist_ok=True)
     files, waiting = {}, None
-    extra = dict(rope or {}, **(pair or {}), **(causal or {}))
+    extra = extra or {}
+    staged = tuple(kind for kind in EXTRA_KINDS if kind in extra)
     tensors = dict(tensors, **extra)
 
     def finish(item):
@@ -460,7 +430,7 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
         ev.synchronize()
         files[kind] = write_data_file(directory, layer, kind, host.numpy(), n, batch)
 
-    for kind in KINDS + tuple(extra):
+    for kind in KINDS + staged:
         t = tensors[kind]
         n, batch = t.shape[-1], (1 if t.dim() == 2 else t.shape[0])
         numel = stat_numel(kind, n, batch)
@@ -473,37 +443,27 @@ def write_layer(directory: str, layer: int, tensors: dict, staging: Staging, arc
             finish(waiting)
         waiting = (kind, n, batch, host, ev)
     finish(waiting)
-    if mean is not None:
-        files[MEAN_KIND] = write_mean_file(directory, layer, mean.detach().cpu().numpy(), arch["n_inner"])
-    if x_mean is not None:
-        files[X_MEAN_KIND] = write_mean_file(directory, layer, x_mean.detach().cpu().numpy(), arch["d_model"], kind=X_MEAN_KIND)
+    for kind, field in VECTOR_KINDS.items():
+        if kind in extra:
+            files[kind] = write_mean_file(directory, layer, extra[kind].detach().cpu().numpy(), arch[field], kind=kind)
     meta = make_sidecar(layer, arch, calibration, model, weights, files, certificates)
     write_sidecar(directory, meta)
     return meta
 
 
-def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, mean=None, x_mean=None, rope=None,
-               pair=None, causal=None) -> dict:
+def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expect: dict, extra: Optional[dict] = None) -> dict:
     """The inverse: checks the sidecar against `expect`, fills the four device tensors, returns the sidecar.  The file of a
-    statistic is read while the one before it is copied to the device and unpacked.  mean: an fp64 [n_inner] device tensor to fill
-    from layer_<i>_mlp_mean.f64 (MODEGPT_MLP_INTERCEPT=1), x_mean: an fp64 [d_model] one to fill from layer_<i>_x_mean.f64
-    (MODEGPT_VO_INTERCEPT=1), rope: {"q_rope", "k_rope": fp64 [heads, hd, hd] device tensors} to fill from layer_<i>_q_rope.f64 /
-    _k_rope.f64 (MODEGPT_QK_ROPE=1), pair: {"qk_pair", "qk_pair_raw": fp64 [n_heads, hd, hd] device tensors} to fill from
-    layer_<i>_qk_pair.f64 / _qk_pair_raw.f64 (MODEGPT_QK_SEQ=1), causal: {"qk_causal", "qk_causal_raw": likewise} to fill from
-    layer_<i>_qk_causal.f64 / _qk_causal_raw.f64 (MODEGPT_QK_CAUSAL=1); a record without the entry is refused before any data is read."""
+    statistic is read while the one before it is copied to the device and unpacked.  extra: file kind -> the fp64 device tensor to
+    fill from layer_<i>_<kind>.f64, for the members of the optional statistics this run demands (calib_stats.STATS); a record
+    without the entry is refused before any data is read."""
     import torch
     from . import ops
     meta = read_sidecar(directory, layer)
     validate_sidecar(meta, expect, layer)
-    if mean is not None:
-        mean_entry = validate_mean_entry(meta, expect["arch"]["n_inner"], layer)
-    if x_mean is not None:
-        x_mean_entry = validate_mean_entry(meta, expect["arch"]["d_model"], layer, kind=X_MEAN_KIND)
-    extra = dict(rope or {}, **(pair or {}), **(causal or {}))
-    for kind in extra:
-        validate_rope_entry(meta, expect["arch"], layer, kind)
+    extra = extra or {}
+    entries = {kind: validate_extra_entry(meta, expect["arch"], layer, kind) for kind in KIND_STAT if kind in extra}
     tensors = dict(tensors, **extra)
-    for kind in KINDS + tuple(extra):
+    for kind in KINDS + tuple(kind for kind in EXTRA_KINDS if kind in extra):
         t = tensors[kind]
         entry = meta["files"][kind]
         numel = stat_numel(kind, entry["n"], entry["batch"])
@@ -516,10 +476,9 @@ def read_layer(directory: str, layer: int, tensors: dict, staging: Staging, expe
             else:
                 t.view(-1).copy_(host, non_blocking=True)
             staging.mark(slot)
-    if mean is not None:
-        mean.copy_(torch.from_numpy(read_mean_file(directory, layer, mean_entry)))
-    if x_mean is not None:
-        x_mean.copy_(torch.from_numpy(read_mean_file(directory, layer, x_mean_entry, kind=X_MEAN_KIND)))
+    for kind in VECTOR_KINDS:
+        if kind in extra:
+            extra[kind].copy_(torch.from_numpy(read_mean_file(directory, layer, entries[kind], kind=kind)))
     return meta
 
 
@@ -548,35 +507,24 @@ def save(adapter, directory: str, calibs, n_samples: int, batch_size: int, datas
                        "n_texts": int(sum(len(b) for b in adapter.calibs)), "n_tokens": int(adapter.calib_tokens)}
         certificates = certificates_in_force(adapter)
     nbytes = 0
-    from . import ops
-    means = getattr(adapter, "mlp_means", None) if ops.mlp_intercept_enabled() else None      # (switch off: today's record, bit for bit)
-    if ops.mlp_intercept_enabled() and targets and (means is None or any(means[i] is None for i in targets)):
-        raise RuntimeError("MODEGPT_MLP_INTERCEPT=1 but the adapter carries no activation means (adapter.mlp_means) to save")
-    x_means = getattr(adapter, "x_means", None) if ops.vo_intercept_enabled() else None         # (likewise)
-    if ops.vo_intercept_enabled() and targets and (x_means is None or any(x_means[i] is None for i in targets)):
-        raise RuntimeError("MODEGPT_VO_INTERCEPT=1 but the adapter carries no input means (adapter.x_means) to save")
-    from .calibration import qk_causal_collected, qk_rope_collected, qk_seq_collected
-    rope = getattr(adapter, "qk_rope_stats", None) if qk_rope_collected(adapter) else None       # (likewise)
-    if qk_rope_collected(adapter) and targets and (rope is None or any(rope[0][i] is None or rope[1][i] is None for i in targets)):
-        raise RuntimeError("MODEGPT_QK_ROPE=1 but the adapter carries no post-RoPE statistics (adapter.qk_rope_stats) to save")
-    pairs = getattr(adapter, "qk_pair_stats", None) if qk_seq_collected(adapter) else None       # (likewise)
-    if qk_seq_collected(adapter) and targets and (pairs is None or any(pairs[0][i] is None or pairs[1][i] is None for i in targets)):
-        raise RuntimeError("MODEGPT_QK_SEQ=1 but the adapter carries no within-sequence statistic (adapter.qk_pair_stats) to save")
-    causals = getattr(adapter, "qk_causal_stats", None) if qk_causal_collected(adapter) else None   # (likewise)
-    if qk_causal_collected(adapter) and targets and (causals is None or
-                                                     any(causals[0][i] is None or causals[1][i] is None for i in targets)):
-        raise RuntimeError("MODEGPT_QK_CAUSAL=1 but the adapter carries no causal statistic (adapter.qk_causal_stats) to save")
+    from .calibration import collected
+    extra = {}      # file kind -> per-layer list, for the optional statistics this run collects (none: today's record, bit for bit)
+    for stat in STATS:
+        if not collected(stat, adapter):
+            continue
+        value = getattr(adapter, stat.stats_attr, None)
+        lists = None if value is None else (value,) if len(stat.kinds) == 1 else tuple(value)
+        if targets and (lists is None or any(lst[i] is None for i in targets for lst in lists)):
+            raise RuntimeError(f"{stat.switch}=1 but the adapter carries no {stat.noun} (adapter.{stat.stats_attr}) to save")
+        if lists is not None:
+            extra.update(zip(stat.kinds, lists))
     if targets:
         staging = _staging_for(arch, cov["mlp"][targets[0]].device)
         for i in targets:
             cal = calibration if loaded is None else loaded[i]["calibration"]
             cert = certificates if loaded is None else loaded[i]["certificates"]
             meta = write_layer(directory, i, {k: cov[k][i] for k in KINDS}, staging, arch, cal, model,
-                               weight_fingerprint(adapter, i), cert, mean=None if means is None else means[i],
-                               x_mean=None if x_means is None else x_means[i],
-                               rope=None if rope is None else {"q_rope": rope[0][i], "k_rope": rope[1][i]},
-                               pair=None if pairs is None else {"qk_pair": pairs[0][i], "qk_pair_raw": pairs[1][i]},
-                               causal=None if causals is None else {"qk_causal": causals[0][i], "qk_causal_raw": causals[1][i]})
+                               weight_fingerprint(adapter, i), cert, extra={kind: lst[i] for kind, lst in extra.items()})
             nbytes += sum(e["bytes"] for e in meta["files"].values())
         torch.cuda.synchronize(staging.device)
     if bi_scores is not None and getattr(adapter, "calib_want_bi", True):
@@ -603,22 +551,14 @@ def load(adapter, directory: str, n_samples: int, batch_size: int, dataset: str,
         read_sidecar(directory, missing[0])      # raises, naming the layer
     sig = SigmaBuffers(adapter, targets)
     metas: Dict[int, dict] = {}
-    adapter.mlp_means = sig.mlp_sums           # (MODEGPT_MLP_INTERCEPT=1: filled below from the mean files; None without the switch)
-    adapter.x_means = sig.x_sums               # (MODEGPT_VO_INTERCEPT=1: likewise)
-    adapter.qk_rope_stats = sig.qk_rope        # (MODEGPT_QK_ROPE=1 on a rotary model: likewise, from the q_rope / k_rope files)
-    adapter.qk_pair_stats = sig.qk_pairs       # (MODEGPT_QK_SEQ=1 beside it: likewise, from the qk_pair / qk_pair_raw files)
-    adapter.qk_causal_stats = sig.qk_causals   # (MODEGPT_QK_CAUSAL=1 beside it: likewise, from the qk_causal / qk_causal_raw files)
+    for stat in STATS:                         # (filled below from the statistic's files; None when this run does not collect it)
+        setattr(adapter, stat.stats_attr, sig.value(stat.name))
     if targets:
         staging = _staging_for(expect["arch"], sig.lists["mlp"][targets[0]].device)
         for i in targets:
             metas[i] = read_layer(directory, i, {k: sig.lists[k][i] for k in KINDS}, staging,
                                   dict(expect, weights=weight_fingerprint(adapter, i)),
-                                  mean=None if sig.mlp_sums is None else sig.mlp_sums[i],
-                                  x_mean=None if sig.x_sums is None else sig.x_sums[i],
-                                  rope=None if sig.q_rope is None else {"q_rope": sig.q_rope[i], "k_rope": sig.k_rope[i]},
-                                  pair=None if sig.qk_pair is None else {"qk_pair": sig.qk_pair[i], "qk_pair_raw": sig.qk_pair_raw[i]},
-                                  causal=None if sig.qk_causal is None else {"qk_causal": sig.qk_causal[i],
-                                                                             "qk_causal_raw": sig.qk_causal_raw[i]})
+                                  extra={kind: lst[i] for kind, lst in sig.extra.items()})
         torch.cuda.synchronize(staging.device)
     adapter.bi_scores = bi_scores
     cert = merge_certificates([m["certificates"] for m in metas.values()])

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import calib_stats, ops
 from .adapters.model_adapter import ModelAdapter
 from .model_utils import dtype_p, local_device
 
@@ -30,82 +30,49 @@ random.seed(1234)
 TOKENS_PER_TEXT_NORMALISER = 2048
 
 
-QK_ROPE_ARCHS = ("llama", "qwen2")      # rotary models whose compressed attention keeps the dropped-column identity
+def collected(stat: calib_stats.Stat, adapter: ModelAdapter, log=None) -> bool:
+    """Whether this run collects (or loads) the optional statistic `stat` (calib_stats.STATS): its switch is on and, for a statistic
+    of the rotary models, the adapter is a Llama / Qwen2 one.  A statistic that needs another one (the within-sequence and the
+    causal statistic are taken on the rotated rows the post-RoPE flush produces) raises there when that one's switch is off.  With
+    the switch on any other architecture nothing is collected and, given a logger, one line says why."""
+    if not stat.enabled():
+        return False
+    arch = adapter.arch
+    if stat.archs is None or arch in stat.archs:
+        if stat.needs is not None:
+            needs = calib_stats.BY_NAME[stat.needs]
+            if not needs.enabled():
+                raise RuntimeError(f"{stat.switch}=1 needs {needs.switch}=1: the {stat.adjective} Q/K statistic is accumulated from the "
+                                   "post-RoPE rows, which are only produced when the post-RoPE statistics are collected")
+        if stat.entry is not None and adapter.head_dim > 128:
+            raise RuntimeError(f"{stat.switch}=1: head_dim {adapter.head_dim} > 128 is not supported by {stat.entry}")
+        return True
+    if log is not None:
+        if "qwen" in arch:
+            log.warning(f"{stat.switch}=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
+                        f"RMSNorm), so the dropped-column identity of the {stat.adjective} statistic does not hold; nothing is collected")
+        else:
+            log.info(f"{stat.switch}=1: {arch} {stat.elsewhere}")
+    return False
 
 
 def qk_rope_collected(adapter: ModelAdapter, log=None) -> bool:
-    """Whether this run collects (or loads) the post-RoPE statistics sigma_q', sigma_k': MODEGPT_QK_ROPE=1 on a Llama / Qwen2
-    adapter.  With the switch on any other architecture nothing is collected and, given a logger, one line says why."""
-    if not ops.qk_rope_enabled():
-        return False
-    arch = adapter.arch
-    if arch in QK_ROPE_ARCHS:
-        return True
-    if log is not None:
-        if "qwen" in arch:
-            log.warning(f"MODEGPT_QK_ROPE=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
-                        "RMSNorm), so the dropped-column identity of the post-RoPE statistic does not hold; nothing is collected")
-        else:
-            log.info(f"MODEGPT_QK_ROPE=1: {arch} has no rotary embedding, the pre-RoPE statistic is already the exact one; nothing "
-                     "more is collected")
-    return False
+    return collected(calib_stats.BY_NAME["qk_rope"], adapter, log)
 
 
 def qk_seq_collected(adapter: ModelAdapter, log=None) -> bool:
-    """Whether this run collects (or loads) the within-sequence Q/K statistic P, P_raw: MODEGPT_QK_SEQ=1 on a Llama / Qwen2 adapter
-    that collects the post-RoPE statistics too -- the statistic is taken on the rotated rows the post-RoPE flush produces, so
-    MODEGPT_QK_SEQ=1 without MODEGPT_QK_ROPE=1 raises there.  On any other architecture nothing is collected and, given a logger,
-    one line says why."""
-    if not ops.qk_seq_enabled():
-        return False
-    arch = adapter.arch
-    if arch in QK_ROPE_ARCHS:
-        if not ops.qk_rope_enabled():
-            raise RuntimeError("MODEGPT_QK_SEQ=1 needs MODEGPT_QK_ROPE=1: the within-sequence Q/K statistic is accumulated from the "
-                               "post-RoPE rows, which are only produced when the post-RoPE statistics are collected")
-        if adapter.head_dim > 128:
-            raise RuntimeError(f"MODEGPT_QK_SEQ=1: head_dim {adapter.head_dim} > 128 is not supported by mdg_qk_pair_accum")
-        return True
-    if log is not None:
-        if "qwen" in arch:
-            log.warning(f"MODEGPT_QK_SEQ=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
-                        "RMSNorm), so the dropped-column identity of the within-sequence statistic does not hold; nothing is collected")
-        else:
-            log.info(f"MODEGPT_QK_SEQ=1: {arch} has no rotary embedding and separate q / k hooks; the within-sequence statistic is "
-                     "not collected for it")
-    return False
+    return collected(calib_stats.BY_NAME["qk_pair"], adapter, log)
 
 
 def qk_causal_collected(adapter: ModelAdapter, log=None) -> bool:
-    """Whether this run collects (or loads) the causal Q/K statistic P^c, P^c_raw: MODEGPT_QK_CAUSAL=1 on a Llama / Qwen2 adapter
-    that collects the post-RoPE statistics too -- the statistic is taken on the rotated rows the post-RoPE flush produces, so
-    MODEGPT_QK_CAUSAL=1 without MODEGPT_QK_ROPE=1 raises there.  Independent of MODEGPT_QK_SEQ.  On any other architecture nothing
-    is collected and, given a logger, one line says why."""
-    if not ops.qk_causal_enabled():
-        return False
-    arch = adapter.arch
-    if arch in QK_ROPE_ARCHS:
-        if not ops.qk_rope_enabled():
-            raise RuntimeError("MODEGPT_QK_CAUSAL=1 needs MODEGPT_QK_ROPE=1: the causal Q/K statistic is accumulated from the "
-                               "post-RoPE rows, which are only produced when the post-RoPE statistics are collected")
-        if adapter.head_dim > 128:
-            raise RuntimeError(f"MODEGPT_QK_CAUSAL=1: head_dim {adapter.head_dim} > 128 is not supported by mdg_qk_causal_accum")
-        return True
-    if log is not None:
-        if "qwen" in arch:
-            log.warning(f"MODEGPT_QK_CAUSAL=1 ignored for {arch}: the compressed model renormalises q / k over the kept columns (masked "
-                        "RMSNorm), so the dropped-column identity of the causal statistic does not hold; nothing is collected")
-        else:
-            log.info(f"MODEGPT_QK_CAUSAL=1: {arch} has no rotary embedding and separate q / k hooks; the causal statistic is "
-                     "not collected for it")
-    return False
+    return collected(calib_stats.BY_NAME["qk_causal"], adapter, log)
 
 
 class SigmaBuffers:
-    """The four statistic families of the target layers (shapes: src/calibration.py:82-96)."""
+    """The four statistic families of the target layers (shapes: src/calibration.py:82-96) in `lists`, and in `extra` the optional
+    statistics this run collects (calib_stats.STATS): file kind -> per-layer list, absent when not collected."""
 
     KINDS = ("mlp", "q", "k", "x")
-    ROPE_KINDS = ("q_rope", "k_rope")
 
     def __init__(self, adapter: ModelAdapter, target_layers: Sequence[int], device=None):
         L = adapter.n_layers
@@ -117,87 +84,36 @@ class SigmaBuffers:
         for i in self.layers:
             for kind, shp in shapes.items():
                 self.lists[kind][i] = torch.zeros(*shp, dtype=dtype_p, device=device)
-        # the column sums of the sigma_mlp activation (MODEGPT_MLP_INTERCEPT=1: the means of the mean-aware refit); None without it
-        self.mlp_sums: Optional[List[Optional[torch.Tensor]]] = None
-        if ops.mlp_intercept_enabled():
-            self.mlp_sums = [None] * L
-            for i in self.layers:
-                self.mlp_sums[i] = torch.zeros(f, dtype=dtype_p, device=device)
-        # ... and of x, the post-norm hidden state (MODEGPT_VO_INTERCEPT=1: the means of the mean-aware V/O truncation); None without it
-        self.x_sums: Optional[List[Optional[torch.Tensor]]] = None
-        if ops.vo_intercept_enabled():
-            self.x_sums = [None] * L
-            for i in self.layers:
-                self.x_sums[i] = torch.zeros(d, dtype=dtype_p, device=device)
-        # the per-head Grams of the post-RoPE rows q', k' (MODEGPT_QK_ROPE=1 on a rotary model): the shapes of q / k; None without it
-        self.q_rope: Optional[List[Optional[torch.Tensor]]] = None
-        self.k_rope: Optional[List[Optional[torch.Tensor]]] = None
-        if qk_rope_collected(adapter, logger):
-            self.q_rope, self.k_rope = [None] * L, [None] * L
-            for i in self.layers:
-                self.q_rope[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
-                self.k_rope[i] = torch.zeros(*shapes["k"], dtype=dtype_p, device=device)
+        shapes.update(n_inner=(f,), d_model=(d,))
+        self.extra: Dict[str, List[Optional[torch.Tensor]]] = {}
+        for stat in calib_stats.STATS:
+            if collected(stat, adapter, logger):
+                self.extra.update({kind: [None] * L for kind in stat.kinds})
+                for i in self.layers:
+                    for kind, shape in stat.members:
+                        self.extra[kind][i] = torch.zeros(*shapes[shape], dtype=dtype_p, device=device)
 
-        # the within-sequence Q/K statistic and its uncentred twin (MODEGPT_QK_SEQ=1 beside MODEGPT_QK_ROPE=1 on a rotary model): per
-        # layer [n_heads, hd, hd], both triangles; None without it
-        self.qk_pair: Optional[List[Optional[torch.Tensor]]] = None
-        self.qk_pair_raw: Optional[List[Optional[torch.Tensor]]] = None
-        if qk_seq_collected(adapter, logger):
-            self.qk_pair, self.qk_pair_raw = [None] * L, [None] * L
-            for i in self.layers:
-                self.qk_pair[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
-                self.qk_pair_raw[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
-
-        # the causal Q/K statistic and its uncentred twin (MODEGPT_QK_CAUSAL=1 beside MODEGPT_QK_ROPE=1 on a rotary model): per layer
-        # [n_heads, hd, hd], both triangles; None without it
-        self.qk_causal: Optional[List[Optional[torch.Tensor]]] = None
-        self.qk_causal_raw: Optional[List[Optional[torch.Tensor]]] = None
-        if qk_causal_collected(adapter, logger):
-            self.qk_causal, self.qk_causal_raw = [None] * L, [None] * L
-            for i in self.layers:
-                self.qk_causal[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
-                self.qk_causal_raw[i] = torch.zeros(*shapes["q"], dtype=dtype_p, device=device)
-
-    @property
-    def qk_causals(self):
-        """(qk_causal, qk_causal_raw), or None without the switch."""
-        return None if self.qk_causal is None else (self.qk_causal, self.qk_causal_raw)
-
-    @property
-    def qk_pairs(self):
-        """(qk_pair, qk_pair_raw), or None without the switch."""
-        return None if self.qk_pair is None else (self.qk_pair, self.qk_pair_raw)
-
-    @property
-    def qk_rope(self):
-        """(q_rope, k_rope), or None without the switch."""
-        return None if self.q_rope is None else (self.q_rope, self.k_rope)
+    def value(self, name: str):
+        """Statistic `name` as the adapter carries it: its per-layer list, or the tuple of its members' lists; None when it is not
+        collected."""
+        lists = tuple(self.extra.get(kind) for kind in calib_stats.BY_NAME[name].kinds)
+        return None if lists[0] is None else lists[0] if len(lists) == 1 else lists
 
     def finalize(self, n_texts: int) -> None:
-        """sigma <- sigma / (n_texts * 2048), lower triangle mirrored into the upper (src/calibration.py:141-146)."""
+        """sigma <- sigma / (n_texts * 2048), lower triangle mirrored into the upper (src/calibration.py:141-146).  The optional
+        statistics take the normaliser their record states, one rounding per entry: the token normaliser for the means (under the
+        normaliser their sigma gets), the post-RoPE Grams (with sigma_q / sigma_k's mirror) and the causal statistic (every query
+        row carries a mean over its keys already), its square for the within-sequence pairs."""
         scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER)
         for i in self.layers:
             for kind in self.KINDS:
                 ops.cov_finalize(self.lists[kind][i], scale)
-            if self.mlp_sums is not None:
-                self.mlp_sums[i].mul_(scale)                 # mu = E[h] under the normaliser sigma_mlp gets: one rounding per entry
-            if self.x_sums is not None:
-                self.x_sums[i].mul_(scale)                   # mu = E[x] under sigma_x's normaliser, likewise
-            if self.q_rope is not None:
-                ops.cov_finalize(self.q_rope[i], scale)      # the same mirror + normaliser as sigma_q / sigma_k
-                ops.cov_finalize(self.k_rope[i], scale)
-            if self.qk_pair is not None:
-                # the token normaliser squared: the mean over the within-sequence pairs in the unit of <sigma_q', sigma_k'> (one
-                # rounding per entry, the same for both triangles)
-                pair_scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER ** 2)
-                self.qk_pair[i].mul_(pair_scale)
-                self.qk_pair_raw[i].mul_(pair_scale)
-            if self.qk_causal is not None:
-                # every query row carries a mean over its keys already, so ONE token normaliser: the mean over the queries of the
-                # variance over the keys each can see, in the unit of the within-sequence figure (one rounding per entry)
-                causal_scale = 1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER)
-                self.qk_causal[i].mul_(causal_scale)
-                self.qk_causal_raw[i].mul_(causal_scale)
+            for kind, lst in self.extra.items():
+                stat = calib_stats.KIND_STAT[kind]
+                if stat.mirror:
+                    ops.cov_finalize(lst[i], scale)
+                else:
+                    lst[i].mul_(1.0 / (n_texts * TOKENS_PER_TEXT_NORMALISER ** stat.token_power))
 
 
 class BlockInfluence:
@@ -267,11 +183,8 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     bi = BlockInfluence(adapter.n_layers)
     blocks = adapter.get_transformer_blocks()
     handles: list = []
-    adapter.mlp_sums = sig.mlp_sums                      # (read by register_hooks; None without MODEGPT_MLP_INTERCEPT=1)
-    adapter.x_sums = sig.x_sums                          # (likewise; None without MODEGPT_VO_INTERCEPT=1)
-    adapter.qk_rope_sums = sig.qk_rope                   # (likewise; None without MODEGPT_QK_ROPE=1 on a rotary model)
-    adapter.qk_pair_sums = sig.qk_pairs                  # (likewise; None without MODEGPT_QK_SEQ=1 beside it)
-    adapter.qk_causal_sums = sig.qk_causals              # (likewise; None without MODEGPT_QK_CAUSAL=1 beside it)
+    for stat in calib_stats.STATS:                       # (read by register_hooks; None when the statistic is not collected)
+        setattr(adapter, stat.sums_attr, sig.value(stat.name))
     for i in targets:
         adapter.register_hooks(i, blocks[i], cov_mlp_list=sig.lists["mlp"], cov_q_list=sig.lists["q"],
                                cov_k_list=sig.lists["k"], cov_x_list=sig.lists["x"], handles=handles, logger=logger)
@@ -307,16 +220,9 @@ def _calibrate_model(adapter: ModelAdapter, n_samples: int, batch_size: int, tar
     adapter.bi_scores = bi_scores
     adapter.calib_tokens = n_tokens       # (how many tokens each statistic summed over: the fp64 route's rounding bound scales with it)
     sig.finalize(n_texts)
-    adapter.mlp_sums = None
-    adapter.mlp_means = sig.mlp_sums                     # per target layer mu = E[h] (None without the switch): compress_nystrom reads it
-    adapter.x_sums = None
-    adapter.x_means = sig.x_sums                         # per target layer mu = E[x] (None without the switch): compress_vo reads it
-    adapter.qk_rope_sums = None
-    adapter.qk_rope_stats = sig.qk_rope                  # (sigma_q', sigma_k') lists (None without the switch): compress_qk reads them
-    adapter.qk_pair_sums = None
-    adapter.qk_pair_stats = sig.qk_pairs                 # (P, P_raw) lists (None without the switch): compress_qk reads them
-    adapter.qk_causal_sums = None
-    adapter.qk_causal_stats = sig.qk_causals             # (P^c, P^c_raw) lists (None without the switch): compress_qk reads them
+    for stat in calib_stats.STATS:                       # (the compressors read these; None when the statistic is not collected)
+        setattr(adapter, stat.sums_attr, None)
+        setattr(adapter, stat.stats_attr, sig.value(stat.name))
     adapter.cov_routes = None  # (counts of an earlier calibration do not describe this one)
     if ops.COV_MODE == "i8":   # the route of every large-statistic launch was picked on the device; read the tally once
         if ops.I8_ROWS:        # (before the reset below, which clears this counter too)

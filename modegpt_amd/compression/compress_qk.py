@@ -7,7 +7,8 @@ from typing import List, Optional
 import torch
 from torch import Tensor
 
-from .. import _lib, ops
+from .. import _lib, calib_stats, ops
+from ..calib_stats import layer_value
 from ..adapters.model_adapter import ModelAdapter
 from ..model_utils import dtype_p, local_device
 from .compress_mlp import I8_GUARANTEED_EPS
@@ -29,6 +30,11 @@ _SQRT_M_DEFAULT_RIDGE = 1e-4  # sqrt_M's default ridge_lambda (compression_utils
 EIGH_ROUTE_MEASURED_ULPS = 41.04     # (at tests/golden tiny_mha sigma_k[2], rho = 1e-4; the synthetic part of the family: 24 .. 39 depending on LAPACK threads)
 EIGH_ROUTE_SAFETY = 4
 EIGH_ROUTE_EPS_ABS = EIGH_ROUTE_SAFETY * EIGH_ROUTE_MEASURED_ULPS * 2.0 ** -53
+
+# ops.qk_select_statistic()'s name of an optional Q/K statistic -> (its record in calib_stats.STATS, what metrics["qk_selection"]
+# calls a selection scored on it).  MODEGPT_<switch>_SELECT=1 selects on it; the refusal when the layer has none names the
+# record's switch, and the switch of the statistic it needs, as the remedy.
+SELECT_STATS = {"rope": ("qk_rope", "post_rope"), "seq": ("qk_pair", "within_sequence"), "causal": ("qk_causal", "within_sequence_causal")}
 
 
 def attention_error_eps(adapter) -> float:
@@ -76,53 +82,38 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
     mode, ridge_q, ridge_k = qk_mode_and_ridges(arch, n_kv != n_heads, adapter.config.ridge_qk)
     cq = cov_q_list.to(device=local_device(), dtype=dtype_p)
     ck = cov_k_list.to(device=local_device(), dtype=dtype_p)
-    # the post-RoPE statistics of the layer (MODEGPT_QK_ROPE=1 at calibration or in the loaded record), or None
-    rope = getattr(adapter, "qk_rope_stats", None)
-    rope = None if rope is None or rope[0][layer_idx] is None or rope[1][layer_idx] is None else \
-        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in rope)
+    # Which statistic the selection is scored on (two select switches set together are refused here, before anything else).
     # MODEGPT_QK_ROPE_SELECT=1: the selection, its certificate and the report's order take (sigma_q', sigma_k') instead of the
-    # reference's pre-RoPE pair, same mode and ridges; everything downstream of the mask is unchanged
-    # (which statistic the selection is scored on; two select switches set together are refused here, before anything else)
+    # reference's pre-RoPE pair, same mode and ridges.  MODEGPT_QK_SEQ_SELECT=1 / MODEGPT_QK_CAUSAL_SELECT=1: they take (P, ones) /
+    # (P^c, ones) with ridges 0 -- a unit's score is then the diagonal of the objective 1^T P[D,D] 1, summed over the group.  No
+    # certificate: mdg_qk_select_margin's error model does not cover the cancellation in the centring.  Everything downstream of
+    # the mask is unchanged.
     statistic = ops.qk_select_statistic()
     by_rope = statistic == "rope"
-    if by_rope and rope is None:
-        raise RuntimeError(f"MODEGPT_QK_ROPE_SELECT=1 but layer {layer_idx} has no post-RoPE statistics (adapter.qk_rope_stats): "
-                           "calibrate, or load a record saved, with MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
-    # the within-sequence statistic of the layer (MODEGPT_QK_SEQ=1 at calibration or in the loaded record): (P, P_raw), or None
-    pair = getattr(adapter, "qk_pair_stats", None)
-    pair = None if pair is None or pair[0][layer_idx] is None or pair[1][layer_idx] is None else \
-        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in pair)
-    # MODEGPT_QK_SEQ_SELECT=1: the selection and the report's order take (P, ones) with ridges 0 -- a unit's score is then the
-    # diagonal of the within-sequence objective 1^T P[D,D] 1, summed over the group.  No certificate: mdg_qk_select_margin's error
-    # model does not cover the cancellation in the centring.  Everything downstream of the mask is unchanged.
-    by_seq = statistic == "seq"
-    if by_seq and pair is None:
-        raise RuntimeError(f"MODEGPT_QK_SEQ_SELECT=1 but layer {layer_idx} has no within-sequence statistic (adapter.qk_pair_stats): "
-                           "calibrate, or load a record saved, with MODEGPT_QK_SEQ=1 and MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
-    # the causal statistic of the layer (MODEGPT_QK_CAUSAL=1 at calibration or in the loaded record): (P^c, P^c_raw), or None
-    causal = getattr(adapter, "qk_causal_stats", None)
-    causal = None if causal is None or causal[0][layer_idx] is None or causal[1][layer_idx] is None else \
-        tuple(t[layer_idx].to(device=local_device(), dtype=dtype_p) for t in causal)
-    # MODEGPT_QK_CAUSAL_SELECT=1: the selection and the report's order take (P^c, ones) with ridges 0, as under MODEGPT_QK_SEQ_SELECT
-    # -- a unit's score is the diagonal of the causal objective 1^T P^c[D,D] 1, summed over the group.  No certificate either.
-    by_causal = statistic == "causal"
-    if by_causal and causal is None:
-        raise RuntimeError(f"MODEGPT_QK_CAUSAL_SELECT=1 but layer {layer_idx} has no causal statistic (adapter.qk_causal_stats): "
-                           "calibrate, or load a record saved, with MODEGPT_QK_CAUSAL=1 and MODEGPT_QK_ROPE=1 on a Llama / Qwen2 model")
-    ones = torch.ones(n_kv, head_dim, head_dim, dtype=dtype_p, device=local_device()) if pair is not None or causal is not None \
-        else None
-    if by_causal:
-        sq, sk, sel_ridges = causal[0], ones, (0.0, 0.0)
-    elif by_seq:
-        sq, sk, sel_ridges = pair[0], ones, (0.0, 0.0)
+    # the layer's optional Q/K statistics (their switch at calibration or in the loaded record), or None: the post-RoPE pair
+    # (sigma_q', sigma_k'), the within-sequence (P, P_raw), the causal (P^c, P^c_raw)
+    stats = {}
+    for select, (name, _) in SELECT_STATS.items():
+        value = layer_value(adapter, name, layer_idx)
+        stats[select] = None if value is None else tuple(t.to(device=local_device(), dtype=dtype_p) for t in value)
+    rope = stats["rope"]
+    if statistic in stats and stats[statistic] is None:
+        stat = calib_stats.BY_NAME[SELECT_STATS[statistic][0]]
+        switches = " and ".join(f"{s.switch}=1" for s in (stat,) + ((calib_stats.BY_NAME[stat.needs],) if stat.needs else ()))
+        raise RuntimeError(f"{stat.switch}_SELECT=1 but layer {layer_idx} has no {stat.noun} (adapter.{stat.stats_attr}): "
+                           f"calibrate, or load a record saved, with {switches} on a Llama / Qwen2 model")
+    sequence = {select: value for select, value in stats.items() if select != "rope" and value is not None}
+    ones = torch.ones(n_kv, head_dim, head_dim, dtype=dtype_p, device=local_device()) if sequence else None
+    if statistic in sequence:
+        sq, sk, sel_ridges = sequence[statistic][0], ones, (0.0, 0.0)
     else:
         (sq, sk), sel_ridges = (rope if by_rope else (cq, ck)), (ridge_q, ridge_k)
     mask, q_rows, k_rows = ops.qk_select(sq, sk, rank, mode, *sel_ridges)
     record = getattr(adapter, "attention_margin", None)           # (a duck-typed adapter without it: no certificate)
-    if by_seq or by_causal:
+    if statistic in sequence:
         note = getattr(adapter, "qk_selection_statistic", None)
         if note is not None:                          # (report_attention_margins writes the entry, with the certificate's absence)
-            note(layer_idx, "within_sequence_causal" if by_causal else "within_sequence")
+            note(layer_idx, SELECT_STATS[statistic][1])
     elif record is not None:
         # the selection's certificate stays on the device until the adapter next waits for the stream (report_attention_margins)
         eps_rel = attention_error_eps(adapter)
@@ -130,7 +121,7 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
                eps_rel, EIGH_ROUTE_EPS_ABS)
         note = getattr(adapter, "qk_selection_statistic", None)
         if rope is not None and note is not None:     # (a run without post-RoPE statistics: the entry is what it always was)
-            note(layer_idx, "post_rope" if by_rope else "pre_rope")
+            note(layer_idx, SELECT_STATS["rope"][1] if by_rope else "pre_rope")
     record_error = getattr(adapter, "qk_error", None) if ops.qk_error_enabled() else None      # (... without this: no logit error)
     if record_error is not None:
         # what the selection loses of the logits, at every rank: the order of ALL units from one more scoring call (the mask above is
@@ -144,20 +135,17 @@ def compress_layer(adapter: ModelAdapter, layer_idx: int, rank: int, cov_q_list:
             # the same curves along the SAME order on (sigma_q', sigma_k'): for a rotary model the exact mean-square logit change
             record_rope(layer_idx, ops.qk_rank_curve(rope[0], rope[1], mode, 0.0, 0.0, order, terms_ridges=(ridge_q, ridge_k)) + (order,),
                         rank)
-        record_seq = getattr(adapter, "qk_error_seq", None)
-        if pair is not None and record_seq is not None:
+        for select in ("seq", "causal"):
             # ... and on the within-sequence statistic: cov_q = P (then P_raw), cov_k = ones -- a product with 1.0 is exact, so the
-            # curve is 1^T P[D,D] 1 over the dropped columns D, the part of the logit change softmax can see (then the whole of it)
-            seq = ops.qk_rank_curve(pair[0], ones, mode, 0.0, 0.0, order)
-            raw_curve = ops.qk_rank_curve(pair[1], ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
-            record_seq(layer_idx, seq + (order, raw_curve), rank)
-        record_causal = getattr(adapter, "qk_error_causal", None)
-        if causal is not None and record_causal is not None:
-            # ... and on the causal statistic, the same way: 1^T P^c[D,D] 1 is the variance of the logit change over the keys each
+            # curve is 1^T P[D,D] 1 over the dropped columns D, the part of the logit change softmax can see (then the whole of it);
+            # and on the causal statistic, the same way: 1^T P^c[D,D] 1 is the variance of the logit change over the keys each
             # query can see, summed over the queries (then, on P^c_raw, the mean square over them)
-            cau = ops.qk_rank_curve(causal[0], ones, mode, 0.0, 0.0, order)
-            raw_curve = ops.qk_rank_curve(causal[1], ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
-            record_causal(layer_idx, cau + (order, raw_curve), rank)
+            record_seq = getattr(adapter, "qk_error_" + select, None)
+            if select in sequence and record_seq is not None:
+                centred, raw = sequence[select]
+                curves = ops.qk_rank_curve(centred, ones, mode, 0.0, 0.0, order)
+                raw_curve = ops.qk_rank_curve(raw, ones, mode, 0.0, 0.0, order, want_greedy=False)[1]
+                record_seq(layer_idx, curves + (order, raw_curve), rank)
     W_q = comps.query_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     W_k = comps.key_proj.weight.detach().to(device=local_device(), dtype=torch.bfloat16)
     Q_heads = ops.gather_rows(W_q, q_rows)   # [n_heads*rank, d]

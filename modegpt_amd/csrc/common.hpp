@@ -132,6 +132,29 @@ constexpr int BK = 16;          // k depth of one LDS stage
 constexpr int PITCH = TILE + 2; // fp64 elements per LDS panel row (pad keeps 16-B alignment, spreads banks)
 constexpr int PANEL = BK * PITCH;
 
+// How 256 threads stage one BK x 128 panel of DT elements in 16-byte chunks (cov.hip's cov_tile, qk_seq.hpp's seq_load / seq_store)
+template <int DT> struct Stage {
+  typedef typename ElemOf<DT>::type T;
+  static constexpr int VEC = 16 / (int)sizeof(T);        // elements per 16-byte chunk
+  static constexpr int CPR = TILE / VEC;                 // chunks per token row
+  static constexpr int CPT = BK * CPR / 256;             // chunks per thread
+  union Chunk {
+    uint4 q;
+    T e[VEC];
+  };
+  // Which (token row, first column) staging chunk c of a BK x 128 panel is.  NOT the obvious c/CPR, c%CPR: a chunk
+  // widens to VEC*8 bytes of fp64, so neighbouring chunks of one row sit 64 B (bf16) apart and the 8 lanes of a
+  // ds_write_b128 group would share 2 of the 8 bank quads (4-way conflict, measured: it starves the fragment
+  // reads).  Rows are 1040 B apart = 1 bank quad (mod 8), so a group of RG rows x 8/RG chunks covers all 8 quads.
+  static constexpr int RG = VEC >= 8 ? 4 : (VEC == 4 ? 2 : 1);
+  static constexpr int CG = 8 / RG;
+  __device__ static __forceinline__ void chunk_rc(int c, int& row, int& col) {
+    const int g = c >> 3, i = c & 7;
+    row = (g % (BK / RG)) * RG + (i % RG);
+    col = ((g / (BK / RG)) * CG + i / RG) * VEC;
+  }
+};
+
 struct Acc {
   d4 v[4][4];  // [sub-tile row sa][sub-tile col sb]
 };

@@ -31,28 +31,6 @@ struct CovArgs {
   int gate_mask, gate_want;
 };
 
-template <int DT> struct Stage {
-  typedef typename ElemOf<DT>::type T;
-  static constexpr int VEC = 16 / (int)sizeof(T);        // elements per 16-byte chunk
-  static constexpr int CPR = TILE / VEC;                 // chunks per token row
-  static constexpr int CPT = BK * CPR / 256;             // chunks per thread
-  union Chunk {
-    uint4 q;
-    T e[VEC];
-  };
-  // Which (token row, first column) staging chunk c of a BK x 128 panel is.  NOT the obvious c/CPR, c%CPR: a chunk
-  // widens to VEC*8 bytes of fp64, so neighbouring chunks of one row sit 64 B (bf16) apart and the 8 lanes of a
-  // ds_write_b128 group would share 2 of the 8 bank quads (4-way conflict, measured: it starves the fragment
-  // reads).  Rows are 1040 B apart = 1 bank quad (mod 8), so a group of RG rows x 8/RG chunks covers all 8 quads.
-  static constexpr int RG = VEC >= 8 ? 4 : (VEC == 4 ? 2 : 1);
-  static constexpr int CG = 8 / RG;
-  __device__ static __forceinline__ void chunk_rc(int c, int& row, int& col) {
-    const int g = c >> 3, i = c & 7;
-    row = (g % (BK / RG)) * RG + (i % RG);
-    col = ((g / (BK / RG)) * CG + i / RG) * VEC;
-  }
-};
-
 // FAST: every tile is full and 16-byte loads are legal, so the stage is one unconditional vector load per
 // chunk and its s_waitcnt can sink below the stage's MFMAs; the generic path (ragged n_feat, unaligned
 // views) goes element by element.

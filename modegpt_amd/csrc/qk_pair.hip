@@ -14,97 +14,24 @@
 // belongs to.  The key column sums m are taken from the staged panel by role 1 (thread t: column t & 127, token rows
 // 8 (t >> 7) .. + 8 of the stage, in ascending order).  After the token loop role 1 hands S = G^k - m m^T / T (then G^k) to
 // role 0 through the LDS the panels no longer need, lane to lane -- wave w and wave w + 4 hold the same entries in the same
-// registers -- and role 0 multiplies in the accumulator layout and writes the workspace slot of (b, h).  qk_pair_fold_kernel
+// registers -- and role 0 multiplies in the accumulator layout and writes the workspace slot of (b, h).  qk_seq_fold_kernel
 // then adds the slots onto pair in ascending b, ONE ADDITION PER SEQUENCE onto the running value, so a call over B sequences
 // gives the bits of B calls over one sequence each.  No atomics, every sum in a fixed order.
 //
 // Symmetry to the bit: entry (a, b) and entry (b, a) of a Gram are the same products accumulated in the same token order by
 // the same instruction, m_a m_b and the two further products commute, so both triangles come out equal without a mirror pass.
 //
-// The staging (Stage, load_panel, store_panel) follows cov.hip's cov_tile -- copied, not shared, so that cov.hip's kernels stay
-// as they are; the tile core (Acc, mma_steps, acc_row / acc_col) is common.hpp's.
-#include "common.hpp"
+// The staging, the fold and the host half of the entry point are qk_seq.hpp's, shared with qk_causal.hip; the tile core (Acc,
+// mma_steps, acc_row / acc_col) is common.hpp's.
+#include "qk_seq.hpp"
 #pragma STDC FP_CONTRACT OFF
 
 namespace mdg {
 namespace {
 
-constexpr int MAX_HD = TILE;
-
-struct PairArgs {
-  const void* q;
-  const void* k;
-  int64_t ld_q, ld_k, T;
-  int n_heads, group, hd;
-  int vec_q, vec_k;
-  double* part;      // [B, n_heads, hd, hd]
-  double* part_raw;  // same, or nullptr
-};
-
-// cov.hip Stage<DT>: the chunk -> (token row, first column) map that spreads a ds_write_b128 group over all bank quads
-template <int DT> struct PStage {
-  typedef typename ElemOf<DT>::type T;
-  static constexpr int VEC = 16 / (int)sizeof(T);
-  static constexpr int CPR = TILE / VEC;
-  static constexpr int CPT = BK * CPR / 256;
-  union Chunk {
-    uint4 q;
-    T e[VEC];
-  };
-  static constexpr int RG = VEC >= 8 ? 4 : (VEC == 4 ? 2 : 1);
-  static constexpr int CG = 8 / RG;
-  __device__ static __forceinline__ void chunk_rc(int c, int& row, int& col) {
-    const int g = c >> 3, i = c & 7;
-    row = (g % (BK / RG)) * RG + (i % RG);
-    col = ((g / (BK / RG)) * CG + i / RG) * VEC;
-  }
-};
-
-// One 16-token stage of one head: rows tok0 .. tok0+15 (below tok_end), columns 0 .. hd-1 of `base` (the head's first element
-// of the sequence's first row).  Everything outside stays zero: a ragged hd and a ragged last stage add exact zeros.
 template <int DT>
-__device__ __forceinline__ void pair_load(const void* base, int64_t ld, int64_t tok0, int64_t tok_end, int hd, int vec_ok,
-                                          int tid, typename PStage<DT>::Chunk* regs) {
-  typedef PStage<DT> S;
-  typedef typename S::T T;
-  const T* x = (const T*)base;
-#pragma unroll
-  for (int p = 0; p < S::CPT; p++) {
-    int row, col;
-    S::chunk_rc(tid + 256 * p, row, col);
-    const int64_t tok = tok0 + row;
-    typename S::Chunk ch;
-    ch.q = make_uint4(0, 0, 0, 0);
-    if (tok < tok_end && col < hd) {
-      const T* src = x + tok * ld + col;
-      if (vec_ok && col + S::VEC <= hd) {
-        ch.q = *(const uint4*)src;
-      } else {
-#pragma unroll
-        for (int e = 0; e < S::VEC; e++)
-          if (col + e < hd) ch.e[e] = src[e];
-      }
-    }
-    regs[p] = ch;
-  }
-}
-
-template <int DT>
-__device__ __forceinline__ void pair_store(double* panel, int tid, const typename PStage<DT>::Chunk* regs) {
-  typedef PStage<DT> S;
-#pragma unroll
-  for (int p = 0; p < S::CPT; p++) {
-    int row, col;
-    S::chunk_rc(tid + 256 * p, row, col);
-    double* dst = panel + row * PITCH + col;
-#pragma unroll
-    for (int e = 0; e < S::VEC; e += 2) *(d2*)(dst + e) = (d2){load_f64<DT>(regs[p].e, e), load_f64<DT>(regs[p].e, e + 1)};
-  }
-}
-
-template <int DT>
-__global__ __launch_bounds__(512) void qk_pair_kernel(PairArgs a) {
-  typedef PStage<DT> S;
+__global__ __launch_bounds__(512) void qk_pair_kernel(SeqArgs a) {
+  typedef Stage<DT> S;
   __shared__ double lds[4 * PANEL];  // Q[2], K[2]; after the token loop: the exchange buffer
   __shared__ double msum[2 * TILE];
   const int role = threadIdx.x >> 8;  // wave-uniform: 0 = query Gram, 1 = key Gram
@@ -125,21 +52,21 @@ __global__ __launch_bounds__(512) void qk_pair_kernel(PairArgs a) {
   const int mcol = tid & (TILE - 1), mrow = (tid >> 7) * (BK / 2);
 
   typename S::Chunk regs[S::CPT];
-  pair_load<DT>(base, ld, 0, a.T, a.hd, vec_ok, tid, regs);
-  pair_store<DT>(panels, tid, regs);
+  seq_load<DT>(base, ld, 0, a.T, a.hd, vec_ok, tid, regs);
+  seq_store<DT, PITCH>(panels, tid, regs);
   __syncthreads();
   for (int64_t s = 0; s < n_stage; s++) {
     const int cur = (int)(s & 1);
     const bool more = s + 1 < n_stage;
     // the next stage's global loads fly while this one is multiplied
-    if (more) pair_load<DT>(base, ld, (s + 1) * BK, a.T, a.hd, vec_ok, tid, regs);
+    if (more) seq_load<DT>(base, ld, (s + 1) * BK, a.T, a.hd, vec_ok, tid, regs);
     const double* P = panels + cur * PANEL;
     mma_stage(P, P, wr, wc, lane, acc);
     if (role) {
 #pragma unroll
       for (int r = 0; r < BK / 2; r++) m += P[(mrow + r) * PITCH + mcol];
     }
-    if (more) pair_store<DT>(panels + (cur ^ 1) * PANEL, tid, regs);
+    if (more) seq_store<DT, PITCH>(panels + (cur ^ 1) * PANEL, tid, regs);
     __syncthreads();
   }
   if (role) msum[tid] = m;
@@ -200,19 +127,10 @@ __global__ __launch_bounds__(512) void qk_pair_kernel(PairArgs a) {
   }
 }
 
-// pair[h][e] = (..((pair[h][e] + part[0][h][e]) + part[1][h][e]) .. + part[B-1][h][e]): ascending b, one rounding per sequence
-__global__ __launch_bounds__(256) void qk_pair_fold_kernel(const double* part, const double* part_raw, int64_t B, int64_t n,
-                                                           double* pair, double* pair_raw) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  double v = pair[e];
-  for (int64_t b = 0; b < B; b++) v += part[b * n + e];
-  pair[e] = v;
-  if (part_raw) {
-    double w = pair_raw[e];
-    for (int64_t b = 0; b < B; b++) w += part_raw[b * n + e];
-    pair_raw[e] = w;
-  }
+void pair_launch(int dtype, const SeqArgs& a, dim3 grid, hipStream_t st) {
+  if (dtype == MDG_BF16) hipLaunchKernelGGL(qk_pair_kernel<MDG_BF16>, grid, dim3(512), 0, st, a);
+  else if (dtype == MDG_F16) hipLaunchKernelGGL(qk_pair_kernel<MDG_F16>, grid, dim3(512), 0, st, a);
+  else hipLaunchKernelGGL(qk_pair_kernel<MDG_F32>, grid, dim3(512), 0, st, a);
 }
 
 }  // namespace
@@ -220,48 +138,10 @@ __global__ __launch_bounds__(256) void qk_pair_fold_kernel(const double* part, c
 
 using namespace mdg;
 
-extern "C" size_t mdg_qk_pair_ws_bytes(int64_t B, int n_heads, int hd, int want_raw) {
-  if (B <= 0 || n_heads <= 0 || hd <= 0) return 0;
-  return (size_t)B * (size_t)n_heads * (size_t)hd * (size_t)hd * sizeof(double) * (want_raw ? 2 : 1);
-}
+extern "C" size_t mdg_qk_pair_ws_bytes(int64_t B, int n_heads, int hd, int want_raw) { return seq_ws_bytes(B, n_heads, hd, want_raw); }
 
 extern "C" int mdg_qk_pair_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, int dtype, int64_t B, int64_t T,
                                  int n_heads, int n_kv, int hd, double* pair, double* pair_raw, void* ws, size_t ws_bytes,
                                  void* stream) {
-  MDG_CLEAR();
-  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16 || dtype == MDG_F32, "mdg_qk_pair_accum: dtype %d (bf16, f16 or f32)", dtype);
-  MDG_CHECK_ARG(hd >= 1 && hd <= MAX_HD, "mdg_qk_pair_accum: head_dim=%d must be >= 1 and <= %d", hd, MAX_HD);
-  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "mdg_qk_pair_accum: n_heads=%d must be a positive multiple of n_kv=%d",
-                n_heads, n_kv);
-  MDG_CHECK_ARG(B >= 0 && T >= 0, "mdg_qk_pair_accum: negative extent (B=%lld T=%lld)", (long long)B, (long long)T);
-  const int64_t wq = (int64_t)n_heads * hd, wk = (int64_t)n_kv * hd;
-  MDG_CHECK_ARG(ld_q >= wq, "mdg_qk_pair_accum: ld_q=%lld < n_heads*head_dim=%lld", (long long)ld_q, (long long)wq);
-  MDG_CHECK_ARG(ld_k >= wk, "mdg_qk_pair_accum: ld_k=%lld < n_kv*head_dim=%lld", (long long)ld_k, (long long)wk);
-  if (B == 0 || T == 0) return MDG_OK;
-  MDG_CHECK_ARG(B <= 0x7fffffff / (int64_t)n_heads && ceil_div((int64_t)n_heads * hd * hd, 256) <= 0x7fffffff,
-                "mdg_qk_pair_accum: B*n_heads = %lld x %d exceeds one launch", (long long)B, n_heads);
-  MDG_CHECK_ARG(q && k && pair && ws, "mdg_qk_pair_accum: null pointer");
-  const size_t need = mdg_qk_pair_ws_bytes(B, n_heads, hd, pair_raw != nullptr);
-  MDG_CHECK_ARG(ws_bytes >= need, "mdg_qk_pair_accum: workspace %zu < required %zu", ws_bytes, need);
-  MDG_CHECK_ARG((uintptr_t)ws % 8 == 0, "mdg_qk_pair_accum: workspace is not 8-byte aligned");
-
-  const int64_t es = (int64_t)dtype_size(dtype);
-  const int64_t n = (int64_t)n_heads * hd * hd;
-  PairArgs a;
-  a.q = q; a.k = k; a.ld_q = ld_q; a.ld_k = ld_k; a.T = T;
-  a.n_heads = n_heads; a.group = n_heads / n_kv; a.hd = hd;
-  // 16-byte loads: the base, every row and every head start must be 16-byte aligned
-  a.vec_q = (uintptr_t)q % 16 == 0 && (ld_q * es) % 16 == 0 && (hd * es) % 16 == 0;
-  a.vec_k = (uintptr_t)k % 16 == 0 && (ld_k * es) % 16 == 0 && (hd * es) % 16 == 0;
-  a.part = (double*)ws;
-  a.part_raw = pair_raw ? (double*)ws + B * n : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(B * n_heads));
-  if (dtype == MDG_BF16) hipLaunchKernelGGL(qk_pair_kernel<MDG_BF16>, grid, dim3(512), 0, st, a);
-  else if (dtype == MDG_F16) hipLaunchKernelGGL(qk_pair_kernel<MDG_F16>, grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL(qk_pair_kernel<MDG_F32>, grid, dim3(512), 0, st, a);
-  MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(qk_pair_fold_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, a.part, a.part_raw, B, n, pair, pair_raw);
-  MDG_LAUNCH_CHECK();
-  return MDG_OK;
+  return seq_accum("mdg_qk_pair_accum", q, ld_q, k, ld_k, dtype, B, T, n_heads, n_kv, hd, pair, pair_raw, ws, ws_bytes, stream, pair_launch);
 }

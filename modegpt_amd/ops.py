@@ -1345,9 +1345,10 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
     return out
 
 
-def _qk_seq_rows(fn: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim):
-    """The argument checks qk_pair_accum and qk_causal_accum share (messages under the caller's name `fn`); returns the two row
-    matrices as [B*T, width] views and the extents as ints."""
+def _qk_seq_accum(stem: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim) -> None:
+    """The body qk_pair_accum and qk_causal_accum share (stem "qk_pair" / "qk_causal"): the argument checks, with messages under
+    the caller's name, the two row matrices as [B*T, width] views, then mdg_<stem>_accum on a workspace of mdg_<stem>_ws_bytes."""
+    fn = stem + "_accum"
     _need_gpu(pair, pair_raw, q_rows, k_rows)
     B, T, n_heads, n_kv, head_dim = int(B), int(T), int(n_heads), int(n_kv), int(head_dim)
     if B < 0 or T < 0:
@@ -1378,7 +1379,14 @@ def _qk_seq_rows(fn: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, h
         if (p is None or p.dtype != torch.float64 or tuple(p.shape) != (n_heads, head_dim, head_dim) or not p.is_contiguous()
                 or p.device != q2.device):
             raise ValueError(f"{fn}: {name} must be a contiguous fp64 [{n_heads}, {head_dim}, {head_dim}] on {q2.device}")
-    return q2, k2, B, T, n_heads, n_kv, head_dim
+    if B * T == 0:
+        return
+    lib = _lib.load()
+    need = getattr(lib, f"mdg_{stem}_ws_bytes")(B, n_heads, head_dim, int(pair_raw is not None))
+    ws, wsp = _ws(need, q2.device)
+    with torch.cuda.device(q2.device):
+        check(getattr(lib, "mdg_" + fn)(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
+                                        head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_" + fn)
 
 
 def qk_pair_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: torch.Tensor, k_rows: torch.Tensor, B: int, T: int,
@@ -1388,15 +1396,7 @@ def qk_pair_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: 
     of one pitch; [B, T, width] views of such rows are taken too -- the rows rope_rows writes), in ascending order,
     pair[h] += G^q (.) (G^k - m m^T / T) and, unless pair_raw is None, pair_raw[h] += G^q (.) G^k.  pair, pair_raw: fp64
     [n_heads, head_dim, head_dim], contiguous, accumulated into."""
-    q2, k2, B, T, n_heads, n_kv, head_dim = _qk_seq_rows("qk_pair_accum", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
-    if B * T == 0:
-        return
-    lib = _lib.load()
-    need = lib.mdg_qk_pair_ws_bytes(B, n_heads, head_dim, int(pair_raw is not None))
-    ws, wsp = _ws(need, q2.device)
-    with torch.cuda.device(q2.device):
-        check(lib.mdg_qk_pair_accum(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
-                                    head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_qk_pair_accum")
+    _qk_seq_accum("qk_pair", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
 
 
 def qk_causal_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows: torch.Tensor, k_rows: torch.Tensor, B: int, T: int,
@@ -1406,15 +1406,7 @@ def qk_causal_accum(pair: torch.Tensor, pair_raw: Optional[torch.Tensor], q_rows
     pair[h] += sum_i (q_i q_i^T) (.) (K_i - m_i m_i^T / n_i) / n_i with the prefix sums K_i, m_i over the keys j <= i, n_i = i + 1,
     and, unless pair_raw is None, pair_raw[h] += sum_i (q_i q_i^T) (.) K_i / n_i.  pair, pair_raw: fp64 [n_heads, head_dim,
     head_dim], contiguous, accumulated into."""
-    q2, k2, B, T, n_heads, n_kv, head_dim = _qk_seq_rows("qk_causal_accum", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
-    if B * T == 0:
-        return
-    lib = _lib.load()
-    need = lib.mdg_qk_causal_ws_bytes(B, n_heads, head_dim, int(pair_raw is not None))
-    ws, wsp = _ws(need, q2.device)
-    with torch.cuda.device(q2.device):
-        check(lib.mdg_qk_causal_accum(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), _DT[q2.dtype], B, T, n_heads, n_kv,
-                                      head_dim, pair.data_ptr(), _p(pair_raw), wsp, need, _stream(q2)), "mdg_qk_causal_accum")
+    _qk_seq_accum("qk_causal", pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim)
 
 
 _ROPE_SCRATCH = {}

@@ -111,18 +111,18 @@ def test_mean_file_reads_back_with_numpy_alone_and_every_refusal_fires_on_metada
     assert back.tobytes() == mu.astype("<f8").tobytes()
     json.dumps(entry)                                                         # plain JSON types
     meta = {"files": {"mlp_mean": dict(entry)}}
-    assert CC.validate_mean_entry(meta, n, layer) == entry
+    assert CC.validate_extra_entry(meta, {"n_inner": n}, layer, "mlp_mean") == entry
     assert np.array_equal(CC.read_mean_file(str(tmp_path), layer, entry), mu)
     # refusals on metadata alone (the data file is not opened: it is deleted first)
     path.rename(tmp_path / "moved")
     with pytest.raises(ValueError, match=r"layer 3: field files\.mlp_mean is missing"):
-        CC.validate_mean_entry({"files": {}}, n, layer)
+        CC.validate_extra_entry({"files": {}}, {"n_inner": n}, layer, "mlp_mean")
     for field, bad in (("n", n + 1), ("bytes", 8 * n + 8), ("layout", "packed_lower"), ("sum_bits", "x"), ("sum_bits", None)):
         broken = {"files": {"mlp_mean": dict(entry, **{field: bad})}}
         with pytest.raises(ValueError, match=rf"layer 3: field files\.mlp_mean\.{field}"):
-            CC.validate_mean_entry(broken, n, layer)
+            CC.validate_extra_entry(broken, {"n_inner": n}, layer, "mlp_mean")
     with pytest.raises(ValueError, match=r"files\.mlp_mean\.n"):
-        CC.validate_mean_entry(meta, n + 2, layer)                            # this run's width differs
+        CC.validate_extra_entry(meta, {"n_inner": n + 2}, layer, "mlp_mean")                  # this run's width differs
     with pytest.raises(FileNotFoundError, match=r"layer 3.*files\.mlp_mean\.file"):
         CC.read_mean_file(str(tmp_path), layer, entry)
     # ... and on the data: a truncated file, a flipped bit

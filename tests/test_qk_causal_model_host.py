@@ -150,8 +150,7 @@ def test_finalisation_scale():
     sig = calibration.SigmaBuffers.__new__(calibration.SigmaBuffers)
     one = lambda: [torch.full((2, 4, 4), 3.0, dtype=torch.float64)]          # noqa: E731
     sig.layers, sig.lists = [0], {k: [torch.zeros(2, 2, dtype=torch.float64)] for k in ("mlp", "x", "q", "k")}
-    sig.mlp_sums = sig.x_sums = sig.q_rope = sig.k_rope = None
-    sig.qk_pair, sig.qk_pair_raw, sig.qk_causal, sig.qk_causal_raw = one(), one(), one(), one()
+    sig.extra = {kind: one() for kind in ("qk_pair", "qk_pair_raw", "qk_causal", "qk_causal_raw")}      # (the means and the post-RoPE pair: absent)
     import modegpt_amd.ops as ops
     real = ops.cov_finalize
     ops.cov_finalize = lambda *a, **kw: None                                 # (the four device statistics are not this test's)
@@ -160,11 +159,12 @@ def test_finalisation_scale():
     finally:
         ops.cov_finalize = real
     n = calibration.TOKENS_PER_TEXT_NORMALISER
-    assert bool((sig.qk_causal[0] == 3.0 * (1.0 / (5 * n))).all()) and bool((sig.qk_causal_raw[0] == 3.0 * (1.0 / (5 * n))).all())
-    assert bool((sig.qk_pair[0] == 3.0 * (1.0 / (5 * n ** 2))).all())
-    assert sig.qk_causals[0] is sig.qk_causal and sig.qk_causals[1] is sig.qk_causal_raw
-    sig.qk_causal = None
-    assert sig.qk_causals is None
+    assert bool((sig.extra["qk_causal"][0] == 3.0 * (1.0 / (5 * n))).all()) and bool((sig.extra["qk_causal_raw"][0] == 3.0 * (1.0 / (5 * n))).all())
+    assert bool((sig.extra["qk_pair"][0] == 3.0 * (1.0 / (5 * n ** 2))).all()) and bool((sig.extra["qk_pair_raw"][0] == 3.0 * (1.0 / (5 * n ** 2))).all())
+    assert sig.value("qk_causal")[0] is sig.extra["qk_causal"] and sig.value("qk_causal")[1] is sig.extra["qk_causal_raw"]
+    assert sig.value("qk_rope") is None and sig.value("mlp_mean") is None and sig.value("x_mean") is None     # absent: skipped
+    del sig.extra["qk_causal"], sig.extra["qk_causal_raw"]
+    assert sig.value("qk_causal") is None
 
 
 # ---------------------------------------------------------------- the decoder
@@ -215,20 +215,20 @@ def test_cache_metadata_round_trip_and_refusals(tmp_path):
     assert files["qk_causal"]["file"] == "layer_1_qk_causal.f64" and files["qk_causal_raw"]["file"] == "layer_1_qk_causal_raw.f64"
     meta = {"files": files}
     for kind in cc.CAUSAL_KINDS:
-        entry = cc.validate_rope_entry(meta, ARCH, 1, kind)
+        entry = cc.validate_extra_entry(meta, ARCH, 1, kind)
         assert {k: entry[k] for k in ("n", "batch", "bytes", "layout")} == {k: files["q"][k] for k in ("n", "batch", "bytes", "layout")}
         out = np.empty(values[kind].size)
         cc.read_data_file(d, 1, kind, entry, out)
         assert np.array_equal(out.view(np.int64), values[kind].view(np.int64))
     with pytest.raises(ValueError, match=r"layer 1\b.*files\.qk_causal_raw is missing.*MODEGPT_QK_CAUSAL=1"):
-        cc.validate_rope_entry({"files": {k: v for k, v in files.items() if k != "qk_causal_raw"}}, ARCH, 1, "qk_causal_raw")
+        cc.validate_extra_entry({"files": {k: v for k, v in files.items() if k != "qk_causal_raw"}}, ARCH, 1, "qk_causal_raw")
     with pytest.raises(ValueError, match=r"layer 1\b.*files\.qk_pair is missing.*MODEGPT_QK_SEQ=1"):
-        cc.validate_rope_entry(meta, ARCH, 1, "qk_pair")
+        cc.validate_extra_entry(meta, ARCH, 1, "qk_pair")
     for field, value in (("n", 4), ("batch", 1), ("bytes", 8), ("layout", "packed_lower")):
         broken = copy.deepcopy(meta)
         broken["files"]["qk_causal"][field] = value
         with pytest.raises(ValueError, match=rf"layer 1\b.*files\.qk_causal\.{field}\b"):
-            cc.validate_rope_entry(broken, ARCH, 1, "qk_causal")
+            cc.validate_extra_entry(broken, ARCH, 1, "qk_causal")
     broken = copy.deepcopy(meta)
     broken["files"]["qk_causal"]["trace_bits"] += 1
     with pytest.raises(ValueError, match=r"layer 1\b.*qk_causal"):

@@ -143,21 +143,21 @@ def test_cache_metadata_round_trip_and_refusals(tmp_path):
     assert files["qk_pair"]["file"] == "layer_1_qk_pair.f64" and files["qk_pair_raw"]["file"] == "layer_1_qk_pair_raw.f64"
     meta = {"files": files}
     for kind in cc.PAIR_KINDS:
-        entry = cc.validate_rope_entry(meta, ARCH, 1, kind)
+        entry = cc.validate_extra_entry(meta, ARCH, 1, kind)
         assert {k: entry[k] for k in ("n", "batch", "bytes", "layout")} == {k: files["q"][k] for k in ("n", "batch", "bytes", "layout")}
         out = np.empty(values[kind].size)
         cc.read_data_file(d, 1, kind, entry, out)
         assert np.array_equal(out.view(np.int64), values[kind].view(np.int64))
     # a record without the entry: refused on metadata alone, naming the layer, the field and the switch
     with pytest.raises(ValueError, match=r"layer 1\b.*files\.qk_pair_raw is missing.*MODEGPT_QK_SEQ=1"):
-        cc.validate_rope_entry({"files": {k: v for k, v in files.items() if k != "qk_pair_raw"}}, ARCH, 1, "qk_pair_raw")
+        cc.validate_extra_entry({"files": {k: v for k, v in files.items() if k != "qk_pair_raw"}}, ARCH, 1, "qk_pair_raw")
     with pytest.raises(ValueError, match=r"layer 1\b.*files\.q_rope is missing.*MODEGPT_QK_ROPE=1"):
-        cc.validate_rope_entry(meta, ARCH, 1, "q_rope")
+        cc.validate_extra_entry(meta, ARCH, 1, "q_rope")
     for field, value in (("n", 4), ("batch", 1), ("bytes", 8), ("layout", "packed_lower")):
         broken = copy.deepcopy(meta)
         broken["files"]["qk_pair"][field] = value
         with pytest.raises(ValueError, match=rf"layer 1\b.*files\.qk_pair\.{field}\b"):
-            cc.validate_rope_entry(broken, ARCH, 1, "qk_pair")
+            cc.validate_extra_entry(broken, ARCH, 1, "qk_pair")
     broken = copy.deepcopy(meta)
     broken["files"]["qk_pair"]["trace_bits"] += 1
     with pytest.raises(ValueError, match=r"layer 1\b.*qk_pair"):

@@ -81,11 +81,11 @@ def test_cache_entries_of_the_rope_statistics_are_validated_like_q_and_k(tmp_pat
     entry = CC.write_data_file(str(tmp_path), 3, "q_rope", vals, 4, 2)
     assert entry["file"] == "layer_3_q_rope.f64" and entry["layout"] == "full" and entry["bytes"] == 8 * 32
     assert sorted(entry) == sorted(CC.write_data_file(str(tmp_path), 3, "q", vals, 4, 2))          # the sidecar fields of q / k
-    assert CC.validate_rope_entry({"files": {"q_rope": entry}}, arch, 3, "q_rope") == entry
+    assert CC.validate_extra_entry({"files": {"q_rope": entry}}, arch, 3, "q_rope") == entry
     out = np.empty(32)
     CC.read_data_file(str(tmp_path), 3, "q_rope", entry, out)
     assert np.array_equal(out.view(np.int64), vals.view(np.int64))
     with pytest.raises(ValueError, match=r"layer 3.*q_rope"):
-        CC.validate_rope_entry({"files": {}}, arch, 3, "q_rope")
+        CC.validate_extra_entry({"files": {}}, arch, 3, "q_rope")
     with pytest.raises(ValueError, match=r"layer 3.*k_rope\.batch"):
-        CC.validate_rope_entry({"files": {"k_rope": entry}}, arch, 3, "k_rope")
+        CC.validate_extra_entry({"files": {"k_rope": entry}}, arch, 3, "k_rope")

@@ -159,16 +159,16 @@ def test_x_mean_file_format_and_refusals(tmp_path):
     assert np.array_equal(np.fromfile(os.path.join(d, "layer_3_x_mean.f64"), "<f8"), mu)
     assert not os.path.exists(os.path.join(d, "layer_3_mlp_mean.f64"))                  # (the MLP mean is another file, another switch)
     meta = {"files": {CC.X_MEAN_KIND: entry}}
-    assert CC.validate_mean_entry(meta, 64, 3, kind=CC.X_MEAN_KIND) == entry
+    assert CC.validate_extra_entry(meta, {"d_model": 64}, 3, CC.X_MEAN_KIND) == entry
     assert np.array_equal(CC.read_mean_file(d, 3, entry, kind=CC.X_MEAN_KIND), mu)
     with pytest.raises(ValueError, match=r"layer 3: field files\.x_mean is missing -- the record was saved without MODEGPT_VO_INTERCEPT=1"):
-        CC.validate_mean_entry({"files": {CC.MEAN_KIND: entry}}, 64, 3, kind=CC.X_MEAN_KIND)
+        CC.validate_extra_entry({"files": {CC.MEAN_KIND: entry}}, {"d_model": 64}, 3, CC.X_MEAN_KIND)
     with pytest.raises(ValueError, match=r"files\.mlp_mean is missing -- the record was saved without MODEGPT_MLP_INTERCEPT=1"):
-        CC.validate_mean_entry(meta, 64, 3)                                              # (the MLP switch's message is what it was)
+        CC.validate_extra_entry(meta, {"n_inner": 64}, 3, CC.MEAN_KIND)                                       # (the MLP switch's message is what it was)
     with pytest.raises(ValueError, match=r"files\.x_mean\.n"):
-        CC.validate_mean_entry(meta, 65, 3, kind=CC.X_MEAN_KIND)
+        CC.validate_extra_entry(meta, {"d_model": 65}, 3, CC.X_MEAN_KIND)
     with pytest.raises(ValueError, match=r"files\.x_mean\.sum_bits"):
-        CC.validate_mean_entry({"files": {CC.X_MEAN_KIND: dict(entry, sum_bits="7")}}, 64, 3, kind=CC.X_MEAN_KIND)
+        CC.validate_extra_entry({"files": {CC.X_MEAN_KIND: dict(entry, sum_bits="7")}}, {"d_model": 64}, 3, CC.X_MEAN_KIND)
     with pytest.raises(ValueError, match="64 entries"):
         CC.write_mean_file(d, 3, mu, 65, kind=CC.X_MEAN_KIND)
     # a flipped bit in the file: the exact sum no longer matches
