@@ -246,7 +246,7 @@ __device__ __forceinline__ double load_any(const void* p, int dt, int64_t i) {
 __device__ __forceinline__ void store_any(void* p, int dt, int64_t i, double v) {
   switch (dt) {
     case MDG_BF16: ((bf16_t*)p)[i] = f64_to_bf16(v); break;
-    case MDG_F16: ((__half*)p)[i] = __float2half((float)v); break;
+    case MDG_F16: ((f16_t*)p)[i] = f64_to_f16(v); break;
     case MDG_F32: ((float*)p)[i] = (float)v; break;
     default: ((double*)p)[i] = v; break;
   }

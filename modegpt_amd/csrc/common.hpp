@@ -85,6 +85,15 @@ __device__ __forceinline__ bf16_t f64_to_bf16(double v) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (bf16_t)(u >> 16);
 }
+// fp64 -> fp16 the way torch's .to(float16) does it: double -> float (RNE), then float -> half (RNE).  The empty asm keeps the two
+// conversions apart: written back to back, the backend merges them into ONE rounding of the double (both carry the `contract` flag
+// of HIP's default -ffp-contract=fast), which differs wherever the fp32 value is a tie of the fp16 grid: 1 + 2^-11 + 2^-30 must give
+// 1, not 1 + 2^-10.
+__device__ __forceinline__ f16_t f64_to_f16(double v) {
+  float f = (float)v;
+  asm volatile("" : "+v"(f));
+  return __half_as_ushort(__float2half(f));
+}
 
 template <int DT> struct ElemOf;
 template <> struct ElemOf<MDG_BF16> { typedef bf16_t type; };

@@ -147,6 +147,82 @@ def cond(A):
     return float(w[-1] / w[0])
 
 
+def lattice_case(d, n, r, seed, repeat=False):
+    """Integer data for mdg_nystrom_intercept: W [d, n] and D^ [d, r] in [-8, 8] (exact in bf16), mu [n] in [-16, 16], b_d [d] in
+    [-64, 64], idx the first r entries of a random permutation (shuffled: any order must do), with `repeat` five of them (fewer where
+    r < 10) overwritten by copies of five others.  Every product and partial sum is a small integer, so any fp64 summation order
+    gives the long double model's bits (lattice_is_exact states the conditions)."""
+    rng = np.random.default_rng(104729 * seed + 31 * n + r)
+    W = rng.integers(-8, 9, size=(d, n)).astype(np.float64)
+    D = rng.integers(-8, 9, size=(d, r)).astype(np.float64)
+    mu = rng.integers(-16, 17, size=n).astype(np.float64)
+    idx = rng.permutation(n)[:r].astype(np.int64)
+    if repeat:
+        k = min(5, r // 2)
+        pos = rng.permutation(r)[:2 * k]
+        idx[pos[:k]] = idx[pos[k:]]
+    b_d = rng.integers(-64, 65, size=d).astype(np.float64)
+    return {"W": W, "D": D, "mu": mu, "idx": idx, "b_d": b_d}
+
+
+def lattice_is_exact(c):
+    """The magnitude conditions under which fp64 evaluates a lattice case without a rounding, in any order: the absolute terms of
+    each of a row's two sums add up to less than 2^20 (so every partial sum, delta and b_d + delta are integers below 2^22, their
+    squares below 2^44 < 2^53), and each of the two sums of squares -- of the rows' absolute-term sums, which dominate the rows --
+    stays below 2^48."""
+    mu = np.abs(c["mu"])
+    a = np.abs(c["W"]) @ mu
+    b = np.abs(c["D"]) @ mu[c["idx"]]
+    t_delta, t_wmu = norm_terms(c["W"], c["D"], c["idx"], c["mu"])
+    return bool(a.max() < 2 ** 20 and b.max() < 2 ** 20 and np.abs(c["b_d"]).max() <= 64 and t_delta < 2 ** 48 and t_wmu < 2 ** 48)
+
+
+def intercept_fp64(W_d, D_hat, idx, mu, b_d=None, order="ascending", chunk=2048):
+    """The intercept in PLAIN fp64, one addition at a time: `ascending` adds the columns left to right, `chunks_reversed` takes the
+    chunks of `chunk` columns last to first (ascending within a chunk, the chunk's sum added to the total).  Returns what
+    intercept() returns, as fp64."""
+    def dots(A, v):
+        A, v = np.asarray(A, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        P = A * v[None, :]
+        if order == "ascending":
+            return np.cumsum(P, axis=1)[:, -1]                 # (cumsum is sequential; np.sum would add pairwise)
+        tot = np.zeros(A.shape[0])
+        for a0 in reversed(range(0, A.shape[1], chunk)):
+            tot = tot + np.cumsum(P[:, a0:a0 + chunk], axis=1)[:, -1]
+        return tot
+    mu = np.asarray(mu, dtype=np.float64)
+    wmu = dots(W_d, mu)
+    dl = wmu - dots(D_hat, mu[np.asarray(idx)])
+    b = dl if b_d is None else np.asarray(b_d, dtype=np.float64) + dl
+    sq = (lambda v: np.cumsum(v * v)[-1]) if order == "ascending" else (lambda v: np.cumsum((v * v)[::-1])[-1])
+    return b, sq(dl), sq(wmu)
+
+
+def generic_case(d, n, r, seed):
+    """Generic data for mdg_nystrom_intercept: W and D^ bf16-rounded Gaussians, mu = |Gaussian| times a per-column power of two in
+    2^-3 .. 2^3, b_d a bf16-rounded Gaussian, idx shuffled.  The reference is intercept(), the tolerance bias_bound()."""
+    rng = np.random.default_rng(15485863 * seed + 31 * n + r)
+    W = bf16_round(rng.standard_normal((d, n)))
+    D = bf16_round(rng.standard_normal((d, r)))
+    mu = np.abs(rng.standard_normal(n)) * 2.0 ** rng.integers(-3, 4, size=n)
+    idx = rng.permutation(n)[:r].astype(np.int64)
+    b_d = bf16_round(rng.standard_normal(d))
+    return {"W": W, "D": D, "mu": mu, "idx": idx, "b_d": b_d}
+
+
+# the shapes (d, n, r) of tests/test_gpu_intercept_kernel.py: the smallest at which each piece of the kernel's structure can go wrong
+# (2048-column LDS chunks, 16-byte vectors of eight, 16 rows per workgroup, 4 per wave, 256 rows per trip of the norms loop)
+INTERCEPT_SHAPES = {
+    "A": (1, 1, 1),               # one row of a 16-row workgroup, no vector
+    "B": (3, 9, 7),               # fewer rows than a wave owns; one vector + tail, tail only
+    "C": (17, 2048, 2048),        # exactly one full chunk; r == n; one row into a second workgroup
+    "D": (16, 2049, 2047),        # a second chunk of length 1; a chunk one short of full
+    "E": (257, 2053, 2049),       # a last chunk of 5 (no vector), of 1; the norms loop's second trip with one row
+    "F": (531, 4105, 3891),       # two full chunks + 9; r = 2048 + 1843; ragged workgroup, ragged wave, third norms trip
+    "G": (40, 6144, 4096),        # three / two full chunks, nothing ragged
+}
+
+
 def make_case(n, r, d, tokens=512, seed=0):
     """h = |Gaussian| * column scale (every mean of the order of its standard deviation), bf16-valued, [tokens, n]; W_d [d, n]
     bf16-valued; C = H^T H / tokens and mu = mean_t h (exact in fp64 for tokens = 512); a selection idx of r sorted columns.  numpy fp64 arrays."""

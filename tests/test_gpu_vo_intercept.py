@@ -213,6 +213,29 @@ def test_nan_containment(dev):
     assert torch.equal(after[1], base[1])                                                # (the operands are back as they were)
 
 
+def test_rounding_goes_through_fp32_as_torch_does(dev):
+    """Zero weights at rank 0 make delta = +0, so bias_f64 is b_o and bias_out the rounding alone -- at values where rounding the double
+    directly differs from rounding it through fp32 (a compiler that merges the two conversions gives 1 + 2^-10 for the second)."""
+    shape = (2, 1, 8, 0, 24)
+    n_heads, n_kv, hd, rank, d = shape
+    b_vals = np.zeros(d)
+    b_vals[:5] = [1 + 2.0 ** -8 + 2.0 ** -30, 1 + 2.0 ** -11 + 2.0 ** -30, 1 + 3 * 2.0 ** -8 - 2.0 ** -30, 1e39, 7e4]
+    zero = lambda rows, width: _place(np.zeros((rows, width)), torch.bfloat16, "tight", dev)                       # noqa: E731
+    (bwv, Wv, ld_wv), (bwo, Wo, ld_wo) = zero(n_kv * hd, d), zero(d, n_heads * hd)
+    ops_ = ((Wv, ld_wv), (Wo, ld_wo), (Wv, ld_wv), (Wo, ld_wo), torch.bfloat16, torch.bfloat16)                    # (rank 0: no factors)
+    mu = torch.from_numpy(np.random.default_rng(2).standard_normal(d)).to(dev)
+    b_o = torch.from_numpy(b_vals).to(dev)
+    got = {}
+    for out_tdt in (torch.bfloat16, torch.float16, torch.float32, torch.float64):
+        bias, b64, norms = _call(dev, ops_, shape, 0, mu, None, b_o, torch.float64, out_tdt)
+        assert np.array_equal(b64.numpy(), b_vals)
+        assert torch.equal(bias, b64.to(out_tdt))
+        got[out_tdt] = bias.double().numpy()
+    inf = float("inf")
+    assert got[torch.bfloat16][0] == 1.0 and got[torch.float16][1] == 1.0 and got[torch.bfloat16][2] == 1.015625
+    assert got[torch.float32][3] == inf and got[torch.bfloat16][3] == inf and got[torch.float16][4] == inf
+
+
 def test_bad_arguments(dev):
     from modegpt_amd import _lib
     lib = _lib.load()

@@ -92,6 +92,49 @@ def test_stored_intercept_zeroes_the_mean_error_of_any_stored_tensor():
     assert sq_on < sq_off and np.abs(mean_off).max() > 1e3 * np.abs(mean_on).max()
 
 
+# ---- the case builders of tests/test_gpu_intercept_kernel.py: why that file may assert equality to the bit
+@pytest.mark.parametrize("name,repeat", [(k, False) for k in M.INTERCEPT_SHAPES] + [("E", True), ("F", True)])
+def test_lattice_case_is_exact_in_fp64_in_any_order(name, repeat):
+    d, n, r = M.INTERCEPT_SHAPES[name]
+    assert n <= 6144 and d <= 531
+    c = M.lattice_case(d, n, r, seed=1, repeat=repeat)
+    W, D, mu, idx, b_d = (c[k] for k in ("W", "D", "mu", "idx", "b_d"))
+    assert W.shape == (d, n) and D.shape == (d, r) and mu.shape == (n,) and idx.shape == (r,) and b_d.shape == (d,)
+    for a, lim in ((W, 8), (D, 8), (mu, 16), (b_d, 64)):
+        assert np.array_equal(a, np.round(a)) and np.abs(a).max() <= lim
+    assert np.array_equal(M.bf16_round(W), W) and np.array_equal(M.bf16_round(D), D)
+    assert idx.min() >= 0 and idx.max() < n
+    distinct = len(np.unique(idx))
+    assert distinct == (r - min(5, r // 2) if repeat else r)
+    if r > 8:
+        assert not np.array_equal(idx, np.sort(idx))                              # shuffled
+    assert M.lattice_is_exact(c)
+    for b in (b_d, None):
+        ref = M.intercept(W, D, idx, mu, b)
+        want = tuple(np.asarray(v).astype(np.float64) for v in ref)
+        assert all(np.array_equal(M.ld(w), np.asarray(v)) for w, v in zip(want, ref))     # the model's values ARE fp64 numbers
+        for order in ("ascending", "chunks_reversed"):
+            got = M.intercept_fp64(W, D, idx, mu, b, order=order)
+            assert all(np.array_equal(g, w) for g, w in zip(got, want)), order
+    assert want[1] < 2 ** 48 and want[2] < 2 ** 48
+
+
+def test_generic_case_fp64_evaluation_stays_inside_the_bias_bound():
+    d, n, r = M.INTERCEPT_SHAPES["E"]
+    c = M.generic_case(d, n, r, seed=1)
+    W, D, mu, idx, b_d = (c[k] for k in ("W", "D", "mu", "idx", "b_d"))
+    assert np.array_equal(M.bf16_round(W), W) and np.array_equal(M.bf16_round(D), D) and np.array_equal(M.bf16_round(b_d), b_d)
+    assert mu.min() > 0 and len(np.unique(idx)) == r and not np.array_equal(idx, np.sort(idx))
+    for b in (b_d, None):
+        ref, _, _ = M.intercept(W, D, idx, mu, b)
+        bound = M.bias_bound(W, D, idx, mu, b)
+        for order in ("ascending", "chunks_reversed"):
+            got, _, _ = M.intercept_fp64(W, D, idx, mu, b, order=order)
+            ratio = float((np.abs(M.ld(got) - ref) / bound).max())
+            print(f"generic E, {order}, b_d {'given' if b is not None else 'none'}: err / bound max {ratio:.3e}")
+            assert ratio <= 1
+
+
 # ---- the saved activation mean (calib_cache: layer_<i>_mlp_mean.f64 and its sidecar entry), host half only
 def test_mean_file_reads_back_with_numpy_alone_and_every_refusal_fires_on_metadata(tmp_path):
     import json
