@@ -32,6 +32,35 @@ def build_metrics(_all_metrics: dict) -> dict:
     return m
 
 
+def _show(v) -> str:
+    return "n/a" if v is None else f"{v:.3e}"
+
+
+def _shift_share(m: dict) -> str:
+    return f"({_show(m['relative_error'])} of its energy); {_show(m['shift_share'])} of the uncentred change is invisible to softmax"
+
+
+# What report_qk_errors reads, in this order: (pending record, attribute the host copies are kept under, metrics key, decoder in ops,
+# the entry's "statistic", whether entry 7 of the record -- the curve on the uncentred statistic -- goes to the decoder, the log line
+# behind "[QK] Layer l: rank r: " from the entry and the layer's pre-RoPE relative error).  The pre-RoPE row comes first: the post-RoPE
+# entries quote its figure; the causal row comes behind the within-sequence one: its decoder takes that entry as seq=.
+_QK_REPORTS = (
+    ("_qk_errors", "qk_errors", "qk_logit_error", "decode_qk_logit_error", None, False,
+     lambda m, pre: f"the kept columns lose {m['relative_error']:.3e} of the logit energy"
+     + ("" if m["diagonal_ratio"] is None else f"; the diagonal rule's estimate is {m['diagonal_ratio']:.3g} x that")
+     + ("" if m["greedy_relative_error"] is None else f"; a greedy order on the full objective loses {m['greedy_relative_error']:.3e}")
+     + ("; NOT monotone in the rank" if m["non_monotone"] else "")),
+    ("_qk_errors_rope", "qk_errors_rope", "qk_logit_error_rope", "decode_qk_logit_error", "post_rope", False,
+     lambda m, pre: f"of the post-RoPE logit energy the kept columns lose {_show(m['relative_error'])} (exact for a rotary model); "
+     f"the pre-RoPE statistic said {_show(pre)}"),
+    ("_qk_errors_seq", "qk_errors_seq", "qk_logit_error_seq", "decode_qk_seq_error", "within_sequence", True,
+     lambda m, pre: f"within-sequence, shift-invariant logit error {_show(m['error'])} " + _shift_share(m)),
+    ("_qk_errors_causal", "qk_errors_causal", "qk_logit_error_causal", "decode_qk_causal_error", "within_sequence_causal", True,
+     lambda m, pre: f"causal within-sequence logit error {_show(m['error'])} " + _shift_share(m)
+     + (f"; {_show(m['over_full'])} x the figure without the causal mask" if "over_full" in m else "")),
+)
+
+
 class ModelAdapter(ABC):
     _metrics: dict = {}
 
@@ -97,6 +126,21 @@ class ModelAdapter(ABC):
             if not isinstance(getattr(self, "metrics", None), dict):
                 self.metrics = {}
             self.metrics.setdefault(key, {}).update({str(k): v for k, v in report.items()})
+
+    def _report_pairs(self, name: str, key: str, fields, prefix: str, sentence: str, log=None) -> dict:
+        """The reports of two squared norms per layer (MLP / V/O intercept, v-bias residual): reads the pairs (a, b) recorded under
+        `name` (16 bytes per layer) and writes metrics[key][str(layer)] = {fields[0]: a, fields[1]: b, "relative": a / b} -- both
+        None when either is not finite, the ratio only for b > 0.  Logs "[prefix] Layer l: " + sentence.format(a, b) per layer."""
+        log = log or logging.getLogger("MoDeGPT")
+        pending = self._take(name)
+        report = {}
+        for layer in sorted(pending):
+            a, b = (float(x) for x in pending[layer].cpu().tolist())
+            ok = math.isfinite(a) and math.isfinite(b)
+            report[layer] = {fields[0]: a if ok else None, fields[1]: b if ok else None, "relative": a / b if ok and b > 0 else None}
+            log.info(f"[{prefix}] Layer {layer}: " + sentence.format(a, b))
+        self._merge_metrics(key, report)
+        return report
 
     # ---- the certificate of the MLP rank selections (not upstream; north_star: "rank selections bit-identical") ----
     def selection_margin(self, layer_idx: int, out8, eps: float) -> None:
@@ -280,88 +324,39 @@ class ModelAdapter(ABC):
         greedy_order, order) and writes metrics["qk_logit_error"][str(layer)] = ops.decode_qk_logit_error(...): the mean-square
         logit the layer's heads carry on the calibration statistic, how much of it the kept columns lose, per kv head and for the
         layer, what the diagonal rule believed it would lose, and what a greedy order on the full objective loses at the same rank
-        ("What the Q/K selection costs the attention logits", says what that is not).  Logs one line per layer."""
+        ("What the Q/K selection costs the attention logits", says what that is not).  The same curves on the post-RoPE
+        (MODEGPT_QK_ROPE=1), within-sequence (MODEGPT_QK_SEQ=1) and causal (MODEGPT_QK_CAUSAL=1) statistics, where compress_qk had
+        them, go the same way through the rows of _QK_REPORTS: to self.qk_errors_rope / _seq / _causal and metrics["qk_logit_error_rope"]
+        (with the pre-RoPE figure beside it) / ["qk_logit_error_seq"] (with the error on the uncentred statistic and the share of it
+        softmax cannot see) / ["qk_logit_error_causal"] (the seq entry's fields plus over_full against the layer's seq entry where
+        there is one).  Logs one line per layer and statistic; returns the pre-RoPE report."""
         log = log or logging.getLogger("MoDeGPT")
-        pending = self._take("_qk_errors")
-        report = {}
-        for layer in sorted(pending):
-            tensors, rank = pending[layer]
-            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
-            self._record("qk_errors", layer, host)
-            curve_h, curve, terms, scale, g_curve = host[:5]
-            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
-            m = report[layer] = ops.decode_qk_logit_error(curve_h.tolist(), curve.tolist(), rank, cols, terms=terms.tolist(),
-                                                          scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist())
-            if m["relative_error"] is None:
-                log.warning(f"[QK] Layer {layer}: logit error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
-                continue
-            greedy, diag = m["greedy_relative_error"], m["diagonal_ratio"]
-            log.info(f"[QK] Layer {layer}: rank {rank}: the kept columns lose {m['relative_error']:.3e} of the logit energy"
-                     + ("" if diag is None else f"; the diagonal rule's estimate is {diag:.3g} x that")
-                     + ("" if greedy is None else f"; a greedy order on the full objective loses {greedy:.3e}")
-                     + ("; NOT monotone in the rank" if m["non_monotone"] else ""))
-        # (decode_qk_logit_error maps every non-finite figure to None, so json.dump never meets a NaN)
-        self._merge_metrics("qk_logit_error", report)
-        # the same curves on the post-RoPE statistics, where compress_qk had them (MODEGPT_QK_ROPE=1): the same decoder, the same
-        # order, under metrics["qk_logit_error_rope"] with the pre-RoPE figure beside it
-        pending_rope = self._take("_qk_errors_rope")
-        rope_report = {}
-        for layer in sorted(pending_rope):
-            tensors, rank = pending_rope[layer]
-            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
-            self._record("qk_errors_rope", layer, host)
-            curve_h, curve, terms, scale, g_curve = host[:5]
-            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
-            m = ops.decode_qk_logit_error(curve_h.tolist(), curve.tolist(), rank, cols, terms=terms.tolist(), scale=scale.tolist(),
-                                          greedy_curve=None if g_curve is None else g_curve.tolist())
-            pre = report.get(layer, {}).get("relative_error")
-            m["statistic"], m["pre_rope_relative_error"] = "post_rope", pre
-            rope_report[layer] = m
-            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
-            log.info(f"[QK] Layer {layer}: rank {rank}: of the post-RoPE logit energy the kept columns lose {show(m['relative_error'])} "
-                     f"(exact for a rotary model); the pre-RoPE statistic said {show(pre)}")
-        self._merge_metrics("qk_logit_error_rope", rope_report)
-        # ... and on the within-sequence statistic, where compress_qk had it (MODEGPT_QK_SEQ=1): the same order, under
-        # metrics["qk_logit_error_seq"], with the error on the uncentred statistic and the share of it softmax cannot see
-        pending_seq = self._take("_qk_errors_seq")
-        seq_report = {}
-        for layer in sorted(pending_seq):
-            tensors, rank = pending_seq[layer]
-            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
-            self._record("qk_errors_seq", layer, host)
-            curve_h, curve, terms, scale, g_curve = host[:5]
-            raw_curve = host[7]
-            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
-            m = ops.decode_qk_seq_error(curve_h.tolist(), curve.tolist(), raw_curve.tolist(), rank, cols, terms=terms.tolist(),
-                                        scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist())
-            m["statistic"] = "within_sequence"
-            seq_report[layer] = m
-            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
-            log.info(f"[QK] Layer {layer}: rank {rank}: within-sequence, shift-invariant logit error {show(m['error'])} "
-                     f"({show(m['relative_error'])} of its energy); {show(m['shift_share'])} of the uncentred change is invisible to softmax")
-        self._merge_metrics("qk_logit_error_seq", seq_report)
-        # ... and on the causal statistic, where compress_qk had it (MODEGPT_QK_CAUSAL=1): the same order, under
-        # metrics["qk_logit_error_causal"], the seq entry's fields plus over_full against the layer's seq entry where there is one
-        pending_causal = self._take("_qk_errors_causal")
-        causal_report = {}
-        for layer in sorted(pending_causal):
-            tensors, rank = pending_causal[layer]
-            host = tuple(None if t is None else t.detach().cpu() for t in tensors)
-            self._record("qk_errors_causal", layer, host)
-            curve_h, curve, terms, scale, g_curve = host[:5]
-            raw_curve = host[7]
-            cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
-            m = ops.decode_qk_causal_error(curve_h.tolist(), curve.tolist(), raw_curve.tolist(), rank, cols, terms=terms.tolist(),
-                                           scale=scale.tolist(), greedy_curve=None if g_curve is None else g_curve.tolist(),
-                                           seq=seq_report.get(layer))
-            m["statistic"] = "within_sequence_causal"
-            causal_report[layer] = m
-            show = lambda v: "n/a" if v is None else f"{v:.3e}"      # noqa: E731
-            log.info(f"[QK] Layer {layer}: rank {rank}: causal within-sequence logit error {show(m['error'])} "
-                     f"({show(m['relative_error'])} of its energy); {show(m['shift_share'])} of the uncentred change is invisible to softmax"
-                     + (f"; {show(m['over_full'])} x the figure without the causal mask" if "over_full" in m else ""))
-        self._merge_metrics("qk_logit_error_causal", causal_report)
-        return report
+        reports = {}
+        for name, attr, key, decoder, statistic, with_raw, line in _QK_REPORTS:
+            pending = self._take(name)
+            report = reports[key] = {}
+            for layer in sorted(pending):
+                tensors, rank = pending[layer]
+                host = tuple(None if t is None else t.detach().cpu() for t in tensors)
+                self._record(attr, layer, host)
+                curve_h, curve, terms, scale, g_curve = host[:5]
+                cols = max(1, self.head_dim // max(1, curve.shape[1] - 1))
+                more = {"seq": reports["qk_logit_error_seq"].get(layer)} if key == "qk_logit_error_causal" else {}
+                m = report[layer] = getattr(ops, decoder)(curve_h.tolist(), curve.tolist(), *((host[7].tolist(),) if with_raw else ()), rank,
+                                                          cols, terms=terms.tolist(), scale=scale.tolist(),
+                                                          greedy_curve=None if g_curve is None else g_curve.tolist(), **more)
+                pre = reports["qk_logit_error"].get(layer, {}).get("relative_error")
+                if statistic is None and m["relative_error"] is None:
+                    log.warning(f"[QK] Layer {layer}: logit error has no usable energy (energy {m['energy']!r}, error {m['error']!r})")
+                    continue
+                if statistic is not None:
+                    m["statistic"] = statistic
+                if statistic == "post_rope":
+                    m["pre_rope_relative_error"] = pre
+                log.info(f"[QK] Layer {layer}: rank {rank}: " + line(m, pre))
+            # (the decoders map every non-finite figure to None, so json.dump never meets a NaN)
+            self._merge_metrics(key, report)
+        return reports["qk_logit_error"]
 
     def qk_error_causal(self, layer_idx: int, tensors, rank: int) -> None:
         """compress_qk hands over ops.qk_rank_curve's outputs on the causal statistic (P^c, ones), the order -- the one of qk_error's
@@ -564,17 +559,8 @@ class ModelAdapter(ABC):
         metrics["mlp_intercept"][str(layer)] = {"offset_norm2": ||delta||^2, "mean_output_norm2": ||W_d mu||^2, "relative": their
         ratio}: delta = W_d mu - D^ mu_k is what the stored down_bias adds to the projection's own bias, W_d mu the mean output of the
         uncompressed projection ("The MLP intercept").  Non-finite figures become None."""
-        log = log or logging.getLogger("MoDeGPT")
-        pending = self._take("_mlp_intercepts")
-        report = {}
-        for layer in sorted(pending):
-            off2, mean2 = (float(x) for x in pending[layer].cpu().tolist())
-            ok = math.isfinite(off2) and math.isfinite(mean2)
-            report[layer] = {"offset_norm2": off2 if ok else None, "mean_output_norm2": mean2 if ok else None,
-                             "relative": off2 / mean2 if ok and mean2 > 0 else None}
-            log.info(f"[MLP] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
-        self._merge_metrics("mlp_intercept", report)
-        return report
+        return self._report_pairs("_mlp_intercepts", "mlp_intercept", ("offset_norm2", "mean_output_norm2"), "MLP",
+                                  "the intercept carries {:.3e} of the mean output {:.3e} (squared norms)", log)
 
     # ---- the intercept of the mean-aware V/O truncation (not upstream; MODEGPT_VO_INTERCEPT=1) ----
     def vo_intercept(self, layer_idx: int, norms) -> None:
@@ -587,17 +573,8 @@ class ModelAdapter(ABC):
         their ratio}: a_g = W_v,g mu + b_v,g, the second figure is the constant the uncompressed attention adds to its output, delta what
         the stored o_bias adds to the projection's own bias -- the part of that constant the stored factors do not carry (DESIGN.md
         section 7, "The V/O intercept").  Non-finite figures become None."""
-        log = log or logging.getLogger("MoDeGPT")
-        pending = self._take("_vo_intercepts")
-        report = {}
-        for layer in sorted(pending):
-            off2, mean2 = (float(x) for x in pending[layer].cpu().tolist())
-            ok = math.isfinite(off2) and math.isfinite(mean2)
-            report[layer] = {"offset_norm2": off2 if ok else None, "mean_output_norm2": mean2 if ok else None,
-                             "relative": off2 / mean2 if ok and mean2 > 0 else None}
-            log.info(f"[VO] Layer {layer}: the intercept carries {off2:.3e} of the mean output {mean2:.3e} (squared norms)")
-        self._merge_metrics("vo_intercept", report)
-        return report
+        return self._report_pairs("_vo_intercepts", "vo_intercept", ("offset_norm2", "mean_output_norm2"), "VO",
+                                  "the intercept carries {:.3e} of the mean output {:.3e} (squared norms)", log)
 
     # ---- what the truncated v_proj cannot carry of a v bias where o_proj has no bias to fold it into (not upstream) ----
     def vo_bias_residual(self, layer_idx: int, resid) -> None:
@@ -609,17 +586,8 @@ class ModelAdapter(ABC):
         metrics["vo_bias_residual"][str(layer)] = {"residual_norm2": ||rho||^2, "constant_norm2": ||sum_h W_o,h b_v||^2,
         "relative": their ratio}: rho = sum_h W_o,h (I - Pi_g) b_v,kv(h) is the part of the constant a v bias adds to the attention
         output that the rank-r v_proj cannot represent ("Projection biases").  Non-finite figures become None."""
-        log = log or logging.getLogger("MoDeGPT")
-        pending = self._take("_vo_bias_residuals")
-        report = {}
-        for layer in sorted(pending):
-            rho2, const2 = (float(x) for x in pending[layer].cpu().tolist())
-            ok = math.isfinite(rho2) and math.isfinite(const2)
-            report[layer] = {"residual_norm2": rho2 if ok else None, "constant_norm2": const2 if ok else None,
-                             "relative": rho2 / const2 if ok and const2 > 0 else None}
-            log.info(f"[VO] Layer {layer}: the truncated v_proj loses {rho2:.3e} of the v bias's output constant {const2:.3e} (squared norms)")
-        self._merge_metrics("vo_bias_residual", report)
-        return report
+        return self._report_pairs("_vo_bias_residuals", "vo_bias_residual", ("residual_norm2", "constant_norm2"), "VO",
+                                  "the truncated v_proj loses {:.3e} of the v bias's output constant {:.3e} (squared norms)", log)
 
     # ---- in-place slicing (model_adapter.py:394-542; upstream's call sites are commented out in favour of the
     #      save_layer -> convert_model route, the methods stay part of the adapter surface) ----

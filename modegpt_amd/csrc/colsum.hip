@@ -1,9 +1,11 @@
 // First moments of the MLP statistic and what is done with them (not upstream: the reference's refit has no intercept):
 //   mdg_col_sum_accum      sum[j] += sum_t f(x[t, j])   in fp64, one pass over x                        (HBM-bound: the bytes of x)
 //   mdg_cov_center         S_ij = fma(-mu_i, mu_j, C_ij), both triangles from the lower one of C          (HBM-bound: 1.5 n^2 8 bytes)
-//   mdg_nystrom_intercept  delta_i = W_d[i, :] mu - D^[i, :] mu[idx], the bias b_d + delta and two norms  (one read of W_d and D^)
+//   mdg_nystrom_intercept  delta_i = W_d[i, :] mu - D^[i, :] mu[idx], the bias b_d + delta and two norms  (one read of W_d and D^;
+//                          the rows and the norms through row_dots.hpp, shared with mdg_vo_intercept and mdg_vo_bias)
 // No atomics anywhere; every sum is taken in an order that depends on the shapes alone, so the bits repeat from run to run.
 #include "common.hpp"
+#include "row_dots.hpp"
 
 using namespace mdg;
 
@@ -167,104 +169,20 @@ __global__ __launch_bounds__(256) void cov_center_kernel(const double* C, int64_
 }
 
 // ---------------------------------------------------------------- intercept
-// A wave owns IC_ROWS / 4 rows, lanes go along the row (coalesced; 16-byte loads of eight 16-bit weights where the operand allows),
-// the vector is staged per chunk of IC_CHUNK columns in LDS.  Every product enters its sum through fma (exact product, one rounding
-// per addition); a lane adds its columns in ascending order, the wave reduces by butterfly: a fixed order.
-constexpr int IC_CHUNK = 2048, IC_ROWS = 16, IC_RPW = IC_ROWS / 4;
-
-// out[rr] = sum_j M[row0 + rr, j] v(j), j < ncols; v(j) = vec[idx[j]] (idx given; an entry outside 0 .. nvecsrc-1 reads NaN) or vec[j].
-// A row beyond d reads row d - 1; the caller drops it.  All 256 threads of the workgroup call this together.
-template <int DT>
-__device__ __forceinline__ void ic_row_dots(const void* M, int64_t ld, int64_t d, int64_t row0, int64_t ncols, const double* vec,
-                                            int64_t nvecsrc, const int64_t* idx, int vec16, double* sv_, double* out) {
-  const int tid = threadIdx.x, lane = tid & 63;
-#pragma unroll
-  for (int rr = 0; rr < IC_RPW; rr++) out[rr] = 0.;
-  for (int64_t a0 = 0; a0 < ncols; a0 += IC_CHUNK) {
-    const int len = (int)(ncols - a0 < IC_CHUNK ? ncols - a0 : IC_CHUNK);
-    __syncthreads();
-    for (int e = tid; e < len; e += 256) {
-      if (idx) {
-        const int64_t id = idx[a0 + e];
-        sv_[e] = (id >= 0 && id < nvecsrc) ? vec[id] : __longlong_as_double(0x7ff8000000000000ll);
-      } else {
-        sv_[e] = vec[a0 + e];
-      }
-    }
-    __syncthreads();
-    int64_t base[IC_RPW];
-    double s[IC_RPW];
-#pragma unroll
-    for (int rr = 0; rr < IC_RPW; rr++) {
-      const int64_t row = row0 + rr < d ? row0 + rr : d - 1;
-      base[rr] = row * ld + a0;
-      s[rr] = 0.;
-    }
-    int done = 0;
-    if ((DT == MDG_BF16 || DT == MDG_F16) && vec16) {
-      for (int v = lane; v < len / 8; v += 64) {
-        uint4 q4[IC_RPW];
-#pragma unroll
-        for (int rr = 0; rr < IC_RPW; rr++) q4[rr] = ((const uint4*)((const unsigned short*)M + base[rr]))[v];
-        const double* vp = sv_ + 8 * v;
-#pragma unroll
-        for (int rr = 0; rr < IC_RPW; rr++) {
-          double x[8];
-          unpack16<DT, 8>(q4[rr], x);
-#pragma unroll
-          for (int k = 0; k < 8; k++) s[rr] = fma(x[k], vp[k], s[rr]);
-        }
-      }
-      done = len / 8 * 8;
-    }
-    for (int e = done + lane; e < len; e += 64) {
-      const double ve = sv_[e];
-#pragma unroll
-      for (int rr = 0; rr < IC_RPW; rr++) s[rr] = fma(load_f64<DT>(M, base[rr] + e), ve, s[rr]);
-    }
-#pragma unroll
-    for (int rr = 0; rr < IC_RPW; rr++) out[rr] += s[rr];
-  }
-#pragma unroll
-  for (int rr = 0; rr < IC_RPW; rr++) {
-    double s = out[rr];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    out[rr] = s;
-  }
-}
-
-__device__ __forceinline__ double load_any(const void* p, int dt, int64_t i) {
-  switch (dt) {
-    case MDG_BF16: return load_f64<MDG_BF16>(p, i);
-    case MDG_F16: return load_f64<MDG_F16>(p, i);
-    case MDG_F32: return load_f64<MDG_F32>(p, i);
-    default: return load_f64<MDG_F64>(p, i);
-  }
-}
-
-// the model's dtype the way torch's .to() rounds an fp64 value: through fp32 for the 16-bit types
-__device__ __forceinline__ void store_any(void* p, int dt, int64_t i, double v) {
-  switch (dt) {
-    case MDG_BF16: ((bf16_t*)p)[i] = f64_to_bf16(v); break;
-    case MDG_F16: ((f16_t*)p)[i] = f64_to_f16(v); break;
-    case MDG_F32: ((float*)p)[i] = (float)v; break;
-    default: ((double*)p)[i] = v; break;
-  }
-}
-
+// The rows of W_d against mu and of D^ against mu[idx] through row_dots (row_dots.hpp), one after the other on the same LDS chunk.
 template <int DT>
 __global__ __launch_bounds__(256) void intercept_rows_kernel(const void* Wd, int64_t ld_wd, int64_t d, int64_t n, const void* Dh,
                                                              int64_t ld_dh, int64_t r, const int64_t* idx, const double* mu, int vec_w,
                                                              int vec_d, const void* b_d, int b_dtype, void* bias_out, int out_dtype,
                                                              double* bias_f64, double* delta_rows, double* wmu_rows) {
-  __shared__ double sv_[IC_CHUNK];
+  __shared__ double sv_[RD_CHUNK];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int64_t row0 = (int64_t)blockIdx.x * IC_ROWS + (int64_t)w * IC_RPW;
-  double a[IC_RPW], b[IC_RPW];
-  ic_row_dots<DT>(Wd, ld_wd, d, row0, n, mu, n, nullptr, vec_w, sv_, a);
-  ic_row_dots<MDG_BF16>(Dh, ld_dh, d, row0, r, mu, n, idx, vec_d, sv_, b);
+  const int64_t row0 = (int64_t)blockIdx.x * RD_ROWS + (int64_t)w * RD_RPW;
+  double a[RD_RPW], b[RD_RPW];
+  row_dots<DT, 1>(Wd, ld_wd, d, row0, (int)n, StageGather{mu, n, nullptr}, vec_w, sv_, a);
+  row_dots<MDG_BF16, 1>(Dh, ld_dh, d, row0, (int)r, StageGather{mu, n, idx}, vec_d, sv_, b);
 #pragma unroll
-  for (int rr = 0; rr < IC_RPW; rr++) {
+  for (int rr = 0; rr < RD_RPW; rr++) {
     const int64_t row = row0 + rr;
     if (lane == 0 && row < d) {
       const double delta = a[rr] - b[rr];
@@ -277,34 +195,7 @@ __global__ __launch_bounds__(256) void intercept_rows_kernel(const void* Wd, int
   }
 }
 
-// norms = (sum_i delta_i^2, sum_i (W_d mu)_i^2): one workgroup, thread t sums rows t, t + 256, ... in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void intercept_norms_kernel(const double* delta_rows, const double* wmu_rows, int64_t d, double* norms) {
-  __shared__ double pd_[256], pw_[256];
-  const int tid = threadIdx.x;
-  double sd = 0., sw = 0.;
-  for (int64_t i = tid; i < d; i += 256) {
-    sd = fma(delta_rows[i], delta_rows[i], sd);
-    sw = fma(wmu_rows[i], wmu_rows[i], sw);
-  }
-  pd_[tid] = sd;
-  pw_[tid] = sw;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      pd_[tid] += pd_[tid + o];
-      pw_[tid] += pw_[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    norms[0] = pd_[0];
-    norms[1] = pw_[0];
-  }
-}
-
 }  // namespace mdg
-
-static bool known_dtype(int dt) { return dt == MDG_BF16 || dt == MDG_F16 || dt == MDG_F32 || dt == MDG_F64; }
 
 extern "C" size_t mdg_col_sum_ws_bytes(int64_t n_tokens, int64_t n) {
   if (n_tokens <= 0 || n <= 0) return 0;
@@ -358,13 +249,13 @@ extern "C" int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64
                 (long long)ld_wd, (long long)ld_down);
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_nystrom_intercept_ws_bytes(d) && (uintptr_t)ws % 8 == 0,
                 "mdg_nystrom_intercept: workspace %zu < required %zu", ws_bytes, mdg_nystrom_intercept_ws_bytes(d));
-  MDG_CHECK_ARG(ceil_div(d, IC_ROWS) < (1ll << 31), "mdg_nystrom_intercept: too many rows");
+  MDG_CHECK_ARG(ceil_div(d, RD_ROWS) < (1ll << 31) && n < (1ll << 31), "mdg_nystrom_intercept: too many rows or columns");
   MDG_CLEAR();
   hipStream_t st = (hipStream_t)stream;
   double *delta_rows = (double*)ws, *wmu_rows = delta_rows + d;
   const int vec_w = w_dtype == MDG_BF16 && (uintptr_t)Wd % 16 == 0 && ld_wd % 8 == 0;
   const int vec_d = (uintptr_t)down_hat % 16 == 0 && ld_down % 8 == 0;
-  const dim3 grid((unsigned)ceil_div(d, IC_ROWS));
+  const dim3 grid((unsigned)ceil_div(d, RD_ROWS));
   if (w_dtype == MDG_BF16)
     hipLaunchKernelGGL(intercept_rows_kernel<MDG_BF16>, grid, dim3(256), 0, st, Wd, ld_wd, d, n, down_hat, ld_down, r, idx, mu, vec_w,
                        vec_d, b_d, b_dtype, bias_out, out_dtype, bias_f64, delta_rows, wmu_rows);
@@ -372,7 +263,7 @@ extern "C" int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64
     hipLaunchKernelGGL(intercept_rows_kernel<MDG_F64>, grid, dim3(256), 0, st, Wd, ld_wd, d, n, down_hat, ld_down, r, idx, mu, vec_w,
                        vec_d, b_d, b_dtype, bias_out, out_dtype, bias_f64, delta_rows, wmu_rows);
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(intercept_norms_kernel, dim3(1), dim3(256), 0, st, delta_rows, wmu_rows, d, norms);
+  hipLaunchKernelGGL(pair_norms_kernel, dim3(1), dim3(256), 0, st, delta_rows, wmu_rows, d, norms);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

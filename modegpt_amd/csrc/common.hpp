@@ -115,6 +115,27 @@ template <> __device__ __forceinline__ double load_f64<MDG_F64>(const void* p, i
   return ((const double*)p)[i];
 }
 
+// One element of a dtype known only at run time (the biases)
+__device__ __forceinline__ double load_any(const void* p, int dt, int64_t i) {
+  switch (dt) {
+    case MDG_BF16: return load_f64<MDG_BF16>(p, i);
+    case MDG_F16: return load_f64<MDG_F16>(p, i);
+    case MDG_F32: return load_f64<MDG_F32>(p, i);
+    default: return load_f64<MDG_F64>(p, i);
+  }
+}
+// the model's dtype the way torch's .to() rounds an fp64 value: through fp32 for the 16-bit types
+__device__ __forceinline__ void store_any(void* p, int dt, int64_t i, double v) {
+  switch (dt) {
+    case MDG_BF16: ((bf16_t*)p)[i] = f64_to_bf16(v); break;
+    case MDG_F16: ((f16_t*)p)[i] = f64_to_f16(v); break;
+    case MDG_F32: ((float*)p)[i] = (float)v; break;
+    default: ((double*)p)[i] = v; break;
+  }
+}
+
+static inline bool known_dtype(int dt) { return dt == MDG_BF16 || dt == MDG_F16 || dt == MDG_F32 || dt == MDG_F64; }
+
 static inline size_t dtype_size(int dt) {
   switch (dt) {
     case MDG_BF16: case MDG_F16: return 2;

@@ -9,6 +9,7 @@
 // :162-223) reduces the same way: B = S V^T W_o,h^T, B B^T = (S V^T)(W_o,h^T W_o,h)(V S) = U_p S_p^2 U_p^T,
 // W_v' = U_p,r^T S^-1 V^T W_v,h,  W_o' = W_o,h V S U_p,r.
 #include "common.hpp"
+#include "row_dots.hpp"
 #include "vo_ws.hpp"
 
 namespace mdg {
@@ -187,125 +188,25 @@ __global__ __launch_bounds__(128) void vo_bias_head_kernel(const double* P, cons
   }
 }
 
-// s_i and rho_i for VO_BIAS_ROWS rows of W_o per workgroup: a wave owns VO_BIAS_ROWS / 4 rows, lanes go along the row (coalesced;
-// vec: eight 16-bit weights per lane and load), the two vectors are staged per chunk of VO_BIAS_CHUNK columns in LDS, already expanded
-// to the query heads' columns.  Every lane sums its columns in ascending order, the wave reduces by butterfly: a fixed order.
-constexpr int VO_BIAS_CHUNK = 2048, VO_BIAS_ROWS = 16;      // (d = 4096: 256 workgroups, one per CU)
+// s_i and rho_i for RD_ROWS rows of W_o per workgroup: one pass of row_dots (row_dots.hpp) carries both vectors, staged already
+// expanded to the query heads' columns, so that W_o is read once.
 template <int DT>
 __global__ __launch_bounds__(256) void vo_bias_rows_kernel(const void* Wo, int64_t ld_wo, int64_t d, int n_cols, int hd, int group,
                                                            const double* bw, const double* u, const void* b_o, int bo_dtype, int vec,
                                                            double* o_bias, double* s_out, double* rho_out) {
-  __shared__ double sb_[VO_BIAS_CHUNK], su_[VO_BIAS_CHUNK];
-  constexpr int RPW = VO_BIAS_ROWS / 4;
+  __shared__ double sv_[2 * RD_CHUNK];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int64_t row0 = (int64_t)blockIdx.x * VO_BIAS_ROWS + (int64_t)w * RPW;
-  double as[RPW], ar[RPW];
+  const int64_t row0 = (int64_t)blockIdx.x * RD_ROWS + (int64_t)w * RD_RPW;
+  double st[2 * RD_RPW];                // s, then rho
+  row_dots<DT, 2>(Wo, ld_wo, d, row0, n_cols, StageHeads<2>{{bw, u}, hd, group}, vec, sv_, st);
 #pragma unroll
-  for (int rr = 0; rr < RPW; rr++) as[rr] = ar[rr] = 0.;
-  for (int a0 = 0; a0 < n_cols; a0 += VO_BIAS_CHUNK) {
-    const int len = n_cols - a0 < VO_BIAS_CHUNK ? n_cols - a0 : VO_BIAS_CHUNK;
-    __syncthreads();
-    for (int e = tid; e < len; e += 256) {
-      const int j = a0 + e, src = (j / (group * hd)) * hd + j % hd;      // column j belongs to kv head j / (group hd)
-      sb_[e] = bw[src];
-      su_[e] = u[src];
-    }
-    __syncthreads();
-    // the wave's rows side by side, so that RPW loads per lane are in flight; a row beyond d reads row d - 1 and is dropped at the end
-    int64_t base[RPW];
-    double s[RPW], t[RPW];
-#pragma unroll
-    for (int rr = 0; rr < RPW; rr++) {
-      const int64_t row = row0 + rr < d ? row0 + rr : d - 1;
-      base[rr] = row * ld_wo + a0;
-      s[rr] = t[rr] = 0.;
-    }
-    int done = 0;
-    if ((DT == MDG_BF16 || DT == MDG_F16) && vec) {
-      for (int v = lane; v < len / 8; v += 64) {
-        uint4 q4[RPW];
-#pragma unroll
-        for (int rr = 0; rr < RPW; rr++) q4[rr] = ((const uint4*)((const unsigned short*)Wo + base[rr]))[v];
-        const double *bp = sb_ + 8 * v, *up = su_ + 8 * v;
-#pragma unroll
-        for (int rr = 0; rr < RPW; rr++) {
-          const unsigned q[4] = {q4[rr].x, q4[rr].y, q4[rr].z, q4[rr].w};
-#pragma unroll
-          for (int k = 0; k < 4; k++) {          // (element 2k in the low half)
-            const unsigned short lo = (unsigned short)(q[k] & 0xffffu), hi = (unsigned short)(q[k] >> 16);
-            const double x0 = DT == MDG_BF16 ? bf16_to_f64(lo) : f16_to_f64(lo);
-            const double x1 = DT == MDG_BF16 ? bf16_to_f64(hi) : f16_to_f64(hi);
-            s[rr] += x0 * bp[2 * k];
-            t[rr] += x0 * up[2 * k];
-            s[rr] += x1 * bp[2 * k + 1];
-            t[rr] += x1 * up[2 * k + 1];
-          }
-        }
-      }
-      done = len / 8 * 8;
-    }
-    for (int e = done + lane; e < len; e += 64) {
-      const double be = sb_[e], ue = su_[e];
-#pragma unroll
-      for (int rr = 0; rr < RPW; rr++) {
-        const double x = load_f64<DT>(Wo, base[rr] + e);
-        s[rr] += x * be;
-        t[rr] += x * ue;
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < RPW; rr++) {
-      as[rr] += s[rr];
-      ar[rr] += t[rr];
-    }
-  }
-#pragma unroll
-  for (int rr = 0; rr < RPW; rr++) {
-    double s = as[rr], t = ar[rr];
-    for (int o = 32; o > 0; o >>= 1) {
-      s += __shfl_xor(s, o, 64);
-      t += __shfl_xor(t, o, 64);
-    }
+  for (int rr = 0; rr < RD_RPW; rr++) {
     const int64_t row = row0 + rr;
     if (lane == 0 && row < d) {
-      s_out[row] = s;
-      rho_out[row] = t;
-      if (o_bias) {
-        double bo = 0.;
-        switch (bo_dtype) {
-          case MDG_BF16: bo = load_f64<MDG_BF16>(b_o, row); break;
-          case MDG_F16: bo = load_f64<MDG_F16>(b_o, row); break;
-          case MDG_F32: bo = load_f64<MDG_F32>(b_o, row); break;
-          default: bo = load_f64<MDG_F64>(b_o, row); break;
-        }
-        o_bias[row] = bo + s;
-      }
+      s_out[row] = st[rr];
+      rho_out[row] = st[RD_RPW + rr];
+      if (o_bias) o_bias[row] = load_any(b_o, bo_dtype, row) + st[rr];
     }
-  }
-}
-
-// resid = (sum_i rho_i^2, sum_i s_i^2): one workgroup, thread t sums rows t, t + 256, ... in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void vo_bias_norms_kernel(const double* s_in, const double* rho_in, int64_t d, double* resid) {
-  __shared__ double ps_[256], pr_[256];
-  const int tid = threadIdx.x;
-  double s = 0., r = 0.;
-  for (int64_t i = tid; i < d; i += 256) {
-    s += s_in[i] * s_in[i];
-    r += rho_in[i] * rho_in[i];
-  }
-  ps_[tid] = s;
-  pr_[tid] = r;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      ps_[tid] += ps_[tid + o];
-      pr_[tid] += pr_[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    resid[0] = pr_[0];
-    resid[1] = ps_[0];
   }
 }
 
@@ -322,10 +223,10 @@ static int vo_bias_launch(const VoWs& w, const void* Wo, int64_t ld_wo, int64_t 
     default: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_F64>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
   }
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vo_bias_rows_kernel<DT>, dim3((unsigned)ceil_div(d, VO_BIAS_ROWS)), dim3(256), 0, st, Wo, ld_wo, d, n_heads * hd, hd,
+  hipLaunchKernelGGL(vo_bias_rows_kernel<DT>, dim3((unsigned)ceil_div(d, RD_ROWS)), dim3(256), 0, st, Wo, ld_wo, d, n_heads * hd, hd,
                      n_heads / n_kv, bw, u, b_o, b_dtype, vec, o_bias, s_rows, rho_rows);
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vo_bias_norms_kernel, dim3(1), dim3(256), 0, st, s_rows, rho_rows, d, resid);
+  hipLaunchKernelGGL(pair_norms_kernel, dim3(1), dim3(256), 0, st, rho_rows, s_rows, d, resid);      // (||rho||^2, ||s||^2)
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }

@@ -6,96 +6,13 @@
 //   row stage    c_i = sum_h W_o,h[i, :] a_kv(h),  delta_i = c_i - sum_h o^_h[i, :] a'_kv(h),  bias = b_o + delta     (one read of W_o, o^)
 //   norms        (sum_i delta_i^2, sum_i c_i^2)                                    one workgroup, a fixed tree
 // No atomics; every sum is taken in an order that depends on the shapes and the operands' alignment alone, so the bits repeat
-// from run to run.  The design is vo_bias_rows_kernel's (vo.hip) and mdg_nystrom_intercept's (colsum.hip).
+// from run to run.  The rows of both stages and the norms go through row_dots.hpp, shared with mdg_nystrom_intercept and mdg_vo_bias.
 #include "common.hpp"
+#include "row_dots.hpp"
 
 using namespace mdg;
 
 namespace mdg {
-
-// A workgroup owns VI_ROWS rows, a wave VI_ROWS / 4 of them; lanes go along the row (coalesced; 16-byte loads of eight 16-bit
-// weights where the operand allows), the vector is staged per chunk of VI_CHUNK columns in LDS.  Every product enters its sum
-// through fma (exact product, one rounding per addition); a lane adds its columns in ascending order, the wave reduces by butterfly.
-constexpr int VI_CHUNK = 2048, VI_ROWS = 16, VI_RPW = VI_ROWS / 4;
-
-// out[rr] = sum_j M[row0 + rr, j] v(j), j < ncols.  width == 0: v(j) = vec[j].  width > 0: the vector holds `width` entries per kv
-// head and column j belongs to query head j / width, kv head j / (group width): v(j) = vec[(j / (group width)) width + j % width].
-// A row beyond nrows reads row nrows - 1; the caller drops it.  All 256 threads of the workgroup call this together.
-template <int DT>
-__device__ __forceinline__ void vi_row_dots(const void* M, int64_t ld, int64_t nrows, int64_t row0, int64_t ncols, const double* vec,
-                                            int width, int group, int vec16, double* sv_, double* out) {
-  const int tid = threadIdx.x, lane = tid & 63;
-#pragma unroll
-  for (int rr = 0; rr < VI_RPW; rr++) out[rr] = 0.;
-  for (int64_t a0 = 0; a0 < ncols; a0 += VI_CHUNK) {
-    const int len = (int)(ncols - a0 < VI_CHUNK ? ncols - a0 : VI_CHUNK);
-    __syncthreads();
-    for (int e = tid; e < len; e += 256) {
-      const int64_t j = a0 + e;
-      sv_[e] = width ? vec[(j / ((int64_t)group * width)) * width + j % width] : vec[j];
-    }
-    __syncthreads();
-    int64_t base[VI_RPW];
-    double s[VI_RPW];
-#pragma unroll
-    for (int rr = 0; rr < VI_RPW; rr++) {
-      const int64_t row = row0 + rr < nrows ? row0 + rr : nrows - 1;
-      base[rr] = row * ld + a0;
-      s[rr] = 0.;
-    }
-    int done = 0;
-    if (DT == MDG_BF16 && vec16) {
-      for (int v = lane; v < len / 8; v += 64) {
-        uint4 q4[VI_RPW];
-#pragma unroll
-        for (int rr = 0; rr < VI_RPW; rr++) q4[rr] = ((const uint4*)((const bf16_t*)M + base[rr]))[v];
-        const double* vp = sv_ + 8 * v;
-#pragma unroll
-        for (int rr = 0; rr < VI_RPW; rr++) {
-          const unsigned q[4] = {q4[rr].x, q4[rr].y, q4[rr].z, q4[rr].w};
-#pragma unroll
-          for (int k = 0; k < 4; k++) {          // (element 2k in the low half)
-            s[rr] = fma(bf16_to_f64((bf16_t)(q[k] & 0xffffu)), vp[2 * k], s[rr]);
-            s[rr] = fma(bf16_to_f64((bf16_t)(q[k] >> 16)), vp[2 * k + 1], s[rr]);
-          }
-        }
-      }
-      done = len / 8 * 8;
-    }
-    for (int e = done + lane; e < len; e += 64) {
-      const double ve = sv_[e];
-#pragma unroll
-      for (int rr = 0; rr < VI_RPW; rr++) s[rr] = fma(load_f64<DT>(M, base[rr] + e), ve, s[rr]);
-    }
-#pragma unroll
-    for (int rr = 0; rr < VI_RPW; rr++) out[rr] += s[rr];
-  }
-#pragma unroll
-  for (int rr = 0; rr < VI_RPW; rr++) {
-    double s = out[rr];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    out[rr] = s;
-  }
-}
-
-__device__ __forceinline__ double vi_load_any(const void* p, int dt, int64_t i) {
-  switch (dt) {
-    case MDG_BF16: return load_f64<MDG_BF16>(p, i);
-    case MDG_F16: return load_f64<MDG_F16>(p, i);
-    case MDG_F32: return load_f64<MDG_F32>(p, i);
-    default: return load_f64<MDG_F64>(p, i);
-  }
-}
-
-// the model's dtype the way torch's .to() rounds an fp64 value: through fp32 for the 16-bit types
-__device__ __forceinline__ void vi_store_any(void* p, int dt, int64_t i, double v) {
-  switch (dt) {
-    case MDG_BF16: ((bf16_t*)p)[i] = f64_to_bf16(v); break;
-    case MDG_F16: ((f16_t*)p)[i] = f64_to_f16(v); break;
-    case MDG_F32: ((float*)p)[i] = (float)v; break;
-    default: ((double*)p)[i] = v; break;
-  }
-}
 
 // Head stage.  Workgroups [0, nb_w) own the n_w = n_kv hd rows of W_v (a = W_v mu + b_v), the rest the n_n = n_kv rank rows of v^
 // (a' = v^ mu): the choice is uniform over the workgroup.
@@ -103,83 +20,57 @@ template <int DTW, int DTN>
 __global__ __launch_bounds__(256) void vo_intercept_head_kernel(const void* Wv, int64_t ld_wv, int64_t n_w, int vec_w, const void* Vn,
                                                                 int64_t ld_v, int64_t n_n, int vec_n, int64_t d, const double* mu,
                                                                 const void* b_v, int b_dtype, int nb_w, double* a, double* a2) {
-  __shared__ double sv_[VI_CHUNK];
+  __shared__ double sv_[RD_CHUNK];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  double s[VI_RPW];
+  double s[RD_RPW];
   if ((int)blockIdx.x < nb_w) {
-    const int64_t row0 = (int64_t)blockIdx.x * VI_ROWS + (int64_t)w * VI_RPW;
-    vi_row_dots<DTW>(Wv, ld_wv, n_w, row0, d, mu, 0, 1, vec_w, sv_, s);
+    const int64_t row0 = (int64_t)blockIdx.x * RD_ROWS + (int64_t)w * RD_RPW;
+    row_dots<DTW, 1>(Wv, ld_wv, n_w, row0, (int)d, StageGather{mu, d, nullptr}, vec_w, sv_, s);
 #pragma unroll
-    for (int rr = 0; rr < VI_RPW; rr++) {
+    for (int rr = 0; rr < RD_RPW; rr++) {
       const int64_t row = row0 + rr;
-      if (lane == 0 && row < n_w) a[row] = b_v ? s[rr] + vi_load_any(b_v, b_dtype, row) : s[rr];
+      if (lane == 0 && row < n_w) a[row] = b_v ? s[rr] + load_any(b_v, b_dtype, row) : s[rr];
     }
   } else {
-    const int64_t row0 = (int64_t)((int)blockIdx.x - nb_w) * VI_ROWS + (int64_t)w * VI_RPW;
-    vi_row_dots<DTN>(Vn, ld_v, n_n, row0, d, mu, 0, 1, vec_n, sv_, s);
+    const int64_t row0 = (int64_t)((int)blockIdx.x - nb_w) * RD_ROWS + (int64_t)w * RD_RPW;
+    row_dots<DTN, 1>(Vn, ld_v, n_n, row0, (int)d, StageGather{mu, d, nullptr}, vec_n, sv_, s);
 #pragma unroll
-    for (int rr = 0; rr < VI_RPW; rr++) {
+    for (int rr = 0; rr < RD_RPW; rr++) {
       const int64_t row = row0 + rr;
       if (lane == 0 && row < n_n) a2[row] = s[rr];
     }
   }
 }
 
-// Row stage: VI_ROWS rows of [W_o | o^] per workgroup against a and a', expanded to the query heads' columns in LDS per chunk.
+// Row stage: RD_ROWS rows of [W_o | o^] per workgroup against a and a', expanded to the query heads' columns in LDS per chunk.
 template <int DTW, int DTN>
 __global__ __launch_bounds__(256) void vo_intercept_rows_kernel(const void* Wo, int64_t ld_wo, int vec_w, const void* On, int64_t ld_o,
                                                                 int vec_n, int64_t d, int n_heads, int group, int hd, int rank,
                                                                 const double* a, const double* a2, const void* b_o, int b_dtype,
                                                                 void* bias_out, int out_dtype, double* bias_f64, double* delta_rows,
                                                                 double* const_rows) {
-  __shared__ double sv_[VI_CHUNK];
+  __shared__ double sv_[RD_CHUNK];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int64_t row0 = (int64_t)blockIdx.x * VI_ROWS + (int64_t)w * VI_RPW;
-  double c[VI_RPW], c2[VI_RPW];
-  vi_row_dots<DTW>(Wo, ld_wo, d, row0, (int64_t)n_heads * hd, a, hd, group, vec_w, sv_, c);
+  const int64_t row0 = (int64_t)blockIdx.x * RD_ROWS + (int64_t)w * RD_RPW;
+  double c[RD_RPW], c2[RD_RPW];
+  row_dots<DTW, 1>(Wo, ld_wo, d, row0, n_heads * hd, StageHeads<1>{{a}, hd, group}, vec_w, sv_, c);
   if (rank > 0) {
-    vi_row_dots<DTN>(On, ld_o, d, row0, (int64_t)n_heads * rank, a2, rank, group, vec_n, sv_, c2);
+    row_dots<DTN, 1>(On, ld_o, d, row0, n_heads * rank, StageHeads<1>{{a2}, rank, group}, vec_n, sv_, c2);
   } else {
 #pragma unroll
-    for (int rr = 0; rr < VI_RPW; rr++) c2[rr] = 0.;
+    for (int rr = 0; rr < RD_RPW; rr++) c2[rr] = 0.;
   }
 #pragma unroll
-  for (int rr = 0; rr < VI_RPW; rr++) {
+  for (int rr = 0; rr < RD_RPW; rr++) {
     const int64_t row = row0 + rr;
     if (lane == 0 && row < d) {
       const double delta = c[rr] - c2[rr];
-      const double bias = b_o ? vi_load_any(b_o, b_dtype, row) + delta : delta;
+      const double bias = b_o ? load_any(b_o, b_dtype, row) + delta : delta;
       delta_rows[row] = delta;
       const_rows[row] = c[rr];
       bias_f64[row] = bias;
-      if (bias_out) vi_store_any(bias_out, out_dtype, row, bias);
+      if (bias_out) store_any(bias_out, out_dtype, row, bias);
     }
-  }
-}
-
-// norms = (sum_i delta_i^2, sum_i c_i^2): one workgroup, thread t sums rows t, t + 256, ... in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void vo_intercept_norms_kernel(const double* delta_rows, const double* const_rows, int64_t d,
-                                                                 double* norms) {
-  __shared__ double pd_[256], pc_[256];
-  const int tid = threadIdx.x;
-  double sd = 0., sc = 0.;
-  for (int64_t i = tid; i < d; i += 256) {
-    sd = fma(delta_rows[i], delta_rows[i], sd);
-    sc = fma(const_rows[i], const_rows[i], sc);
-  }
-  pd_[tid] = sd;
-  pc_[tid] = sc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      pd_[tid] += pd_[tid + o];
-      pc_[tid] += pc_[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    norms[0] = pd_[0];
-    norms[1] = pc_[0];
   }
 }
 
@@ -196,22 +87,20 @@ template <int DTW, int DTN>
 static int vo_intercept_launch(const ViArgs& p, hipStream_t st) {
   const int64_t n_w = (int64_t)p.n_kv * p.hd, n_n = (int64_t)p.n_kv * p.rank;
   double *a = p.ws, *a2 = a + n_w, *delta_rows = a2 + n_n, *const_rows = delta_rows + p.d;
-  const int nb_w = (int)ceil_div(n_w, VI_ROWS), nb_n = (int)ceil_div(n_n, VI_ROWS);
+  const int nb_w = (int)ceil_div(n_w, RD_ROWS), nb_n = (int)ceil_div(n_n, RD_ROWS);
   hipLaunchKernelGGL((vo_intercept_head_kernel<DTW, DTN>), dim3((unsigned)(nb_w + nb_n)), dim3(256), 0, st, p.Wv, p.ld_wv, n_w, p.vec_wv,
                      p.Vn, p.ld_v, n_n, p.vec_v, p.d, p.mu, p.b_v, p.b_dtype, nb_w, a, a2);
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL((vo_intercept_rows_kernel<DTW, DTN>), dim3((unsigned)ceil_div(p.d, VI_ROWS)), dim3(256), 0, st, p.Wo, p.ld_wo,
+  hipLaunchKernelGGL((vo_intercept_rows_kernel<DTW, DTN>), dim3((unsigned)ceil_div(p.d, RD_ROWS)), dim3(256), 0, st, p.Wo, p.ld_wo,
                      p.vec_wo, p.On, p.ld_o, p.vec_o, p.d, p.n_heads, p.n_heads / p.n_kv, p.hd, p.rank, a, a2, p.b_o, p.b_dtype,
                      p.bias_out, p.out_dtype, p.bias_f64, delta_rows, const_rows);
   MDG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vo_intercept_norms_kernel, dim3(1), dim3(256), 0, st, delta_rows, const_rows, p.d, p.norms);
+  hipLaunchKernelGGL(pair_norms_kernel, dim3(1), dim3(256), 0, st, delta_rows, const_rows, p.d, p.norms);
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }
 
 }  // namespace mdg
-
-static bool vi_known_dtype(int dt) { return dt == MDG_BF16 || dt == MDG_F16 || dt == MDG_F32 || dt == MDG_F64; }
 
 extern "C" size_t mdg_vo_intercept_ws_bytes(int64_t d, int n_kv, int hd, int rank) {
   if (d <= 0 || n_kv <= 0 || hd <= 0 || rank < 0 || rank > hd) return 0;
@@ -230,14 +119,15 @@ extern "C" int mdg_vo_intercept(const void* Wv, int64_t ld_wv, const void* Wo, i
   MDG_CHECK_ARG(rank == 0 || (v_new && o_new), "mdg_vo_intercept: rank %d needs the stored factors (null pointer)", rank);
   MDG_CHECK_ARG(rank == 0 || new_dtype == MDG_BF16 || new_dtype == MDG_F64, "mdg_vo_intercept: the factors must be bf16 or f64 (got %d)",
                 new_dtype);
-  MDG_CHECK_ARG(((!b_v && !b_o) || vi_known_dtype(b_dtype)) && (!bias_out || vi_known_dtype(out_dtype)),
+  MDG_CHECK_ARG(((!b_v && !b_o) || known_dtype(b_dtype)) && (!bias_out || known_dtype(out_dtype)),
                 "mdg_vo_intercept: unsupported bias dtype");
   MDG_CHECK_ARG(d > 0 && ld_wv >= d && ld_wo >= (int64_t)n_heads * hd && (rank == 0 || (ld_v >= d && ld_o >= (int64_t)n_heads * rank)),
                 "mdg_vo_intercept: bad leading dimensions (d=%lld ld_wv=%lld ld_wo=%lld ld_v=%lld ld_o=%lld)", (long long)d,
                 (long long)ld_wv, (long long)ld_wo, (long long)ld_v, (long long)ld_o);
   MDG_CHECK_ARG(ws && (uintptr_t)ws % 8 == 0 && ws_bytes >= mdg_vo_intercept_ws_bytes(d, n_kv, hd, rank),
                 "mdg_vo_intercept: workspace %zu < required %zu", ws_bytes, mdg_vo_intercept_ws_bytes(d, n_kv, hd, rank));
-  MDG_CHECK_ARG(ceil_div(d, VI_ROWS) < (1ll << 31) && (int64_t)n_kv * (2 * hd) < (1ll << 31), "mdg_vo_intercept: too many rows");
+  MDG_CHECK_ARG(d < (1ll << 31) && (int64_t)n_kv * (2 * hd) < (1ll << 31) && (int64_t)n_heads * hd < (1ll << 31),
+                "mdg_vo_intercept: too many rows or columns");      // (row_dots counts columns in 32 bits)
   MDG_CLEAR();
   const auto vec = [](const void* p, int64_t ld, int dt) { return (int)(dt == MDG_BF16 && (uintptr_t)p % 16 == 0 && ld % 8 == 0); };
   const int ndt = rank > 0 ? new_dtype : MDG_BF16;      // (rank 0: the factors are not read)

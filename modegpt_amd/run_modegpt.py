@@ -31,6 +31,21 @@ from .model_utils import reload_compressed_model, save_compressed_model, start_m
 LAYERS_PER_STEP = 48          # src/run_modegpt.py:107
 DEFAULT_ORDER = "mlp,qk,vo"   # upstream leaves --order unset and then fails on `"mlp" in None`
 
+# The adapter's reports, read once per chunk where the host waits for the chains anyway, in this order (what each reads and the switch
+# that makes a compressor record it: the method's docstring in adapters/model_adapter.py):
+LAYER_REPORTS = (
+    "report_selection_margins",     # certificates of the chunk's MLP rank selections -> metrics["mlp_selection"], warnings
+    "report_mlp_greedy",            # the greedy selections' own numbers -> metrics["mlp_greedy"], "no certificate" entries
+    "report_rank_curves",           # what each of them costs at every rank -> metrics["mlp_rank_curve"]
+    "report_output_errors",         # what the stored tensors lose (behind the curves: excess_over_optimum) -> metrics["mlp_output_error"]
+    "report_mlp_intercepts",        # what the refit's intercepts carry -> metrics["mlp_intercept"]
+    "report_vo_intercepts",         # what the V/O truncation's intercepts carry -> metrics["vo_intercept"]
+    "report_vo_errors",             # what the stored v_proj / o_proj lose -> metrics["vo_output_error"]
+    "report_qk_errors",             # what the Q/K pair selections lose of the logits -> metrics["qk_logit_error"] and its kin
+    "report_vo_bias_residuals",     # what a truncated v_proj loses of a carried v bias -> metrics["vo_bias_residual"]
+    "report_attention_margins",     # the QK pair selections' / VO truncations' certificates, last -> metrics["qk_selection"], ["vo_spectrum"]
+)
+
 logger = logging.getLogger("MoDeGPT")
 
 
@@ -113,36 +128,10 @@ def compress_chunk(adapter: ModelAdapter, config: CompressionConfig, chunk: List
         compress_vo(adapter=adapter, cov=cov_x, keep_ratios=keep, target_layers=mine)
     del cov_mlp, cov_q, cov_k, cov_x
     _free()
-    report = getattr(adapter, "report_selection_margins", None)     # (a duck-typed adapter has none)
-    if report is not None:
-        report(logger)                          # certificates of this chunk's MLP rank selections -> metrics["mlp_selection"], warnings
-    report = getattr(adapter, "report_mlp_greedy", None)
-    if report is not None:
-        report(logger)                          # ... the greedy selections' own numbers (MODEGPT_MLP_GREEDY=T) -> metrics["mlp_greedy"], "no certificate" entries
-    report = getattr(adapter, "report_rank_curves", None)
-    if report is not None:
-        report(logger)                          # ... what each of them costs at every rank (MODEGPT_RANK_CURVE=1) -> metrics["mlp_rank_curve"]
-    report = getattr(adapter, "report_output_errors", None)
-    if report is not None:
-        report(logger)                          # ... what the stored tensors lose (MODEGPT_OUTPUT_ERROR=1; behind the curves: excess_over_optimum) -> metrics["mlp_output_error"]
-    report = getattr(adapter, "report_mlp_intercepts", None)
-    if report is not None:
-        report(logger)                          # ... what the refit's intercepts carry (MODEGPT_MLP_INTERCEPT=1) -> metrics["mlp_intercept"]
-    report = getattr(adapter, "report_vo_intercepts", None)
-    if report is not None:
-        report(logger)                          # ... what the V/O truncation's intercepts carry (MODEGPT_VO_INTERCEPT=1) -> metrics["vo_intercept"]
-    report = getattr(adapter, "report_vo_errors", None)
-    if report is not None:
-        report(logger)                          # ... what the stored v_proj / o_proj lose (MODEGPT_VO_ERROR=1) -> metrics["vo_output_error"]
-    report = getattr(adapter, "report_qk_errors", None)
-    if report is not None:
-        report(logger)                          # ... what the Q/K pair selections lose of the logits (MODEGPT_QK_ERROR=1) -> metrics["qk_logit_error"]
-    report = getattr(adapter, "report_vo_bias_residuals", None)
-    if report is not None:
-        report(logger)                          # ... what a truncated v_proj loses of a carried v bias (Qwen2; MODEGPT_KEEP_BIAS=1) -> metrics["vo_bias_residual"]
-    report = getattr(adapter, "report_attention_margins", None)
-    if report is not None:
-        report(logger)                          # ... and of its QK pair selections / VO truncations -> metrics["qk_selection"], ["vo_spectrum"]
+    for name in LAYER_REPORTS:
+        report = getattr(adapter, name, None)     # (a duck-typed adapter has only some of them)
+        if report is not None:
+            report(logger)
     return sharding.gather_layer_artifacts(adapter, chunk, mine, masks, rank, world)
 
 

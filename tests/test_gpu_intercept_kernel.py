@@ -1,4 +1,4 @@
-"""GPU: mdg_nystrom_intercept (colsum.hip: ic_row_dots, intercept_rows_kernel, intercept_norms_kernel) through the raw C ABI, run the
+"""GPU: mdg_nystrom_intercept (colsum.hip: intercept_rows_kernel; row_dots.hpp: row_dots, pair_norms_kernel) through the raw C ABI, run the
 way production runs it: more than one 2048-column LDS chunk, ragged last chunks, operands that take the scalar path, every dtype.
 
 Every operand sits inside a larger buffer.  Inputs have NaN pads behind column n (or r) of every row and behind the last row, and must
