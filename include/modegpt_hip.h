@@ -56,7 +56,8 @@ extern "C" {
                                 added under 10: mdg_rope_rows (the rotary embedding of a projection output in its own layout: post-RoPE statistics);
                                 added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic);
                                 added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective);
-                                added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic) */
+                                added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic);
+                                added under 10: mdg_attn_fwd (fused causal attention forward for compressed heads of unequal q/k and v width) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -957,6 +958,38 @@ int mdg_qk_pair_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, 
 size_t mdg_qk_causal_ws_bytes(int64_t B, int n_heads, int hd, int want_raw);
 int mdg_qk_causal_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, int dtype, int64_t B, int64_t T, int n_heads,
                         int n_kv, int hd, double* pair, double* pair_raw, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ fused attention forward for compressed heads
+ * The attention product of a compressed layer: q/k heads of width r_qk and v/o heads of width r_vo, each arbitrary per layer,
+ * flash-style in one kernel (csrc/attn.hip); nothing of size T x S touches HBM.  Additive entry, ABI version unchanged.
+ *   q    [B, n_heads, T, r_qk] contiguous: what mdg_rope_gather writes
+ *   k    [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]: last dimension contiguous, batch / head / token strides in elements (a cache
+ *        may hand back views of longer buffers)
+ *   out  [B*T, n_heads*r_vo] rows of pitch ld_out elements: the token-major rows o_proj reads; elements of a row beyond
+ *        n_heads*r_vo are not written
+ *   dtype  MDG_BF16 or MDG_F16, of all four
+ *   out[b, i, h, :] = softmax_j( scale * q[b, h, i, :] . k[b, g, j, :] ) v[b, g, :, :],   g = h / (n_heads / n_kv)
+ * over the keys query i sees: with causal != 0 the keys j <= i + (S - T) (prefill S == T, chunked prefill, decode T == 1), every
+ * key otherwise.  A query that sees no key (S == 0) gets zeros.
+ * Arithmetic: logits in fp32 from exact element products on v_mfma_f32_32x32x16_{bf16,f16}; online softmax with running maximum
+ * and sum in fp32, scale * log2(e) folded into one multiply, exp2; the probabilities rounded to the element dtype for the second
+ * product; the output accumulated in fp32, divided by the fp32 sum and rounded once.  With u the element type's unit roundoff
+ * (2^-9 bf16, 2^-11 f16) and |scale * logit| <= 20:   |out - exact| <= 4 u max_j |v[b, g, j, c]|   entry-wise (u max|v| from
+ * rounding the probabilities, u |out| from rounding the output, fp32 accumulation and exp2 below u together; the 4 is twice that).
+ * Widths that are no multiple of the MFMA k-step or tile are zero-padded in LDS and registers; the caller pads nothing.  Aligned
+ * 16-byte loads of an operand whose base and strides are multiples of 16 bytes; otherwise a narrower path (16-byte loads at the
+ * elements' 2-byte alignment, a row's last partial chunk element by element), chosen per operand on the host.  No atomics; every
+ * run gives the same bits.  Only enqueues.
+ * Out of scope: split-key (flash-decoding) scheduling for T == 1 (decode is correct, not fast), sliding windows, padding and
+ * arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
+ * MDG_ERR_BAD_ARG (with a message, before any device work): a dtype other than bf16 / f16, negative extent, n_heads % n_kv != 0,
+ * r_qk odd or outside 2..256, r_vo outside 1..256, causal with S < T, a token stride below the row width, ld_out < n_heads*r_vo,
+ * a scale that is not finite and positive, a NULL operand of a non-empty call, an out whose byte range (pitch included)
+ * intersects that of q, k or v.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
+int mdg_attn_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads, int n_kv,
+                 int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                 int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, void* out,
+                 int64_t ld_out, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -1,0 +1,445 @@
+// Fused causal attention forward for compressed heads: q/k head width r_qk (even, <= 256) and v/o head width r_vo (any, <= 256)
+// are independent and arbitrary -- the shapes a compressed layer has (patchers/compressed_attention.py), which the fused back
+// ends behind torch's sdpa (one width for q, k and v) are not written for.  Flash-style: nothing of size T x S touches HBM.
+//   q [B, n_heads, T, r_qk] contiguous (what mdg_rope_gather writes), k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo] strided with a
+//   contiguous last dimension (a cache's view), out [B*T, n_heads*r_vo] rows of pitch ld_out: the token-major rows o_proj reads.
+//
+// Tiling.  256 threads = 4 waves; a wave owns one UNIT = 32 consecutive queries of one query head and keeps its whole state in
+// registers.  Units of a (batch, kv head) are ordered (query tile, head of the group), a workgroup takes 4 consecutive units, so
+// the 4 waves share every K/V tile the workgroup stages: with a group of 4 heads a kv head is read once per query tile of the
+// group; with 8 heads twice, with 1 head once per 128 queries.  Key tiles of 64 are staged in LDS by all 256 threads:
+//   Ks [64 keys][DQ + 8]   row-major, columns >= r_qk and keys >= S zero-filled (the padding lives in LDS only)
+//   Vs [DV cols][64 + 8]   TRANSPOSED, and the keys of each 32-key half in the permuted order the second product needs (below)
+// First product  S^T = K Q^T  on v_mfma_f32_32x32x16: A = K rows from LDS (one 16-byte read per k-step), B = the wave's Q
+// fragments, loaded once from HBM into registers.  The result has the QUERY on the lane (col = lane & 31) and 16 keys in the
+// lane's registers (key = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)), so the row maximum and sum are in-lane reductions plus one
+// exchange between the lane halves, and the rescale of the output accumulator is a per-lane scalar.
+// Second product  O^T = V^T P^T: P^T is the first product's accumulator, rounded to the element type in registers and used as the
+// B operand with no lane movement (cdna_hip_programming.md section 3, "an accumulator tile as the next MFMA's operand").  Inside
+// k-step s element j of lane half h is then key 16 s + 8 (j >> 2) + 4 h + (j & 3) of the 32-key half, not key 16 s + 8 h + j; Vs
+// stores key kappa at position 16 s + 8 h + 4 ((kappa >> 3) & 1) + (kappa & 3) so that a lane's A fragment is again one 16-byte read.
+// Online softmax over 64 keys at a time: running maximum and sum in fp32, scale * log2(e) folded into one multiply, exp2.
+// Staging is split into fetch (HBM -> registers) and commit (registers -> LDS): the next tile's fetch is issued before the current
+// tile's products, and the templates up to 128 / 128 are built for two waves per SIMD, so loads overlap matrix work.
+// Causal: query i sees keys j <= i + (S - T).  Key tiles above a wave's last query are skipped; only tiles that cross the limit of
+// one of the wave's queries (or the end of the keys) apply the mask.
+//
+// Load paths, chosen on the host per operand from its address and strides: aligned 16-byte loads when base and every stride are
+// multiples of 16 bytes; otherwise (r_vo = 77 in bf16 has 154-byte rows) 16-byte loads at 2-byte alignment; a row's tail chunk of
+// fewer than 8 elements is always read element by element.  The output is stored 8 bytes at a time when out, ld_out and r_vo
+// allow it, element-wise otherwise.
+//
+// Out of scope: split-key (flash-decoding) scheduling for T == 1 (decode is correct, a wave then carries one query), sliding
+// windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
+#include <math.h>
+
+#include "common.hpp"
+
+namespace mdg {
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int WAVES = 4;
+constexpr int QT = 32;   // queries per wave
+constexpr int KT = 64;   // keys per LDS stage
+constexpr int VP = KT + 8;  // Vs pitch in elements (144 B: 16-byte aligned rows)
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+template <int DT> struct Mma;
+template <> struct Mma<MDG_BF16> {
+  typedef __bf16 E;
+  typedef __bf16 frag __attribute__((ext_vector_type(8)));
+  __device__ static __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+};
+template <> struct Mma<MDG_F16> {
+  typedef _Float16 E;
+  typedef _Float16 frag __attribute__((ext_vector_type(8)));
+  __device__ static __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  }
+};
+
+struct AttnArgs {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* out;
+  int64_t T, S, ld_out, units;
+  int64_t kbs, khs, kts, vbs, vhs, vts;
+  int n_heads, n_kv, G, r_qk, r_vo, causal;
+  int wg_per_bg;  // workgroups per (batch, kv head)
+  int vec_q, vec_k, vec_v, vec_o;
+  float c;  // scale * log2(e)
+};
+
+// 8 consecutive elements of a row starting at column c0 (a multiple of 8); columns >= width read as zero.  `vec`: the row start
+// is 16-byte aligned.  The narrower path reads a whole chunk as 16 bytes at the elements' own 2-byte alignment (global memory takes
+// unaligned dword loads; where the target does not, the compiler splits the load) and a row's tail chunk element by element.
+typedef unsigned u32x4u __attribute__((ext_vector_type(4), aligned(2)));
+template <typename E> __device__ __forceinline__ u32x4 load8(const E* row, int c0, int width, bool vec) {
+  u32x4 z = {0u, 0u, 0u, 0u};
+  if (c0 >= width) return z;
+  if (c0 + 8 <= width) {
+    if (vec) return *(const u32x4*)(row + c0);
+    const u32x4u w = *(const u32x4u*)(row + c0);
+    return (u32x4){w[0], w[1], w[2], w[3]};
+  }
+  const unsigned short* p = (const unsigned short*)row;
+  unsigned e[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) e[j] = c0 + j < width ? (unsigned)p[c0 + j] : 0u;
+  z.x = e[0] | (e[1] << 16);
+  z.y = e[2] | (e[3] << 16);
+  z.z = e[4] | (e[5] << 16);
+  z.w = e[6] | (e[7] << 16);
+  return z;
+}
+
+__device__ __forceinline__ unsigned half_of(unsigned w, int odd) { return odd ? (w >> 16) : (w & 0xffffu); }
+
+template <int DT, int NQ, int NV>
+__global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fwd_kernel(AttnArgs a) {
+  typedef typename Mma<DT>::E E;
+  typedef typename Mma<DT>::frag frag;
+  constexpr int KP = NQ * 16 + 8;  // Ks pitch in elements
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  E* Ks = (E*)smem;       // [KT][KP]
+  E* Vs = Ks + KT * KP;   // [NV * 32][VP]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+  const int64_t bg = (int64_t)blockIdx.x / a.wg_per_bg;
+  const int wgi = a.wg_per_bg - 1 - (int)((int64_t)blockIdx.x - bg * a.wg_per_bg);  // the longest key ranges start first
+  const int64_t b = bg / a.n_kv;
+  const int g = (int)(bg - b * a.n_kv);
+  const int64_t u0 = (int64_t)wgi * WAVES, u = u0 + wave;
+  const bool live = u < a.units;
+  const int64_t qt = u / a.G;
+  const int head = g * a.G + (int)(u - qt * a.G);
+  const int64_t q0 = qt * QT, qi = q0 + r;
+  const int64_t shift = a.S - a.T;
+  const int nq = (a.r_qk + 15) >> 4, nv = (a.r_vo + 31) >> 5;
+
+  // key range of this wave and of the workgroup (its last live unit sees the most keys)
+  int64_t wave_end = 0;
+  if (live) {
+    const int64_t qlast = q0 + QT - 1 < a.T - 1 ? q0 + QT - 1 : a.T - 1;
+    wave_end = a.causal && qlast + shift + 1 < a.S ? qlast + shift + 1 : a.S;
+  }
+  int64_t wg_end;
+  {
+    const int64_t ul = u0 + WAVES - 1 < a.units - 1 ? u0 + WAVES - 1 : a.units - 1;
+    const int64_t ql0 = (ul / a.G) * QT;
+    const int64_t ql = ql0 + QT - 1 < a.T - 1 ? ql0 + QT - 1 : a.T - 1;
+    wg_end = a.causal && ql + shift + 1 < a.S ? ql + shift + 1 : a.S;
+  }
+
+  // the wave's Q^T fragments: B[k = 8h + j][col = query r] of k-step s is q[query r][16 s + 8 h + j]
+  const bool qok = live && qi < a.T;
+  frag qf[NQ];
+  {
+    const E* qrow = (const E*)a.q + ((b * a.n_heads + head) * a.T + (qok ? qi : 0)) * a.r_qk;
+#pragma unroll
+    for (int s = 0; s < NQ; s++) {
+      u32x4 w = {0u, 0u, 0u, 0u};
+      if (qok) w = load8(qrow, 16 * s + 8 * hh, a.r_qk, a.vec_q != 0);
+      qf[s] = __builtin_bit_cast(frag, w);
+    }
+  }
+
+  f32x16 o[NV];
+#pragma unroll
+  for (int ct = 0; ct < NV; ct++)
+#pragma unroll
+    for (int i = 0; i < 16; i++) o[ct][i] = 0.f;
+  float m = -INFINITY, l = 0.f;
+
+  const E* kbase = (const E*)a.k + b * a.kbs + (int64_t)g * a.khs;
+  const E* vbase = (const E*)a.v + b * a.vbs + (int64_t)g * a.vhs;
+  const int kcpr = nq * 2;   // 8-element chunks per K row
+  const int vcpr = nv * 4;   // 8-element chunks per V row
+
+  // Staging in two halves: fetch (HBM -> registers) and commit (registers -> LDS).  With PREFETCH the next tile's fetch is issued
+  // before the products of the current one, so its latency hides under them; the widest template has no registers to spare.
+  constexpr bool PREFETCH = !(NQ == 16 && NV == 8);
+  constexpr int KIT = (KT * NQ * 2 + THREADS - 1) / THREADS;  // K chunks per thread at the template's widest r_qk
+  constexpr int VIT = (16 * NV * 4 + THREADS - 1) / THREADS;  // V items (4 keys x 8 columns) per thread
+  u32x4 kreg[KIT], vreg[VIT][4];
+  auto fetch = [&](int64_t t0) {
+#pragma unroll
+    for (int it = 0; it < KIT; it++) {
+      const int idx = tid + it * THREADS;
+      kreg[it] = (u32x4){0u, 0u, 0u, 0u};
+      if (idx < KT * kcpr) {
+        const int row = idx / kcpr, c0 = (idx - row * kcpr) * 8;
+        const int64_t key = t0 + row;
+        if (key < a.S) kreg[it] = load8(kbase + key * a.kts, c0, a.r_qk, a.vec_k != 0);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < VIT; it++) {
+      const int idx = tid + it * THREADS;
+      const int mq = idx & 15, c0 = (idx >> 4) * 8;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int64_t key = t0 + 4 * mq + i;
+        vreg[it][i] = (u32x4){0u, 0u, 0u, 0u};
+        if (idx < 16 * vcpr && key < a.S) vreg[it][i] = load8(vbase + key * a.vts, c0, a.r_vo, a.vec_v != 0);
+      }
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int it = 0; it < KIT; it++) {
+      const int idx = tid + it * THREADS;
+      if (idx < KT * kcpr) {
+        const int row = idx / kcpr, c0 = (idx - row * kcpr) * 8;
+        *(u32x4*)(Ks + row * KP + c0) = kreg[it];
+      }
+    }
+    // V: an item is 4 consecutive keys x 8 columns; its 8 transposed 8-byte packs land at the keys' permuted position
+#pragma unroll
+    for (int it = 0; it < VIT; it++) {
+      const int idx = tid + it * THREADS;
+      if (idx < 16 * vcpr) {
+        const int mq = idx & 15, c0 = (idx >> 4) * 8;
+        const int kap = (4 * mq) & 31;
+        const int pos = ((4 * mq) & 32) + (kap & 16) + ((kap >> 2) & 1) * 8 + ((kap >> 3) & 1) * 4;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          u32x2 p;
+          p.x = half_of(vreg[it][0][j >> 1], j & 1) | (half_of(vreg[it][1][j >> 1], j & 1) << 16);
+          p.y = half_of(vreg[it][2][j >> 1], j & 1) | (half_of(vreg[it][3][j >> 1], j & 1) << 16);
+          *(u32x2*)(Vs + (c0 + j) * VP + pos) = p;
+        }
+      }
+    }
+  };
+
+  if (PREFETCH && wg_end > 0) fetch(0);
+  for (int64_t t0 = 0; t0 < wg_end; t0 += KT) {
+    __syncthreads();  // every wave is done with the previous tile
+    if constexpr (PREFETCH) {
+      commit();
+    } else {  // item by item: nothing of the tile stays in registers (written out: through shared per-item helpers the compiler put
+              // kreg / vreg into scratch memory)
+      for (int idx = tid; idx < KT * kcpr; idx += THREADS) {
+        const int row = idx / kcpr, c0 = (idx - row * kcpr) * 8;
+        const int64_t key = t0 + row;
+        u32x4 w = {0u, 0u, 0u, 0u};
+        if (key < a.S) w = load8(kbase + key * a.kts, c0, a.r_qk, a.vec_k != 0);
+        *(u32x4*)(Ks + row * KP + c0) = w;
+      }
+      // V: an item is 4 consecutive keys x 8 columns; its 8 transposed 8-byte packs land at the keys' permuted position
+      for (int idx = tid; idx < 16 * vcpr; idx += THREADS) {
+        const int mq = idx & 15, c0 = (idx >> 4) * 8;
+        u32x4 w[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int64_t key = t0 + 4 * mq + i;
+          w[i] = (u32x4){0u, 0u, 0u, 0u};
+          if (key < a.S) w[i] = load8(vbase + key * a.vts, c0, a.r_vo, a.vec_v != 0);
+        }
+        const int kap = (4 * mq) & 31;
+        const int pos = ((4 * mq) & 32) + (kap & 16) + ((kap >> 2) & 1) * 8 + ((kap >> 3) & 1) * 4;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          u32x2 p;
+          p.x = half_of(w[0][j >> 1], j & 1) | (half_of(w[1][j >> 1], j & 1) << 16);
+          p.y = half_of(w[2][j >> 1], j & 1) | (half_of(w[3][j >> 1], j & 1) << 16);
+          *(u32x2*)(Vs + (c0 + j) * VP + pos) = p;
+        }
+      }
+    }
+    __syncthreads();
+    if (PREFETCH && t0 + KT < wg_end) fetch(t0 + KT);
+    if (!live || t0 >= wave_end) continue;  // wave-uniform; the barriers above are outside
+
+    float t[2][16];
+#pragma unroll
+    for (int sub = 0; sub < 2; sub++) {
+      f32x16 st;
+#pragma unroll
+      for (int i = 0; i < 16; i++) st[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NQ; s++) {
+        if (s < nq) {  // wave-uniform; a break would keep the loop rolled and qf in scratch
+          const frag ka = *(const frag*)(Ks + (sub * 32 + r) * KP + 16 * s + 8 * hh);
+          st = Mma<DT>::mfma(ka, qf[s], st);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 16; i++) t[sub][i] = st[i] * a.c;
+    }
+    const bool need_mask = t0 + KT > a.S || (a.causal && t0 + KT - 1 > q0 + shift);
+    if (need_mask) {
+      int64_t lim = a.S - 1;
+      if (a.causal && qi + shift < lim) lim = qi + shift;
+      const int64_t d = lim - t0;  // keys of this tile beyond d are not admitted
+      const int rel = d < -1 ? -1 : d > KT ? KT : (int)d;
+#pragma unroll
+      for (int sub = 0; sub < 2; sub++)
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+          if (sub * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh > rel) t[sub][i] = -INFINITY;
+    }
+    float mx = t[0][0];
+#pragma unroll
+    for (int sub = 0; sub < 2; sub++)
+#pragma unroll
+      for (int i = 0; i < 16; i++) mx = fmaxf(mx, t[sub][i]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m, mx);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;  // a query with no admitted key yet: every p is exp2(-inf) = 0
+    const float alpha = __builtin_amdgcn_exp2f(m - m_use);
+    m = m_new;
+    float sum = 0.f;
+    frag pf[2][2];
+#pragma unroll
+    for (int sub = 0; sub < 2; sub++)
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const float p = __builtin_amdgcn_exp2f(t[sub][i] - m_use);
+        sum += p;
+        pf[sub][i >> 3][i & 7] = (E)p;
+      }
+    l = l * alpha + sum;
+#pragma unroll
+    for (int ct = 0; ct < NV; ct++) {
+      if (ct >= nv) continue;
+#pragma unroll
+      for (int i = 0; i < 16; i++) o[ct][i] *= alpha;
+#pragma unroll
+      for (int sub = 0; sub < 2; sub++)
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+          const frag va = *(const frag*)(Vs + (ct * 32 + r) * VP + sub * 32 + s * 16 + hh * 8);
+          o[ct] = Mma<DT>::mfma(va, pf[sub][s], o[ct]);
+        }
+    }
+  }
+
+  const float lt = l + __shfl_xor(l, 32);  // the two lane halves of a query hold the sums of their own keys
+  if (!qok) return;
+  const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+  E* orow = (E*)a.out + (b * a.T + qi) * a.ld_out + (int64_t)head * a.r_vo;
+#pragma unroll
+  for (int ct = 0; ct < NV; ct++) {
+    if (ct >= nv) continue;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; q4++) {
+      const int c = ct * 32 + 8 * q4 + 4 * hh;  // registers 4 q4 .. 4 q4 + 3 are columns c .. c + 3
+      typedef E e4 __attribute__((ext_vector_type(4)));
+      e4 e;
+#pragma unroll
+      for (int i = 0; i < 4; i++) e[i] = (E)(o[ct][4 * q4 + i] * inv);
+      if (a.vec_o && c + 4 <= a.r_vo) {
+        *(e4*)(orow + c) = e;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (c + i < a.r_vo) orow[c + i] = e[i];
+      }
+    }
+  }
+}
+
+template <int DT, int NQ, int NV> int launch_attn(const AttnArgs& a, dim3 grid, hipStream_t st) {
+  const size_t lds = ((size_t)KT * (NQ * 16 + 8) + (size_t)NV * 32 * VP) * 2;
+  if (lds > 64 * 1024)
+    MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV>), grid, dim3(THREADS), lds, st, a);
+  return MDG_OK;
+}
+
+template <int DT, int NQ> int launch_attn_v(const AttnArgs& a, dim3 grid, hipStream_t st) {
+  if (a.r_vo <= 64) return launch_attn<DT, NQ, 2>(a, grid, st);
+  if (a.r_vo <= 128) return launch_attn<DT, NQ, 4>(a, grid, st);
+  return launch_attn<DT, NQ, 8>(a, grid, st);
+}
+
+template <int DT> int launch_attn_q(const AttnArgs& a, dim3 grid, hipStream_t st) {
+  if (a.r_qk <= 64) return launch_attn_v<DT, 4>(a, grid, st);
+  if (a.r_qk <= 128) return launch_attn_v<DT, 8>(a, grid, st);
+  return launch_attn_v<DT, 16>(a, grid, st);
+}
+
+// the byte range [lo, hi) a strided [B, H, N, width] operand spans
+void span_of(const void* p, int64_t B, int64_t bs, int64_t H, int64_t hs, int64_t N, int64_t ts, int64_t width, size_t es,
+             uintptr_t& lo, uintptr_t& hi) {
+  int64_t mn = 0, mxe = 0;
+  const int64_t ext[3] = {(B - 1) * bs, (H - 1) * hs, (N - 1) * ts};
+  for (int i = 0; i < 3; i++) {
+    if (ext[i] < 0) mn += ext[i];
+    else mxe += ext[i];
+  }
+  lo = (uintptr_t)p + (uintptr_t)(mn * (int64_t)es);
+  hi = (uintptr_t)p + (uintptr_t)((mxe + width) * (int64_t)es);
+}
+
+}  // namespace
+}  // namespace mdg
+
+using namespace mdg;
+
+extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
+                            int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                            int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
+                            void* out, int64_t ld_out, void* stream) {
+  MDG_CLEAR();
+  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16, "mdg_attn_fwd: dtype %d (bf16 or f16; fp32 inputs are out of scope)", dtype);
+  MDG_CHECK_ARG(B >= 0 && T >= 0 && S >= 0, "mdg_attn_fwd: negative extent");
+  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "mdg_attn_fwd: n_heads=%d is not a positive multiple of n_kv=%d",
+                n_heads, n_kv);
+  MDG_CHECK_ARG(r_qk >= 2 && r_qk <= 256 && r_qk % 2 == 0, "mdg_attn_fwd: r_qk=%d must be even, >= 2 and <= 256", r_qk);
+  MDG_CHECK_ARG(r_vo >= 1 && r_vo <= 256, "mdg_attn_fwd: r_vo=%d must be in 1..256", r_vo);
+  MDG_CHECK_ARG(!(causal && S < T), "mdg_attn_fwd: causal with S=%lld < T=%lld keys", (long long)S, (long long)T);
+  MDG_CHECK_ARG(k_token_stride >= r_qk, "mdg_attn_fwd: k token stride %lld < r_qk=%d", (long long)k_token_stride, r_qk);
+  MDG_CHECK_ARG(v_token_stride >= r_vo, "mdg_attn_fwd: v token stride %lld < r_vo=%d", (long long)v_token_stride, r_vo);
+  const int64_t width = (int64_t)n_heads * r_vo;
+  MDG_CHECK_ARG(ld_out >= width, "mdg_attn_fwd: ld_out=%lld < n_heads*r_vo=%lld", (long long)ld_out, (long long)width);
+  MDG_CHECK_ARG(isfinite(scale) && scale > 0.0, "mdg_attn_fwd: scale %g must be finite and positive", scale);
+  MDG_CHECK_ARG(T == 0 || B <= INT64_MAX / T / n_heads / 256, "mdg_attn_fwd: B*T overflows");
+  if (B == 0 || T == 0) return MDG_OK;
+  MDG_CHECK_ARG(q && out && (S == 0 || (k && v)), "mdg_attn_fwd: null pointer");
+  const size_t es = dtype_size(dtype);
+  {
+    uintptr_t ol, oh, lo, hi;
+    span_of(out, 1, 0, 1, 0, B * T, ld_out, width, es, ol, oh);
+    span_of(q, 1, 0, 1, 0, B * n_heads * T, r_qk, r_qk, es, lo, hi);
+    MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps q");
+    if (S > 0) {
+      span_of(k, B, k_batch_stride, n_kv, k_head_stride, S, k_token_stride, r_qk, es, lo, hi);
+      MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps k");
+      span_of(v, B, v_batch_stride, n_kv, v_head_stride, S, v_token_stride, r_vo, es, lo, hi);
+      MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps v");
+    }
+  }
+
+  AttnArgs a;
+  a.q = q; a.k = k; a.v = v; a.out = out;
+  a.T = T; a.S = S; a.ld_out = ld_out;
+  a.kbs = k_batch_stride; a.khs = k_head_stride; a.kts = k_token_stride;
+  a.vbs = v_batch_stride; a.vhs = v_head_stride; a.vts = v_token_stride;
+  a.n_heads = n_heads; a.n_kv = n_kv; a.G = n_heads / n_kv; a.r_qk = r_qk; a.r_vo = r_vo; a.causal = causal != 0;
+  a.units = ceil_div(T, QT) * a.G;
+  const int64_t wg = ceil_div(a.units, WAVES);
+  MDG_CHECK_ARG(wg <= 0x7fffffff && B * n_kv <= 0x7fffffff / wg, "mdg_attn_fwd: B=%lld, T=%lld exceed one launch", (long long)B,
+                (long long)T);
+  a.wg_per_bg = (int)wg;
+  a.vec_q = (uintptr_t)q % 16 == 0 && r_qk % 8 == 0;
+  a.vec_k = (uintptr_t)k % 16 == 0 && k_batch_stride % 8 == 0 && k_head_stride % 8 == 0 && k_token_stride % 8 == 0;
+  a.vec_v = (uintptr_t)v % 16 == 0 && v_batch_stride % 8 == 0 && v_head_stride % 8 == 0 && v_token_stride % 8 == 0;
+  a.vec_o = (uintptr_t)out % 8 == 0 && ld_out % 4 == 0 && r_vo % 4 == 0;
+  a.c = (float)(scale * 1.4426950408889634);
+  const dim3 grid((unsigned)(B * n_kv * wg));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MDG_BF16) MDG_TRY(launch_attn_q<MDG_BF16>(a, grid, st));
+  else MDG_TRY(launch_attn_q<MDG_F16>(a, grid, st));
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}

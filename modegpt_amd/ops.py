@@ -1345,6 +1345,48 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
     return out
 
 
+def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused attention forward for compressed heads (mdg_attn_fwd): q [B, n_heads, T, r_qk], k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]
+    (bf16 / f16; r_qk even, r_qk != r_vo allowed, both <= 256) -> [B, T, n_heads, r_vo], the token-major layout o_proj reads.  With
+    `causal`, query i sees the keys j <= i + (S - T).  k and v may be views of longer buffers (a static cache): their strides are
+    taken as they are, only a non-unit last stride is refused.  `out`: a caller-owned [B, T, n_heads, r_vo] tensor of q's dtype whose
+    last two dimensions are contiguous and whose rows have one pitch (it is returned); it must not overlap q, k or v."""
+    _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f"attn_fwd: q, k, v must be 4-D, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"attn_fwd: q, k, v must share bf16 or f16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    B, n_heads, T, r_qk = q.shape
+    n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    if tuple(k.shape) != (B, n_kv, S, r_qk) or tuple(v.shape) != (B, n_kv, S, r_vo):
+        raise ValueError(f"attn_fwd: k {tuple(k.shape)} / v {tuple(v.shape)} do not fit q {tuple(q.shape)}: "
+                         f"k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]")
+    q, k, v = q.detach(), k.detach(), v.detach()
+    if not q.is_contiguous():
+        q = q.contiguous()
+    for name, t in (("k", k), ("v", v)):
+        if t.shape[3] > 1 and t.stride(3) != 1:
+            raise ValueError(f"attn_fwd: {name} must have a contiguous last dimension, got strides {t.stride()}")
+    if out is None:
+        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
+    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
+          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
+          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"attn_fwd: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
+                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    # the stride of an axis of extent 1 is arbitrary in torch: the pitch of the [B*T] rows comes from an axis that has one
+    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    k_ts = k.stride(2) if S > 1 else r_qk
+    v_ts = v.stride(2) if S > 1 else r_vo
+    with torch.cuda.device(q.device):
+        check(lib.mdg_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
+                               k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
+                               float(scale), 1 if causal else 0, out.data_ptr(), ld_out, _stream(q)), "mdg_attn_fwd")
+    return out
+
+
 def _qk_seq_accum(stem: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim) -> None:
     """The body qk_pair_accum and qk_causal_accum share (stem "qk_pair" / "qk_causal"): the argument checks, with messages under
     the caller's name, the two row matrices as [B*T, width] views, then mdg_<stem>_accum on a workspace of mdg_<stem>_ws_bytes."""

@@ -15,7 +15,10 @@ stock HF modules and gives their attention the compressed semantics, with the el
   * softmax scale = (compressed q/k head width) ** -0.5                          (LlamaRebuild.py:266,282)
   * OPT: no RoPE, no mask; q is pre-scaled by the compressed width, attention runs with scale 1  (OPTRebuild.py:144-163)
   * the attention product itself goes through HF's attention interface exactly as in the stock modules
-    (config._attn_implementation: sdpa / eager / ...) -- PyTorch plumbing, not part of this engine
+    (config._attn_implementation: sdpa / eager / ...) -- PyTorch plumbing, not part of this engine -- unless
+    MODEGPT_FUSED_ATTN=1: then a call without a mask, a sliding window or requested weights (the condition under which HF's own
+    sdpa path asks for is_causal) runs modegpt_amd.ops.attn_fwd (csrc/attn.hip), a flash-style kernel that takes r_qk != r_vo
+    as they are and writes the token-major rows o_proj reads.  Which one served is counted in ATTN_CALLS.  Off by default.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -44,6 +47,7 @@ import torch.nn as nn
 
 logger = logging.getLogger("MoDeGPT")
 PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_gather / by the torch expression
+ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by mdg_attn_fwd / by HF's attention interface
 _HIP_OPS = None
 _HIP_BROKEN = None                      # why the engine, although installed here, cannot serve (its library failed to load)
 
@@ -133,6 +137,41 @@ def _attention_interface(module):
     return eager if impl == "eager" else ALL_ATTENTION_FUNCTIONS[impl]
 
 
+def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_weights=False):
+    """The attention product of both forwards: q [B, n_h, T, r_qk], k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo] -> (rows for
+    o_proj [B, T, n_h * r_vo], weights).  MODEGPT_FUSED_ATTN=1 sends a call that needs no mask tensor to mdg_attn_fwd: no
+    attention_mask (with one, HF's interface serves the call as it always did: nothing is inspected, nothing syncs), the module
+    causal, no sliding window, no weights requested, no gradients, bf16 / f16 on a GPU with the engine's library loaded.  Query i
+    then sees the keys j <= i + (S - T): prefill, and decode with a cache.  With MODEGPT_REQUIRE_HIP=1 as well, a call that meets
+    the conditions but cannot be served by the kernel (the engine's library does not load, a width outside the kernel's range, a
+    strided last dimension) raises instead of taking the interface."""
+    B, T = q.shape[0], q.shape[2]
+    if os.environ.get("MODEGPT_FUSED_ATTN", "0") == "1":
+        eligible = (attention_mask is None and getattr(self, "is_causal", True) is not False
+                    and getattr(self, "sliding_window", None) is None
+                    and not (want_weights or kwargs.get("output_attentions", False))
+                    and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad))
+                    and q.is_cuda and q.dtype in (torch.bfloat16, torch.float16))
+        if eligible:
+            why = None
+            if _hip_ops() is None:
+                why = f"modegpt_amd cannot serve ({_HIP_BROKEN or 'not importable'})"
+            elif q.shape[-1] % 2 or q.shape[-1] > 256 or v.shape[-1] > 256:
+                why = f"head widths r_qk={q.shape[-1]} (even, <= 256), r_vo={v.shape[-1]} (<= 256)"
+            elif k.stride(-1) != 1 or v.stride(-1) != 1:
+                why = "k / v without a contiguous last dimension"
+            if why is None:
+                ATTN_CALLS["hip"] += 1
+                out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=True)            # [B, T, n_h, r_vo]
+                return out.view(B, T, -1), None
+            if os.environ.get("MODEGPT_REQUIRE_HIP", "0") == "1":
+                raise RuntimeError("compressed attention: MODEGPT_FUSED_ATTN=1 and MODEGPT_REQUIRE_HIP=1 but mdg_attn_fwd cannot "
+                                   f"serve this call: {why}")
+    ATTN_CALLS["interface"] += 1
+    out, weights = _attention_interface(self)(self, q, k, v, attention_mask, dropout=0.0, scaling=scaling, **(extra or {}), **kwargs)
+    return out.reshape(B, T, -1).contiguous(), weights
+
+
 def _rope_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
     """Llama / Qwen2 / Qwen3 (RoPE, optional GQA, optional per-head q/k RMSNorm; projection biases, where the modules carry them,
     act before the norm and the rotation as in the stock modules)."""
@@ -166,9 +205,8 @@ def _rope_forward(self, hidden_states, position_embeddings=None, attention_mask=
     if past_key_values is not None:
         k, v = past_key_values.update(k, v, self.layer_idx)
     extra = {"sliding_window": self.sliding_window} if getattr(self, "sliding_window", None) is not None else {}
-    out, weights = _attention_interface(self)(self, q, k, v, attention_mask, dropout=0.0, scaling=float(r_qk) ** -0.5,
-                                              **extra, **kwargs)
-    return self.o_proj(out.reshape(B, T, -1).contiguous()), weights
+    out, weights = _attend(self, q, k, v, attention_mask, float(r_qk) ** -0.5, kwargs, extra)
+    return self.o_proj(out), weights
 
 
 def _opt_forward(self, hidden_states, past_key_values=None, attention_mask=None, output_attentions=False, **kwargs):
@@ -184,8 +222,8 @@ def _opt_forward(self, hidden_states, past_key_values=None, attention_mask=None,
     v = v.view(B, T, n_h, v.shape[-1] // n_h).transpose(1, 2)
     if past_key_values is not None:
         k, v = past_key_values.update(k, v, self.layer_idx)
-    out, weights = _attention_interface(self)(self, q, k, v, attention_mask, dropout=0.0, scaling=1.0, **kwargs)
-    return self.out_proj(out.reshape(B, T, -1).contiguous()), (weights if output_attentions else None)
+    out, weights = _attend(self, q, k, v, attention_mask, 1.0, kwargs, want_weights=bool(output_attentions))
+    return self.out_proj(out), (weights if output_attentions else None)
 
 
 def _check_mask(mask: torch.Tensor, n_kv: int, head_dim: int, layer: int) -> torch.Tensor:
