@@ -57,7 +57,8 @@ extern "C" {
                                 added under 10: mdg_qk_pair_ws_bytes, mdg_qk_pair_accum (the within-sequence, shift-invariant Q/K statistic);
                                 added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective);
                                 added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic);
-                                added under 10: mdg_attn_fwd (fused causal attention forward for compressed heads of unequal q/k and v width) */
+                                added under 10: mdg_attn_fwd (fused causal attention forward for compressed heads of unequal q/k and v width);
+                                added under 10: mdg_attn_decode_ws_bytes, mdg_attn_decode_splits, mdg_attn_decode (the same product on a split-key decode schedule) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -980,8 +981,8 @@ int mdg_qk_causal_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k
  * 16-byte loads of an operand whose base and strides are multiples of 16 bytes; otherwise a narrower path (16-byte loads at the
  * elements' 2-byte alignment, a row's last partial chunk element by element), chosen per operand on the host.  No atomics; every
  * run gives the same bits.  Only enqueues.
- * Out of scope: split-key (flash-decoding) scheduling for T == 1 (decode is correct, not fast), sliding windows, padding and
- * arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
+ * Decode (T * n_heads / n_kv <= 32) has a schedule of its own: mdg_attn_decode below; here it is correct, not fast.
+ * Out of scope: sliding windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
  * MDG_ERR_BAD_ARG (with a message, before any device work): a dtype other than bf16 / f16, negative extent, n_heads % n_kv != 0,
  * r_qk odd or outside 2..256, r_vo outside 1..256, causal with S < T, a token stride below the row width, ld_out < n_heads*r_vo,
  * a scale that is not finite and positive, a NULL operand of a non-empty call, an out whose byte range (pitch included)
@@ -990,6 +991,36 @@ int mdg_attn_fwd(const void* q, const void* k, const void* v, int dtype, int64_t
                  int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
                  int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, void* out,
                  int64_t ld_out, void* stream);
+
+/* ------------------------------------------------------------------ split-key (flash-decoding) attention for compressed heads
+ * mdg_attn_fwd's product on a decode schedule (csrc/attn_decode.hip), for T * G <= 32 with G = n_heads / n_kv: every query row of a
+ * kv head fits the 32 query columns of one MFMA tile (column c = query c / G, head of the group c % G), so one read of a kv head's K
+ * and V serves the whole group.  T == 1 at any group up to 32, short speculative or chunked steps, MHA up to T == 32.  Operands,
+ * dtype, widths, strides, causal rule (query i sees keys j <= i + S - T), out layout and error bound are mdg_attn_fwd's.  Additive
+ * entries, ABI version unchanged.
+ * The keys are cut into `splits` contiguous chunks of L = 64 * ceil(ceil(S / 64) / splits) keys; one workgroup per (batch, kv head,
+ * chunk) runs the online softmax over its chunk and writes an unnormalised fp32 partial to the caller's workspace
+ *   ws [B][n_heads][T][splits][RP + 4] floats, RP = r_vo rounded up to 4: O_s at [0, RP), m_s (log2 domain) at [RP], l_s at [RP + 1];
+ * a second kernel on the same stream forms  M = max_s m_s,  out = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s  in fp32 and rounds
+ * once.  A chunk with no admitted key for a query (an empty range: splits may exceed the key tiles; or one wholly beyond the causal
+ * limit) has m_s = -inf, l_s = 0, O_s = 0 and contributes exactly nothing; a row with no admitted key at all (S == 0) gets zeros.
+ * Two launches ordered by the stream; no counters, flags or atomics; every run gives the same bits.  The workspace holds nothing
+ * between calls and need not be initialised.  Bound, with |scale * logit| <= 20:  |out - exact| <= 4 u max_j |v[b, g, j, c]|
+ * entry-wise, as for mdg_attn_fwd: the partials and the combine are fp32, the only roundings to the element type are the
+ * probabilities and the final store.
+ *   mdg_attn_decode_ws_bytes  the workspace size: B * T * n_heads * splits * (RP + 4) * 4 (0 when an argument is not positive)
+ *   mdg_attn_decode_splits    the default split count, a pure host function: enough workgroups to give each of n_cu compute units
+ *                             one, but no chunk under 4 key tiles (one for each wave of the workgroup):
+ *                             clamp(n_cu / (B * n_kv), 1, min(ceil(ceil(S / 64) / 4), 256)); 1 for arguments that are not positive
+ * MDG_ERR_BAD_ARG (with a message, before any device work): what mdg_attn_fwd refuses, and T * G > 32, splits outside 1..256, a
+ * NULL, short (ws_bytes < mdg_attn_decode_ws_bytes) or not 16-byte aligned workspace, a workspace that overlaps q, k, v or out.
+ * B == 0 or T == 0 launches nothing and returns MDG_OK. */
+int64_t mdg_attn_decode_ws_bytes(int64_t B, int64_t T, int n_heads, int r_vo, int splits);
+int mdg_attn_decode_splits(int64_t B, int n_kv, int64_t S, int n_cu);
+int mdg_attn_decode(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads, int n_kv,
+                    int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, int splits,
+                    void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

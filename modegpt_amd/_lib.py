@@ -120,6 +120,10 @@ SIGNATURES = {
     "mdg_qk_causal_accum": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _sz, _ptr]),
     "mdg_attn_fwd": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f64,
                              _i32, _ptr, _i64, _ptr]),
+    "mdg_attn_decode_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "mdg_attn_decode_splits": (_i32, [_i64, _i32, _i64, _i32]),
+    "mdg_attn_decode": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f64,
+                                _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr]),
     "mdg_comm_unique_id": (_i32, [_ptr]),
     "mdg_comm_init": (_i32, [C.POINTER(_ptr), _i32, _i32, _ptr]),
     "mdg_allgather_layers": (_i32, [_ptr, _ptr, _sz, _ptr, _ptr]),

@@ -29,40 +29,21 @@
 // fewer than 8 elements is always read element by element.  The output is stored 8 bytes at a time when out, ld_out and r_vo
 // allow it, element-wise otherwise.
 //
-// Out of scope: split-key (flash-decoding) scheduling for T == 1 (decode is correct, a wave then carries one query), sliding
-// windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
+// Decode (T * group <= 32) has a schedule of its own, split over the keys: attn_decode.hip.  Here it is correct, a wave then carries
+// one query.  Out of scope: sliding windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32
+// inputs.
 #include <math.h>
 
-#include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace mdg {
 namespace {
 
+using namespace attn;
+
 constexpr int THREADS = 256;
 constexpr int WAVES = 4;
 constexpr int QT = 32;   // queries per wave
-constexpr int KT = 64;   // keys per LDS stage
-constexpr int VP = KT + 8;  // Vs pitch in elements (144 B: 16-byte aligned rows)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-template <int DT> struct Mma;
-template <> struct Mma<MDG_BF16> {
-  typedef __bf16 E;
-  typedef __bf16 frag __attribute__((ext_vector_type(8)));
-  __device__ static __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma<MDG_F16> {
-  typedef _Float16 E;
-  typedef _Float16 frag __attribute__((ext_vector_type(8)));
-  __device__ static __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 struct AttnArgs {
   const void* q;
@@ -76,31 +57,6 @@ struct AttnArgs {
   int vec_q, vec_k, vec_v, vec_o;
   float c;  // scale * log2(e)
 };
-
-// 8 consecutive elements of a row starting at column c0 (a multiple of 8); columns >= width read as zero.  `vec`: the row start
-// is 16-byte aligned.  The narrower path reads a whole chunk as 16 bytes at the elements' own 2-byte alignment (global memory takes
-// unaligned dword loads; where the target does not, the compiler splits the load) and a row's tail chunk element by element.
-typedef unsigned u32x4u __attribute__((ext_vector_type(4), aligned(2)));
-template <typename E> __device__ __forceinline__ u32x4 load8(const E* row, int c0, int width, bool vec) {
-  u32x4 z = {0u, 0u, 0u, 0u};
-  if (c0 >= width) return z;
-  if (c0 + 8 <= width) {
-    if (vec) return *(const u32x4*)(row + c0);
-    const u32x4u w = *(const u32x4u*)(row + c0);
-    return (u32x4){w[0], w[1], w[2], w[3]};
-  }
-  const unsigned short* p = (const unsigned short*)row;
-  unsigned e[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) e[j] = c0 + j < width ? (unsigned)p[c0 + j] : 0u;
-  z.x = e[0] | (e[1] << 16);
-  z.y = e[2] | (e[3] << 16);
-  z.z = e[4] | (e[5] << 16);
-  z.w = e[6] | (e[7] << 16);
-  return z;
-}
-
-__device__ __forceinline__ unsigned half_of(unsigned w, int odd) { return odd ? (w >> 16) : (w & 0xffffu); }
 
 template <int DT, int NQ, int NV>
 __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fwd_kernel(AttnArgs a) {
@@ -366,19 +322,6 @@ template <int DT> int launch_attn_q(const AttnArgs& a, dim3 grid, hipStream_t st
   if (a.r_qk <= 64) return launch_attn_v<DT, 4>(a, grid, st);
   if (a.r_qk <= 128) return launch_attn_v<DT, 8>(a, grid, st);
   return launch_attn_v<DT, 16>(a, grid, st);
-}
-
-// the byte range [lo, hi) a strided [B, H, N, width] operand spans
-void span_of(const void* p, int64_t B, int64_t bs, int64_t H, int64_t hs, int64_t N, int64_t ts, int64_t width, size_t es,
-             uintptr_t& lo, uintptr_t& hi) {
-  int64_t mn = 0, mxe = 0;
-  const int64_t ext[3] = {(B - 1) * bs, (H - 1) * hs, (N - 1) * ts};
-  for (int i = 0; i < 3; i++) {
-    if (ext[i] < 0) mn += ext[i];
-    else mxe += ext[i];
-  }
-  lo = (uintptr_t)p + (uintptr_t)(mn * (int64_t)es);
-  hi = (uintptr_t)p + (uintptr_t)((mxe + width) * (int64_t)es);
 }
 
 }  // namespace

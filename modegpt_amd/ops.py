@@ -1345,6 +1345,37 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
     return out
 
 
+def _attn_operands(fn: str, q, k, v, out):
+    """The tensor checks attn_fwd and attn_decode share: (q, k, v, out, ld_out, k token stride, v token stride)."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f"{fn}: q, k, v must be 4-D, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"{fn}: q, k, v must share bf16 or f16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    B, n_heads, T, r_qk = q.shape
+    n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    if tuple(k.shape) != (B, n_kv, S, r_qk) or tuple(v.shape) != (B, n_kv, S, r_vo):
+        raise ValueError(f"{fn}: k {tuple(k.shape)} / v {tuple(v.shape)} do not fit q {tuple(q.shape)}: "
+                         f"k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]")
+    q, k, v = q.detach(), k.detach(), v.detach()
+    if not q.is_contiguous():
+        q = q.contiguous()
+    for name, t in (("k", k), ("v", v)):
+        if t.shape[3] > 1 and t.stride(3) != 1:
+            raise ValueError(f"{fn}: {name} must have a contiguous last dimension, got strides {t.stride()}")
+    if out is None:
+        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
+    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
+          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
+          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"{fn}: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
+                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    # the stride of an axis of extent 1 is arbitrary in torch: the pitch of the [B*T] rows comes from an axis that has one
+    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    k_ts = k.stride(2) if S > 1 else r_qk
+    v_ts = v.stride(2) if S > 1 else r_vo
+    return q, k, v, out, ld_out, k_ts, v_ts
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused attention forward for compressed heads (mdg_attn_fwd): q [B, n_heads, T, r_qk], k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]
@@ -1354,36 +1385,53 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
     last two dimensions are contiguous and whose rows have one pitch (it is returned); it must not overlap q, k or v."""
     _need_gpu(q, k, v, out)
     lib = _lib.load()
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError(f"attn_fwd: q, k, v must be 4-D, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"attn_fwd: q, k, v must share bf16 or f16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_fwd", q, k, v, out)
     B, n_heads, T, r_qk = q.shape
     n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
-    if tuple(k.shape) != (B, n_kv, S, r_qk) or tuple(v.shape) != (B, n_kv, S, r_vo):
-        raise ValueError(f"attn_fwd: k {tuple(k.shape)} / v {tuple(v.shape)} do not fit q {tuple(q.shape)}: "
-                         f"k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]")
-    q, k, v = q.detach(), k.detach(), v.detach()
-    if not q.is_contiguous():
-        q = q.contiguous()
-    for name, t in (("k", k), ("v", v)):
-        if t.shape[3] > 1 and t.stride(3) != 1:
-            raise ValueError(f"attn_fwd: {name} must have a contiguous last dimension, got strides {t.stride()}")
-    if out is None:
-        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
-    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
-          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
-          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
-        raise ValueError(f"attn_fwd: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
-                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
-    # the stride of an axis of extent 1 is arbitrary in torch: the pitch of the [B*T] rows comes from an axis that has one
-    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
-    k_ts = k.stride(2) if S > 1 else r_qk
-    v_ts = v.stride(2) if S > 1 else r_vo
     with torch.cuda.device(q.device):
         check(lib.mdg_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
                                k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
                                float(scale), 1 if causal else 0, out.data_ptr(), ld_out, _stream(q)), "mdg_attn_fwd")
+    return out
+
+
+ATTN_DECODE_COLUMNS = 32     # mdg_attn_decode's domain: T * (n_heads / n_kv) query columns of one MFMA tile
+
+
+def attn_decode_splits(B: int, n_kv: int, S: int, device) -> int:
+    """The default split count of attn_decode for a shape on `device` (mdg_attn_decode_splits with the device's CU count)."""
+    n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+    return int(_lib.load().mdg_attn_decode_splits(int(B), int(n_kv), int(S), int(n_cu)))
+
+
+def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
+                splits: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_fwd's product on the split-key decode schedule (mdg_attn_decode), for T * (n_heads / n_kv) <= 32: same operands, same
+    `out` contract, same result within the same bound.  The keys are cut into `splits` chunks, one workgroup each per (batch, kv
+    head), and a second kernel combines the fp32 partials; `splits=None` asks mdg_attn_decode_splits with the device's CU count.
+    The workspace is a torch.empty on q's device."""
+    _need_gpu(q, k, v, out)
+    lib = _lib.load()
+    q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_decode", q, k, v, out)
+    B, n_heads, T, r_qk = q.shape
+    n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
+        raise ValueError(f"attn_decode: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit "
+                         f"{ATTN_DECODE_COLUMNS} columns (attn_fwd takes the rest)")
+    if splits is None:
+        splits = attn_decode_splits(B, n_kv, S, q.device)
+    splits = int(splits)
+    if not 1 <= splits <= 256:
+        raise ValueError(f"attn_decode: splits={splits} must be within 1 .. 256")
+    if B == 0 or T == 0:
+        return out
+    ws_bytes = int(lib.mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib.mdg_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
+                                  k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
+                                  float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(), ld_out,
+                                  _stream(q)), "mdg_attn_decode")
     return out
 
 

@@ -19,6 +19,9 @@ stock HF modules and gives their attention the compressed semantics, with the el
     MODEGPT_FUSED_ATTN=1: then a call without a mask, a sliding window or requested weights (the condition under which HF's own
     sdpa path asks for is_causal) runs modegpt_amd.ops.attn_fwd (csrc/attn.hip), a flash-style kernel that takes r_qk != r_vo
     as they are and writes the token-major rows o_proj reads.  Which one served is counted in ATTN_CALLS.  Off by default.
+    MODEGPT_FUSED_ATTN_DECODE=1 beside it (no effect alone) sends those of these calls whose queries of one kv head fit one MFMA
+    tile -- T * (n_heads / n_kv) <= 32: decode steps, short chunks -- to modegpt_amd.ops.attn_decode (csrc/attn_decode.hip), the
+    same product split over the keys so that a small batch fills the device.  Which kernel served is counted in ATTN_KERNELS.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -47,7 +50,10 @@ import torch.nn as nn
 
 logger = logging.getLogger("MoDeGPT")
 PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_gather / by the torch expression
-ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by mdg_attn_fwd / by HF's attention interface
+ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
+ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1)
+_DECODE_COLUMNS = 32                    # mdg_attn_decode's domain: T * (n_heads / n_kv) query columns of one MFMA tile
+_DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
 _HIP_BROKEN = None                      # why the engine, although installed here, cannot serve (its library failed to load)
 
@@ -142,7 +148,8 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
     o_proj [B, T, n_h * r_vo], weights).  MODEGPT_FUSED_ATTN=1 sends a call that needs no mask tensor to mdg_attn_fwd: no
     attention_mask (with one, HF's interface serves the call as it always did: nothing is inspected, nothing syncs), the module
     causal, no sliding window, no weights requested, no gradients, bf16 / f16 on a GPU with the engine's library loaded.  Query i
-    then sees the keys j <= i + (S - T): prefill, and decode with a cache.  With MODEGPT_REQUIRE_HIP=1 as well, a call that meets
+    then sees the keys j <= i + (S - T): prefill, and decode with a cache.  With MODEGPT_FUSED_ATTN_DECODE=1 as well, those of these
+    calls with T * (n_h / n_kv) <= 32 run mdg_attn_decode, the split-key schedule.  With MODEGPT_REQUIRE_HIP=1 as well, a call that meets
     the conditions but cannot be served by the kernel (the engine's library does not load, a width outside the kernel's range, a
     strided last dimension) raises instead of taking the interface."""
     B, T = q.shape[0], q.shape[2]
@@ -162,7 +169,14 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
                 why = "k / v without a contiguous last dimension"
             if why is None:
                 ATTN_CALLS["hip"] += 1
-                out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=True)            # [B, T, n_h, r_vo]
+                n_h, n_kv = q.shape[1], k.shape[1]
+                if (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
+                        and T * (n_h // n_kv) <= _DECODE_COLUMNS):
+                    ATTN_KERNELS["decode"] += 1
+                    out = _hip_ops().attn_decode(q, k, v, float(scaling), causal=True, splits=_DECODE_SPLITS)
+                else:
+                    ATTN_KERNELS["fwd"] += 1
+                    out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=True)        # [B, T, n_h, r_vo]
                 return out.view(B, T, -1), None
             if os.environ.get("MODEGPT_REQUIRE_HIP", "0") == "1":
                 raise RuntimeError("compressed attention: MODEGPT_FUSED_ATTN=1 and MODEGPT_REQUIRE_HIP=1 but mdg_attn_fwd cannot "
