@@ -58,7 +58,8 @@ extern "C" {
                                 added under 10: mdg_nystrom_greedy_ws_bytes, mdg_nystrom_greedy_select (MLP columns by block-greedy descent on the refit's objective);
                                 added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic);
                                 added under 10: mdg_attn_fwd (fused causal attention forward for compressed heads of unequal q/k and v width);
-                                added under 10: mdg_attn_decode_ws_bytes, mdg_attn_decode_splits, mdg_attn_decode (the same product on a split-key decode schedule) */
+                                added under 10: mdg_attn_decode_ws_bytes, mdg_attn_decode_splits, mdg_attn_decode (the same product on a split-key decode schedule);
+                                added under 10: mdg_attn_mask_summary_bytes, mdg_attn_mask_summary, mdg_attn_fwd_masked, mdg_attn_decode_masked (both products under a bool mask) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -982,7 +983,8 @@ int mdg_qk_causal_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k
  * elements' 2-byte alignment, a row's last partial chunk element by element), chosen per operand on the host.  No atomics; every
  * run gives the same bits.  Only enqueues.
  * Decode (T * n_heads / n_kv <= 32) has a schedule of its own: mdg_attn_decode below; here it is correct, not fast.
- * Out of scope: sliding windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32 inputs.
+ * Bool masks (padded batches): mdg_attn_fwd_masked / mdg_attn_decode_masked below.
+ * Out of scope: sliding windows, additive float masks, dropout, returning attention weights, a backward pass, fp32 inputs.
  * MDG_ERR_BAD_ARG (with a message, before any device work): a dtype other than bf16 / f16, negative extent, n_heads % n_kv != 0,
  * r_qk odd or outside 2..256, r_vo outside 1..256, causal with S < T, a token stride below the row width, ld_out < n_heads*r_vo,
  * a scale that is not finite and positive, a NULL operand of a non-empty call, an out whose byte range (pitch included)
@@ -1021,6 +1023,52 @@ int mdg_attn_decode(const void* q, const void* k, const void* v, int dtype, int6
                     int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
                     int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, int splits,
                     void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream);
+
+/* ------------------------------------------------------------------ bool masks on both attention kernels (padded batches)
+ * mdg_attn_fwd / mdg_attn_decode with a bool mask tensor, taken as a framework hands it over (Transformers' sdpa_mask: the causal
+ * rule ANDed with the padding columns, expanded): nothing is inspected on the host, nothing synchronises, no form is assumed.
+ * Additive entries, ABI version unchanged; the unmasked entries and their kernels are as they were.
+ *   mask  logical [B, Hm, T, S], Hm == 1 (one mask for every head) or Hm == n_heads; ONE BYTE per element, non-zero admits; batch,
+ *         head and query strides in BYTES, any of them may be 0 (an expanded axis); the key stride is 1
+ * Key j is admitted for query (b, h, i) iff mask[b, Hm == 1 ? 0 : h, i, j] != 0 and, with causal != 0, also j <= i + S - T.  A
+ * query with no admitted key gets zeros (the rule of S == 0; -inf - -inf is never formed).  A masked logit is set to -inf before
+ * the running maximum, where the causal rule sets it, so its probability is exactly 0 and a masked key's k row is never seen (it may
+ * hold Inf or NaN); v at masked keys must be FINITE (0 x NaN, as for torch's sdpa).  Everything else -- operands, widths, strides,
+ * out rows, arithmetic, determinism, no atomics -- is the unmasked entry's, and |out - exact| <= 4 u max_j |v[b, g, j, c]| holds
+ * with the maximum over the admitted keys.
+ * Prefill reads a tile summary first:
+ *   mdg_attn_mask_summary_bytes  B * Hm * ceil(T / 32) * ceil(S / 64) (0 when an argument is not positive): a pure host function
+ *   mdg_attn_mask_summary        one pass over the mask writes summary[B][Hm][ceil(T/32)][ceil(S/64)] bytes: 0 = no element of the
+ *                                32-query x 64-key tile admitted, 1 = every element, 2 = mixed; positions beyond T or S are
+ *                                ignored.  4-byte loads when the mask's base and strides are multiples of 4, byte loads otherwise.
+ *   mdg_attn_fwd_masked          mdg_attn_fwd's arguments, then the mask and its summary.  Enqueue mdg_attn_mask_summary on the same
+ *                                stream first: two launches ordered by the stream, no counters, no flags.  A key tile that admits
+ *                                nothing for all units of a workgroup is not staged (left padding; the causal triangle when
+ *                                causal == 0 and the rule lives in the mask); a wave skips a tile that admits nothing for its unit,
+ *                                runs the unmasked code on a tile that admits everything, and reads the mask (4-byte loads when
+ *                                base and strides allow, chosen on the host) only for a mixed tile.
+ *   mdg_attn_decode_masked       mdg_attn_decode's arguments, then the mask: column c reads the mask row of query c / G (head
+ *                                c % G of the group when Hm == n_heads) directly, S bytes per row; no summary, no extra
+ *                                workspace; every key tile is still loaded.  The combine kernel is mdg_attn_decode's.
+ * MDG_ERR_BAD_ARG (with a message, before any device work): what the unmasked entry refuses, and Hm not in {1, n_heads}, a negative
+ * mask stride, a NULL mask or summary of a non-empty call, a summary shorter than mdg_attn_mask_summary_bytes, a mask or summary
+ * (decode: a mask or workspace) whose byte span -- computed with the strides, an axis of stride 0 counting extent 1 -- intersects
+ * out's.  mdg_attn_mask_summary refuses a negative extent or stride, Hm < 1, a NULL or short summary, a summary inside the mask.
+ * Out of scope: additive float masks, sliding windows, one summary for all layers of a forward, skipping whole cache chunks in
+ * decode, varlen / packed layouts without a mask tensor, a backward pass. */
+int64_t mdg_attn_mask_summary_bytes(int64_t B, int Hm, int64_t T, int64_t S);
+int mdg_attn_mask_summary(const void* mask, int64_t B, int Hm, int64_t T, int64_t S, int64_t mask_batch_stride,
+                          int64_t mask_head_stride, int64_t mask_query_stride, void* summary, int64_t summary_bytes, void* stream);
+int mdg_attn_fwd_masked(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
+                        int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                        int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, void* out,
+                        int64_t ld_out, void* stream, const void* mask, int Hm, int64_t mask_batch_stride,
+                        int64_t mask_head_stride, int64_t mask_query_stride, const void* summary, int64_t summary_bytes);
+int mdg_attn_decode_masked(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
+                           int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                           int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
+                           int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream, const void* mask,
+                           int Hm, int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -124,6 +124,12 @@ SIGNATURES = {
     "mdg_attn_decode_splits": (_i32, [_i64, _i32, _i64, _i32]),
     "mdg_attn_decode": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f64,
                                 _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr]),
+    "mdg_attn_mask_summary_bytes": (_i64, [_i64, _i32, _i64, _i64]),
+    "mdg_attn_mask_summary": (_i32, [_ptr, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _ptr, _i64, _ptr]),
+    "mdg_attn_fwd_masked": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64,
+                                    _f64, _i32, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64, _ptr, _i64]),
+    "mdg_attn_decode_masked": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64,
+                                       _i64, _f64, _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64]),
     "mdg_comm_unique_id": (_i32, [_ptr]),
     "mdg_comm_init": (_i32, [C.POINTER(_ptr), _i32, _i32, _ptr]),
     "mdg_allgather_layers": (_i32, [_ptr, _ptr, _sz, _ptr, _ptr]),

@@ -30,8 +30,8 @@
 // allow it, element-wise otherwise.
 //
 // Decode (T * group <= 32) has a schedule of its own, split over the keys: attn_decode.hip.  Here it is correct, a wave then carries
-// one query.  Out of scope: sliding windows, padding and arbitrary masks, dropout, returning attention weights, a backward pass, fp32
-// inputs.
+// one query.  Bool masks (padded batches): the MASKED variant below, behind mdg_attn_fwd_masked, with attn_mask.hip's tile summary.
+// Out of scope: sliding windows, additive float masks, dropout, returning attention weights, a backward pass, fp32 inputs.
 #include <math.h>
 
 #include "attn_tile.hpp"
@@ -58,8 +58,14 @@ struct AttnArgs {
   float c;  // scale * log2(e)
 };
 
-template <int DT, int NQ, int NV>
-__global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fwd_kernel(AttnArgs a) {
+// MASKED (mdg_attn_fwd_masked; `mk` is unused otherwise and the unmasked instantiations compile to the instructions they had before
+// the flag existed): every tile is first looked up in the caller's tile summary.  Tiles
+// that admit nothing for all of the workgroup's units are neither staged nor visited -- every thread derives that from the same
+// summary bytes (lane x of every wave reads the bytes of tile 64 grp + x and a ballot makes a 64-tile word), so the decision is
+// workgroup-uniform and the two barriers are skipped together; a wave skips the products of a tile that admits nothing for its own
+// unit, runs the unmasked code on a tile that admits everything, and reads the mask only for a mixed tile.
+template <int DT, int NQ, int NV, bool MASKED>
+__global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fwd_kernel(AttnArgs a, MaskArgs mk) {
   typedef typename Mma<DT>::E E;
   typedef typename Mma<DT>::frag frag;
   constexpr int KP = NQ * 16 + 8;  // Ks pitch in elements
@@ -176,8 +182,56 @@ __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fw
     }
   };
 
-  if (PREFETCH && wg_end > 0) fetch(0);
-  for (int64_t t0 = 0; t0 < wg_end; t0 += KT) {
+  // MASKED: the summary words of the 64 key tiles [64 grp, 64 grp + 64): bit x of wg_any = tile 64 grp + x admits something for one
+  // of the workgroup's units, of my_any / my_mix = for this wave's unit / only part of it.  All wave-uniform.
+  int64_t grp = -1;
+  unsigned long long wg_any = 0, my_any = 0, my_mix = 0;
+  const unsigned char* mrow = nullptr;  // the lane's mask row
+  auto next_live = [&](int64_t tile) -> int64_t {  // the first key tile >= tile the workgroup has to stage; ktiles when none
+    while (tile < mk.ktiles) {
+      const int64_t gq = tile >> 6;
+      if (gq != grp) {
+        grp = gq;
+        const int64_t kt = gq * 64 + lane;
+        unsigned any = 0, mine = 0;
+        if (kt < mk.ktiles) {
+#pragma unroll
+          for (int w = 0; w < WAVES; w++) {
+            const int64_t uw = u0 + w;
+            if (uw < a.units) {
+              const int64_t qtw = uw / a.G;
+              const int64_t hw = mk.per_head ? g * a.G + (uw - qtw * a.G) : 0;
+              const int64_t mh = mk.per_head ? a.n_heads : 1;
+              const unsigned s = mk.summary[((b * mh + hw) * mk.qtiles + qtw) * mk.ktiles + kt];
+              any |= s;
+              if (w == wave) mine = s;
+            }
+          }
+        }
+        wg_any = __ballot(any != 0);
+        my_any = __ballot(mine != 0);
+        my_mix = __ballot(mine == MASK_MIXED);
+      }
+      const unsigned long long rest = wg_any >> (tile & 63);
+      if (rest) return tile + __builtin_ctzll(rest);
+      tile = (gq + 1) << 6;
+    }
+    return mk.ktiles;
+  };
+  int64_t first = 0, tn = 0;  // MASKED: the first live tile's key, the next one's
+  if constexpr (MASKED) {
+    const int64_t hm = mk.per_head ? head : 0;
+    mrow = mk.mask + b * mk.mbs + hm * mk.mhs + (qi < a.T ? qi : a.T - 1) * mk.mqs;
+    first = next_live(0) * KT;
+  }
+  if (PREFETCH && wg_end > first) fetch(first);
+  for (int64_t t0 = first; t0 < wg_end; t0 = MASKED ? tn : t0 + KT) {
+    bool none = false, mixed = false;
+    if constexpr (MASKED) {  // this tile's state for the wave's unit, taken before next_live moves the words on
+      const int x = (int)(t0 / KT) & 63;
+      none = !((my_any >> x) & 1);
+      mixed = (my_mix >> x) & 1;
+    }
     __syncthreads();  // every wave is done with the previous tile
     if constexpr (PREFETCH) {
       commit();
@@ -212,8 +266,21 @@ __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fw
       }
     }
     __syncthreads();
-    if (PREFETCH && t0 + KT < wg_end) fetch(t0 + KT);
+    if constexpr (MASKED) {  // the prefetch targets the next LIVE tile
+      tn = next_live(t0 / KT + 1) * KT;
+      if (PREFETCH && tn < wg_end) fetch(tn);
+    } else {
+      if (PREFETCH && t0 + KT < wg_end) fetch(t0 + KT);
+    }
     if (!live || t0 >= wave_end) continue;  // wave-uniform; the barriers above are outside
+    unsigned mb[2] = {0u, 0u};
+    if constexpr (MASKED) {
+      if (none) continue;  // wave-uniform as well
+      if (mixed) {         // issued before the first product, used after it
+#pragma unroll
+        for (int sub = 0; sub < 2; sub++) mb[sub] = mask_bits16(mrow, t0 + 32 * sub + 4 * hh, a.S, mk.vec != 0);
+      }
+    }
 
     float t[2][16];
 #pragma unroll
@@ -242,6 +309,15 @@ __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fw
 #pragma unroll
         for (int i = 0; i < 16; i++)
           if (sub * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh > rel) t[sub][i] = -INFINITY;
+    }
+    if constexpr (MASKED) {
+      if (mixed) {
+#pragma unroll
+        for (int sub = 0; sub < 2; sub++)
+#pragma unroll
+          for (int i = 0; i < 16; i++)
+            if (!((mb[sub] >> i) & 1)) t[sub][i] = -INFINITY;
+      }
     }
     float mx = t[0][0];
 #pragma unroll
@@ -304,62 +380,79 @@ __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fw
   }
 }
 
-template <int DT, int NQ, int NV> int launch_attn(const AttnArgs& a, dim3 grid, hipStream_t st) {
+template <int DT, int NQ, int NV> int launch_attn(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
   const size_t lds = ((size_t)KT * (NQ * 16 + 8) + (size_t)NV * 32 * VP) * 2;
+  if (mk) {
+    if (lds > 64 * 1024)
+      MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+    hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV, true>), grid, dim3(THREADS), lds, st, a, *mk);
+    return MDG_OK;
+  }
   if (lds > 64 * 1024)
-    MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV>), grid, dim3(THREADS), lds, st, a);
+    MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+  hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV, false>), grid, dim3(THREADS), lds, st, a, MaskArgs{});
   return MDG_OK;
 }
 
-template <int DT, int NQ> int launch_attn_v(const AttnArgs& a, dim3 grid, hipStream_t st) {
-  if (a.r_vo <= 64) return launch_attn<DT, NQ, 2>(a, grid, st);
-  if (a.r_vo <= 128) return launch_attn<DT, NQ, 4>(a, grid, st);
-  return launch_attn<DT, NQ, 8>(a, grid, st);
+template <int DT, int NQ> int launch_attn_v(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
+  if (a.r_vo <= 64) return launch_attn<DT, NQ, 2>(a, mk, grid, st);
+  if (a.r_vo <= 128) return launch_attn<DT, NQ, 4>(a, mk, grid, st);
+  return launch_attn<DT, NQ, 8>(a, mk, grid, st);
 }
 
-template <int DT> int launch_attn_q(const AttnArgs& a, dim3 grid, hipStream_t st) {
-  if (a.r_qk <= 64) return launch_attn_v<DT, 4>(a, grid, st);
-  if (a.r_qk <= 128) return launch_attn_v<DT, 8>(a, grid, st);
-  return launch_attn_v<DT, 16>(a, grid, st);
+template <int DT> int launch_attn_q(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
+  if (a.r_qk <= 64) return launch_attn_v<DT, 4>(a, mk, grid, st);
+  if (a.r_qk <= 128) return launch_attn_v<DT, 8>(a, mk, grid, st);
+  return launch_attn_v<DT, 16>(a, mk, grid, st);
 }
 
-}  // namespace
-}  // namespace mdg
-
-using namespace mdg;
-
-extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
-                            int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
-                            int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
-                            void* out, int64_t ld_out, void* stream) {
+// Both entries: `fn` names the caller in the messages; `masked` marks mdg_attn_fwd_masked (mask .. summary_bytes are its arguments).
+int attn_fwd_entry(const char* fn, bool masked, const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S,
+                   int n_heads, int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                   int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, void* out,
+                   int64_t ld_out, void* stream, const void* mask, int Hm, int64_t mbs, int64_t mhs, int64_t mqs, const void* summary,
+                   int64_t summary_bytes) {
   MDG_CLEAR();
-  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16, "mdg_attn_fwd: dtype %d (bf16 or f16; fp32 inputs are out of scope)", dtype);
-  MDG_CHECK_ARG(B >= 0 && T >= 0 && S >= 0, "mdg_attn_fwd: negative extent");
-  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "mdg_attn_fwd: n_heads=%d is not a positive multiple of n_kv=%d",
-                n_heads, n_kv);
-  MDG_CHECK_ARG(r_qk >= 2 && r_qk <= 256 && r_qk % 2 == 0, "mdg_attn_fwd: r_qk=%d must be even, >= 2 and <= 256", r_qk);
-  MDG_CHECK_ARG(r_vo >= 1 && r_vo <= 256, "mdg_attn_fwd: r_vo=%d must be in 1..256", r_vo);
-  MDG_CHECK_ARG(!(causal && S < T), "mdg_attn_fwd: causal with S=%lld < T=%lld keys", (long long)S, (long long)T);
-  MDG_CHECK_ARG(k_token_stride >= r_qk, "mdg_attn_fwd: k token stride %lld < r_qk=%d", (long long)k_token_stride, r_qk);
-  MDG_CHECK_ARG(v_token_stride >= r_vo, "mdg_attn_fwd: v token stride %lld < r_vo=%d", (long long)v_token_stride, r_vo);
+  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16, "%s: dtype %d (bf16 or f16; fp32 inputs are out of scope)", fn, dtype);
+  MDG_CHECK_ARG(B >= 0 && T >= 0 && S >= 0, "%s: negative extent", fn);
+  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "%s: n_heads=%d is not a positive multiple of n_kv=%d", fn, n_heads,
+                n_kv);
+  MDG_CHECK_ARG(r_qk >= 2 && r_qk <= 256 && r_qk % 2 == 0, "%s: r_qk=%d must be even, >= 2 and <= 256", fn, r_qk);
+  MDG_CHECK_ARG(r_vo >= 1 && r_vo <= 256, "%s: r_vo=%d must be in 1..256", fn, r_vo);
+  MDG_CHECK_ARG(!(causal && S < T), "%s: causal with S=%lld < T=%lld keys", fn, (long long)S, (long long)T);
+  MDG_CHECK_ARG(k_token_stride >= r_qk, "%s: k token stride %lld < r_qk=%d", fn, (long long)k_token_stride, r_qk);
+  MDG_CHECK_ARG(v_token_stride >= r_vo, "%s: v token stride %lld < r_vo=%d", fn, (long long)v_token_stride, r_vo);
   const int64_t width = (int64_t)n_heads * r_vo;
-  MDG_CHECK_ARG(ld_out >= width, "mdg_attn_fwd: ld_out=%lld < n_heads*r_vo=%lld", (long long)ld_out, (long long)width);
-  MDG_CHECK_ARG(isfinite(scale) && scale > 0.0, "mdg_attn_fwd: scale %g must be finite and positive", scale);
-  MDG_CHECK_ARG(T == 0 || B <= INT64_MAX / T / n_heads / 256, "mdg_attn_fwd: B*T overflows");
+  MDG_CHECK_ARG(ld_out >= width, "%s: ld_out=%lld < n_heads*r_vo=%lld", fn, (long long)ld_out, (long long)width);
+  MDG_CHECK_ARG(isfinite(scale) && scale > 0.0, "%s: scale %g must be finite and positive", fn, scale);
+  MDG_CHECK_ARG(T == 0 || B <= INT64_MAX / T / n_heads / 256, "%s: B*T overflows", fn);
   if (B == 0 || T == 0) return MDG_OK;
-  MDG_CHECK_ARG(q && out && (S == 0 || (k && v)), "mdg_attn_fwd: null pointer");
+  MDG_CHECK_ARG(q && out && (S == 0 || (k && v)), "%s: null pointer", fn);
   const size_t es = dtype_size(dtype);
+  MaskArgs mk{};
   {
     uintptr_t ol, oh, lo, hi;
     span_of(out, 1, 0, 1, 0, B * T, ld_out, width, es, ol, oh);
     span_of(q, 1, 0, 1, 0, B * n_heads * T, r_qk, r_qk, es, lo, hi);
-    MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps q");
+    MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps q", fn);
     if (S > 0) {
       span_of(k, B, k_batch_stride, n_kv, k_head_stride, S, k_token_stride, r_qk, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps k");
+      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps k", fn);
       span_of(v, B, v_batch_stride, n_kv, v_head_stride, S, v_token_stride, r_vo, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "mdg_attn_fwd: out overlaps v");
+      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps v", fn);
+    }
+    if (masked) {
+      MDG_TRY(mask_args(fn, mask, B, Hm, n_heads, T, S, mbs, mhs, mqs, ol, oh, mk));
+      const int64_t need = mdg_attn_mask_summary_bytes(B, Hm, T, S);
+      MDG_CHECK_ARG(summary != nullptr || need == 0, "%s: null summary", fn);
+      MDG_CHECK_ARG(summary_bytes >= need, "%s: summary of %lld bytes is short of mdg_attn_mask_summary_bytes = %lld", fn,
+                    (long long)summary_bytes, (long long)need);
+      lo = (uintptr_t)summary;
+      hi = lo + (uintptr_t)need;
+      MDG_CHECK_ARG(need == 0 || hi <= ol || oh <= lo, "%s: out overlaps summary", fn);
+      mk.summary = (const unsigned char*)summary;
     }
   }
 
@@ -371,7 +464,7 @@ extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dty
   a.n_heads = n_heads; a.n_kv = n_kv; a.G = n_heads / n_kv; a.r_qk = r_qk; a.r_vo = r_vo; a.causal = causal != 0;
   a.units = ceil_div(T, QT) * a.G;
   const int64_t wg = ceil_div(a.units, WAVES);
-  MDG_CHECK_ARG(wg <= 0x7fffffff && B * n_kv <= 0x7fffffff / wg, "mdg_attn_fwd: B=%lld, T=%lld exceed one launch", (long long)B,
+  MDG_CHECK_ARG(wg <= 0x7fffffff && B * n_kv <= 0x7fffffff / wg, "%s: B=%lld, T=%lld exceed one launch", fn, (long long)B,
                 (long long)T);
   a.wg_per_bg = (int)wg;
   a.vec_q = (uintptr_t)q % 16 == 0 && r_qk % 8 == 0;
@@ -381,8 +474,34 @@ extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dty
   a.c = (float)(scale * 1.4426950408889634);
   const dim3 grid((unsigned)(B * n_kv * wg));
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MDG_BF16) MDG_TRY(launch_attn_q<MDG_BF16>(a, grid, st));
-  else MDG_TRY(launch_attn_q<MDG_F16>(a, grid, st));
+  const MaskArgs* pm = masked ? &mk : nullptr;
+  if (dtype == MDG_BF16) MDG_TRY(launch_attn_q<MDG_BF16>(a, pm, grid, st));
+  else MDG_TRY(launch_attn_q<MDG_F16>(a, pm, grid, st));
   MDG_LAUNCH_CHECK();
   return MDG_OK;
+}
+
+}  // namespace
+}  // namespace mdg
+
+using namespace mdg;
+
+extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
+                            int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
+                            int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
+                            void* out, int64_t ld_out, void* stream) {
+  return attn_fwd_entry("mdg_attn_fwd", false, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride,
+                        k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream, nullptr,
+                        1, 0, 0, 0, nullptr, 0);
+}
+
+extern "C" int mdg_attn_fwd_masked(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S,
+                                   int n_heads, int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride,
+                                   int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
+                                   double scale, int causal, void* out, int64_t ld_out, void* stream, const void* mask, int Hm,
+                                   int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride,
+                                   const void* summary, int64_t summary_bytes) {
+  return attn_fwd_entry("mdg_attn_fwd_masked", true, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride,
+                        k_head_stride, k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out,
+                        stream, mask, Hm, mask_batch_stride, mask_head_stride, mask_query_stride, summary, summary_bytes);
 }

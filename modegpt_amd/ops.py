@@ -1376,18 +1376,76 @@ def _attn_operands(fn: str, q, k, v, out):
     return q, k, v, out, ld_out, k_ts, v_ts
 
 
+def _attn_mask(fn: str, mask, q, k):
+    """The checks of a bool mask for attn_fwd / attn_decode: torch.bool, 4-D, on q's device, [B or 1, 1 or n_heads, T, S] with a unit
+    last stride.  Returns (Hm, batch stride, head stride, query stride) in bytes -- torch.bool has one byte per element; an axis
+    of extent 1 (or an expanded one) has stride 0."""
+    B, n_heads, T = q.shape[0], q.shape[1], q.shape[2]
+    S = k.shape[2]
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() != 4:
+        raise ValueError(f"{fn}: mask must be a 4-D torch.bool tensor, got "
+                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    if mask.device != q.device:
+        raise ValueError(f"{fn}: mask on {mask.device}, q on {q.device}")
+    if (mask.shape[0] not in (1, B) or mask.shape[1] not in (1, n_heads) or mask.shape[2] != T or mask.shape[3] != S):
+        raise ValueError(f"{fn}: mask {tuple(mask.shape)} is not [{B} or 1, 1 or {n_heads}, {T}, {S}]")
+    if S > 1 and mask.stride(3) != 1:
+        raise ValueError(f"{fn}: mask must have a contiguous last dimension, got strides {mask.stride()}")
+    if any(mask.stride(d) < 0 for d in range(3)):
+        raise ValueError(f"{fn}: mask with a negative stride {mask.stride()}")
+    st = [0 if mask.shape[d] == 1 else mask.stride(d) for d in range(3)]
+    return mask.shape[1], st[0], st[1], st[2]
+
+
+def attn_mask_summary(mask: torch.Tensor, B: Optional[int] = None) -> torch.Tensor:
+    """The tile summary attn_fwd reads (mdg_attn_mask_summary): bool mask [B or 1, Hm, T, S] with a unit last stride -> uint8
+    [B, Hm, ceil(T / 32), ceil(S / 64)], 0 = the 32-query x 64-key tile admits nothing, 1 = everything, 2 = mixed."""
+    _need_gpu(mask)
+    if mask.dtype != torch.bool or mask.dim() != 4 or (mask.shape[3] > 1 and mask.stride(3) != 1):
+        raise ValueError(f"attn_mask_summary: mask must be a 4-D torch.bool tensor with a contiguous last dimension, got {mask.dtype} "
+                         f"{tuple(mask.shape)} strides {mask.stride()}")
+    B = mask.shape[0] if B is None else int(B)
+    if mask.shape[0] not in (1, B):
+        raise ValueError(f"attn_mask_summary: mask batch {mask.shape[0]} is not {B} or 1")
+    Hm, T, S = mask.shape[1], mask.shape[2], mask.shape[3]
+    st = [0 if mask.shape[d] == 1 else mask.stride(d) for d in range(3)]
+    lib = _lib.load()
+    summary = torch.empty(B, Hm, -(-T // 32), -(-S // 64), dtype=torch.uint8, device=mask.device)
+    if summary.numel():
+        with torch.cuda.device(mask.device):
+            check(lib.mdg_attn_mask_summary(mask.data_ptr(), B, Hm, T, S, st[0], st[1], st[2], summary.data_ptr(), summary.numel(),
+                                            _stream(mask)), "mdg_attn_mask_summary")
+    return summary
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
-             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused attention forward for compressed heads (mdg_attn_fwd): q [B, n_heads, T, r_qk], k [B, n_kv, S, r_qk], v [B, n_kv, S, r_vo]
     (bf16 / f16; r_qk even, r_qk != r_vo allowed, both <= 256) -> [B, T, n_heads, r_vo], the token-major layout o_proj reads.  With
     `causal`, query i sees the keys j <= i + (S - T).  k and v may be views of longer buffers (a static cache): their strides are
     taken as they are, only a non-unit last stride is refused.  `out`: a caller-owned [B, T, n_heads, r_vo] tensor of q's dtype whose
-    last two dimensions are contiguous and whose rows have one pitch (it is returned); it must not overlap q, k or v."""
+    last two dimensions are contiguous and whose rows have one pitch (it is returned); it must not overlap q, k or v.
+    `mask`: a torch.bool [B or 1, 1 or n_heads, T, S] tensor with a unit last stride, taken as it is (expanded axes included): key j
+    is admitted for query (b, h, i) iff the mask says so (and the causal rule, with `causal`); a query with no admitted key gets
+    zeros; v must be finite at masked keys.  The call then builds the mask's tile summary (mdg_attn_mask_summary, a launch of its
+    own on the same stream) and runs mdg_attn_fwd_masked.  Nothing is cached across calls and nothing synchronises."""
     _need_gpu(q, k, v, out)
     lib = _lib.load()
     q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_fwd", q, k, v, out)
     B, n_heads, T, r_qk = q.shape
     n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    if mask is not None:
+        Hm, m_bs, m_hs, m_qs = _attn_mask("attn_fwd", mask, q, k)
+        n_sum = int(lib.mdg_attn_mask_summary_bytes(B, Hm, T, S))
+        summary = torch.empty(max(n_sum, 1), dtype=torch.uint8, device=q.device)
+        with torch.cuda.device(q.device):
+            check(lib.mdg_attn_mask_summary(mask.data_ptr(), B, Hm, T, S, m_bs, m_hs, m_qs, summary.data_ptr(), n_sum, _stream(q)),
+                  "mdg_attn_mask_summary")
+            check(lib.mdg_attn_fwd_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
+                                          k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
+                                          float(scale), 1 if causal else 0, out.data_ptr(), ld_out, _stream(q),
+                                          mask.data_ptr(), Hm, m_bs, m_hs, m_qs, summary.data_ptr(), n_sum), "mdg_attn_fwd_masked")
+        return out
     with torch.cuda.device(q.device):
         check(lib.mdg_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
                                k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
@@ -1405,11 +1463,11 @@ def attn_decode_splits(B: int, n_kv: int, S: int, device) -> int:
 
 
 def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
-                splits: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                splits: Optional[int] = None, out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """attn_fwd's product on the split-key decode schedule (mdg_attn_decode), for T * (n_heads / n_kv) <= 32: same operands, same
     `out` contract, same result within the same bound.  The keys are cut into `splits` chunks, one workgroup each per (batch, kv
     head), and a second kernel combines the fp32 partials; `splits=None` asks mdg_attn_decode_splits with the device's CU count.
-    The workspace is a torch.empty on q's device."""
+    The workspace is a torch.empty on q's device.  `mask`: attn_fwd's, read directly by mdg_attn_decode_masked (no summary)."""
     _need_gpu(q, k, v, out)
     lib = _lib.load()
     q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_decode", q, k, v, out)
@@ -1427,6 +1485,14 @@ def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
         return out
     ws_bytes = int(lib.mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits))
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    if mask is not None:
+        Hm, m_bs, m_hs, m_qs = _attn_mask("attn_decode", mask, q, k)
+        with torch.cuda.device(q.device):
+            check(lib.mdg_attn_decode_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk,
+                                             r_vo, k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
+                                             float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(),
+                                             ld_out, _stream(q), mask.data_ptr(), Hm, m_bs, m_hs, m_qs), "mdg_attn_decode_masked")
+        return out
     with torch.cuda.device(q.device):
         check(lib.mdg_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
                                   k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,

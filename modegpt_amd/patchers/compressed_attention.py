@@ -22,6 +22,12 @@ stock HF modules and gives their attention the compressed semantics, with the el
     MODEGPT_FUSED_ATTN_DECODE=1 beside it (no effect alone) sends those of these calls whose queries of one kv head fit one MFMA
     tile -- T * (n_heads / n_kv) <= 32: decode steps, short chunks -- to modegpt_amd.ops.attn_decode (csrc/attn_decode.hip), the
     same product split over the keys so that a small batch fills the device.  Which kernel served is counted in ATTN_KERNELS.
+    MODEGPT_FUSED_ATTN_MASK=1 beside MODEGPT_FUSED_ATTN=1 (no effect alone) also serves the calls that come WITH a mask, when it is
+    the bool [B or 1, 1 or n_heads, T, S] tensor with a unit last stride that Transformers builds for a padded batch
+    (masking_utils.sdpa_mask: the causal rule ANDed with the padding columns, expanded): batched generate with left padding,
+    batched evaluation, serving loops.  The kernels take the mask as it is (causal=False: the mask alone decides), nothing is
+    inspected and nothing syncs; such calls are also counted in ATTN_MASKED.  Any other mask (additive float, another rank, strided
+    keys) and modules with a sliding window stay on the interface.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -52,6 +58,7 @@ logger = logging.getLogger("MoDeGPT")
 PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_gather / by the torch expression
 ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
 ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1)
+ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
 _DECODE_COLUMNS = 32                    # mdg_attn_decode's domain: T * (n_heads / n_kv) query columns of one MFMA tile
 _DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
@@ -151,10 +158,28 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
     then sees the keys j <= i + (S - T): prefill, and decode with a cache.  With MODEGPT_FUSED_ATTN_DECODE=1 as well, those of these
     calls with T * (n_h / n_kv) <= 32 run mdg_attn_decode, the split-key schedule.  With MODEGPT_REQUIRE_HIP=1 as well, a call that meets
     the conditions but cannot be served by the kernel (the engine's library does not load, a width outside the kernel's range, a
-    strided last dimension) raises instead of taking the interface."""
+    strided last dimension) raises instead of taking the interface.  MODEGPT_FUSED_ATTN_MASK=1 as well: a call with an
+    attention_mask is served too when the mask is a bool [B or 1, 1 or n_h, T, S] tensor on q's device with a unit last stride --
+    decided from dtype, shape and strides alone -- by the masked entries with causal=False; with MODEGPT_REQUIRE_HIP=1 any other
+    mask raises with the reason."""
     B, T = q.shape[0], q.shape[2]
     if os.environ.get("MODEGPT_FUSED_ATTN", "0") == "1":
-        eligible = (attention_mask is None and getattr(self, "is_causal", True) is not False
+        mask = None
+        why_mask = None
+        if attention_mask is not None and os.environ.get("MODEGPT_FUSED_ATTN_MASK", "0") == "1":
+            am = attention_mask
+            if not isinstance(am, torch.Tensor) or am.dtype != torch.bool:
+                why_mask = f"a mask that is not a torch.bool tensor ({getattr(am, 'dtype', type(am))}; additive masks are out of scope)"
+            elif am.dim() != 4 or am.shape[0] not in (1, B) or am.shape[1] not in (1, q.shape[1]) or tuple(am.shape[2:]) != (T, k.shape[2]):
+                why_mask = f"a mask of shape {tuple(am.shape)}, not [B or 1, 1 or n_heads, T={T}, S={k.shape[2]}]"
+            elif am.device != q.device:
+                why_mask = f"a mask on {am.device}"
+            elif (am.shape[3] > 1 and am.stride(3) != 1) or any(am.stride(d) < 0 for d in range(3)):
+                why_mask = f"a mask with strides {am.stride()} (the keys must be contiguous)"
+            else:
+                mask = am
+        eligible = ((attention_mask is None or mask is not None or why_mask is not None)
+                    and getattr(self, "is_causal", True) is not False
                     and getattr(self, "sliding_window", None) is None
                     and not (want_weights or kwargs.get("output_attentions", False))
                     and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad))
@@ -167,15 +192,23 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
                 why = f"head widths r_qk={q.shape[-1]} (even, <= 256), r_vo={v.shape[-1]} (<= 256)"
             elif k.stride(-1) != 1 or v.stride(-1) != 1:
                 why = "k / v without a contiguous last dimension"
+            elif why_mask is not None:
+                why = why_mask
             if why is None:
                 ATTN_CALLS["hip"] += 1
                 n_h, n_kv = q.shape[1], k.shape[1]
-                if (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
-                        and T * (n_h // n_kv) <= _DECODE_COLUMNS):
-                    ATTN_KERNELS["decode"] += 1
+                decode = (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
+                          and T * (n_h // n_kv) <= _DECODE_COLUMNS)
+                ATTN_KERNELS["decode" if decode else "fwd"] += 1
+                if mask is not None:                                     # the mask alone decides: it carries the causal rule
+                    ATTN_MASKED["decode" if decode else "fwd"] += 1
+                    if decode:
+                        out = _hip_ops().attn_decode(q, k, v, float(scaling), causal=False, splits=_DECODE_SPLITS, mask=mask)
+                    else:
+                        out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=False, mask=mask)
+                elif decode:
                     out = _hip_ops().attn_decode(q, k, v, float(scaling), causal=True, splits=_DECODE_SPLITS)
                 else:
-                    ATTN_KERNELS["fwd"] += 1
                     out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=True)        # [B, T, n_h, r_vo]
                 return out.view(B, T, -1), None
             if os.environ.get("MODEGPT_REQUIRE_HIP", "0") == "1":
