@@ -152,3 +152,46 @@ def test_covariance_of_a_batch_beyond_4gib(ops, dev, monkeypatch):
         else:
             assert spot < 1e-12, ("cov_accum_multi f64", spot)
         assert trace < 1e-12, (mode, trace)
+
+
+def _cache_views_past_the_edge(p, v_probe, dev):
+    """k, v [2, n_kv, S, r] as views of torch.empty buffers a little over 2^31 elements each: batch 1 starts beyond byte 2^32.
+    Only the viewed rows are written."""
+    views = []
+    for t in (p.k, v_probe):
+        Bt, KV, S, r = t.shape
+        batch_stride = (1 << 31) + 64
+        buf = torch.empty(batch_stride + KV * S * r, dtype=t.dtype, device=dev)
+        view = buf.as_strided((Bt, KV, S, r), (batch_stride, S * r, r, 1))
+        assert view.stride(0) * t.element_size() > 1 << 32 and buf.numel() > 1 << 31
+        view.copy_(t.to(dev))
+        views.append(view)
+    return views
+
+
+@pytest.mark.parametrize("kernel, T, S, splits", [("fwd", 33, 33, None), ("decode", 1, 130, 3)], ids=["fwd", "decode"])
+def test_attention_cache_views_past_2_31_elements(ops, dev, kernel, T, S, splits):
+    """mdg_attn_fwd and mdg_attn_decode on k and v whose batch stride puts batch 1 more than 4 GiB from the base, with the weight
+    probe of tests/attn_ref.py (widths 90 / 77, bf16): every key's softmax weight is exact, so a row of batch 1 read through a
+    32-bit offset -- batch 0's rows, or unwritten memory -- fails bit equality on w(b, g) alone."""
+    from tests import attn_ref as R
+    width = (90, 77, 8, 2)
+    p = R.probe_case("bf16", width, T, S)
+    q = p.q.to(dev)
+    for ad in list(R.probe_admissions(T, S, width[2]))[:2]:              # unmasked: causal, full
+        lo, hi, _ = R.probe_expected(p, "bf16", ad.adm, width)
+        outs = []
+        for j0 in p.windows:
+            k, v = _cache_views_past_the_edge(p, R.probe_values(p, "bf16", j0), dev)
+            if kernel == "fwd":
+                outs.append(ops.attn_fwd(q, k, v, p.scale, causal=ad.causal))
+            else:
+                outs.append(ops.attn_decode(q, k, v, p.scale, causal=ad.causal, splits=splits))
+            torch.cuda.synchronize()
+            del k, v
+        got = torch.cat(outs, dim=3).contiguous().view(torch.int16).cpu()
+        ok = (got == lo) | (got == hi)
+        if not bool(ok.all()):
+            b, i, h, key = (~ok).nonzero()[0].tolist()
+            raise AssertionError(f"{kernel} causal={ad.causal}: weight of key {key} for (b, i, h) = ({b}, {i}, {h}) has bits "
+                                 f"{int(got[b, i, h, key]):#06x}, want {int(lo[b, i, h, key]):#06x}; {int((~ok).sum())} entries differ")

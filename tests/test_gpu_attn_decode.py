@@ -37,6 +37,12 @@ SHAPES = [
     (90, 77, 3, 64, 12, 4),      # G = 3: a non-power-of-two column map; S exactly one tile
     (64, 64, 1, 63, 4, 4),       # the neighbours of one tile
     (64, 64, 1, 65, 4, 4),
+    (62, 65, 1, 65, 4, 4),       # the other six (NQ, NV) templates (attn_ref.template_of), at the bucket edges: (4, 4)
+    (30, 129, 4, 130, 8, 2),     # (4, 8)
+    (66, 33, 1, 130, 8, 1),      # (8, 2)
+    (128, 255, 4, 65, 4, 2),     # (8, 8)
+    (130, 64, 4, 130, 12, 4),    # (16, 2), G = 3
+    (200, 128, 1, 65, 2, 2),     # (16, 4)
 ]
 SPLITS = (1, 2, 3, 7, 256)
 
@@ -97,6 +103,21 @@ def test_random_data_within_the_derived_bound(ops, dev, dt, shape, causal):
     # default split count: the rule, with this device's CU count
     got = ops.attn_decode(c.q.to(dev), c.k.to(dev), c.v.to(dev), c.scale, causal=causal).cpu()
     assert bool(((got.double() - c.want).abs() <= bound).all())
+
+
+@pytest.mark.parametrize("shape", R.sweep_shapes(R.SWEEP_DECODE_TS), ids=R.shape_id)
+@pytest.mark.parametrize("dt", sorted(R.DTYPES))
+def test_trip_count_sweep_within_the_derived_bound(ops, dev, dt, shape):
+    """Every k-step count nq = 1 .. 16 and every column-tile count nv = 1 .. 8 (attn_ref.SWEEP), causal, the bound unchanged.  T = 16
+    with the sweep's group of 2: the kernel's domain ends at T * G = 32, the prefill sweep's T = 33 is outside it."""
+    c = R.random_case(dt, shape, True)
+    bound = 4.0 * R.UNIT_ROUNDOFF[dt] * c.vmax
+    for splits in SPLITS:
+        for name, got in run_layouts(ops, dev, c, splits):
+            err = (got.double() - c.want).abs()
+            worst = float((err / bound.clamp(min=1e-300)).max())
+            print(f"{dt} {R.shape_id(shape)} splits={splits} {name}: max err / bound = {worst:.3f}")
+            assert bool((err <= bound).all()), f"{name}, {splits} splits: max err / bound = {worst:.3f}"
 
 
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))

@@ -99,6 +99,19 @@ def test_random_data_within_the_derived_bound(ops, dev, dt, shape, causal):
         assert bool((err <= bound).all()), f"{name}: max err / bound = {worst:.3f}"
 
 
+@pytest.mark.parametrize("shape", R.sweep_shapes(R.SWEEP_FWD_TS), ids=R.shape_id)
+@pytest.mark.parametrize("dt", sorted(R.DTYPES))
+def test_trip_count_sweep_within_the_derived_bound(ops, dev, dt, shape):
+    """Every k-step count nq = 1 .. 16 and every column-tile count nv = 1 .. 8 (attn_ref.SWEEP), causal, the bound unchanged."""
+    c = R.random_case(dt, shape, True)
+    bound = 4.0 * R.UNIT_ROUNDOFF[dt] * c.vmax
+    for name, got in run_layouts(ops, dev, c):
+        err = (got.double() - c.want).abs()
+        worst = float((err / bound.clamp(min=1e-300)).max())
+        print(f"{dt} {R.shape_id(shape)} {name}: max err / bound = {worst:.3f}")
+        assert bool((err <= bound).all()), f"{name}: max err / bound = {worst:.3f}"
+
+
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_a_non_trivial_scale(ops, dev, dt):
     shape = (90, 77, 200, 200, 8, 2)

@@ -9,7 +9,8 @@
   bound       random data, |scale * logit| <= 20: |out - fp64 masked softmax| <= 4 u max|v| over the admitted keys
   not read    k rows at masked keys hold +-Inf: same bits as with zeros there
 
-Widths 90 / 77 (the 128 / 128 templates), 64 / 64 and 256 / 256; groups of 4 and 1; bf16 and f16."""
+Widths 90 / 77 (the 128 / 128 templates), 64 / 64 and 256 / 256 at every shape; the other six (NQ, NV) templates (EDGE_WIDTHS) at one
+prefill and one decode shape each; groups of 4, 3 and 1; bf16 and f16."""
 import pytest
 import torch
 
@@ -22,6 +23,19 @@ WIDTHS = [(90, 77, 8, 2), (64, 64, 4, 4), (256, 256, 2, 2)]
 FWD_TS = [(100, 100), (37, 165)]
 DECODE_TS = [(1, 63), (1, 64), (1, 65), (1, 300), (4, 63), (4, 64), (4, 65), (4, 300)]
 SPLITS = (1, 3, 7)
+# The other six (NQ, NV) templates (tests/attn_ref.template_of), at the bucket edges.  WIDTHS keep every (T, S) above; these run one
+# prefill and one decode shape each (the fp64 CPU reference of the bound test is what takes the time).
+EDGE_WIDTHS = [(62, 65, 4, 4), (30, 129, 6, 2), (66, 33, 8, 2), (128, 255, 4, 4), (130, 64, 8, 2), (200, 128, 2, 2)]
+EDGE_FWD_TS = [(37, 165)]
+EDGE_DECODE_TS = [(4, 130)]
+
+
+def fwd_ts(w):
+    return FWD_TS if w in WIDTHS else EDGE_FWD_TS
+
+
+def decode_ts(w):
+    return DECODE_TS if w in WIDTHS else EDGE_DECODE_TS
 
 
 def wid(w):
@@ -112,10 +126,10 @@ def _random_qkv(dt, w, T, S, dev, seed=0):
     return q, k, v, scale
 
 
-@pytest.mark.parametrize("w", WIDTHS, ids=wid)
+@pytest.mark.parametrize("w", WIDTHS + EDGE_WIDTHS, ids=wid)
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_identities_bit_for_bit_prefill(ops, dev, dt, w):
-    for T, S in FWD_TS:
+    for T, S in fwd_ts(w):
         q, k, v, scale = (t.to(dev) if isinstance(t, torch.Tensor) else t for t in _random_qkv(dt, w, T, S, dev))
         plain = {c: ops.attn_fwd(q, k, v, scale, causal=c) for c in (True, False)}
         ones = torch.ones(1, 1, T, S, dtype=torch.bool, device=dev).expand(R.B, 1, T, S)
@@ -128,11 +142,11 @@ def test_identities_bit_for_bit_prefill(ops, dev, dt, w):
             assert torch.equal(R.bits(got), R.bits(plain[True])), (T, S, "causal rule in the mask, causal", c)
 
 
-@pytest.mark.parametrize("w", WIDTHS, ids=wid)
+@pytest.mark.parametrize("w", WIDTHS + EDGE_WIDTHS, ids=wid)
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_identities_bit_for_bit_decode(ops, dev, dt, w):
     G = w[2] // w[3]
-    for T, S in DECODE_TS:
+    for T, S in decode_ts(w):
         if T * G > 32:
             continue
         q, k, v, scale = (t.to(dev) if isinstance(t, torch.Tensor) else t for t in _random_qkv(dt, w, T, S, dev))
@@ -221,12 +235,12 @@ def one_hot_masked(c, pads):
 
 
 @pytest.mark.parametrize("pads", [(0, 5), (64, 70)], ids=["pad0-5", "pad64-70"])
-@pytest.mark.parametrize("w", WIDTHS, ids=wid)
+@pytest.mark.parametrize("w", WIDTHS + EDGE_WIDTHS, ids=wid)
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_one_hot_best_admitted_key_bit_for_bit_prefill(dev, dt, w, pads):
     r_qk, r_vo, H, KV = w
     empty_rows = 0
-    for T, S in FWD_TS:
+    for T, S in fwd_ts(w):
         c = R.exact_case(dt, (r_qk, r_vo, T, S, H, KV), True)
         adm, want, some = one_hot_masked(c, pads)
         empty_rows += int((~some).sum())
@@ -240,17 +254,17 @@ def test_one_hot_best_admitted_key_bit_for_bit_prefill(dev, dt, w, pads):
                 b, i, h, col = (~same).nonzero()[0].tolist()
                 raise AssertionError(f"T={T} S={S} causal={causal}: out[{b}, {i}, {h}, {col}] = {float(got[b, i, h, col])!r}, want "
                                      f"{float(want[b, i, h, col])!r}; {int((~same).sum())} entries differ")
-    assert pads != (64, 70) or empty_rows > 0                                # T = S = 100 with 70 pads: 70 queries see nothing
+    assert pads != (64, 70) or w not in WIDTHS or empty_rows > 0             # T = S = 100 with 70 pads: 70 queries see nothing
 
 
 @pytest.mark.parametrize("pads", [(0, 5), (64, 70)], ids=["pad0-5", "pad64-70"])
-@pytest.mark.parametrize("w", WIDTHS, ids=wid)
+@pytest.mark.parametrize("w", WIDTHS + EDGE_WIDTHS, ids=wid)
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_one_hot_best_admitted_key_bit_for_bit_decode(dev, dt, w, pads):
     r_qk, r_vo, H, KV = w
     G = H // KV
     empty_rows = 0
-    for T, S in [(4, 200), (1, 65), (4, 68)]:
+    for T, S in [(4, 200), (1, 65), (4, 68)] if w in WIDTHS else EDGE_DECODE_TS:
         assert T * G <= 32
         c = R.exact_case(dt, (r_qk, r_vo, T, S, H, KV), True)
         adm, want, some = one_hot_masked(c, pads)
@@ -266,7 +280,7 @@ def test_one_hot_best_admitted_key_bit_for_bit_decode(dev, dt, w, pads):
                     raise AssertionError(f"T={T} S={S} causal={causal} splits={splits}: out[{b}, {i}, {h}, {col}] = "
                                          f"{float(got[b, i, h, col])!r}, want {float(want[b, i, h, col])!r}; "
                                          f"{int((~same).sum())} entries differ")
-    assert pads != (64, 70) or empty_rows > 0                                # S = 65, 68 under 70 pads: nothing admitted at all
+    assert pads != (64, 70) or w not in WIDTHS or empty_rows > 0             # S = 65, 68 under 70 pads: nothing admitted at all
 
 
 # ---------------------------------------------------------------------------------------------------------------- bound
@@ -306,13 +320,13 @@ def bound_masks(kind, layout, H, T, S, dev, seed):
 LAYOUTS = ["contiguous", "batch-stride-0", "query-stride-0", "per-head"]
 
 
-@pytest.mark.parametrize("w", WIDTHS, ids=wid)
+@pytest.mark.parametrize("w", WIDTHS + EDGE_WIDTHS, ids=wid)
 @pytest.mark.parametrize("dt", sorted(R.DTYPES))
 def test_random_data_within_the_derived_bound(ops, dev, dt, w):
     u = R.UNIT_ROUNDOFF[dt]
     H, G = w[2], w[2] // w[3]
     worst = {"fwd": 0.0, "decode": 0.0}
-    for T, S in FWD_TS + [(4, 300), (1, 65)]:
+    for T, S in FWD_TS + [(4, 300), (1, 65)] if w in WIDTHS else EDGE_FWD_TS + EDGE_DECODE_TS:
         q, k, v, scale = _random_qkv(dt, w, T, S, dev, seed=5)
         qd, kd, vd = q.to(dev), k.to(dev), v.to(dev)
         for kind in ("bernoulli", "causal-pad", "last-key"):
