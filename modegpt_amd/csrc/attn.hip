@@ -380,103 +380,51 @@ __global__ __launch_bounds__(THREADS, (NQ <= 8 && NV <= 4) ? 2 : 1) void attn_fw
   }
 }
 
-template <int DT, int NQ, int NV> int launch_attn(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
-  const size_t lds = ((size_t)KT * (NQ * 16 + 8) + (size_t)NV * 32 * VP) * 2;
-  if (mk) {
-    if (lds > 64 * 1024)
-      MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-    hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV, true>), grid, dim3(THREADS), lds, st, a, *mk);
-    return MDG_OK;
-  }
-  if (lds > 64 * 1024)
-    MDG_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<DT, NQ, NV, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  hipLaunchKernelGGL((attn_fwd_kernel<DT, NQ, NV, false>), grid, dim3(THREADS), lds, st, a, MaskArgs{});
-  return MDG_OK;
+template <int DT> int launch_attn(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
+  return with_template(a.r_qk, a.r_vo, [&](auto nq, auto nv) {
+    constexpr int NQ = decltype(nq)::value, NV = decltype(nv)::value;
+    const size_t lds = ((size_t)KT * (NQ * 16 + 8) + (size_t)NV * 32 * VP) * 2;
+    if (mk) return launch(attn_fwd_kernel<DT, NQ, NV, true>, grid, THREADS, lds, st, a, *mk);
+    return launch(attn_fwd_kernel<DT, NQ, NV, false>, grid, THREADS, lds, st, a, MaskArgs{});
+  });
 }
 
-template <int DT, int NQ> int launch_attn_v(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
-  if (a.r_vo <= 64) return launch_attn<DT, NQ, 2>(a, mk, grid, st);
-  if (a.r_vo <= 128) return launch_attn<DT, NQ, 4>(a, mk, grid, st);
-  return launch_attn<DT, NQ, 8>(a, mk, grid, st);
-}
-
-template <int DT> int launch_attn_q(const AttnArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
-  if (a.r_qk <= 64) return launch_attn_v<DT, 4>(a, mk, grid, st);
-  if (a.r_qk <= 128) return launch_attn_v<DT, 8>(a, mk, grid, st);
-  return launch_attn_v<DT, 16>(a, mk, grid, st);
-}
-
-// Both entries: `fn` names the caller in the messages; `masked` marks mdg_attn_fwd_masked (mask .. summary_bytes are its arguments).
-int attn_fwd_entry(const char* fn, bool masked, const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S,
-                   int n_heads, int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
-                   int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal, void* out,
-                   int64_t ld_out, void* stream, const void* mask, int Hm, int64_t mbs, int64_t mhs, int64_t mqs, const void* summary,
-                   int64_t summary_bytes) {
+// Both entries: `fn` names the caller in the messages; `m`, `summary` and `summary_bytes` are mdg_attn_fwd_masked's (m null otherwise).
+int attn_fwd_entry(const char* fn, const Call& p, const MaskCall* m, const void* summary, int64_t summary_bytes) {
   MDG_CLEAR();
-  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16, "%s: dtype %d (bf16 or f16; fp32 inputs are out of scope)", fn, dtype);
-  MDG_CHECK_ARG(B >= 0 && T >= 0 && S >= 0, "%s: negative extent", fn);
-  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "%s: n_heads=%d is not a positive multiple of n_kv=%d", fn, n_heads,
-                n_kv);
-  MDG_CHECK_ARG(r_qk >= 2 && r_qk <= 256 && r_qk % 2 == 0, "%s: r_qk=%d must be even, >= 2 and <= 256", fn, r_qk);
-  MDG_CHECK_ARG(r_vo >= 1 && r_vo <= 256, "%s: r_vo=%d must be in 1..256", fn, r_vo);
-  MDG_CHECK_ARG(!(causal && S < T), "%s: causal with S=%lld < T=%lld keys", fn, (long long)S, (long long)T);
-  MDG_CHECK_ARG(k_token_stride >= r_qk, "%s: k token stride %lld < r_qk=%d", fn, (long long)k_token_stride, r_qk);
-  MDG_CHECK_ARG(v_token_stride >= r_vo, "%s: v token stride %lld < r_vo=%d", fn, (long long)v_token_stride, r_vo);
-  const int64_t width = (int64_t)n_heads * r_vo;
-  MDG_CHECK_ARG(ld_out >= width, "%s: ld_out=%lld < n_heads*r_vo=%lld", fn, (long long)ld_out, (long long)width);
-  MDG_CHECK_ARG(isfinite(scale) && scale > 0.0, "%s: scale %g must be finite and positive", fn, scale);
-  MDG_CHECK_ARG(T == 0 || B <= INT64_MAX / T / n_heads / 256, "%s: B*T overflows", fn);
-  if (B == 0 || T == 0) return MDG_OK;
-  MDG_CHECK_ARG(q && out && (S == 0 || (k && v)), "%s: null pointer", fn);
-  const size_t es = dtype_size(dtype);
+  MDG_TRY(check_widths(fn, p));
+  MDG_TRY(check_layout(fn, p));
+  MDG_CHECK_ARG(p.T == 0 || p.B <= INT64_MAX / p.T / p.n_heads / 256, "%s: B*T overflows", fn);
+  if (p.B == 0 || p.T == 0) return MDG_OK;
+  MDG_TRY(check_pointers(fn, p));
+  Span sp[4];  // out, q, k, v
+  operand_spans(p, sp);
+  for (int i = 1; i < 4; i++) MDG_TRY(apart(fn, sp, 1, sp[i]));
   MaskArgs mk{};
-  {
-    uintptr_t ol, oh, lo, hi;
-    span_of(out, 1, 0, 1, 0, B * T, ld_out, width, es, ol, oh);
-    span_of(q, 1, 0, 1, 0, B * n_heads * T, r_qk, r_qk, es, lo, hi);
-    MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps q", fn);
-    if (S > 0) {
-      span_of(k, B, k_batch_stride, n_kv, k_head_stride, S, k_token_stride, r_qk, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps k", fn);
-      span_of(v, B, v_batch_stride, n_kv, v_head_stride, S, v_token_stride, r_vo, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps v", fn);
-    }
-    if (masked) {
-      MDG_TRY(mask_args(fn, mask, B, Hm, n_heads, T, S, mbs, mhs, mqs, ol, oh, mk));
-      const int64_t need = mdg_attn_mask_summary_bytes(B, Hm, T, S);
-      MDG_CHECK_ARG(summary != nullptr || need == 0, "%s: null summary", fn);
-      MDG_CHECK_ARG(summary_bytes >= need, "%s: summary of %lld bytes is short of mdg_attn_mask_summary_bytes = %lld", fn,
-                    (long long)summary_bytes, (long long)need);
-      lo = (uintptr_t)summary;
-      hi = lo + (uintptr_t)need;
-      MDG_CHECK_ARG(need == 0 || hi <= ol || oh <= lo, "%s: out overlaps summary", fn);
-      mk.summary = (const unsigned char*)summary;
-    }
+  if (m) {  // the mask's own checks come before its span, the summary's before the summary's
+    Span s;
+    MDG_TRY(mask_args(fn, p, *m, mk, s));
+    MDG_TRY(apart(fn, sp, 1, s));
+    const int64_t need = mdg_attn_mask_summary_bytes(p.B, m->Hm, p.T, p.S);
+    MDG_CHECK_ARG(summary != nullptr || need == 0, "%s: null summary", fn);
+    MDG_CHECK_ARG(summary_bytes >= need, "%s: summary of %lld bytes is short of mdg_attn_mask_summary_bytes = %lld", fn,
+                  (long long)summary_bytes, (long long)need);
+    MDG_TRY(apart(fn, sp, 1, Span{"summary", (uintptr_t)summary, (uintptr_t)summary + (uintptr_t)need}));
+    mk.summary = (const unsigned char*)summary;
   }
 
   AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out;
-  a.T = T; a.S = S; a.ld_out = ld_out;
-  a.kbs = k_batch_stride; a.khs = k_head_stride; a.kts = k_token_stride;
-  a.vbs = v_batch_stride; a.vhs = v_head_stride; a.vts = v_token_stride;
-  a.n_heads = n_heads; a.n_kv = n_kv; a.G = n_heads / n_kv; a.r_qk = r_qk; a.r_vo = r_vo; a.causal = causal != 0;
-  a.units = ceil_div(T, QT) * a.G;
+  fill_args(a, p);
+  a.units = ceil_div(p.T, QT) * a.G;
   const int64_t wg = ceil_div(a.units, WAVES);
-  MDG_CHECK_ARG(wg <= 0x7fffffff && B * n_kv <= 0x7fffffff / wg, "%s: B=%lld, T=%lld exceed one launch", fn, (long long)B,
-                (long long)T);
+  MDG_CHECK_ARG(wg <= 0x7fffffff && p.B * p.n_kv <= 0x7fffffff / wg, "%s: B=%lld, T=%lld exceed one launch", fn, (long long)p.B,
+                (long long)p.T);
   a.wg_per_bg = (int)wg;
-  a.vec_q = (uintptr_t)q % 16 == 0 && r_qk % 8 == 0;
-  a.vec_k = (uintptr_t)k % 16 == 0 && k_batch_stride % 8 == 0 && k_head_stride % 8 == 0 && k_token_stride % 8 == 0;
-  a.vec_v = (uintptr_t)v % 16 == 0 && v_batch_stride % 8 == 0 && v_head_stride % 8 == 0 && v_token_stride % 8 == 0;
-  a.vec_o = (uintptr_t)out % 8 == 0 && ld_out % 4 == 0 && r_vo % 4 == 0;
-  a.c = (float)(scale * 1.4426950408889634);
-  const dim3 grid((unsigned)(B * n_kv * wg));
-  hipStream_t st = (hipStream_t)stream;
-  const MaskArgs* pm = masked ? &mk : nullptr;
-  if (dtype == MDG_BF16) MDG_TRY(launch_attn_q<MDG_BF16>(a, pm, grid, st));
-  else MDG_TRY(launch_attn_q<MDG_F16>(a, pm, grid, st));
+  a.vec_o = (uintptr_t)p.out % 8 == 0 && p.ld_out % 4 == 0 && p.r_vo % 4 == 0;
+  const dim3 grid((unsigned)(p.B * p.n_kv * wg));
+  const MaskArgs* pm = m ? &mk : nullptr;
+  if (p.dtype == MDG_BF16) MDG_TRY(launch_attn<MDG_BF16>(a, pm, grid, (hipStream_t)p.stream));
+  else MDG_TRY(launch_attn<MDG_F16>(a, pm, grid, (hipStream_t)p.stream));
   MDG_LAUNCH_CHECK();
   return MDG_OK;
 }
@@ -490,9 +438,9 @@ extern "C" int mdg_attn_fwd(const void* q, const void* k, const void* v, int dty
                             int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride,
                             int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
                             void* out, int64_t ld_out, void* stream) {
-  return attn_fwd_entry("mdg_attn_fwd", false, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride,
-                        k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream, nullptr,
-                        1, 0, 0, 0, nullptr, 0);
+  const Call p = {q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride, k_token_stride,
+                  v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream};
+  return attn_fwd_entry("mdg_attn_fwd", p, nullptr, nullptr, 0);
 }
 
 extern "C" int mdg_attn_fwd_masked(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S,
@@ -501,7 +449,8 @@ extern "C" int mdg_attn_fwd_masked(const void* q, const void* k, const void* v, 
                                    double scale, int causal, void* out, int64_t ld_out, void* stream, const void* mask, int Hm,
                                    int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride,
                                    const void* summary, int64_t summary_bytes) {
-  return attn_fwd_entry("mdg_attn_fwd_masked", true, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride,
-                        k_head_stride, k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out,
-                        stream, mask, Hm, mask_batch_stride, mask_head_stride, mask_query_stride, summary, summary_bytes);
+  const Call p = {q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride, k_token_stride,
+                  v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream};
+  const MaskCall m = {mask, Hm, mask_batch_stride, mask_head_stride, mask_query_stride};
+  return attn_fwd_entry("mdg_attn_fwd_masked", p, &m, summary, summary_bytes);
 }

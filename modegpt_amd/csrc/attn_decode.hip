@@ -367,32 +367,13 @@ template <int DT> __global__ __launch_bounds__(MAX_SPLITS) void attn_combine_ker
   orow[tid] = (E)(acc * inv);
 }
 
-template <int DT, int NQ, int NV> int launch_decode(const DecodeArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
-  const size_t lds = (size_t)WAVES * NV * 32 * VP * 2;
-  if (mk) {
-    if (lds > 64 * 1024)
-      MDG_HIP(hipFuncSetAttribute((const void*)attn_decode_kernel<DT, NQ, NV, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-    hipLaunchKernelGGL((attn_decode_kernel<DT, NQ, NV, true>), grid, dim3(THREADS), lds, st, a, *mk);
-    return MDG_OK;
-  }
-  if (lds > 64 * 1024)
-    MDG_HIP(hipFuncSetAttribute((const void*)attn_decode_kernel<DT, NQ, NV, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  hipLaunchKernelGGL((attn_decode_kernel<DT, NQ, NV, false>), grid, dim3(THREADS), lds, st, a, MaskArgs{});
-  return MDG_OK;
-}
-
-template <int DT, int NQ> int launch_decode_v(const DecodeArgs& a, const MaskArgs* mk, dim3 grid, hipStream_t st) {
-  if (a.r_vo <= 64) return launch_decode<DT, NQ, 2>(a, mk, grid, st);
-  if (a.r_vo <= 128) return launch_decode<DT, NQ, 4>(a, mk, grid, st);
-  return launch_decode<DT, NQ, 8>(a, mk, grid, st);
-}
-
-template <int DT> int launch_decode_q(const DecodeArgs& a, const MaskArgs* mk, dim3 grid, dim3 rows, hipStream_t st) {
-  if (a.r_qk <= 64) MDG_TRY((launch_decode_v<DT, 4>(a, mk, grid, st)));
-  else if (a.r_qk <= 128) MDG_TRY((launch_decode_v<DT, 8>(a, mk, grid, st)));
-  else MDG_TRY((launch_decode_v<DT, 16>(a, mk, grid, st)));
+template <int DT> int launch_decode(const DecodeArgs& a, const MaskArgs* mk, dim3 grid, dim3 rows, hipStream_t st) {
+  MDG_TRY(with_template(a.r_qk, a.r_vo, [&](auto nq, auto nv) {
+    constexpr int NQ = decltype(nq)::value, NV = decltype(nv)::value;
+    const size_t lds = (size_t)WAVES * NV * 32 * VP * 2;
+    if (mk) return launch(attn_decode_kernel<DT, NQ, NV, true>, grid, THREADS, lds, st, a, *mk);
+    return launch(attn_decode_kernel<DT, NQ, NV, false>, grid, THREADS, lds, st, a, MaskArgs{});
+  }));
   MDG_LAUNCH_CHECK();
   hipLaunchKernelGGL((attn_combine_kernel<DT>), rows, dim3(MAX_SPLITS), 0, st, a);
   return MDG_OK;
@@ -404,13 +385,6 @@ int64_t ws_row_floats(int r_vo) { return (int64_t)((r_vo + 3) / 4 * 4 + 4); }
 }  // namespace mdg
 
 using namespace mdg;
-
-// Both entries: `fn` names the caller in the messages; `masked` marks mdg_attn_decode_masked (mask .. mqs are its arguments).
-static int attn_decode_entry(const char* fn, bool masked, const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T,
-                             int64_t S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride,
-                             int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
-                             double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out,
-                             void* stream, const void* mask, int Hm, int64_t mbs, int64_t mhs, int64_t mqs);
 
 extern "C" int64_t mdg_attn_decode_ws_bytes(int64_t B, int64_t T, int n_heads, int r_vo, int splits) {
   if (B <= 0 || T <= 0 || n_heads <= 0 || r_vo <= 0 || splits <= 0) return 0;
@@ -427,14 +401,60 @@ extern "C" int mdg_attn_decode_splits(int64_t B, int n_kv, int64_t S, int n_cu) 
   return (int)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
+// Both entries: `fn` names the caller in the messages; `m` is mdg_attn_decode_masked's (null otherwise).
+static int attn_decode_entry(const char* fn, const Call& p, const MaskCall* m, int splits, void* ws, int64_t ws_bytes) {
+  MDG_CLEAR();
+  MDG_TRY(check_widths(fn, p));
+  const int G = p.n_heads / p.n_kv;
+  MDG_CHECK_ARG(p.T * G <= COLS, "%s: T=%lld queries x group of %d heads exceed the tile of %d columns (use mdg_attn_fwd)", fn,
+                (long long)p.T, G, COLS);
+  MDG_CHECK_ARG(splits >= 1 && splits <= MAX_SPLITS, "%s: splits=%d must be in 1..%d", fn, splits, MAX_SPLITS);
+  MDG_TRY(check_layout(fn, p));
+  MDG_CHECK_ARG(p.T == 0 || p.B <= INT64_MAX / p.T / p.n_heads / MAX_SPLITS / 1040, "%s: B*T overflows", fn);
+  if (p.B == 0 || p.T == 0) return MDG_OK;
+  MDG_TRY(check_pointers(fn, p));
+  const int64_t need = mdg_attn_decode_ws_bytes(p.B, p.T, p.n_heads, p.r_vo, splits);
+  MDG_CHECK_ARG(ws != nullptr, "%s: null workspace", fn);
+  MDG_CHECK_ARG(ws_bytes >= need, "%s: workspace of %lld bytes is short of mdg_attn_decode_ws_bytes = %lld", fn,
+                (long long)ws_bytes, (long long)need);
+  MDG_CHECK_ARG((uintptr_t)ws % 16 == 0, "%s: workspace must be 16-byte aligned", fn);
+  Span sp[4];  // out, q, k, v
+  operand_spans(p, sp);
+  const Span target[2] = {sp[0], Span{"workspace", (uintptr_t)ws, (uintptr_t)ws + (uintptr_t)need}};
+  MDG_TRY(apart(fn, target + 1, 1, sp[0]));
+  MaskArgs mk{};
+  if (m) {  // the mask's own checks and its span come before q, k and v
+    Span s;
+    MDG_TRY(mask_args(fn, p, *m, mk, s));
+    MDG_TRY(apart(fn, target, 2, s));
+  }
+  for (int i = 1; i < 4; i++) MDG_TRY(apart(fn, target, 2, sp[i]));
+
+  DecodeArgs a;
+  fill_args(a, p);
+  a.ws = (float*)ws;
+  a.L = KT * ceil_div(ceil_div(p.S, KT), splits);
+  a.splits = splits;
+  a.cols = (int)p.T * G;
+  a.rp = (p.r_vo + 3) / 4 * 4;
+  MDG_CHECK_ARG(p.B * p.n_kv <= 0x7fffffff / splits && p.B * p.n_heads * p.T <= 0x7fffffff, "%s: B=%lld exceeds one launch", fn,
+                (long long)p.B);
+  const dim3 grid((unsigned)(p.B * p.n_kv * splits)), rows((unsigned)(p.B * p.n_heads * p.T));
+  const MaskArgs* pm = m ? &mk : nullptr;
+  if (p.dtype == MDG_BF16) MDG_TRY(launch_decode<MDG_BF16>(a, pm, grid, rows, (hipStream_t)p.stream));
+  else MDG_TRY(launch_decode<MDG_F16>(a, pm, grid, rows, (hipStream_t)p.stream));
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}
+
 extern "C" int mdg_attn_decode(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S, int n_heads,
                                int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride,
                                int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
                                double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out,
                                void* stream) {
-  return attn_decode_entry("mdg_attn_decode", false, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride,
-                           k_head_stride, k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, splits, ws,
-                           ws_bytes, out, ld_out, stream, nullptr, 1, 0, 0, 0);
+  const Call p = {q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride, k_token_stride,
+                  v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream};
+  return attn_decode_entry("mdg_attn_decode", p, nullptr, splits, ws, ws_bytes);
 }
 
 extern "C" int mdg_attn_decode_masked(const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T, int64_t S,
@@ -443,88 +463,8 @@ extern "C" int mdg_attn_decode_masked(const void* q, const void* k, const void* 
                                       int64_t v_token_stride, double scale, int causal, int splits, void* ws, int64_t ws_bytes,
                                       void* out, int64_t ld_out, void* stream, const void* mask, int Hm, int64_t mask_batch_stride,
                                       int64_t mask_head_stride, int64_t mask_query_stride) {
-  return attn_decode_entry("mdg_attn_decode_masked", true, q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride,
-                           k_head_stride, k_token_stride, v_batch_stride, v_head_stride, v_token_stride, scale, causal, splits, ws,
-                           ws_bytes, out, ld_out, stream, mask, Hm, mask_batch_stride, mask_head_stride, mask_query_stride);
-}
-
-static int attn_decode_entry(const char* fn, bool masked, const void* q, const void* k, const void* v, int dtype, int64_t B, int64_t T,
-                             int64_t S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t k_batch_stride, int64_t k_head_stride,
-                             int64_t k_token_stride, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride,
-                             double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out,
-                             void* stream, const void* mask, int Hm, int64_t mbs, int64_t mhs, int64_t mqs) {
-  MDG_CLEAR();
-  MDG_CHECK_ARG(dtype == MDG_BF16 || dtype == MDG_F16, "%s: dtype %d (bf16 or f16; fp32 inputs are out of scope)", fn, dtype);
-  MDG_CHECK_ARG(B >= 0 && T >= 0 && S >= 0, "%s: negative extent", fn);
-  MDG_CHECK_ARG(n_heads > 0 && n_kv > 0 && n_heads % n_kv == 0, "%s: n_heads=%d is not a positive multiple of n_kv=%d", fn,
-                n_heads, n_kv);
-  MDG_CHECK_ARG(r_qk >= 2 && r_qk <= 256 && r_qk % 2 == 0, "%s: r_qk=%d must be even, >= 2 and <= 256", fn, r_qk);
-  MDG_CHECK_ARG(r_vo >= 1 && r_vo <= 256, "%s: r_vo=%d must be in 1..256", fn, r_vo);
-  const int G = n_heads / n_kv;
-  MDG_CHECK_ARG(T * G <= COLS, "%s: T=%lld queries x group of %d heads exceed the tile of %d columns (use mdg_attn_fwd)", fn,
-                (long long)T, G, COLS);
-  MDG_CHECK_ARG(splits >= 1 && splits <= MAX_SPLITS, "%s: splits=%d must be in 1..%d", fn, splits, MAX_SPLITS);
-  MDG_CHECK_ARG(!(causal && S < T), "%s: causal with S=%lld < T=%lld keys", fn, (long long)S, (long long)T);
-  MDG_CHECK_ARG(k_token_stride >= r_qk, "%s: k token stride %lld < r_qk=%d", fn, (long long)k_token_stride, r_qk);
-  MDG_CHECK_ARG(v_token_stride >= r_vo, "%s: v token stride %lld < r_vo=%d", fn, (long long)v_token_stride, r_vo);
-  const int64_t width = (int64_t)n_heads * r_vo;
-  MDG_CHECK_ARG(ld_out >= width, "%s: ld_out=%lld < n_heads*r_vo=%lld", fn, (long long)ld_out, (long long)width);
-  MDG_CHECK_ARG(isfinite(scale) && scale > 0.0, "%s: scale %g must be finite and positive", fn, scale);
-  MDG_CHECK_ARG(T == 0 || B <= INT64_MAX / T / n_heads / MAX_SPLITS / 1040, "%s: B*T overflows", fn);
-  if (B == 0 || T == 0) return MDG_OK;
-  MDG_CHECK_ARG(q && out && (S == 0 || (k && v)), "%s: null pointer", fn);
-  const int64_t need = mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits);
-  MDG_CHECK_ARG(ws != nullptr, "%s: null workspace", fn);
-  MDG_CHECK_ARG(ws_bytes >= need, "%s: workspace of %lld bytes is short of mdg_attn_decode_ws_bytes = %lld", fn,
-                (long long)ws_bytes, (long long)need);
-  MDG_CHECK_ARG((uintptr_t)ws % 16 == 0, "%s: workspace must be 16-byte aligned", fn);
-  const size_t es = dtype_size(dtype);
-  MaskArgs mk{};
-  {
-    const uintptr_t wl = (uintptr_t)ws, wh = wl + (uintptr_t)need;
-    uintptr_t ol, oh, lo, hi;
-    span_of(out, 1, 0, 1, 0, B * T, ld_out, width, es, ol, oh);
-    MDG_CHECK_ARG(oh <= wl || wh <= ol, "%s: workspace overlaps out", fn);
-    if (masked) {
-      MDG_TRY(mask_args(fn, mask, B, Hm, n_heads, T, S, mbs, mhs, mqs, ol, oh, mk));
-      if (S > 0) {
-        mask_span_of(mask, B, mbs, Hm, mhs, T, mqs, S, lo, hi);
-        MDG_CHECK_ARG(hi <= wl || wh <= lo, "%s: workspace overlaps mask", fn);
-      }
-    }
-    span_of(q, 1, 0, 1, 0, B * n_heads * T, r_qk, r_qk, es, lo, hi);
-    MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps q", fn);
-    MDG_CHECK_ARG(hi <= wl || wh <= lo, "%s: workspace overlaps q", fn);
-    if (S > 0) {
-      span_of(k, B, k_batch_stride, n_kv, k_head_stride, S, k_token_stride, r_qk, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps k", fn);
-      MDG_CHECK_ARG(hi <= wl || wh <= lo, "%s: workspace overlaps k", fn);
-      span_of(v, B, v_batch_stride, n_kv, v_head_stride, S, v_token_stride, r_vo, es, lo, hi);
-      MDG_CHECK_ARG(hi <= ol || oh <= lo, "%s: out overlaps v", fn);
-      MDG_CHECK_ARG(hi <= wl || wh <= lo, "%s: workspace overlaps v", fn);
-    }
-  }
-
-  DecodeArgs a;
-  a.q = q; a.k = k; a.v = v; a.ws = (float*)ws; a.out = out;
-  a.T = T; a.S = S; a.ld_out = ld_out;
-  a.L = KT * ceil_div(ceil_div(S, KT), splits);
-  a.kbs = k_batch_stride; a.khs = k_head_stride; a.kts = k_token_stride;
-  a.vbs = v_batch_stride; a.vhs = v_head_stride; a.vts = v_token_stride;
-  a.n_heads = n_heads; a.n_kv = n_kv; a.G = G; a.r_qk = r_qk; a.r_vo = r_vo; a.causal = causal != 0; a.splits = splits;
-  a.cols = (int)T * G;
-  a.rp = (r_vo + 3) / 4 * 4;
-  MDG_CHECK_ARG(B * n_kv <= 0x7fffffff / splits && B * n_heads * T <= 0x7fffffff, "%s: B=%lld exceeds one launch", fn,
-                (long long)B);
-  a.vec_q = (uintptr_t)q % 16 == 0 && r_qk % 8 == 0;
-  a.vec_k = (uintptr_t)k % 16 == 0 && k_batch_stride % 8 == 0 && k_head_stride % 8 == 0 && k_token_stride % 8 == 0;
-  a.vec_v = (uintptr_t)v % 16 == 0 && v_batch_stride % 8 == 0 && v_head_stride % 8 == 0 && v_token_stride % 8 == 0;
-  a.c = (float)(scale * 1.4426950408889634);
-  const dim3 grid((unsigned)(B * n_kv * splits)), rows((unsigned)(B * n_heads * T));
-  hipStream_t st = (hipStream_t)stream;
-  const MaskArgs* pm = masked ? &mk : nullptr;
-  if (dtype == MDG_BF16) MDG_TRY(launch_decode_q<MDG_BF16>(a, pm, grid, rows, st));
-  else MDG_TRY(launch_decode_q<MDG_F16>(a, pm, grid, rows, st));
-  MDG_LAUNCH_CHECK();
-  return MDG_OK;
+  const Call p = {q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, k_batch_stride, k_head_stride, k_token_stride,
+                  v_batch_stride, v_head_stride, v_token_stride, scale, causal, out, ld_out, stream};
+  const MaskCall m = {mask, Hm, mask_batch_stride, mask_head_stride, mask_query_stride};
+  return attn_decode_entry("mdg_attn_decode_masked", p, &m, splits, ws, ws_bytes);
 }

@@ -1345,8 +1345,10 @@ def rope_rows(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: in
     return out
 
 
-def _attn_operands(fn: str, q, k, v, out):
-    """The tensor checks attn_fwd and attn_decode share: (q, k, v, out, ld_out, k token stride, v token stride)."""
+def _attn_operands(fn: str, q, k, v, out, scale, causal):
+    """The tensor checks attn_fwd and attn_decode share, and what their calls share: (q, k, v, out, the extents (B, T, S, n_heads, n_kv,
+    r_qk, r_vo), the 19 arguments every mdg_attn_* entry begins with -- q .. causal --, and out, ld_out, stream that follow the entry's
+    own)."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f"{fn}: q, k, v must be 4-D, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
     if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
@@ -1373,7 +1375,10 @@ def _attn_operands(fn: str, q, k, v, out):
     ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
     k_ts = k.stride(2) if S > 1 else r_qk
     v_ts = v.stride(2) if S > 1 else r_vo
-    return q, k, v, out, ld_out, k_ts, v_ts
+    dims = (B, T, S, n_heads, n_kv, r_qk, r_vo)
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], *dims, k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
+            float(scale), 1 if causal else 0)
+    return q, k, v, out, dims, head, (out.data_ptr(), ld_out, _stream(q))
 
 
 def _attn_mask(fn: str, mask, q, k):
@@ -1397,6 +1402,19 @@ def _attn_mask(fn: str, mask, q, k):
     return mask.shape[1], st[0], st[1], st[2]
 
 
+def _attn_mask_summary(mask, B, Hm, T, S, strides):
+    """The mdg_attn_mask_summary launch of attn_mask_summary and attn_fwd, on the mask's device and its current stream: (a flat uint8
+    buffer of at least one byte, the bytes of it that hold the summary); nothing is launched for an empty summary."""
+    lib = _lib.load()
+    n = int(lib.mdg_attn_mask_summary_bytes(B, Hm, T, S))
+    summary = torch.empty(max(n, 1), dtype=torch.uint8, device=mask.device)
+    if n:
+        with torch.cuda.device(mask.device):
+            check(lib.mdg_attn_mask_summary(mask.data_ptr(), B, Hm, T, S, *strides, summary.data_ptr(), n, _stream(mask)),
+                  "mdg_attn_mask_summary")
+    return summary, n
+
+
 def attn_mask_summary(mask: torch.Tensor, B: Optional[int] = None) -> torch.Tensor:
     """The tile summary attn_fwd reads (mdg_attn_mask_summary): bool mask [B or 1, Hm, T, S] with a unit last stride -> uint8
     [B, Hm, ceil(T / 32), ceil(S / 64)], 0 = the 32-query x 64-key tile admits nothing, 1 = everything, 2 = mixed."""
@@ -1408,14 +1426,8 @@ def attn_mask_summary(mask: torch.Tensor, B: Optional[int] = None) -> torch.Tens
     if mask.shape[0] not in (1, B):
         raise ValueError(f"attn_mask_summary: mask batch {mask.shape[0]} is not {B} or 1")
     Hm, T, S = mask.shape[1], mask.shape[2], mask.shape[3]
-    st = [0 if mask.shape[d] == 1 else mask.stride(d) for d in range(3)]
-    lib = _lib.load()
-    summary = torch.empty(B, Hm, -(-T // 32), -(-S // 64), dtype=torch.uint8, device=mask.device)
-    if summary.numel():
-        with torch.cuda.device(mask.device):
-            check(lib.mdg_attn_mask_summary(mask.data_ptr(), B, Hm, T, S, st[0], st[1], st[2], summary.data_ptr(), summary.numel(),
-                                            _stream(mask)), "mdg_attn_mask_summary")
-    return summary
+    summary, n = _attn_mask_summary(mask, B, Hm, T, S, [0 if mask.shape[d] == 1 else mask.stride(d) for d in range(3)])
+    return summary[:n].view(B, Hm, -(-T // 32), -(-S // 64))
 
 
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: bool = True,
@@ -1431,29 +1443,19 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, ca
     own on the same stream) and runs mdg_attn_fwd_masked.  Nothing is cached across calls and nothing synchronises."""
     _need_gpu(q, k, v, out)
     lib = _lib.load()
-    q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_fwd", q, k, v, out)
-    B, n_heads, T, r_qk = q.shape
-    n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    q, k, v, out, (B, T, S, *_), head, tail = _attn_operands("attn_fwd", q, k, v, out, scale, causal)
+    entry, masked = "mdg_attn_fwd", ()
     if mask is not None:
-        Hm, m_bs, m_hs, m_qs = _attn_mask("attn_fwd", mask, q, k)
-        n_sum = int(lib.mdg_attn_mask_summary_bytes(B, Hm, T, S))
-        summary = torch.empty(max(n_sum, 1), dtype=torch.uint8, device=q.device)
-        with torch.cuda.device(q.device):
-            check(lib.mdg_attn_mask_summary(mask.data_ptr(), B, Hm, T, S, m_bs, m_hs, m_qs, summary.data_ptr(), n_sum, _stream(q)),
-                  "mdg_attn_mask_summary")
-            check(lib.mdg_attn_fwd_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
-                                          k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
-                                          float(scale), 1 if causal else 0, out.data_ptr(), ld_out, _stream(q),
-                                          mask.data_ptr(), Hm, m_bs, m_hs, m_qs, summary.data_ptr(), n_sum), "mdg_attn_fwd_masked")
-        return out
+        Hm, *m_strides = _attn_mask("attn_fwd", mask, q, k)
+        summary, n_sum = _attn_mask_summary(mask, B, Hm, T, S, m_strides)
+        entry, masked = "mdg_attn_fwd_masked", (mask.data_ptr(), Hm, *m_strides, summary.data_ptr(), n_sum)
     with torch.cuda.device(q.device):
-        check(lib.mdg_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
-                               k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
-                               float(scale), 1 if causal else 0, out.data_ptr(), ld_out, _stream(q)), "mdg_attn_fwd")
+        check(getattr(lib, entry)(*head, *tail, *masked), entry)
     return out
 
 
 ATTN_DECODE_COLUMNS = 32     # mdg_attn_decode's domain: T * (n_heads / n_kv) query columns of one MFMA tile
+ATTN_DECODE_MAX_SPLITS = 256  # the most chunks mdg_attn_decode cuts the keys into (its combine kernel has one thread per chunk)
 
 
 def attn_decode_splits(B: int, n_kv: int, S: int, device) -> int:
@@ -1470,34 +1472,24 @@ def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
     The workspace is a torch.empty on q's device.  `mask`: attn_fwd's, read directly by mdg_attn_decode_masked (no summary)."""
     _need_gpu(q, k, v, out)
     lib = _lib.load()
-    q, k, v, out, ld_out, k_ts, v_ts = _attn_operands("attn_decode", q, k, v, out)
-    B, n_heads, T, r_qk = q.shape
-    n_kv, S, r_vo = k.shape[1], k.shape[2], v.shape[3]
+    q, k, v, out, (B, T, S, n_heads, n_kv, _, r_vo), head, tail = _attn_operands("attn_decode", q, k, v, out, scale, causal)
     if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
         raise ValueError(f"attn_decode: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit "
                          f"{ATTN_DECODE_COLUMNS} columns (attn_fwd takes the rest)")
     if splits is None:
         splits = attn_decode_splits(B, n_kv, S, q.device)
     splits = int(splits)
-    if not 1 <= splits <= 256:
-        raise ValueError(f"attn_decode: splits={splits} must be within 1 .. 256")
+    if not 1 <= splits <= ATTN_DECODE_MAX_SPLITS:
+        raise ValueError(f"attn_decode: splits={splits} must be within 1 .. {ATTN_DECODE_MAX_SPLITS}")
     if B == 0 or T == 0:
         return out
     ws_bytes = int(lib.mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits))
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    entry, masked = "mdg_attn_decode", ()
     if mask is not None:
-        Hm, m_bs, m_hs, m_qs = _attn_mask("attn_decode", mask, q, k)
-        with torch.cuda.device(q.device):
-            check(lib.mdg_attn_decode_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk,
-                                             r_vo, k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
-                                             float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(),
-                                             ld_out, _stream(q), mask.data_ptr(), Hm, m_bs, m_hs, m_qs), "mdg_attn_decode_masked")
-        return out
+        entry, masked = "mdg_attn_decode_masked", (mask.data_ptr(), *_attn_mask("attn_decode", mask, q, k))
     with torch.cuda.device(q.device):
-        check(lib.mdg_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo,
-                                  k.stride(0), k.stride(1), k_ts, v.stride(0), v.stride(1), v_ts,
-                                  float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(), ld_out,
-                                  _stream(q)), "mdg_attn_decode")
+        check(getattr(lib, entry)(*head, splits, ws.data_ptr(), ws_bytes, *tail, *masked), entry)
     return out
 
 

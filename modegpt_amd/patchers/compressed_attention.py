@@ -59,7 +59,6 @@ PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_ga
 ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
 ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1)
 ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
-_DECODE_COLUMNS = 32                    # mdg_attn_decode's domain: T * (n_heads / n_kv) query columns of one MFMA tile
 _DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
 _HIP_BROKEN = None                      # why the engine, although installed here, cannot serve (its library failed to load)
@@ -197,19 +196,16 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
             if why is None:
                 ATTN_CALLS["hip"] += 1
                 n_h, n_kv = q.shape[1], k.shape[1]
+                ops = _hip_ops()
                 decode = (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
-                          and T * (n_h // n_kv) <= _DECODE_COLUMNS)
-                ATTN_KERNELS["decode" if decode else "fwd"] += 1
-                if mask is not None:                                     # the mask alone decides: it carries the causal rule
-                    ATTN_MASKED["decode" if decode else "fwd"] += 1
-                    if decode:
-                        out = _hip_ops().attn_decode(q, k, v, float(scaling), causal=False, splits=_DECODE_SPLITS, mask=mask)
-                    else:
-                        out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=False, mask=mask)
-                elif decode:
-                    out = _hip_ops().attn_decode(q, k, v, float(scaling), causal=True, splits=_DECODE_SPLITS)
-                else:
-                    out = _hip_ops().attn_fwd(q, k, v, float(scaling), causal=True)        # [B, T, n_h, r_vo]
+                          and T * (n_h // n_kv) <= ops.ATTN_DECODE_COLUMNS)
+                kernel = "decode" if decode else "fwd"
+                ATTN_KERNELS[kernel] += 1
+                if mask is not None:
+                    ATTN_MASKED[kernel] += 1
+                fn, own = (ops.attn_decode, {"splits": _DECODE_SPLITS}) if decode else (ops.attn_fwd, {})
+                # with a mask the mask alone decides: it carries the causal rule
+                out = fn(q, k, v, float(scaling), causal=mask is None, mask=mask, **own)   # [B, T, n_h, r_vo]
                 return out.view(B, T, -1), None
             if os.environ.get("MODEGPT_REQUIRE_HIP", "0") == "1":
                 raise RuntimeError("compressed attention: MODEGPT_FUSED_ATTN=1 and MODEGPT_REQUIRE_HIP=1 but mdg_attn_fwd cannot "

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from modegpt_amd import _lib
-from tests.test_attn_fwd_host import _tiny
+from tests.test_attn_fwd_host import FAR, K, O, Q, V, _tiny, refused
 
 
 def _ws_bytes(B, T, n_heads, r_vo, splits):
@@ -15,53 +15,113 @@ def _ws_bytes(B, T, n_heads, r_vo, splits):
     return B * T * n_heads * splits * ((r_vo + 3) // 4 * 4 + 4) * 4
 
 
+W = 0x500000                                              # the workspace: like Q, K, V, O never dereferenced
+NEED = _ws_bytes(2, 5, 4, 3, 3)                           # 3840 bytes for call_decode's defaults
+
+
+def call_decode(lib, q=Q, k=K, v=V, dtype=_lib.MDG_BF16, B=2, T=5, S=9, n_heads=4, n_kv=2, r_qk=6, r_vo=3, kbs=2 * 9 * 6, khs=9 * 6,
+                kts=6, vbs=2 * 9 * 3, vhs=9 * 3, vts=3, scale=0.5, causal=1, splits=3, ws=W, ws_bytes=NEED, out=O, ld_out=12):
+    return lib.mdg_attn_decode(q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, kbs, khs, kts, vbs, vhs, vts, scale, causal,
+                               splits, ws, ws_bytes, out, ld_out, None)
+
+
 def test_bad_arguments_return_a_status_and_a_message_without_a_device():
     lib = _lib.load()
-    Q, K, V, O, W = 0x100000, 0x200000, 0x300000, 0x400000, 0x500000  # never dereferenced: every call below is refused before any device work
     inf, nan = float("inf"), float("nan")
-    need = _ws_bytes(2, 5, 4, 3, 3)
+    need = NEED
 
-    def call(q=Q, k=K, v=V, dtype=_lib.MDG_BF16, B=2, T=5, S=9, n_heads=4, n_kv=2, r_qk=6, r_vo=3, kbs=2 * 9 * 6, khs=9 * 6, kts=6,
-             vbs=2 * 9 * 3, vhs=9 * 3, vts=3, scale=0.5, causal=1, splits=3, ws=W, ws_bytes=need, out=O, ld_out=12):
-        return lib.mdg_attn_decode(q, k, v, dtype, B, T, S, n_heads, n_kv, r_qk, r_vo, kbs, khs, kts, vbs, vhs, vts, scale, causal,
-                                   splits, ws, ws_bytes, out, ld_out, None)
+    def call(**kw):
+        return call_decode(lib, **kw)
 
-    assert lib.mdg_attn_decode_ws_bytes(2, 5, 4, 3, 3) == need
-    bad = [(dict(dtype=99), "dtype"), (dict(dtype=_lib.MDG_F32), "dtype"), (dict(dtype=_lib.MDG_F64), "dtype"),
-           (dict(B=-1), "negative"), (dict(T=-1), "negative"), (dict(S=-1, causal=0), "negative"),
-           (dict(n_heads=5), "n_kv"), (dict(n_kv=0), "n_kv"), (dict(n_kv=3), "n_kv"),
-           (dict(r_qk=5), "even"), (dict(r_qk=0), "even"), (dict(r_qk=258, kts=258), "256"),
-           (dict(r_vo=0), "r_vo"), (dict(r_vo=257, vts=257, ld_out=4 * 257), "r_vo"),
+    assert lib.mdg_attn_decode_ws_bytes(2, 5, 4, 3, 3) == need == 3840
+    tile = " exceed the tile of 32 columns (use mdg_attn_fwd)"
+    short = " bytes is short of mdg_attn_decode_ws_bytes = "
+    bad = [  # dtype
+           (dict(dtype=99), "mdg_attn_decode: dtype 99 (bf16 or f16; fp32 inputs are out of scope)"),
+           (dict(dtype=_lib.MDG_F32), "mdg_attn_decode: dtype 2 (bf16 or f16; fp32 inputs are out of scope)"),
+           (dict(dtype=_lib.MDG_F64), "mdg_attn_decode: dtype 3 (bf16 or f16; fp32 inputs are out of scope)"),
+           # negative
+           (dict(B=-1), "mdg_attn_decode: negative extent"), (dict(T=-1), "mdg_attn_decode: negative extent"),
+           (dict(S=-1, causal=0), "mdg_attn_decode: negative extent"),
+           # n_kv
+           (dict(n_heads=5), "mdg_attn_decode: n_heads=5 is not a positive multiple of n_kv=2"),
+           (dict(n_kv=0), "mdg_attn_decode: n_heads=4 is not a positive multiple of n_kv=0"),
+           (dict(n_kv=3), "mdg_attn_decode: n_heads=4 is not a positive multiple of n_kv=3"),
+           # even, 256
+           (dict(r_qk=5), "mdg_attn_decode: r_qk=5 must be even, >= 2 and <= 256"),
+           (dict(r_qk=0), "mdg_attn_decode: r_qk=0 must be even, >= 2 and <= 256"),
+           (dict(r_qk=258, kts=258), "mdg_attn_decode: r_qk=258 must be even, >= 2 and <= 256"),
+           # r_vo
+           (dict(r_vo=0), "mdg_attn_decode: r_vo=0 must be in 1..256"),
+           (dict(r_vo=257, vts=257, ld_out=4 * 257), "mdg_attn_decode: r_vo=257 must be in 1..256"),
            # the tile: T * G = 33 (MHA, 33 queries), 17 * 2 = 34, 1 * 33
-           (dict(T=33, S=40, n_heads=2, n_kv=2, ld_out=6), "tile"), (dict(T=17, S=20), "tile"),
-           (dict(T=1, n_heads=33, n_kv=1, ld_out=99), "tile"),
-           (dict(splits=0), "splits"), (dict(splits=257), "splits"), (dict(splits=-1), "splits"),
-           (dict(S=4), "causal"),
-           (dict(kts=5), "stride"), (dict(vts=2), "stride"),
-           (dict(ld_out=11), "ld_out"),
-           (dict(scale=0.0), "scale"), (dict(scale=-1.0), "scale"), (dict(scale=inf), "scale"), (dict(scale=nan), "scale"),
-           (dict(q=None), "null"), (dict(k=None), "null"), (dict(v=None), "null"), (dict(out=None), "null"),
-           (dict(ws=None), "null workspace"), (dict(ws_bytes=need - 1), "short"), (dict(ws_bytes=0), "short"),
-           (dict(splits=4), "short"),                                    # one more split than the workspace was sized for
-           (dict(ws=W + 4), "aligned"),
-           (dict(out=Q), "overlap"), (dict(out=Q + 2 * (2 * 4 * 5 * 6 - 1)), "overlap"), (dict(q=O + 2), "overlap"),
-           (dict(out=K + 2 * 50), "overlap"), (dict(out=V + 2 * 100), "overlap"),
-           (dict(k=O + 2 * 119), "overlap"), (dict(v=O - 2 * 107), "overlap"),
+           (dict(T=33, S=40, n_heads=2, n_kv=2, ld_out=6), "mdg_attn_decode: T=33 queries x group of 1 heads" + tile),
+           (dict(T=17, S=20), "mdg_attn_decode: T=17 queries x group of 2 heads" + tile),
+           (dict(T=1, n_heads=33, n_kv=1, ld_out=99), "mdg_attn_decode: T=1 queries x group of 33 heads" + tile),
+           # splits
+           (dict(splits=0), "mdg_attn_decode: splits=0 must be in 1..256"),
+           (dict(splits=257), "mdg_attn_decode: splits=257 must be in 1..256"),
+           (dict(splits=-1), "mdg_attn_decode: splits=-1 must be in 1..256"),
+           # causal
+           (dict(S=4), "mdg_attn_decode: causal with S=4 < T=5 keys"),
+           # stride
+           (dict(kts=5), "mdg_attn_decode: k token stride 5 < r_qk=6"), (dict(vts=2), "mdg_attn_decode: v token stride 2 < r_vo=3"),
+           # ld_out
+           (dict(ld_out=11), "mdg_attn_decode: ld_out=11 < n_heads*r_vo=12"),
+           # scale
+           (dict(scale=0.0), "mdg_attn_decode: scale 0 must be finite and positive"),
+           (dict(scale=-1.0), "mdg_attn_decode: scale -1 must be finite and positive"),
+           (dict(scale=inf), "mdg_attn_decode: scale inf must be finite and positive"),
+           (dict(scale=nan), "mdg_attn_decode: scale nan must be finite and positive"),
+           # null
+           (dict(q=None), "mdg_attn_decode: null pointer"), (dict(k=None), "mdg_attn_decode: null pointer"),
+           (dict(v=None), "mdg_attn_decode: null pointer"), (dict(out=None), "mdg_attn_decode: null pointer"),
+           # null workspace, short, aligned
+           (dict(ws=None), "mdg_attn_decode: null workspace"),
+           (dict(ws_bytes=need - 1), "mdg_attn_decode: workspace of 3839" + short + "3840"),
+           (dict(ws_bytes=0), "mdg_attn_decode: workspace of 0" + short + "3840"),
+           (dict(splits=4), "mdg_attn_decode: workspace of 3840" + short + "5120"),   # one more split than the workspace was sized for
+           (dict(ws=W + 4), "mdg_attn_decode: workspace must be 16-byte aligned"),
+           # overlap
+           (dict(out=Q), "mdg_attn_decode: out overlaps q"), (dict(out=Q + 2 * (2 * 4 * 5 * 6 - 1)), "mdg_attn_decode: out overlaps q"),
+           (dict(q=O + 2), "mdg_attn_decode: out overlaps q"),
+           (dict(out=K + 2 * 50), "mdg_attn_decode: out overlaps k"), (dict(out=V + 2 * 100), "mdg_attn_decode: out overlaps v"),
+           (dict(k=O + 2 * 119), "mdg_attn_decode: out overlaps k"), (dict(v=O - 2 * 107), "mdg_attn_decode: out overlaps v"),
            # the workspace against each operand: its first and its last byte inside the operand's span, and the operand inside it
-           (dict(ws=Q), "workspace overlaps q"), (dict(ws=Q + 2 * 2 * 4 * 5 * 6 - 16), "workspace overlaps q"),
-           (dict(q=W + need - 2), "workspace overlaps q"),
-           (dict(ws=K + 16), "workspace overlaps k"), (dict(k=W + need - 2), "workspace overlaps k"),
-           (dict(ws=V + 16), "workspace overlaps v"), (dict(v=W + need - 2), "workspace overlaps v"),
-           (dict(ws=O), "workspace overlaps out"), (dict(ws=O + 2 * 10 * 12 - 16), "workspace overlaps out"),
-           (dict(out=W + need - 2), "workspace overlaps out")]
-    for kw, word in bad:
-        assert call(**kw) == _lib.MDG_ERR_BAD_ARG, kw
-        assert word in lib.mdg_last_error().decode(), (kw, lib.mdg_last_error())
-        with pytest.raises(RuntimeError):
-            _lib.check(call(**kw), "mdg_attn_decode")
+           (dict(ws=Q), "mdg_attn_decode: workspace overlaps q"),
+           (dict(ws=Q + 2 * 2 * 4 * 5 * 6 - 16), "mdg_attn_decode: workspace overlaps q"),
+           (dict(q=W + need - 2), "mdg_attn_decode: workspace overlaps q"),
+           (dict(ws=K + 16), "mdg_attn_decode: workspace overlaps k"), (dict(k=W + need - 2), "mdg_attn_decode: workspace overlaps k"),
+           (dict(ws=V + 16), "mdg_attn_decode: workspace overlaps v"), (dict(v=W + need - 2), "mdg_attn_decode: workspace overlaps v"),
+           (dict(ws=O), "mdg_attn_decode: workspace overlaps out"),
+           (dict(ws=O + 2 * 10 * 12 - 16), "mdg_attn_decode: workspace overlaps out"),
+           (dict(out=W + need - 2), "mdg_attn_decode: workspace overlaps out"),
+           # the entry's own bounds: the index overflow before the empty call and the pointers, the launch bound after the spans
+           (dict(B=2 ** 50), "mdg_attn_decode: B*T overflows"),
+           (dict(B=2 ** 31, out=FAR, ws=FAR // 2, ws_bytes=2 ** 31 * 1920), "mdg_attn_decode: B=2147483648 exceeds one launch"),
+           # two faults at once: the first check in the order above decides
+           (dict(dtype=99, B=-1), "mdg_attn_decode: dtype 99 (bf16 or f16; fp32 inputs are out of scope)"),
+           (dict(r_qk=5, T=17, S=20), "mdg_attn_decode: r_qk=5 must be even, >= 2 and <= 256"),
+           (dict(r_vo=0, T=17, S=20), "mdg_attn_decode: r_vo=0 must be in 1..256"),
+           (dict(T=17, S=20, splits=0), "mdg_attn_decode: T=17 queries x group of 2 heads" + tile),
+           (dict(splits=0, S=4), "mdg_attn_decode: splits=0 must be in 1..256"),
+           (dict(S=4, kts=5), "mdg_attn_decode: causal with S=4 < T=5 keys"),
+           (dict(scale=0.0, B=2 ** 50), "mdg_attn_decode: scale 0 must be finite and positive"),
+           (dict(B=2 ** 50, q=None), "mdg_attn_decode: B*T overflows"),
+           (dict(q=None, ws=None), "mdg_attn_decode: null pointer"),
+           (dict(ws=None, ws_bytes=0), "mdg_attn_decode: null workspace"),
+           (dict(ws=W + 4, ws_bytes=need - 1), "mdg_attn_decode: workspace of 3839" + short + "3840"),
+           (dict(ws=W + 4, out=W), "mdg_attn_decode: workspace must be 16-byte aligned"),
+           (dict(ws=O, q=O), "mdg_attn_decode: workspace overlaps out"),
+           (dict(out=Q, k=Q), "mdg_attn_decode: out overlaps q"), (dict(out=Q, ws=Q + 256), "mdg_attn_decode: out overlaps q"),
+           (dict(ws=Q, out=K), "mdg_attn_decode: workspace overlaps q"),
+           (dict(ws=K, out=V), "mdg_attn_decode: workspace overlaps k"),
+           (dict(out=K, v=K), "mdg_attn_decode: out overlaps k")]
+    refused(lib, call, bad, "mdg_attn_decode")
     # the neighbours of the refused extents are not refused for THAT reason: T * G = 32 passes the tile check (and then fails on the
     # workspace this call did not size for it)
-    assert call(T=16, S=20, ws_bytes=0) == _lib.MDG_ERR_BAD_ARG and "short" in lib.mdg_last_error().decode()
+    assert call(T=16, S=20, ws_bytes=0) == _lib.MDG_ERR_BAD_ARG
+    assert lib.mdg_last_error().decode() == "mdg_attn_decode: workspace of 0" + short + "12288"
     # an empty call is not an error and launches nothing, whatever the pointers
     assert call(B=0, q=None, out=None, ws=None, ws_bytes=0) == _lib.MDG_OK
     assert call(T=0, k=None, v=None, ws=None, ws_bytes=0) == _lib.MDG_OK
