@@ -324,12 +324,13 @@ size_t mdg_potrf_inv_diag_elems(int64_t n);
 int mdg_potrf_lower(double* A, int64_t n, int64_t lda, double* inv_diag, void* stream);
 /* X (n x nrhs, ldx, in place) <- (L L^T)^-1 X by blocks of 2048 rows: the diagonal blocks of L are inverted explicitly
  * (recursive doubling from inv_diag), a block's substitution is one triangular-aware GEMM with that inverse, one rank-2048
- * GEMM carries its solution on.  ws: mdg_potrs_lower_ws_bytes(n, nrhs) (the block inverses + a second right-hand-side buffer).
+ * GEMM carries its solution on.  ws: mdg_potrs_lower_ws_bytes(n, nrhs) (the block inverses, the doubling's scratch and a second
+ * right-hand-side buffer: potrs_layout in csrc/chol.hip).
  * Replaces torch.cholesky_solve at compress_mlp.py:57. */
 size_t mdg_potrs_lower_ws_bytes(int64_t n, int64_t nrhs);
 int mdg_potrs_lower(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* X, int64_t nrhs,
                     int64_t ldx, void* ws, size_t ws_bytes, void* stream);
-/* out[j] = ((L L^T)^-1)_jj = || L^-1 e_j ||^2.  ws: mdg_inv_diag_of_spd_ws_bytes(n).
+/* out[j] = ((L L^T)^-1)_jj = || L^-1 e_j ||^2.  ws: mdg_chol_inverse_diag_ws_bytes(n) (inv_diag_layout in csrc/chol.hip).
  * Replaces torch.cholesky_inverse + torch.diag at compress_mlp.py:21-23. */
 size_t mdg_chol_inverse_diag_ws_bytes(int64_t n);
 int mdg_chol_inverse_diag(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* out,
@@ -395,11 +396,10 @@ int mdg_gather_rows_16(const void* src, int64_t ld_src, const int64_t* rows, int
  * PRECONDITION: the entries of idx are distinct and in 0 .. n-1 (any order).  A repeated index makes C_kk singular up to eps
  * already; the result is then unspecified (nothing is written out of bounds: the complement list is cut at n - r entries, and
  * an entry outside 0 .. n-1 names no column of the complement).
- * ws: mdg_nystrom_down_ws_bytes(n, r, d) = 8 (r r' + mdg_potrf_inv_diag_elems(r) + r d) + mdg_potrs_lower_ws_bytes(r, d), r' = r
- * rounded up to 16 -- C_kk, its inverted diagonal blocks, the right-hand side, the substitution's workspace -- rounded up to 16,
- * + 16 + 8 r K' + 8 d K' + 8 (n - r) + 4 n, each term rounded up to 16: C[k,k'] as fp64 [r][K'], W_d[:,k'] as [d][K'] in W_d's
- * own dtype (sized for fp64), the complement list and its marks; K' = n - r rounded up to 16, the padding columns written as
- * zeros by the call (the workspace may hold anything).  SYNCHRONISES. */
+ * ws: mdg_nystrom_down_ws_bytes(n, r, d), 8-byte aligned; nystrom_layout in csrc/mlp.hip states the blocks -- C_kk (rows r rounded
+ * up to 16), its inverted diagonal blocks, the right-hand side and the substitution's workspace, then from a 16-byte address
+ * C[k,k'] as fp64 [r][K'], W_d[:,k'] as [d][K'] in W_d's own dtype (sized for fp64), the complement list and its marks; K' = n - r
+ * rounded up to 16, the padding columns written as zeros by the call (the workspace may hold anything).  SYNCHRONISES. */
 size_t mdg_nystrom_down_ws_bytes(int64_t n, int64_t r, int64_t d);
 int mdg_nystrom_down(const double* C, int64_t n, int64_t ldc, const int64_t* idx, int64_t r, const void* Wd,
                      int64_t d, int64_t ld_wd, int w_dtype, double eps, void* down_out, int64_t ld_out, double* down_f64,
@@ -429,7 +429,7 @@ int mdg_nystrom_down_overlapped(const double* C, int64_t n, int64_t ldc, const i
  * element.  A thread adds its tokens in ascending order; the partial row of every 128-token chunk goes to the workspace, and a second
  * kernel adds the partials in ascending chunk order and the total to sum[j].  No atomics: the same bits from run to run.  A column
  * is only ever added to itself: a NaN or Inf stays in its column.  Nothing beyond column n of a row is read.
- * ws: mdg_col_sum_ws_bytes(n_tokens, n) = 8 n ceil(n_tokens / 128) bytes, 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG for a null
+ * ws: mdg_col_sum_ws_bytes(n_tokens, n) bytes (one partial row per chunk: col_sum_layout in csrc/colsum.hip), 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG for a null
  * pointer, an unknown dtype, n_tokens or n < 1, ld < n, a misaligned pointer or a workspace that is too small. */
 size_t mdg_col_sum_ws_bytes(int64_t n_tokens, int64_t n);
 int mdg_col_sum_accum(const void* x, int dtype, int64_t n_tokens, int64_t n, int64_t ld, int relu, double* sum, void* ws,
@@ -449,7 +449,7 @@ int mdg_cov_center(const double* C, int64_t n, int64_t ldc, const double* mu, do
  * leading dimension allow), mu and mu[idx] are staged in LDS per 2048 columns; a lane adds its columns in ascending order, the wave
  * reduces by butterfly.  No atomics: the same bits from run to run.  A NaN in row i of W_d or D^ reaches bias entry i alone (and
  * both norms); an entry of idx outside 0 .. n-1 reads no memory and contributes NaN.
- * ws: mdg_nystrom_intercept_ws_bytes(d) = 16 d bytes (delta and W_d mu per row), 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG
+ * ws: mdg_nystrom_intercept_ws_bytes(d) bytes (delta and W_d mu per row: intercept_layout in csrc/colsum.hip), 8-byte aligned.  Only enqueues.  MDG_ERR_BAD_ARG
  * for a null pointer, an unsupported dtype, d, n or r < 1, r > n, ld_wd < n, ld_down < r, or a workspace that is too small. */
 size_t mdg_nystrom_intercept_ws_bytes(int64_t d);
 int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64_t ld_wd, int w_dtype, const void* down_hat, int64_t r,
@@ -471,9 +471,9 @@ int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64_t ld_wd, i
  * MDG_BF16 or MDG_F64 as in mdg_nystrom_down; a NaN in W_d gives NaN in curve[0 .. p] (p: at least the NaN column's position in
  * `order`) and MDG_OK.  eps is added in fp64 with one rounding per diagonal entry, as mdg_nystrom_down adds it.  curve: [n + 1].
  * No atomics, every sum in a fixed order: bit-identical from run to run.
- * ws: mdg_nystrom_rank_curve_ws_bytes(n, d) = 8 n n' + 8 (2 d n') bytes, n' = n rounded up to 16 (the gathered matrix / its
- * factor, W_d[:, order] and Z in fp64) + the inverted diagonal blocks of the factorisation (mdg_potrf_inv_diag_elems(n) doubles:
- * 128 KB per 128 columns) + 20 n bytes: 2.6 GB at n = 14336, d = 4096 -- per call in flight.
+ * ws: mdg_nystrom_rank_curve_ws_bytes(n, d) bytes (rank_curve_layout in csrc/rank_curve.hip: the gathered matrix / its factor,
+ * W_d[:, order] and Z in fp64 with rows of n rounded up to 16, the inverted diagonal blocks of the factorisation, the column norms,
+ * the clamped order and its marks): 2.6 GB at n = 14336, d = 4096 -- per call in flight.
  * Status: follows the deferred-status convention.  Between mdg_deferred_status_begin / _end the call only enqueues and merges the
  * factorisation's pivot word into the device status; outside, it SYNCHRONISES once, behind the factorisation, to return
  * MDG_ERR_NOT_PD (curve is then not written), and enqueues the rest. */
@@ -506,7 +506,7 @@ int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, const int64_
  * atomics, every sum in a fixed order: bit-identical from run to run.
  * r == 0 writes objective[0 .. rounds] = J_0 and nothing else (order may then be NULL).  Non-finite input: order is still r
  * distinct indices in 0 .. n-1, objectives may be NaN, the status may be MDG_ERR_NOT_PD, nothing is written out of bounds.
- * ws: mdg_nystrom_greedy_ws_bytes(n, d, r, rounds) bytes, 16-byte aligned: about 8 n' (d + r + max(m, min(n, 2048))) for B, Yt and
+ * ws: mdg_nystrom_greedy_ws_bytes(n, d, r, rounds) bytes, 16-byte aligned (greedy_layout in csrc/greedy.hip): about 8 n' (d + r + max(m, min(n, 2048))) for B, Yt and
  * the panel, 8 m' (2.25 m + 2 d + r) for K, its inverse and the picked columns (m = ceil(r / T); n', m' rounded up to 16) and
  * 8 n' (38 + ceil(n / 1024) / 2) for the vectors and the pick's counts, and for T > 1 min(8 m n', 2^24) doubles for the K-split
  * partial panels: 2.0 GB at n = 14336, d = 4096, r = 10035, T = 32.  0 for arguments the call refuses.
@@ -538,8 +538,8 @@ int mdg_nystrom_greedy_select(const double* C, int64_t n, int64_t ldc, const voi
  * One 128-row block of U against the lower-triangle tiles of C on v_mfma_f64_16x16x4_f64, U formed while staging, the row dot
  * product folded into the epilogue: d n (n + 1) flop, the product U C is never written.  No atomics, every sum in a fixed order:
  * bit-identical from run to run.
- * ws: mdg_mlp_output_error_ws_bytes(n, d) = 4 n (the inverse index map, int32, padded to 16 bytes) + 16 d ceil(n / 128) bytes (the
- * per-tile-column partial sums of e and unorm2): 7.4 MB at n = 14336, d = 4096.
+ * ws: mdg_mlp_output_error_ws_bytes(n, d) bytes (out_err_layout in csrc/out_err.hip: the inverse index map, then from a 16-byte
+ * boundary the per-tile-column partial sums of e and unorm2): 7.4 MB at n = 14336, d = 4096.
  * Status: there is no factorisation -- the call only enqueues, never synchronises, and is the same inside and outside
  * mdg_deferred_status_begin / _end.  MDG_ERR_BAD_ARG for n <= 0, d <= 0, r < 0, r > n, ldc < n, ld_wd < n, an unsupported dtype,
  * a workspace that is too small, or r > 0 without down / idx. */
@@ -708,8 +708,8 @@ int mdg_vo_bias(void* ws, size_t ws_bytes, const void* Wo, int64_t ld_wo, int w_
  * norms: thread t adds rows t, t + 256, ... ascending, then a fixed tree.  One read of each operand, no atomics: the same bits from
  * run to run.  A NaN in row i of W_o or o_new reaches bias entry i alone (and the norms); a NaN in one kv head's W_v, v_new or b_v
  * reaches every bias entry (every row sums over all heads) and the norms.
- * ws: mdg_vo_intercept_ws_bytes(d, n_kv, hd, rank) = 8 (n_kv (hd + rank) + 2 d) bytes (a, a', delta and the constant per row), 8-byte
- * aligned, its own (not mdg_vo_compress's: the call also serves factors from elsewhere).  Only enqueues.  MDG_ERR_BAD_ARG for a null
+ * ws: mdg_vo_intercept_ws_bytes(d, n_kv, hd, rank) bytes (vo_intercept_layout in csrc/vo_mean.hip: a, a', delta and the constant
+ * per row), 8-byte aligned, its own (not mdg_vo_compress's: the call also serves factors from elsewhere).  Only enqueues.  MDG_ERR_BAD_ARG for a null
  * required pointer, an unsupported dtype or head layout, a rank outside the range, ld_wv or ld_v < d, ld_wo < n_heads hd,
  * ld_o < n_heads rank, a workspace that is too small, or rank > 0 without v_new / o_new. */
 size_t mdg_vo_intercept_ws_bytes(int64_t d, int n_kv, int hd, int rank);
@@ -746,8 +746,8 @@ int mdg_vo_intercept(const void* Wv, int64_t ld_wv, const void* Wo, int64_t ld_w
  * A NaN in row k of one head's W_o or o' gives NaN in e[h][k] (and dnorm2[h][k]) of that head alone; a NaN in one kv head's W_v or
  * v' reaches every channel of that group's heads and no other group; a NaN in cov_x reaches everything; MDG_OK in every case.
  * No atomics, every sum in a fixed order: bit-identical from run to run, and e is the same bits with and without dnorm2.
- * ws: mdg_vo_output_error_ws_bytes(d, n_heads, n_kv, hd, rank) = 8 (n_kv n d + 2 n_kv n^2 + 2 ceil(n / 128) n_heads d) bytes,
- * n = hd + rank: T, the two Grams, the tile-column partials.
+ * ws: mdg_vo_output_error_ws_bytes(d, n_heads, n_kv, hd, rank) bytes (vo_err_layout in csrc/vo_err.hip: with n = hd + rank, T
+ * [n_kv][n][d], the two Grams, the tile-column partials).
  * Status: there is no factorisation -- the call only enqueues, never synchronises, and is the same inside and outside
  * mdg_deferred_status_begin / _end.  MDG_ERR_BAD_ARG for a null pointer, an unsupported head layout or rank, a leading dimension
  * that is too small (ldc, ld_wv, ld_v < d; ld_wo < n_heads hd; ld_o < n_heads rank), an unsupported dtype, a workspace that is too
@@ -766,7 +766,7 @@ int mdg_vo_output_error(const double* cov_x, int64_t d, int64_t ldc, const void*
  * rank r, sum over the group's heads and channels of (e + rho dnorm2) of mdg_vo_output_error equals curve[g][r] in exact
  * arithmetic.  Grouped: it is the error of the REFERENCE'S choice of subspace (which ignores W_o), not the minimum over all
  * rank-r factorisations.  ||W_o,h v_i||^2 as the column norms of W_o,h V_g (fp64 GEMM): accurate to (hd + d) 2^-53 relative to
- * itself.  ws: mdg_vo_rank_curve_ws_bytes = 8 n_heads hd (d + ceil(d / 256)) bytes (grouped), 0 (MHA; ws may then be NULL).
+ * itself.  ws: mdg_vo_rank_curve_ws_bytes bytes (grouped; vo_curve_layout in csrc/vo_err.hip), 0 (MHA; ws may then be NULL).
  * A NaN eigenvalue stays a NaN.  Only enqueues.  MDG_ERR_BAD_ARG for a null pointer, an unsupported head layout or dtype,
  * ld_wo < n_heads hd, or a workspace that is too small. */
 size_t mdg_vo_rank_curve_ws_bytes(int64_t d, int n_heads, int n_kv, int hd);
@@ -801,7 +801,7 @@ size_t mdg_sqrt_psd_small_ws_bytes(int64_t n, int64_t batch);
  * "mdg_sqrt_psd_large: the input holds non-finite values (NaN or Inf)" (as mdg_sqrt_psd_small's), root, inv_root and evals_out
  * all NaN.  Block Jacobi then runs no sweep; the Newton-Schulz route reads the flag with its first residual, after one GEMM
  * and one shift pass, and does not go on to the eigen route.  MDG_ERR_BAD_ARG (nothing launched, outputs untouched) for a null M / root / ws, n <= 0, ld < n,
- * or ws_bytes < mdg_sqrt_psd_large_ws_bytes(n) -- query it: it holds the per-row partial sums too.
+ * or ws_bytes < mdg_sqrt_psd_large_ws_bytes(n) -- the larger of the two routes' layouts (newton_layout, jacobi_layout in csrc/eigh.hip).
  * Accuracy (tests/test_gpu_sqrt_large.py, against long double): both routes within max(4 e_ref, n 2^-52) of the truth in the
  * relative Frobenius norm, e_ref the larger fp64 CPU error of LAPACK's eigh formula and of the route's own algorithm.
  * That is what was measured.  The CONTRACT of the eigen route is what its stopping rule implies: it returns the function of a
@@ -886,7 +886,8 @@ int mdg_rope_rows(const void* x, int dtype, int64_t ld_x, int64_t B, int64_t T, 
  *      bf16 / f16 / f32 (widened to fp64 exactly on load): the layouts mdg_rope_rows writes.  Rows b*T .. b*T+T-1 are sequence b.
  *   pair, pair_raw  [n_heads, hd, hd] fp64 contiguous, ACCUMULATED INTO; pair_raw may be NULL.  For b = 0 .. B-1 in ascending
  *      order   pair[h] += G^q_{b,h} (.) (G^k_{b,kv} - m m^T / T),   pair_raw[h] += G^q_{b,h} (.) G^k_{b,kv};  nothing is normalised.
- *   ws  mdg_qk_pair_ws_bytes(B, n_heads, hd, pair_raw != NULL) = 8 B n_heads hd^2 (twice that with pair_raw) bytes, 8-byte aligned.
+ *   ws  mdg_qk_pair_ws_bytes(B, n_heads, hd, pair_raw != NULL) bytes, 8-byte aligned (seq_layout in csrc/qk_seq.hpp: one slot per
+ *       sequence and head, a second set with pair_raw).
  * hd <= 128: one workgroup per (sequence, query head) holds both 128x128 Grams in accumulator registers, on
  * v_mfma_f64_16x16x4_f64; a second kernel adds the per-sequence products onto pair, one addition per sequence in ascending b.
  * So one call over B sequences gives the bits of B single-sequence calls in that order, and every run gives the same bits: no
@@ -923,7 +924,8 @@ int mdg_qk_pair_accum(const void* q, int64_t ld_q, const void* k, int64_t ld_k, 
  *      row b*T its position 0.
  *   pair, pair_raw  [n_heads, hd, hd] fp64 contiguous, ACCUMULATED INTO; pair_raw may be NULL.  For b = 0 .. B-1 in ascending order
  *      pair[h] += (sequence b's sum over i of the first expression), pair_raw[h] += (the second); nothing is normalised.
- *   ws  mdg_qk_causal_ws_bytes(B, n_heads, hd, pair_raw != NULL) = 8 B n_heads hd^2 (twice that with pair_raw) bytes, 8-byte aligned.
+ *   ws  mdg_qk_causal_ws_bytes(B, n_heads, hd, pair_raw != NULL) bytes, 8-byte aligned (seq_layout in csrc/qk_seq.hpp: one slot per
+ *       sequence and head, a second set with pair_raw).
  * The expression evaluated, per sequence, for i = 0 .. T-1 in ascending order, per entry (a, b), in fp64 (fma: one rounding):
  *   m_i[a] = m_{i-1}[a] + k_i[a]           r = 1.0 / (double)n_i  (correctly rounded)
  *   K = fma(k_i[a], k_i[b], K)             w = (q_i[a] * q_i[b]) * r                      t = fma(-(m_i[a] * m_i[b]), r, K)

@@ -464,15 +464,44 @@ int tri_inverse_doubling(const double* L, int64_t n, int64_t ldl, const double* 
   return MDG_OK;
 }
 
+size_t tri_inverse_scratch_elems(int64_t n, int64_t s_limit) { return (size_t)n * s_limit / 4 + NB * NB; }
+
+// The workspace of chol_inverse_diag: X = inv(L), dense [n][n], and the doubling's scratch
+struct InvDiagWs {
+  double *X, *T;
+};
+static InvDiagWs inv_diag_layout(Carve& c, int64_t n) {
+  InvDiagWs w;
+  w.X = c.take<double>((size_t)n * n);
+  w.T = c.take<double>(tri_inverse_scratch_elems(n, n));
+  return w;
+}
+// The sensitivity pass's two vectors, laid over T once the doubling is done with it
+struct SensWs {
+  double *d, *u;   // sqrt(diag C), |X| d
+  size_t bytes;
+};
+static SensWs sens_layout(double* T, int64_t n) {
+  Carve c(T);
+  SensWs w;
+  w.d = c.take<double>((size_t)n);
+  w.u = c.take<double>((size_t)n);
+  w.bytes = c.off;
+  return w;
+}
+
 // X = inv(L), then column norms.  sens != nullptr: also the first-order sensitivities of out[j] to an entry-wise relative
 // perturbation of C (C, ldc: the matrix whose diagonal scales the perturbation; T, free again after the doubling, holds d and u).
-int chol_inverse_diag(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* out, double* X,
-                      double* T, hipStream_t st, const double* C = nullptr, int64_t ldc = 0, double* sens = nullptr) {
+int chol_inverse_diag(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* out, const InvDiagWs& w,
+                      hipStream_t st, const double* C = nullptr, int64_t ldc = 0, double* sens = nullptr) {
   const int64_t ldx = n;
+  double *X = w.X, *T = w.T;
+  const SensWs sw = sens_layout(T, n);
+  // (holds for every n: n^2 / 4 + 128^2 - 2 n = (n / 2 - 2)^2 + 16380)
+  MDG_CHECK_ARG(!sens || sw.bytes <= tri_inverse_scratch_elems(n, n) * sizeof(double), "chol_inverse_diag: the sensitivity vectors do not fit T");
   MDG_TRY(tri_inverse_doubling(L, n, ldl, inv_diag, X, ldx, T, n, st));
   if (sens) {
-    double* d = T;          // (T has n^2 / 4 + 128^2 elements >= 2 n)
-    double* u = T + n;
+    double *d = sw.d, *u = sw.u;
     hipLaunchKernelGGL(sqrt_diag_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, C, ldc, n, d);
     hipLaunchKernelGGL(lower_abs_rowsum_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, X, ldx, n, d, u);
     hipLaunchKernelGGL(lower_colnorm2_kernel<true>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, X, ldx, n, out, u, sens);
@@ -495,15 +524,17 @@ constexpr int NBS = MDG_CHOL_NBS;
 // inside every outer block -- 2 x n / 128 steps of a 128-row multiply (32 workgroups) and a thin update, ~85 us a step
 // whatever the flops: 24.5 ms for n = 10035, nrhs = 4096, of which the carries are 12.  Out of place between X and a
 // second right-hand-side buffer: forward X -> W, backward W -> X.
-size_t potrs_ws_elems(int64_t n, int64_t nrhs) {
-  return (size_t)n * NBS + (size_t)n + ((size_t)n * NBS / 4 + NB * NB) + (size_t)n * nrhs;
+PotrsWs potrs_layout(Carve& c, int64_t n, int64_t nrhs) {
+  PotrsWs w;
+  w.Linv = c.take<double>((size_t)n * NBS + (size_t)n);   // skewed [n][NBS]: inv of every NBS-wide diagonal block
+  w.T = c.take<double>(tri_inverse_scratch_elems(n, NBS));
+  w.W = c.take<double>((size_t)n * nrhs);                 // [n][nrhs]
+  return w;
 }
 
 int potrs_lower(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* X, int64_t nrhs, int64_t ldx,
-                double* ws, hipStream_t st) {
-  double* Linv = ws;                                   // skewed [n][NBS]: inv of every NBS-wide diagonal block
-  double* T = Linv + (size_t)n * NBS + n;
-  double* W = T + ((size_t)n * NBS / 4 + NB * NB);     // [n][nrhs]
+                const PotrsWs& ws, hipStream_t st) {
+  double *Linv = ws.Linv, *T = ws.T, *W = ws.W;
   MDG_TRY(tri_inverse_doubling(L, n, ldl, inv_diag, Linv, NBS, T, NBS, st));
   for (int64_t J0 = 0; J0 < n; J0 += NBS) {  // L Y = B:  W_J = inv(L_JJ) X_J;  X[Jend:] -= L[Jend:, J] W_J
     const int64_t Jend = J0 + NBS < n ? J0 + NBS : n, nbj = Jend - J0;
@@ -548,7 +579,9 @@ extern "C" int mdg_potrf_lower(double* A, int64_t n, int64_t lda, double* inv_di
 
 extern "C" size_t mdg_potrs_lower_ws_bytes(int64_t n, int64_t nrhs) {
   if (n <= 0 || nrhs <= 0) return 0;
-  return potrs_ws_elems(n, nrhs) * sizeof(double);
+  Carve c(nullptr);
+  potrs_layout(c, n, nrhs);
+  return c.off;
 }
 
 extern "C" int mdg_potrs_lower(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* X,
@@ -557,11 +590,14 @@ extern "C" int mdg_potrs_lower(const double* L, int64_t n, int64_t ldl, const do
   MDG_CHECK_ARG(L && inv_diag && X && n > 0 && nrhs > 0 && ldl >= n && ldx >= nrhs, "mdg_potrs_lower: bad arguments");
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_potrs_lower_ws_bytes(n, nrhs), "mdg_potrs_lower: workspace %zu < required %zu", ws_bytes,
                 mdg_potrs_lower_ws_bytes(n, nrhs));
-  return potrs_lower(L, n, ldl, inv_diag, X, nrhs, ldx, (double*)ws, (hipStream_t)stream);
+  Carve c(ws);
+  return potrs_lower(L, n, ldl, inv_diag, X, nrhs, ldx, potrs_layout(c, n, nrhs), (hipStream_t)stream);
 }
 
 extern "C" size_t mdg_chol_inverse_diag_ws_bytes(int64_t n) {
-  return ((size_t)n * n + (size_t)n * n / 4 + NB * NB) * sizeof(double);
+  Carve c(nullptr);
+  inv_diag_layout(c, n);
+  return c.off;
 }
 
 extern "C" int mdg_chol_inverse_diag(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* out,
@@ -569,15 +605,27 @@ extern "C" int mdg_chol_inverse_diag(const double* L, int64_t n, int64_t ldl, co
   MDG_CLEAR();
   MDG_CHECK_ARG(L && inv_diag && out && n > 0 && ldl >= n, "mdg_chol_inverse_diag: bad arguments");
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_chol_inverse_diag_ws_bytes(n), "mdg_chol_inverse_diag: workspace too small");
-  double* X = (double*)ws;
-  double* T = X + (size_t)n * n;
-  return chol_inverse_diag(L, n, ldl, inv_diag, out, X, T, (hipStream_t)stream);
+  Carve c(ws);
+  return chol_inverse_diag(L, n, ldl, inv_diag, out, inv_diag_layout(c, n), (hipStream_t)stream);
 }
 
-extern "C" size_t mdg_ridge_scores_ws_bytes(int64_t n) {
-  return (size_t)n * n * sizeof(double) + mdg_potrf_inv_diag_elems(n) * sizeof(double) +
-         mdg_chol_inverse_diag_ws_bytes(n);
+// C + ridge I and its factor [n][n] | the inverted diagonal blocks | the workspace of chol_inverse_diag
+struct RidgeWs {
+  double *L, *inv;
+  InvDiagWs id;
+  size_t bytes;
+};
+static RidgeWs ridge_layout(void* ws, int64_t n) {
+  Carve c(ws);
+  RidgeWs w;
+  w.L = c.take<double>((size_t)n * n);
+  w.inv = c.take<double>(mdg_potrf_inv_diag_elems(n));
+  w.id = inv_diag_layout(c, n);
+  w.bytes = c.off;
+  return w;
 }
+
+extern "C" size_t mdg_ridge_scores_ws_bytes(int64_t n) { return ridge_layout(nullptr, n).bytes; }
 
 extern "C" int mdg_ridge_scores(const double* C, int64_t n, int64_t ldc, double ridge, double* scores, double* sens, void* ws,
                                 size_t ws_bytes, void* stream) {
@@ -586,10 +634,8 @@ extern "C" int mdg_ridge_scores(const double* C, int64_t n, int64_t ldc, double 
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_ridge_scores_ws_bytes(n), "mdg_ridge_scores: workspace %zu < required %zu",
                 ws_bytes, mdg_ridge_scores_ws_bytes(n));
   hipStream_t st = (hipStream_t)stream;
-  double* Lb = (double*)ws;
-  double* inv = Lb + (size_t)n * n;
-  double* rest = inv + mdg_potrf_inv_diag_elems(n);
-  MDG_TRY(copy_lower(C, ldc, nullptr, Lb, n, n, ridge, st));
-  MDG_TRY(potrf_lower(Lb, n, n, inv, st));
-  return chol_inverse_diag(Lb, n, n, inv, scores, rest, rest + (size_t)n * n, st, C, ldc, sens);
+  const RidgeWs w = ridge_layout(ws, n);
+  MDG_TRY(copy_lower(C, ldc, nullptr, w.L, n, n, ridge, st));
+  MDG_TRY(potrf_lower(w.L, n, n, w.inv, st));
+  return chol_inverse_diag(w.L, n, n, w.inv, scores, w.id, st, C, ldc, sens);
 }

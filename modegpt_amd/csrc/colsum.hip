@@ -195,11 +195,36 @@ __global__ __launch_bounds__(256) void intercept_rows_kernel(const void* Wd, int
   }
 }
 
+struct ColSumWs {
+  double* part;   // [ceil(n_tokens / COL_SUM_CHUNK)][n]: the partial row of every chunk
+  size_t bytes;
+};
+static ColSumWs col_sum_layout(void* ws, int64_t n_tokens, int64_t n) {
+  Carve c(ws);
+  ColSumWs w;
+  w.part = c.take<double>((size_t)ceil_div(n_tokens, COL_SUM_CHUNK) * (size_t)n);
+  w.bytes = c.off;
+  return w;
+}
+
+struct InterceptWs {
+  double *delta_rows, *wmu_rows;   // [d] each
+  size_t bytes;
+};
+static InterceptWs intercept_layout(void* ws, int64_t d) {
+  Carve c(ws);
+  InterceptWs w;
+  w.delta_rows = c.take<double>((size_t)d);
+  w.wmu_rows = c.take<double>((size_t)d);
+  w.bytes = c.off;
+  return w;
+}
+
 }  // namespace mdg
 
 extern "C" size_t mdg_col_sum_ws_bytes(int64_t n_tokens, int64_t n) {
   if (n_tokens <= 0 || n <= 0) return 0;
-  return (size_t)ceil_div(n_tokens, COL_SUM_CHUNK) * (size_t)n * sizeof(double);
+  return col_sum_layout(nullptr, n_tokens, n).bytes;
 }
 
 extern "C" int mdg_col_sum_accum(const void* x, int dtype, int64_t n_tokens, int64_t n, int64_t ld, int relu, double* sum, void* ws,
@@ -215,11 +240,12 @@ extern "C" int mdg_col_sum_accum(const void* x, int dtype, int64_t n_tokens, int
   MDG_CHECK_ARG(ceil_div(n_tokens, COL_SUM_CHUNK) < (1ll << 31) && ceil_div(n, 256) < 65536, "mdg_col_sum_accum: grid too large");
   MDG_CLEAR();
   hipStream_t st = (hipStream_t)stream;
+  double* part = col_sum_layout(ws, n_tokens, n).part;
   switch (dtype) {
-    case MDG_BF16: return col_sum_launch<MDG_BF16>(x, n_tokens, n, ld, relu, sum, (double*)ws, st);
-    case MDG_F16: return col_sum_launch<MDG_F16>(x, n_tokens, n, ld, relu, sum, (double*)ws, st);
-    case MDG_F32: return col_sum_launch<MDG_F32>(x, n_tokens, n, ld, relu, sum, (double*)ws, st);
-    default: return col_sum_launch<MDG_F64>(x, n_tokens, n, ld, relu, sum, (double*)ws, st);
+    case MDG_BF16: return col_sum_launch<MDG_BF16>(x, n_tokens, n, ld, relu, sum, part, st);
+    case MDG_F16: return col_sum_launch<MDG_F16>(x, n_tokens, n, ld, relu, sum, part, st);
+    case MDG_F32: return col_sum_launch<MDG_F32>(x, n_tokens, n, ld, relu, sum, part, st);
+    default: return col_sum_launch<MDG_F64>(x, n_tokens, n, ld, relu, sum, part, st);
   }
 }
 
@@ -235,7 +261,7 @@ extern "C" int mdg_cov_center(const double* C, int64_t n, int64_t ldc, const dou
   return MDG_OK;
 }
 
-extern "C" size_t mdg_nystrom_intercept_ws_bytes(int64_t d) { return d > 0 ? 2 * (size_t)d * sizeof(double) : 0; }
+extern "C" size_t mdg_nystrom_intercept_ws_bytes(int64_t d) { return d > 0 ? intercept_layout(nullptr, d).bytes : 0; }
 
 extern "C" int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64_t ld_wd, int w_dtype, const void* down_hat, int64_t r,
                                      int64_t ld_down, const int64_t* idx, const double* mu, const void* b_d, int b_dtype,
@@ -252,7 +278,8 @@ extern "C" int mdg_nystrom_intercept(const void* Wd, int64_t d, int64_t n, int64
   MDG_CHECK_ARG(ceil_div(d, RD_ROWS) < (1ll << 31) && n < (1ll << 31), "mdg_nystrom_intercept: too many rows or columns");
   MDG_CLEAR();
   hipStream_t st = (hipStream_t)stream;
-  double *delta_rows = (double*)ws, *wmu_rows = delta_rows + d;
+  const InterceptWs w = intercept_layout(ws, d);
+  double *delta_rows = w.delta_rows, *wmu_rows = w.wmu_rows;
   const int vec_w = w_dtype == MDG_BF16 && (uintptr_t)Wd % 16 == 0 && ld_wd % 8 == 0;
   const int vec_d = (uintptr_t)down_hat % 16 == 0 && ld_down % 8 == 0;
   const dim3 grid((unsigned)ceil_div(d, RD_ROWS));

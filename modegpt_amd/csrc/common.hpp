@@ -148,6 +148,32 @@ static inline size_t dtype_size(int dt) {
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// ---------------------------------------------------------------- workspaces
+// A caller-allocated workspace is cut up by ONE function, x_layout(ws, dims...): a plain struct of typed pointers plus `bytes`,
+// filled by takes from a Carve in the order of the blocks.  With ws == nullptr every pointer is null and only the offsets count:
+// mdg_x_ws_bytes is x_layout(nullptr, dims...).bytes.  A layout that is part of another takes the Carve by reference.
+// (Host only.  `align` rounds the OFFSET up; the entries say what they ask of the address of ws itself.)
+struct Carve {
+  char* base;
+  size_t off;
+  explicit Carve(void* ws) : base((char*)ws), off(0) {}
+  template <class T>
+  T* take(size_t count, size_t align = alignof(T)) {
+    off = align_up(off, align);
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += count * sizeof(T);
+    return p;
+  }
+};
+
+// chol.hip's scratch, as mlp.hip and greedy.hip embed it.  T of tri_inverse_doubling(.., s_limit): the batched products of one
+// level -- n / 2s pairs of s x s blocks, s < s_limit: at most n s_limit / 4 elements -- and one 128 x 128 block of margin.
+size_t tri_inverse_scratch_elems(int64_t n, int64_t s_limit);
+struct PotrsWs {
+  double *Linv, *T, *W;   // inverses of the diagonal blocks (skewed), the doubling's scratch, the second right-hand-side buffer
+};
+PotrsWs potrs_layout(Carve& c, int64_t n, int64_t nrhs);
+
 // ---------------------------------------------------------------- fp64 MFMA tile core
 // One workgroup = 256 threads = 4 waves arranged 2x2; workgroup tile 128x128, wave tile 64x64 built from
 // 4x4 v_mfma_f64_16x16x4_f64 sub-tiles.  Operand panels live in LDS as fp64, [k][128 + PAD] (k-major).

@@ -415,23 +415,73 @@ int sqrt_large_nonfinite(int64_t n, double* root, double* inv_root, double* eval
 }
 
 constexpr int NS_MAX_STEPS = 64;
-constexpr int NS_RED = 80;  // doubles: [0] ||A||_F^2, [1 + k] residual^2 of step k, [72] the non-finite flag (an int)
+constexpr int NS_RED = 80;  // doubles, cleared as one: red [72] and the 8 that hold the non-finite flag
+
+// The two routes of mdg_sqrt_psd_large lay one buffer out each; its size is the larger of the two.
+struct NewtonWs {
+  double *Y, *Z, *T, *Y2, *Z2;   // [n][n] each
+  double* red;                   // [0] ||A||_F^2, [1 + k] residual^2 of step k
+  int* bad;                      // the non-finite flag
+  double* part;                  // [n] per-row partial sums, added in a fixed order by sum_rows_kernel
+  size_t bytes;
+};
+NewtonWs newton_layout(void* ws, int64_t n) {
+  const size_t nn = (size_t)n * n;
+  Carve c(ws);
+  NewtonWs w;
+  w.Y = c.take<double>(nn);
+  w.Z = c.take<double>(nn);
+  w.T = c.take<double>(nn);
+  w.Y2 = c.take<double>(nn);
+  w.Z2 = c.take<double>(nn);
+  w.red = c.take<double>(NS_RED - 8);
+  static_assert(NS_RED - 8 >= 1 + NS_MAX_STEPS, "red holds one residual per step");
+  w.bad = c.take<int>(16);   // (one used: the last 8 of the NS_RED doubles)
+  w.part = c.take<double>((size_t)n);
+  w.bytes = c.off;
+  return w;
+}
+
+struct JacobiWs {
+  double *A, *A2, *V, *V2;   // [np][np] each, np = n rounded up to 128
+  double *D, *J;             // [np / 128][128][128]: the diagonal blocks and their inner eigenvectors
+  double* ev;                // [np]
+  double* part;              // [2][np] per-row off^2 / total^2, added in a fixed order by sum_rows_kernel
+  double* red;               // [0] off^2, [1] total^2
+  int *dflag, *bad;          // the inner solves' flag; a NaN or Inf in the lower triangle of M
+  int* perm;                 // [np / 64] round-robin source block of every destination block
+  size_t bytes;
+};
+JacobiWs jacobi_layout(void* ws, int64_t n) {
+  const size_t np = (size_t)ceil_div(n, 128) * 128, m = np / 128, nb = 2 * m;
+  Carve c(ws);
+  JacobiWs w;
+  w.A = c.take<double>(np * np);
+  w.A2 = c.take<double>(np * np);
+  w.V = c.take<double>(np * np);
+  w.V2 = c.take<double>(np * np);
+  w.D = c.take<double>(m * 128 * 128);
+  w.J = c.take<double>(m * 128 * 128);
+  w.ev = c.take<double>(np);
+  w.part = c.take<double>(2 * np);
+  w.red = c.take<double>(8);
+  w.dflag = c.take<int>(1);
+  w.bad = c.take<int>(1);
+  c.take<int>(14);                           // (the rest of the flags' 64 bytes)
+  w.perm = c.take<int>(2 * nb);              // (nb used: the size has always counted them twice)
+  c.take<char>(48 * sizeof(double) + 256);   // unused: the rest of the 64 doubles and the 256 bytes the size has always ended with
+  w.bytes = c.off;
+  return w;
+}
 
 // returns MDG_OK with *ok = 1 when the iteration reached round-off, *ok = 0 when it did not (caller falls back);
 // *nonfinite = 1 (and *ok = 0) when the load pass met a NaN or Inf: read with the first step's residual, no round trip of its own
-int sqrt_psd_newton(const double* M, int64_t n, int64_t ld, double ridge, double* root, double* inv_root, double* ws,
+int sqrt_psd_newton(const double* M, int64_t n, int64_t ld, double ridge, double* root, double* inv_root, const NewtonWs& w,
                     hipStream_t st, int* ok, int* nonfinite) {
   *ok = 0;
   *nonfinite = 0;
-  const int64_t nn = n * n;
-  double* Y = ws;
-  double* Z = Y + nn;
-  double* T = Z + nn;
-  double* Y2 = T + nn;
-  double* Z2 = Y2 + nn;
-  double* red = Z2 + nn;
-  int* bad = (int*)(red + 72);
-  double* part = red + NS_RED;  // [n] per-row partial sums, added in a fixed order by sum_rows_kernel
+  double *Y = w.Y, *Z = w.Z, *T = w.T, *Y2 = w.Y2, *Z2 = w.Z2, *red = w.red, *part = w.part;
+  int* bad = w.bad;
   MDG_HIP(hipMemsetAsync(red, 0, NS_RED * sizeof(double), st));
   hipLaunchKernelGGL(ns_load_kernel, dim3((unsigned)n), dim3(256), 0, st, M, n, ld, ridge, Y, part, bad);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, part, n, red);
@@ -474,10 +524,7 @@ int sqrt_psd_newton(const double* M, int64_t n, int64_t ld, double ridge, double
 using namespace mdg;
 
 extern "C" size_t mdg_sqrt_psd_large_ws_bytes(int64_t n) {
-  const size_t np = (size_t)ceil_div(n, 128) * 128;
-  // (+ 2 np / + n doubles: the per-row partial sums of the off-norm / of ||A||_F^2 and the Newton-Schulz residual)
-  const size_t jacobi = (4 * np * np + 2 * (np / 128) * 128 * 128 + 3 * np + 64) * sizeof(double) + 2 * (np / 64) * sizeof(int) + 256;
-  const size_t newton = (5 * (size_t)n * n + NS_RED + (size_t)n) * sizeof(double);
+  const size_t jacobi = jacobi_layout(nullptr, n).bytes, newton = newton_layout(nullptr, n).bytes;
   return jacobi > newton ? jacobi : newton;
 }
 
@@ -489,23 +536,14 @@ extern "C" int mdg_sqrt_psd_large(const double* M, int64_t n, int64_t ld, double
   hipStream_t st = (hipStream_t)stream;
   if (!scaled && !evals_out && ridge >= 1e-12 && !MDG_KNOB("MDG_SQRT_JACOBI")) {
     int ok = 0, nonfinite = 0;
-    MDG_TRY(sqrt_psd_newton(M, n, ld, ridge, root, inv_root, (double*)ws, st, &ok, &nonfinite));
+    MDG_TRY(sqrt_psd_newton(M, n, ld, ridge, root, inv_root, newton_layout(ws, n), st, &ok, &nonfinite));
     if (nonfinite) return sqrt_large_nonfinite(n, root, inv_root, evals_out, st);
     if (ok) return MDG_OK;  // otherwise: the eigen route below, which implements the reference's clamps
   }
   const int64_t np = ceil_div(n, 128) * 128, m = np / 128, nb = 2 * m;
-  double* A = (double*)ws;
-  double* A2 = A + np * np;
-  double* V = A2 + np * np;
-  double* V2 = V + np * np;
-  double* D = V2 + np * np;
-  double* J = D + m * 128 * 128;
-  double* ev = J + m * 128 * 128;
-  double* part = ev + np;         // [2][np] per-row off^2 / total^2, added in a fixed order by sum_rows_kernel
-  double* red = part + 2 * np;    // [0] off^2, [1] total^2
-  int* dflag = (int*)(red + 8);
-  int* bad = dflag + 1;           // a NaN or Inf in the lower triangle of M
-  int* perm = (int*)(red + 16);   // round-robin source block of every destination block
+  const JacobiWs w = jacobi_layout(ws, n);
+  double *A = w.A, *A2 = w.A2, *V = w.V, *V2 = w.V2, *D = w.D, *J = w.J, *ev = w.ev, *part = w.part, *red = w.red;
+  int *dflag = w.dflag, *bad = w.bad, *perm = w.perm;
   // round-robin rotation of the 64-blocks: pairs are (2i, 2i+1); block 0 stays, the others move one seat
   {
     int host_perm[2 * 1024];
@@ -612,9 +650,24 @@ extern "C" int mdg_syevj_batched(double* A, int64_t n, int64_t batch, double* ev
   return rc;
 }
 
-extern "C" size_t mdg_sqrt_psd_small_ws_bytes(int64_t n, int64_t batch) {
-  return (size_t)batch * (2 * n * n + n) * sizeof(double) + 64;
+struct SqrtSmallWs {
+  double *Acopy, *evecs;   // [batch][n][n] each
+  double* evals;           // [batch][n]
+  int* dflag;              // the Jacobi flag
+  size_t bytes;
+};
+static SqrtSmallWs sqrt_small_layout(void* ws, int64_t n, int64_t batch) {
+  Carve c(ws);
+  SqrtSmallWs w;
+  w.Acopy = c.take<double>((size_t)batch * n * n);
+  w.evecs = c.take<double>((size_t)batch * n * n);
+  w.evals = c.take<double>((size_t)batch * n);
+  w.dflag = c.take<int>(16);   // (one used, 64 bytes reserved)
+  w.bytes = c.off;
+  return w;
 }
+
+extern "C" size_t mdg_sqrt_psd_small_ws_bytes(int64_t n, int64_t batch) { return sqrt_small_layout(nullptr, n, batch).bytes; }
 
 extern "C" int mdg_sqrt_psd_small(const double* M, int64_t n, int64_t batch, double ridge, int scaled, double* root,
                                   double* inv_root, double* evals_out, void* ws, size_t ws_bytes, void* stream) {
@@ -622,10 +675,9 @@ extern "C" int mdg_sqrt_psd_small(const double* M, int64_t n, int64_t batch, dou
   MDG_CHECK_ARG(M && root && n > 0 && batch > 0, "mdg_sqrt_psd_small: bad arguments");
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_sqrt_psd_small_ws_bytes(n, batch), "mdg_sqrt_psd_small: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  double* Acopy = (double*)ws;
-  double* evecs = Acopy + batch * n * n;
-  double* evals = evecs + batch * n * n;
-  int* dflag = (int*)(evals + batch * n);
+  const SqrtSmallWs w = sqrt_small_layout(ws, n, batch);
+  double *Acopy = w.Acopy, *evecs = w.evecs, *evals = w.evals;
+  int* dflag = w.dflag;
   MDG_HIP(hipMemcpyAsync(Acopy, M, (size_t)batch * n * n * sizeof(double), hipMemcpyDeviceToDevice, st));
   MDG_TRY(syevj_batched(Acopy, n, batch, evals, evecs, dflag, st));
   hipLaunchKernelGGL(sqrt_rebuild_kernel, dim3((unsigned)batch), dim3(256), 0, st, evals, evecs, (int)n, ridge, scaled,

@@ -266,40 +266,47 @@ __global__ __launch_bounds__(256) void greedy_fill_kernel(double* p, int64_t cou
 
 static int64_t gr_pitch(int64_t n) { return (n + 15) / 16 * 16; }
 
-// the workspace, in doubles from its start (every block starts on a 16-byte boundary)
+// the workspace (every block starts on a 16-byte boundary)
 struct GreedyWs {
   int64_t np, mp, dp, m_max, pm, rounds;
-  size_t B, Yt, Pt, K, inv, Linv, T, YP, parts, BP, Gt, dM, dR, gain, key, cbw, sq, bw, taken, elig, part, ndead, total;
-  GreedyWs(int64_t n, int64_t d, int64_t r, int64_t rounds_in) {
-    rounds = r < rounds_in ? r : rounds_in;                       // (T > r counts as r)
-    m_max = rounds > 0 ? ceil_div(r, rounds) : 0;
-    np = gr_pitch(n); mp = gr_pitch(m_max > 0 ? m_max : 1); dp = gr_pitch(d);
-    const int64_t chunk = n < GR_CHUNK ? n : GR_CHUNK;
-    pm = m_max > chunk ? m_max : chunk;
-    size_t o = 0;
-    auto take = [&](size_t elems) { size_t at = o; o += (elems + 1) / 2 * 2; return at; };
-    B = take((size_t)d * np);
-    Yt = take((size_t)r * np);
-    Pt = take((size_t)pm * np);
-    K = take((size_t)m_max * mp);
-    inv = take(m_max > 0 ? mdg_potrf_inv_diag_elems(m_max) : 0);
-    Linv = take((size_t)m_max * mp + mp);
-    T = take((size_t)m_max * m_max / 4 + 128 * 128);
-    YP = take(rounds > 1 ? (size_t)(r - m_max) * mp : 0);         // (the last round's picks meet at most r - m_last rows of Yt)
-    {   // the K-split partial panels: splits x m x np <= GR_SPLIT_TILES tiles of 128 x 128 by the rule that picks the split count
-      const size_t cap = (size_t)GR_SPLIT_TILES * 128 * 128, all = (size_t)GR_SPLIT_MAX * m_max * np;
-      parts = take(rounds > 1 ? (all < cap ? all : cap) : 0);
-    }
-    BP = take((size_t)d * mp);
-    Gt = take((size_t)m_max * dp);
-    dM = take(np); dR = take(np); gain = take(np); key = take(np); cbw = take(np);
-    sq = take((size_t)GR_RS * np); bw = take((size_t)GR_RS * np);
-    taken = take(np / 2); elig = take(np / 2);                    // (ints)
-    part = take((size_t)ceil_div(n, PK_SLAB) * (np / 2));            // (ints: the pick's slab counts)
-    ndead = take(2);
-    total = o;
-  }
+  double *B, *Yt, *Pt, *K, *inv, *Linv, *T, *YP, *parts, *BP, *Gt, *dM, *dR, *gain, *key, *cbw, *sq, *bw;
+  int *taken, *elig, *part;
+  int64_t* ndead;
+  size_t bytes;
 };
+static GreedyWs greedy_layout(void* ws, int64_t n, int64_t d, int64_t r, int64_t rounds_in) {
+  GreedyWs w;
+  w.rounds = r < rounds_in ? r : rounds_in;                       // (T > r counts as r)
+  w.m_max = w.rounds > 0 ? ceil_div(r, w.rounds) : 0;
+  w.np = gr_pitch(n); w.mp = gr_pitch(w.m_max > 0 ? w.m_max : 1); w.dp = gr_pitch(d);
+  const int64_t chunk = n < GR_CHUNK ? n : GR_CHUNK;
+  w.pm = w.m_max > chunk ? w.m_max : chunk;
+  const int64_t np = w.np, mp = w.mp, dp = w.dp, m_max = w.m_max, rounds = w.rounds;
+  Carve c(ws);
+  auto take = [&](size_t elems) { return c.take<double>(elems, 16); };
+  auto take_int = [&](size_t elems) { return c.take<int>(elems, 16); };
+  w.B = take((size_t)d * np);
+  w.Yt = take((size_t)r * np);
+  w.Pt = take((size_t)w.pm * np);
+  w.K = take((size_t)m_max * mp);
+  w.inv = take(m_max > 0 ? mdg_potrf_inv_diag_elems(m_max) : 0);
+  w.Linv = take((size_t)m_max * mp + mp);
+  w.T = take(tri_inverse_scratch_elems(m_max, m_max));
+  w.YP = take(rounds > 1 ? (size_t)(r - m_max) * mp : 0);       // (the last round's picks meet at most r - m_last rows of Yt)
+  {   // the K-split partial panels: splits x m x np <= GR_SPLIT_TILES tiles of 128 x 128 by the rule that picks the split count
+    const size_t cap = (size_t)GR_SPLIT_TILES * 128 * 128, all = (size_t)GR_SPLIT_MAX * m_max * np;
+    w.parts = take(rounds > 1 ? (all < cap ? all : cap) : 0);
+  }
+  w.BP = take((size_t)d * mp);
+  w.Gt = take((size_t)m_max * dp);
+  w.dM = take(np); w.dR = take(np); w.gain = take(np); w.key = take(np); w.cbw = take(np);
+  w.sq = take((size_t)GR_RS * np); w.bw = take((size_t)GR_RS * np);
+  w.taken = take_int(np); w.elig = take_int(np);
+  w.part = take_int((size_t)ceil_div(n, PK_SLAB) * np);         // (the pick's slab counts)
+  w.ndead = c.take<int64_t>(2, 16);                             // (one used)
+  w.bytes = c.off;
+  return w;
+}
 
 }  // namespace mdg
 
@@ -307,7 +314,7 @@ using namespace mdg;
 
 extern "C" size_t mdg_nystrom_greedy_ws_bytes(int64_t n, int64_t d, int64_t r, int64_t rounds) {
   if (n <= 0 || d <= 0 || r < 0 || r > n || rounds < 1) return 0;
-  return GreedyWs(n, d, r, rounds).total * sizeof(double);
+  return greedy_layout(nullptr, n, d, r, rounds).bytes;
 }
 
 extern "C" int mdg_nystrom_greedy_select(const double* C, int64_t n, int64_t ldc, const void* Wd, int64_t d, int64_t ld_wd, int w_dtype,
@@ -325,13 +332,11 @@ extern "C" int mdg_nystrom_greedy_select(const double* C, int64_t n, int64_t ldc
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_nystrom_greedy_ws_bytes(n, d, r, rounds), "mdg_nystrom_greedy_select: workspace %zu < required %zu",
                 ws_bytes, mdg_nystrom_greedy_ws_bytes(n, d, r, rounds));
   hipStream_t st = (hipStream_t)stream;
-  const GreedyWs L(n, d, r, rounds);
-  double* w = (double*)ws;
-  double *B = w + L.B, *Yt = w + L.Yt, *Pt = w + L.Pt, *Km = w + L.K, *inv = w + L.inv, *Linv = w + L.Linv, *Tt = w + L.T, *YP = w + L.YP, *parts = w + L.parts,
-         *BP = w + L.BP, *Gt = w + L.Gt, *dM = w + L.dM, *dR = w + L.dR, *gain = w + L.gain, *key = w + L.key, *cbw = w + L.cbw,
-         *sq = w + L.sq, *bw = w + L.bw;
-  int *taken = (int*)(w + L.taken), *elig = (int*)(w + L.elig), *part = (int*)(w + L.part);
-  int64_t* ndead = (int64_t*)(w + L.ndead);
+  const GreedyWs L = greedy_layout(ws, n, d, r, rounds);
+  double *B = L.B, *Yt = L.Yt, *Pt = L.Pt, *Km = L.K, *inv = L.inv, *Linv = L.Linv, *Tt = L.T, *YP = L.YP, *parts = L.parts, *BP = L.BP,
+         *Gt = L.Gt, *dM = L.dM, *dR = L.dR, *gain = L.gain, *key = L.key, *cbw = L.cbw, *sq = L.sq, *bw = L.bw;
+  int *taken = L.taken, *elig = L.elig, *part = L.part;
+  int64_t* ndead = L.ndead;
   const int64_t np = L.np, mp = L.mp, dp = L.dp, T = L.rounds;
   const unsigned gn = (unsigned)ceil_div(n, 256);
   const int64_t slab_rows = ceil_div(ceil_div(d, GR_RS), 4) * 4;         // (whole groups of the four waves' rows)

@@ -14,8 +14,7 @@ int gemm_f64(int64_t M, int64_t N, int64_t K, double alpha, const void* A, int a
              hipStream_t st);
 int potrf_lower(double* A, int64_t n, int64_t lda, double* inv_diag, hipStream_t st);
 int potrs_lower(const double* L, int64_t n, int64_t ldl, const double* inv_diag, double* X, int64_t nrhs, int64_t ldx,
-                double* ws, hipStream_t st);
-size_t potrs_ws_elems(int64_t n, int64_t nrhs);
+                const PotrsWs& ws, hipStream_t st);
 int copy_lower(const double* src, int64_t ld_src, const int64_t* idx, double* dst, int64_t ldd, int64_t n,
                double ridge, hipStream_t st);
 }  // namespace mdg
@@ -29,16 +28,38 @@ static int64_t ckk_pitch(int64_t r) { return (r + 15) / 16 * 16; }
 // The compacted operands' row pitch: n - r rounded up to a whole number of GEMM stages (BK = 16 elements: also a multiple of the
 // 16-byte staging unit of either dtype), so that every tile of the product takes the vector staging path.
 static int64_t comp_pitch(int64_t n, int64_t r) { return (n - r + BK - 1) / BK * BK; }
-// [C_kk | inverted diagonal blocks | X | substitution workspace] as doubles, then, each from a 16-byte boundary:
-// C[k,k'] fp64 [r][Kp] | W_d[:,k'] [d][Kp] (sized for fp64) | k' int64 [n - r] | marks int32 [n].
-static size_t solve_part_bytes(int64_t r, int64_t d) {
-  return ((size_t)r * ckk_pitch(r) + mdg_potrf_inv_diag_elems(r) + (size_t)r * d + potrs_ws_elems(r, d)) * sizeof(double);
-}
-extern "C" size_t mdg_nystrom_down_ws_bytes(int64_t n, int64_t r, int64_t d) {
+// The solve part, doubles: C_kk [r][ckk_pitch] | inverted diagonal blocks | X [r][d] | the substitution's workspace.  Then the
+// tail, each block from a 16-byte boundary: C[k,k'] fp64 [r][Kp] | W_d[:,k'] [d][Kp] (sized for fp64) | k' int64 [n - r] | marks
+// int32 [n].  The tail starts on a 16-byte ADDRESS (the vector staging path of the product reads it), while ws itself need only
+// hold doubles: NYS_ALIGN_SLACK bytes are reserved for what moving the tail up to that address can cost.  For a 16-byte aligned
+// ws the tail sits at the solve part's size rounded up to 16 and the slack lies unused behind the marks.
+constexpr size_t NYS_ALIGN_SLACK = 16;
+struct NystromWs {
+  double *Ckk, *inv, *X;
+  PotrsWs solve;
+  double* Cbar;
+  void* Wbar;
+  int64_t* comp;
+  int* marks;
+  size_t bytes;
+};
+static NystromWs nystrom_layout(void* ws, int64_t n, int64_t r, int64_t d) {
   const size_t Kp = (size_t)comp_pitch(n, r);
-  return align_up(solve_part_bytes(r, d), 16) + 16 + align_up((size_t)r * Kp * 8, 16) + align_up((size_t)d * Kp * 8, 16) +
-         align_up((size_t)(n - r) * 8, 16) + align_up((size_t)n * 4, 16);
+  NystromWs w;
+  Carve c(ws);
+  w.Ckk = c.take<double>((size_t)r * ckk_pitch(r));
+  w.inv = c.take<double>(mdg_potrf_inv_diag_elems(r));
+  w.X = c.take<double>((size_t)r * d);
+  w.solve = potrs_layout(c, r, d);
+  Carve t(ws ? (void*)align_up((size_t)((uintptr_t)ws + c.off), 16) : nullptr);
+  w.Cbar = t.take<double>((size_t)r * Kp);
+  w.Wbar = t.take<double>((size_t)d * Kp, 16);
+  w.comp = t.take<int64_t>((size_t)(n - r), 16);
+  w.marks = t.take<int>((size_t)n, 16);
+  w.bytes = align_up(c.off, 16) + NYS_ALIGN_SLACK + align_up(t.off, 16);
+  return w;
 }
+extern "C" size_t mdg_nystrom_down_ws_bytes(int64_t n, int64_t r, int64_t d) { return nystrom_layout(nullptr, n, r, d).bytes; }
 
 namespace mdg {
 
@@ -162,17 +183,13 @@ static int nystrom_down(const double* C, int64_t n, int64_t ldc, const int64_t* 
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_nystrom_down_ws_bytes(n, r, d), "mdg_nystrom_down: workspace %zu < required %zu",
                 ws_bytes, mdg_nystrom_down_ws_bytes(n, r, d));
   hipStream_t st = (hipStream_t)stream;
-  double* Ckk = (double*)ws;
+  const NystromWs w = nystrom_layout(ws, n, r, d);
+  double *Ckk = w.Ckk, *inv = w.inv, *X = w.X, *Cbar = w.Cbar;
+  void* Wbar = w.Wbar;
+  int64_t* comp = w.comp;
+  int* marks = w.marks;
   const int64_t ldk = ckk_pitch(r);
-  double* inv = Ckk + (size_t)r * ldk;
-  double* X = inv + mdg_potrf_inv_diag_elems(r);
-  double* solve_ws = X + (size_t)r * d;
   const int64_t K = n - r, Kp = comp_pitch(n, r);
-  char* tail = (char*)align_up((size_t)((uintptr_t)ws + solve_part_bytes(r, d)), 16);
-  double* Cbar = (double*)tail;
-  void* Wbar = tail + align_up((size_t)r * Kp * 8, 16);
-  int64_t* comp = (int64_t*)((char*)Wbar + align_up((size_t)d * Kp * 8, 16));
-  int* marks = (int*)((char*)comp + align_up((size_t)K * 8, 16));
   const bool w_bf16 = w_dtype == MDG_BF16;
   dim3 tiles((unsigned)ceil_div(d, 32), (unsigned)ceil_div(r, 32));
   MDG_CHECK_ARG(tiles.y < 65536 && d < (1ll << 31), "mdg_nystrom_down: too many rows");
@@ -208,7 +225,7 @@ static int nystrom_down(const double* C, int64_t n, int64_t ldc, const int64_t* 
   const int rc_potrf = potrf_lower(Ckk, r, ldk, inv, st);         // compress_mlp.py:56
   if (side_stream) MDG_HIP(hipStreamWaitEvent(st, (hipEvent_t)ev_join, 0));   // (also on failure: the workspace is the caller's to free)
   if (rc_potrf != MDG_OK) return rc_potrf;
-  MDG_TRY(potrs_lower(Ckk, r, ldk, inv, X, d, d, solve_ws, st));  // compress_mlp.py:57
+  MDG_TRY(potrs_lower(Ckk, r, ldk, inv, X, d, d, w.solve, st));  // compress_mlp.py:57
   // W_d[:,k]^T + X: [r, d] fp64 -> down_f64, and [d, r] bf16       compress_mlp.py:61,97
   if (w_bf16)
     hipLaunchKernelGGL(add_cast_transpose_kernel<MDG_BF16>, tiles, dim3(256), 0, st, X, idx, r, n, Wd, d, ld_wd, (bf16_t*)down_out, ld_out, down_f64);

@@ -83,7 +83,23 @@ __global__ __launch_bounds__(256, 2) void out_err_kernel(OutErrArgs g) {
   }
 }
 
-static size_t oe_pos_bytes(int64_t n) { return align_up((size_t)n * sizeof(int), 16); }
+// pos [n] (int32, padded to 16 bytes); the partials of e and of unorm2, [ceil(n / 128)][d] doubles each, part_u right behind
+// part_e: the two plane sets of quad_reduce_kernel
+struct OutErrWs {
+  int* pos;
+  double *part_e, *part_u;
+  size_t bytes;
+};
+static OutErrWs out_err_layout(void* ws, int64_t n, int64_t d) {
+  const size_t plane = (size_t)ceil_div(n, TILE) * (size_t)d;
+  Carve c(ws);
+  OutErrWs w;
+  w.pos = c.take<int>((size_t)n);
+  w.part_e = c.take<double>(plane, 16);
+  w.part_u = c.take<double>(plane);
+  w.bytes = c.off;
+  return w;
+}
 
 }  // namespace mdg
 
@@ -91,8 +107,7 @@ using namespace mdg;
 
 extern "C" size_t mdg_mlp_output_error_ws_bytes(int64_t n, int64_t d) {
   if (n <= 0 || d <= 0) return 0;
-  // pos [n] (int32, padded to 16 bytes); the partials of e and of unorm2, [ceil(n / 128)][d] doubles each
-  return oe_pos_bytes(n) + 2 * (size_t)ceil_div(n, TILE) * (size_t)d * sizeof(double);
+  return out_err_layout(nullptr, n, d).bytes;
 }
 
 extern "C" int mdg_mlp_output_error(const double* C, int64_t n, int64_t ldc, const void* Wd, int64_t d, int64_t ld_wd, int w_dtype,
@@ -114,9 +129,9 @@ extern "C" int mdg_mlp_output_error(const double* C, int64_t n, int64_t ldc, con
   const int64_t tiles_n = ceil_div(n, TILE), tiles_d = ceil_div(d, TILE);
   MDG_CHECK_ARG(tiles_n * tiles_d < (1ll << 31), "mdg_mlp_output_error: grid too large");
   hipStream_t st = (hipStream_t)stream;
-  int* pos = (int*)ws;
-  double* part_e = (double*)((char*)ws + oe_pos_bytes(n));
-  double* part_u = part_e + (size_t)tiles_n * (size_t)d;
+  const OutErrWs w = out_err_layout(ws, n, d);
+  int* pos = w.pos;
+  double *part_e = w.part_e, *part_u = w.part_u;
   if (sub) {
     hipLaunchKernelGGL(oe_pos_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, idx, r, n, pos);
     MDG_LAUNCH_CHECK();

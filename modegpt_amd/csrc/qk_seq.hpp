@@ -80,9 +80,22 @@ static __global__ __launch_bounds__(256) void qk_seq_fold_kernel(const double* p
   }
 }
 
+struct SeqWs {
+  double *part, *part_raw;   // [B][n_heads][hd][hd] each: the slots of SeqArgs; part_raw only where the raw statistic is wanted
+  size_t bytes;
+};
+static inline SeqWs seq_layout(void* ws, int64_t B, int n_heads, int hd, int want_raw) {
+  const size_t slots = (size_t)B * (size_t)n_heads * (size_t)hd * (size_t)hd;
+  Carve c(ws);
+  SeqWs w;
+  w.part = c.take<double>(slots);
+  w.part_raw = want_raw ? c.take<double>(slots) : nullptr;
+  w.bytes = c.off;
+  return w;
+}
 static inline size_t seq_ws_bytes(int64_t B, int n_heads, int hd, int want_raw) {
   if (B <= 0 || n_heads <= 0 || hd <= 0) return 0;
-  return (size_t)B * (size_t)n_heads * (size_t)hd * (size_t)hd * sizeof(double) * (want_raw ? 2 : 1);
+  return seq_layout(nullptr, B, n_heads, hd, want_raw).bytes;
 }
 
 // The host half of the entry point `name` (its messages carry it): checks, arguments, then launch(dtype, args, grid, stream) --
@@ -116,8 +129,9 @@ static int seq_accum(const char* name, const void* q, int64_t ld_q, const void* 
   // 16-byte loads: the base, every row and every head start must be 16-byte aligned
   a.vec_q = (uintptr_t)q % 16 == 0 && (ld_q * es) % 16 == 0 && (hd * es) % 16 == 0;
   a.vec_k = (uintptr_t)k % 16 == 0 && (ld_k * es) % 16 == 0 && (hd * es) % 16 == 0;
-  a.part = (double*)ws;
-  a.part_raw = pair_raw ? (double*)ws + B * n : nullptr;
+  const SeqWs w = seq_layout(ws, B, n_heads, hd, pair_raw != nullptr);
+  a.part = w.part;
+  a.part_raw = w.part_raw;
   hipStream_t st = (hipStream_t)stream;
   launch(dtype, a, dim3((unsigned)(B * n_heads)), st);
   MDG_LAUNCH_CHECK();

@@ -145,16 +145,35 @@ __global__ __launch_bounds__(SCAN_T) void suffix_sum_kernel(const double* c, int
 
 static int64_t rc_pitch(int64_t n) { return (n + 15) / 16 * 16; }   // rows of L, W_pi and Z on 16-byte boundaries (mlp.hip ckk_pitch)
 
+// L [n][np], inv_diag, W_pi [d][np], Z [d][np], c [np] (doubles); the clamped order [n] (int64); seen [np] (int)
+struct RankCurveWs {
+  double *L, *inv, *Wp, *Z, *c;
+  int64_t* oc;
+  int* seen;
+  size_t bytes;
+};
+static RankCurveWs rank_curve_layout(void* ws, int64_t n, int64_t d) {
+  const size_t np = (size_t)rc_pitch(n);
+  Carve c(ws);
+  RankCurveWs w;
+  w.L = c.take<double>((size_t)n * np);
+  w.inv = c.take<double>(mdg_potrf_inv_diag_elems(n));
+  w.Wp = c.take<double>((size_t)d * np);
+  w.Z = c.take<double>((size_t)d * np);
+  w.c = c.take<double>(np);
+  w.oc = c.take<int64_t>((size_t)n);
+  w.seen = c.take<int>(np);
+  w.bytes = c.off;
+  return w;
+}
+
 }  // namespace mdg
 
 using namespace mdg;
 
 extern "C" size_t mdg_nystrom_rank_curve_ws_bytes(int64_t n, int64_t d) {
   if (n <= 0 || d <= 0) return 0;
-  const size_t np = (size_t)rc_pitch(n);
-  // L [n][np], inv_diag, W_pi [d][np], Z [d][np], c [np] (doubles); the clamped order [n] (int64); seen [np] (int)
-  return ((size_t)n * np + mdg_potrf_inv_diag_elems(n) + 2 * (size_t)d * np + np) * sizeof(double) + (size_t)n * sizeof(int64_t) +
-         np * sizeof(int);
+  return rank_curve_layout(nullptr, n, d).bytes;
 }
 
 extern "C" int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, const int64_t* order, const void* Wd, int64_t d,
@@ -170,13 +189,10 @@ extern "C" int mdg_nystrom_rank_curve(const double* C, int64_t n, int64_t ldc, c
                 ws_bytes, mdg_nystrom_rank_curve_ws_bytes(n, d));
   hipStream_t st = (hipStream_t)stream;
   const int64_t np = rc_pitch(n);
-  double* L = (double*)ws;
-  double* inv = L + (size_t)n * np;
-  double* Wp = inv + mdg_potrf_inv_diag_elems(n);
-  double* Z = Wp + (size_t)d * np;
-  double* c = Z + (size_t)d * np;
-  int64_t* oc = (int64_t*)(c + np);
-  int* seen = (int*)(oc + n);
+  const RankCurveWs w = rank_curve_layout(ws, n, d);
+  double *L = w.L, *inv = w.inv, *Wp = w.Wp, *Z = w.Z, *c = w.c;
+  int64_t* oc = w.oc;
+  int* seen = w.seen;
   const unsigned gn = (unsigned)ceil_div(n, 256);
   hipLaunchKernelGGL(order_clamp_kernel, dim3(gn), dim3(256), 0, st, order, n, oc, seen);
   MDG_LAUNCH_CHECK();

@@ -214,8 +214,8 @@ template <int DT>
 static int vo_bias_launch(const VoWs& w, const void* Wo, int64_t ld_wo, int64_t d, const void* b_v, const void* b_o, int b_dtype,
                           int n_heads, int n_kv, int hd, int rank, double* o_bias, double* v_bias, double* resid, int vec,
                           hipStream_t st) {
-  const int64_t a = (int64_t)n_kv * hd;
-  double *bw = w.T, *u = w.T + a, *s_rows = w.T + 2 * a, *rho_rows = s_rows + d;
+  const VoBiasWs sw = vo_bias_layout(w.T, d, n_kv, hd);
+  double *bw = sw.bw, *u = sw.u, *s_rows = sw.s_rows, *rho_rows = sw.rho_rows;
   switch (b_dtype) {
     case MDG_BF16: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_BF16>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
     case MDG_F16: hipLaunchKernelGGL(vo_bias_head_kernel<MDG_F16>, dim3(n_kv), dim3(128), 0, st, w.P, w.Q, b_v, hd, rank, v_bias, bw, u); break;
@@ -354,7 +354,8 @@ extern "C" int mdg_vo_bias(void* ws, size_t ws_bytes, const void* Wo, int64_t ld
   MDG_CHECK_ARG(b_o ? o_bias != nullptr : v_bias != nullptr, "mdg_vo_bias: o_bias is required with b_o, v_bias without it");
   MDG_CHECK_ARG(ws && ws_bytes >= mdg_vo_compress_ws_bytes(d, n_heads, n_kv, hd), "mdg_vo_bias: workspace too small");
   // (the scratch lives in the workspace's T block, n_kv hd d doubles: see vo_bias_head_kernel)
-  MDG_CHECK_ARG(2 * ((int64_t)n_kv * hd + d) <= (int64_t)n_kv * hd * d, "mdg_vo_bias: d = %lld too small for the scratch", (long long)d);
+  MDG_CHECK_ARG(vo_bias_layout(nullptr, d, n_kv, hd).bytes / sizeof(double) <= (size_t)n_kv * hd * (size_t)d,
+                "mdg_vo_bias: d = %lld too small for the scratch", (long long)d);
   VoWs w = vo_layout(ws, d, n_heads, n_kv, hd);
   hipStream_t st = (hipStream_t)stream;
   const int vec = w_dtype != MDG_F64 && (uintptr_t)Wo % 16 == 0 && ld_wo % 8 == 0;

@@ -83,12 +83,12 @@ struct VoErrWs {
 
 static VoErrWs vo_err_layout(void* ws, int64_t d, int n_heads, int n_kv, int hd, int rank) {
   VoErrWs w;
-  double* p = (double*)ws;
+  Carve c(ws);
   const size_t n = (size_t)hd + (size_t)rank;
-  w.T = p;     p += (size_t)n_kv * n * (size_t)d;                                   // V_g C
-  w.gram = p;  p += 2 * (size_t)n_kv * n * n;                                       // V_g C V_g^T, V_g V_g^T
-  w.part = p;  p += 2 * (size_t)ceil_div((int64_t)n, TILE) * (size_t)n_heads * (size_t)d;    // the tile-column partials of e and dnorm2
-  w.bytes = (size_t)((char*)p - (char*)ws);
+  w.T = c.take<double>((size_t)n_kv * n * (size_t)d);                                            // V_g C
+  w.gram = c.take<double>(2 * (size_t)n_kv * n * n);                                             // V_g C V_g^T, V_g V_g^T
+  w.part = c.take<double>(2 * (size_t)ceil_div((int64_t)n, TILE) * (size_t)n_heads * (size_t)d);   // the tile-column partials of e and dnorm2
+  w.bytes = c.off;
   return w;
 }
 
@@ -144,6 +144,20 @@ __global__ __launch_bounds__(128) void vo_curve_kernel(const double* lam_all, co
       out[a] = s;
     }
   }
+}
+
+// Z [n_heads][d][hd] and the chunk partials of its column norms [n_heads][ceil(d / 256)][hd]
+struct VoCurveWs {
+  double *Z, *pn;
+  size_t bytes;
+};
+static VoCurveWs vo_curve_layout(void* ws, int64_t d, int n_heads, int hd) {
+  VoCurveWs w;
+  Carve c(ws);
+  w.Z = c.take<double>((size_t)n_heads * (size_t)d * hd);
+  w.pn = c.take<double>((size_t)n_heads * (size_t)ceil_div(d, VO_CURVE_CHUNK) * hd);
+  w.bytes = c.off;
+  return w;
 }
 
 static bool vo_head_layout_ok(int n_heads, int n_kv, int hd) {
@@ -232,8 +246,7 @@ extern "C" int mdg_vo_output_error(const double* cov_x, int64_t d, int64_t ldc, 
 
 extern "C" size_t mdg_vo_rank_curve_ws_bytes(int64_t d, int n_heads, int n_kv, int hd) {
   if (d <= 0 || !vo_head_layout_ok(n_heads, n_kv, hd) || n_heads == n_kv) return 0;       // MHA: the second spectrum alone
-  // Z [n_heads][d][hd] and the chunk partials of its column norms [n_heads][ceil(d / 256)][hd]
-  return ((size_t)n_heads * (size_t)d * hd + (size_t)n_heads * (size_t)ceil_div(d, VO_CURVE_CHUNK) * hd) * sizeof(double);
+  return vo_curve_layout(nullptr, d, n_heads, hd).bytes;
 }
 
 extern "C" int mdg_vo_rank_curve(const void* vo_ws, size_t vo_ws_bytes, const void* Wo, int64_t ld_wo, int w_dtype, int64_t d,
@@ -257,8 +270,8 @@ extern "C" int mdg_vo_rank_curve(const void* vo_ws, size_t vo_ws_bytes, const vo
   }
   const int64_t n_chunk = ceil_div(d, VO_CURVE_CHUNK);
   MDG_CHECK_ARG(n_chunk < (1ll << 31) && n_heads < 65536, "mdg_vo_rank_curve: grid too large");
-  double* Z = (double*)ws;
-  double* pn = Z + (size_t)n_heads * (size_t)d * hd;
+  const VoCurveWs cw = vo_curve_layout(ws, d, n_heads, hd);
+  double *Z = cw.Z, *pn = cw.pn;
   const int64_t wsz = w_dtype == MDG_BF16 ? 2 : 8, hh = (int64_t)hd * hd;
   // Z[kv * group + j] = W_o,h V_kv                                                                     [d, hd] per query head
   for (int j = 0; j < group; j++)

@@ -74,19 +74,36 @@ __global__ __launch_bounds__(256) void vo_intercept_rows_kernel(const void* Wo, 
   }
 }
 
+struct VoInterceptWs {
+  double *a, *a2;                     // [n_kv][hd] W_v mu + b_v, [n_kv][rank] V^ mu: the heads' halves of the two products
+  double *delta_rows, *const_rows;    // [d] each
+  size_t bytes;
+};
+static VoInterceptWs vo_intercept_layout(void* ws, int64_t d, int n_kv, int hd, int rank) {
+  Carve c(ws);
+  VoInterceptWs w;
+  w.a = c.take<double>((size_t)n_kv * (size_t)hd);
+  w.a2 = c.take<double>((size_t)n_kv * (size_t)rank);
+  w.delta_rows = c.take<double>((size_t)d);
+  w.const_rows = c.take<double>((size_t)d);
+  w.bytes = c.off;
+  return w;
+}
+
 struct ViArgs {
   const void *Wv, *Wo, *Vn, *On, *b_v, *b_o;
   int64_t ld_wv, ld_wo, ld_v, ld_o, d;
   int n_heads, n_kv, hd, rank, b_dtype, out_dtype, vec_wv, vec_wo, vec_v, vec_o;
   const double* mu;
   void* bias_out;
-  double *bias_f64, *norms, *ws;
+  double *bias_f64, *norms;
+  VoInterceptWs ws;
 };
 
 template <int DTW, int DTN>
 static int vo_intercept_launch(const ViArgs& p, hipStream_t st) {
   const int64_t n_w = (int64_t)p.n_kv * p.hd, n_n = (int64_t)p.n_kv * p.rank;
-  double *a = p.ws, *a2 = a + n_w, *delta_rows = a2 + n_n, *const_rows = delta_rows + p.d;
+  double *a = p.ws.a, *a2 = p.ws.a2, *delta_rows = p.ws.delta_rows, *const_rows = p.ws.const_rows;
   const int nb_w = (int)ceil_div(n_w, RD_ROWS), nb_n = (int)ceil_div(n_n, RD_ROWS);
   hipLaunchKernelGGL((vo_intercept_head_kernel<DTW, DTN>), dim3((unsigned)(nb_w + nb_n)), dim3(256), 0, st, p.Wv, p.ld_wv, n_w, p.vec_wv,
                      p.Vn, p.ld_v, n_n, p.vec_v, p.d, p.mu, p.b_v, p.b_dtype, nb_w, a, a2);
@@ -104,7 +121,7 @@ static int vo_intercept_launch(const ViArgs& p, hipStream_t st) {
 
 extern "C" size_t mdg_vo_intercept_ws_bytes(int64_t d, int n_kv, int hd, int rank) {
   if (d <= 0 || n_kv <= 0 || hd <= 0 || rank < 0 || rank > hd) return 0;
-  return ((size_t)n_kv * (size_t)(hd + rank) + 2 * (size_t)d) * sizeof(double);
+  return mdg::vo_intercept_layout(nullptr, d, n_kv, hd, rank).bytes;
 }
 
 extern "C" int mdg_vo_intercept(const void* Wv, int64_t ld_wv, const void* Wo, int64_t ld_wo, int w_dtype, const void* v_new, int64_t ld_v,
@@ -137,7 +154,7 @@ extern "C" int mdg_vo_intercept(const void* Wv, int64_t ld_wv, const void* Wo, i
   p.n_heads = n_heads; p.n_kv = n_kv; p.hd = hd; p.rank = rank; p.b_dtype = b_dtype; p.out_dtype = out_dtype;
   p.vec_wv = vec(Wv, ld_wv, w_dtype); p.vec_wo = vec(Wo, ld_wo, w_dtype);
   p.vec_v = rank > 0 ? vec(v_new, ld_v, ndt) : 0; p.vec_o = rank > 0 ? vec(o_new, ld_o, ndt) : 0;
-  p.mu = mu; p.bias_out = bias_out; p.bias_f64 = bias_f64; p.norms = norms; p.ws = (double*)ws;
+  p.mu = mu; p.bias_out = bias_out; p.bias_f64 = bias_f64; p.norms = norms; p.ws = vo_intercept_layout(ws, d, n_kv, hd, rank);
   hipStream_t st = (hipStream_t)stream;
   if (w_dtype == MDG_BF16)
     return ndt == MDG_BF16 ? vo_intercept_launch<MDG_BF16, MDG_BF16>(p, st) : vo_intercept_launch<MDG_BF16, MDG_F64>(p, st);
