@@ -1101,6 +1101,12 @@ int mdg_probe_mfma_f64(int iters, double* tflops, void* stream);
  * gives way, ~0.68 of nominal on an MI355X -- the ceiling of ANY int8 kernel on random data, before a single byte is loaded).
  * bench.py states both next to the kernel's achieved rate.  SYNCHRONISES. */
 int mdg_probe_mfma_i8(int iters, int random_operands, double* tops, void* stream);
+/* The same register-only loop on either int8 MFMA shape, to compare them on one device: shape = 32 runs the kernel of
+ * mdg_probe_mfma_i8 (8 x v_mfma_i32_32x32x32_i8 per iteration), shape = 16 runs 16 x v_mfma_i32_16x16x64_i8 per iteration on
+ * sixteen independent accumulators -- the same operands in the same rotation and the same int8 op count per wave.
+ * waves_per_simd = 1 or 2 (the product kernels run two).  The chip may hold a different clock on the two shapes under its
+ * power cap, so the ratio on random operands, not cycles per op, says which is faster.  SYNCHRONISES. */
+int mdg_probe_mfma_i8_shape(int shape, int waves_per_simd, int iters, int random_operands, double* tops, void* stream);
 
 #ifdef __cplusplus
 }

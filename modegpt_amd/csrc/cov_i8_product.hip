@@ -145,9 +145,24 @@ constexpr int RING3 = MDG_I8_RING3;   // LDS stages of the three-plane (exact ro
 #ifndef MDG_I8_KSS3
 #define MDG_I8_KSS3 2
 #endif
-#ifndef MDG_I8_DEFER3
-#define MDG_I8_DEFER3 8     // MFMAs a loads-first wave of the three-plane kernel holds back across the barrier (see DEFER5)
+// MFMA shape of the three-plane kernel.  32: v_mfma_i32_32x32x32_i8, one per k-step, plane pair and 32 x 32 block of the wave tile
+// (18 per wave and k-step).  16: v_mfma_i32_16x16x64_i8, whose K = 64 is the TWO k-steps of a stage: one per stage, plane pair and
+// 16 x 16 block (72 per wave and stage, half the cycles each) -- the same int32 class sums, so not a bit of sigma changes.  Cycles
+// per op are equal; what differs is the clock the chip holds under its power cap (mdg_probe_mfma_i8_shape; DESIGN.md section 7,
+// "The 16x16x64 MFMA shape").
+#ifndef MDG_I8_SHAPE3
+#define MDG_I8_SHAPE3 16
 #endif
+static_assert(MDG_I8_SHAPE3 == 16 || MDG_I8_SHAPE3 == 32, "MDG_I8_SHAPE3: 16 (v_mfma_i32_16x16x64_i8) or 32 (v_mfma_i32_32x32x32_i8)");
+static_assert(MDG_I8_SHAPE3 == 32 || MDG_I8_KSS3 == 2, "one 16x16x64 MFMA takes the two k-steps of a stage");
+#ifndef MDG_I8_DEFER3
+// MFMAs a loads-first wave of the three-plane kernel holds back across the barrier (see DEFER5), in MFMAs of the shape built (72
+// per wave and stage on the 16-wide shape, 36 on the 32-wide).  Measured at the sigma_mlp shape, Gaussian columns, product launch
+// alone, one box (profiles/i8_shape3_defer_sweep.json): 32-wide, 8 deferred 19.31 ms; 16-wide with 0 / 4 / 8 / 12 / 16 / 20 / 24
+// deferred 18.00 / 17.92 / 17.95 / 17.86 / 17.67-18.28 / 20.65 / 21.74 -- flat up to 16 within the run-to-run spread, a cliff above.
+#define MDG_I8_DEFER3 (MDG_I8_SHAPE3 == 16 ? 12 : 8)
+#endif
+constexpr bool shape16(int planes) { return planes == 3 && MDG_I8_SHAPE3 == 16; }
 constexpr int steps_per_stage(int planes) { return planes == 3 ? MDG_I8_KSS3 : 1; }
 constexpr bool wide_tile(int planes) { return planes != 6; }   // 128 x 128 tiles (six planes: 128 x 64)
 constexpr int ring_depth(int planes) { return planes == 3 ? RING3 : wide_tile(planes) ? RING5 : 4; }
@@ -155,7 +170,8 @@ constexpr int ring_depth(int planes) { return planes == 3 ? RING3 : wide_tile(pl
 // with the 160 accumulators of a wide tile hipcc spills inside the loop, see RING5)
 constexpr bool prefetch_frags(int planes) { return !wide_tile(planes); }
 // P = 3 is the product of the EXACT route: planes 0 .. 2 only, ALL nine plane pairs (classes 0 .. 4), no piece masks -- the same tile
-// code with nothing conditional left in the k-step (24 KB stages, 36 fragment registers beside the 160 accumulators)
+// code with nothing conditional left in the k-step (24 KB stages, 36 fragment registers beside the 160 accumulators; 40 on the
+// 16x16x64 shape, MDG_I8_SHAPE3)
 constexpr int classes_of(int planes) { return planes == 3 ? 5 : planes; }
 // tile shape per route, for the kernels and the host's LDS-size and grid arithmetic
 template <int P> struct TileShape {
@@ -186,6 +202,9 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
   constexpr bool PREFETCH = prefetch_frags(P);     // the next step's fragments are read before the barrier (needs RING >= 4)
   static_assert(KSS == 1 || (P == 3 && !PREFETCH), "several k-steps per stage: the unconditional three-plane k-step only");
   constexpr int NCLS = classes_of(P);              // digit classes s + t kept: 0 .. NCLS - 1
+  // the 16x16x64 shape (three planes): the 64 x 32 wave tile is 4 x 2 blocks of 16 x 16, one MFMA per block, plane pair and STAGE
+  constexpr bool S16 = shape16(P);
+  static_assert(!S16 || (KSS == 2 && WB == 2), "the 16x16x64 shape: stages of two k-steps, 64 x 32 wave tiles");
   // the wave index through readfirstlane: hipcc then knows it is wave-uniform and the staging code becomes scalar (SGPR piece
   // addresses, s_cbranch on the piece tests, M0 from SGPRs) instead of exec-masked branches with a v_readfirstlane per piece
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -248,11 +267,66 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
     }
   };
 
-  i32x16 acc[NCLS][WB];
+  i32x16 acc[NCLS][WB];                  // [class][32-row block]: 32 x 32 blocks (unused, and gone, with S16)
+  i32x4 acc16[S16 ? NCLS : 1][4][2];     // [class][16-row block][16-column block]: 16 x 16 blocks (S16 only)
 #pragma unroll
   for (int k = 0; k < NCLS; k++)
 #pragma unroll
     for (int b = 0; b < WB; b++) acc[k][b] = (i32x16)0;
+#pragma unroll
+  for (int k = 0; k < (S16 ? NCLS : 1); k++)
+#pragma unroll
+    for (int ab = 0; ab < 4; ab++)
+#pragma unroll
+      for (int bb = 0; bb < 2; bb++) acc16[k][ab][bb] = (i32x4)0;
+
+  // The same fold from 16 x 16 blocks: lane l, register v of block (ab, bb) is row 16 ab + 4 (l / 16) + v, column 16 bb + l % 16 of
+  // the wave tile.  Two 16-row blocks at a time, the same 16 loads in flight per lane, the same expression per element.
+  auto flush16 = [&]() {
+    const int col = bj * TJ + wc * 32 + (lane & 15);   // (of column block 0; block 1: + 16)
+    int row0 = bi * TI + wr * 64 + 4 * (lane >> 4);
+    asm volatile("" : "+v"(row0));                      // (see flush)
+    int e_col[2];
+    double sc_j[2];
+#pragma unroll
+    for (int bb = 0; bb < 2; bb++) {
+      e_col[bb] = pr.emax[col + 16 * bb];
+      sc_j[bb] = ldexp(1.0, (e_col[bb] & 255) - 172);
+    }
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+      double* const p = fold + (int64_t)(row0 + b * 32 - fold_row0) * fold_ld + (col - fold_col0);
+      const int* const e = pr.emax + row0 + b * 32;
+      int er[8];
+      double old[16];
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const int off = (i & 3) + 16 * (i >> 2);
+        er[i] = e[off];
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) old[2 * i + bb] = p[(int64_t)off * fold_ld + 16 * bb];
+      }
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const int off = (i & 3) + 16 * (i >> 2);
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) {
+          double v = 0.;
+#pragma unroll
+          for (int k = NCLS - 1; k >= 0; k--) v += ldexp((double)acc16[S16 ? k : 0][2 * b + (i >> 2)][bb][i & 3], 80 - 8 * k);
+          if (col + 16 * bb <= row0 + b * 32 + off && !((e_col[bb] | er[i]) & EMAX_COLUMN_OUT))
+            p[(int64_t)off * fold_ld + 16 * bb] = old[2 * i + bb] + v * sc_j[bb] * ldexp(1.0, (er[i] & 255) - 172);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < (S16 ? NCLS : 1); k++)
+#pragma unroll
+      for (int ab = 0; ab < 4; ab++)
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) acc16[k][ab][bb] = (i32x4)0;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
 
   // sigma[i][j] += 2^(E_i + E_j - 344) * sum_k acc_k 256^(10 - k)  =  (sum_k acc_k 2^(80 - 8k)) * 2^(E_i - 172) * 2^(E_j - 172)
   auto flush = [&]() {
@@ -332,6 +406,7 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
 #ifdef MDG_I8_STAMPS
   unsigned long long ta = 0, tb = 0, tc = 0, td = 0, te = 0, s_wait = 0, s_issue = 0, s_comp = 0, s_tail = 0, t_begin;
   const unsigned executed_before = executed;
+  const unsigned long long w_begin = wall_clock64();   // 100 MHz: with t_begin, the clock this tile ran at
   MDG_STAMP(t_begin);
 #endif
   const int r = lane & 31, h = lane >> 5;
@@ -345,6 +420,47 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
       for (int b = 0; b < WB; b++) fa[s][b] = *(const i32x4*)(base + s * PA + (wr * WB + b) * 1024 + h * 512 + r * 16);
       fb[s] = *(const i32x4*)(base + P * PA + s * PB + wc * 1024 + h * 512 + r * 16);
     }
+  };
+  // S16: an operand of v_mfma_i32_16x16x64_i8 is 16 rows x 64 k-bytes, lane l holding 16 bytes of row l % 16 -- lane group l / 16 =
+  // g takes them from k-step g >> 1 of the stage, half g & 1 of the row's 32 bytes (both operands alike, so the order of the k
+  // bytes inside the instruction does not matter to the sum).  The rows come from the same 1 KB pieces (2 halves x 32 rows x 16 B):
+  // 16-row block x of a panel is rows 16 (x & 1) .. of piece x >> 1.  B's three planes stay in registers for the stage (24), A's
+  // are read one plane at a time (16): all nine would be 72 beside the 160 accumulators.
+  i32x4 fa16[4], fb16[MIN_DEPTH][2];
+  const unsigned frag16 = ((lane >> 4) >> 1) * STEP_BYTES + ((lane >> 4) & 1) * 512 + (lane & 15) * 16;
+  // one_step: the stage holds ONE k-step (the odd end of a tile segment or k-chunk) -- lane groups 2 and 3 multiply zeros
+  auto load_fb16 = [&](int stage_buf, bool one_step) {
+    const unsigned char* base = lds + stage_buf * STAGE_BYTES + frag16 + P * PA + wc * 1024;
+#pragma unroll
+    for (int t = 0; t < MIN_DEPTH; t++)
+#pragma unroll
+      for (int bb = 0; bb < 2; bb++) fb16[t][bb] = *(const i32x4*)(base + t * PB + bb * 256);
+    if (one_step && lane >= 32) {
+#pragma unroll
+      for (int t = 0; t < MIN_DEPTH; t++)
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) fb16[t][bb] = (i32x4)0;
+    }
+  };
+  auto load_fa16 = [&](int stage_buf, int s) {
+    const unsigned char* base = lds + stage_buf * STAGE_BYTES + frag16 + s * PA + wr * WB * 1024;
+#pragma unroll
+    for (int ab = 0; ab < 4; ab++) fa16[ab] = *(const i32x4*)(base + (ab >> 1) * 1024 + (ab & 1) * 256);
+  };
+  constexpr int N16 = 9 * 4 * 2, N16_PLANE = 3 * 4 * 2;   // MFMAs per wave and stage; of them with one plane of A
+  // the MFMAs of A's plane s in (t, row block, column block) order, those with stage index in [lo, hi)
+  auto mfma16_plane = [&](int s, int lo, int hi) {
+    int idx = s * N16_PLANE;
+#pragma unroll
+    for (int t = 0; t < MIN_DEPTH; t++)
+#pragma unroll
+      for (int ab = 0; ab < 4; ab++)
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) {
+          if (idx >= lo && idx < hi)
+            acc16[S16 ? s + t : 0][ab][bb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa16[ab], fb16[t][bb], acc16[S16 ? s + t : 0][ab][bb], 0, 0, 0);
+          idx++;
+        }
   };
   // the deeper planes of a step, each present one a block of its own (fragment read + its pairs).  A deep plane only pairs with
   // planes 0 (and 1) of the other panel (s + t < P), so the blocks are independent and simply add:
@@ -385,6 +501,7 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
   // of them, held back across the barrier by the loads-first waves (six planes: none -- 37.2 ms per call without, 55 ms with 3 - 5
   // deferred: the loads-first waves then lose their fragment prefetch)
   constexpr int DEFER = PREFETCH ? 0 : P == 3 ? MDG_I8_DEFER3 : DEFER5;
+  static_assert(!S16 || DEFER <= N16_PLANE, "the deferred MFMAs are of A's last plane: its fragments and B's stay in registers");
   auto rotate = [&]() {
 #pragma unroll
     for (int i = 0; i < D; i++) {
@@ -438,13 +555,33 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
         // at every step boundary otherwise (fragments of the previous step are still in this wave's registers: it re-reads
         // them only after its loads are out)
         if (DEFER && kt > k0) {
-          mfma_run(N_UNCOND - DEFER, N_UNCOND);
+          if constexpr (S16) mfma16_plane(MIN_DEPTH - 1, N16 - DEFER, N16);
+          else mfma_run(N_UNCOND - DEFER, N_UNCOND);
           __builtin_amdgcn_sched_barrier(0);
         }
         refill();
         __builtin_amdgcn_sched_barrier(0);
       }
       MDG_STAMP(tc);
+      if constexpr (S16) {
+        // the whole stage in one pass: B's planes, then A's one by one, each re-read into the same registers once the MFMAs of the
+        // plane before are issued (the SIMD's other wave, half a stage out of phase, has the matrix pipe meanwhile)
+        const bool one_step = kt + 1 >= k1;
+        load_fb16(buf, one_step);
+#pragma unroll
+        for (int s = 0; s < MIN_DEPTH; s++) {
+          load_fa16(buf, s);
+          if (s < MIN_DEPTH - 1) {
+            mfma16_plane(s, 0, N16);
+            __builtin_amdgcn_sched_barrier(0);
+          } else {
+            mfma16_plane(s, 0, N16 - DEFER);
+            if (DEFER == 0 || !loads_first) mfma16_plane(s, N16 - DEFER, N16);
+          }
+        }
+        // (in 32x32x32 units, as the host's dense count: one 16x16x64 is half of one, and the zero half of an odd end is not work)
+        executed += UNCOND_PAIRS * WB * (one_step ? 1 : KSS);
+      } else {
       if (!PREFETCH || (DEFER && loads_first)) load_frags(buf);
       if (KSS > 1) {
         // the stage's k-steps but the last, whole: the fragment registers are re-read once their MFMAs are issued (the SIMD's other
@@ -462,6 +599,7 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
       if (DEFER == 0 || !loads_first) mfma_run(N_UNCOND - DEFER, N_UNCOND);
       deep_planes(buf, mA[0], mB[0]);
       executed += UNCOND_PAIRS * WB;
+      }
       if (PREFETCH) {
       // next step's fragments: stage kt + 1 has been complete since THIS step's barrier (its loads went out three steps ago
       // and every wave waited for its share before the barrier), so the read latency hides behind the refill / the barrier
@@ -480,6 +618,10 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
 #endif
       rotate();
     }
+    if constexpr (S16) {
+      if (DEFER && loads_first) mfma16_plane(MIN_DEPTH - 1, N16 - DEFER, N16);   // (as below)
+      flush16();
+    } else {
     if (DEFER && loads_first) {   // the deferred MFMAs of the segment's last step (its fragments are still in registers)
 #pragma unroll
       for (int s = 0, idx = 0; s < MIN_DEPTH; s++)
@@ -494,6 +636,7 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
           }
     }
     flush();
+    }
   }
 #ifdef MDG_I8_STAMPS
   if (a.stamps && lane == 0 && blockIdx.x < STAMP_WGS) {
@@ -501,6 +644,7 @@ __device__ __forceinline__ void i8_syrk_tile(const SyrkArgs& a, const SyrkProble
     MDG_STAMP(t_end);
     unsigned long long* o = a.stamps + ((size_t)blockIdx.x * NW + wave) * 8;
     o[0] = s_wait; o[1] = s_issue; o[2] = s_comp; o[3] = s_tail; o[4] = t_end - t_begin; o[5] = executed - executed_before; o[6] = ke - kb;   // (of the workgroup's LAST tile or k-chunk)
+    o[7] = wall_clock64() - w_begin;
   }
 #endif
 }
@@ -885,9 +1029,11 @@ int report_product_diagnostics(const I8Call& c) {
     MDG_HIP(hipStreamSynchronize(st));
     double sum[2][6] = {};
     long cnt[2] = {};
+    std::vector<double> ghz;   // in-kernel clock per wave: s_memtime cycles / 100 MHz wall ticks around its last tile
     for (int w = 0; w < STAMP_WGS * NW; w++) {
       const unsigned long long* o = host + (size_t)w * 8;
       if (!o[6]) continue;
+      if (o[7]) ghz.push_back((double)o[4] / (double)o[7] * 0.1);
       const int role = (w % NW) >= NW / 2;
       for (int i = 0; i < 6; i++) sum[role][i] += (double)o[i] / (double)o[6];
       cnt[role]++;
@@ -898,6 +1044,11 @@ int report_product_diagnostics(const I8Call& c) {
                         "wait+refill-last %.0f  | whole tile / nk %.0f  mfma/step %.1f  (%ld waves)\n", n, role ? "4-7" : "0-3",
                 sum[role][0] / cnt[role], sum[role][1] / cnt[role], sum[role][2] / cnt[role], sum[role][3] / cnt[role],
                 sum[role][4] / cnt[role], sum[role][5] / cnt[role], cnt[role]);
+    if (!ghz.empty()) {
+      std::sort(ghz.begin(), ghz.end());
+      fprintf(stderr, "[stamps n=%d] in-kernel clock (s_memtime / s_memrealtime x 100 MHz), median over %zu waves: %.3f GHz\n", n, ghz.size(),
+              ghz[ghz.size() / 2]);
+    }
   }
 #endif
 #ifdef MDG_I8_WGTIMES

@@ -1601,6 +1601,16 @@ def probe_mfma_i8(iters: int = 200000, random_operands: bool = True) -> float:
     return out.value
 
 
+def probe_mfma_i8_shape(shape: int, iters: int = 200000, random_operands: bool = True, waves_per_simd: int = 1) -> float:
+    """probe_mfma_i8's loop on either int8 MFMA shape (32: v_mfma_i32_32x32x32_i8, 16: v_mfma_i32_16x16x64_i8) at the same
+    int8 op count per wave, in TOP/s: under the power cap the chip may hold a different clock on the two shapes."""
+    lib = _lib.load()
+    out = C.c_double(0.0)
+    check(lib.mdg_probe_mfma_i8_shape(shape, waves_per_simd, iters, int(random_operands), C.byref(out),
+                                      torch.cuda.current_stream().cuda_stream), "mdg_probe_mfma_i8_shape")
+    return out.value
+
+
 def device_info(device: int = 0):
     lib = _lib.load()
     name = C.create_string_buffer(64)
