@@ -59,7 +59,9 @@ extern "C" {
                                 added under 10: mdg_qk_causal_ws_bytes, mdg_qk_causal_accum (the causal Q/K statistic);
                                 added under 10: mdg_attn_fwd (fused causal attention forward for compressed heads of unequal q/k and v width);
                                 added under 10: mdg_attn_decode_ws_bytes, mdg_attn_decode_splits, mdg_attn_decode (the same product on a split-key decode schedule);
-                                added under 10: mdg_attn_mask_summary_bytes, mdg_attn_mask_summary, mdg_attn_fwd_masked, mdg_attn_decode_masked (both products under a bool mask) */
+                                added under 10: mdg_attn_mask_summary_bytes, mdg_attn_mask_summary, mdg_attn_fwd_masked, mdg_attn_decode_masked (both products under a bool mask);
+                                added under 10: mdg_kv8_pitch, mdg_kv8_append, mdg_kv8_dequant, mdg_attn_decode_kv8 (an fp8 KV cache for compressed heads:
+                                its layout, the append, the read-back and the split-key decode product straight from it) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -1071,6 +1073,50 @@ int mdg_attn_decode_masked(const void* q, const void* k, const void* v, int dtyp
                            int64_t v_batch_stride, int64_t v_head_stride, int64_t v_token_stride, double scale, int causal,
                            int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream, const void* mask,
                            int Hm, int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride);
+
+/* ------------------------------------------------------------------ fp8 KV cache of compressed heads (csrc/kv8.hip, csrc/attn_decode_kv8.hip)
+ * THE LAYOUT, for K and for V of one layer (additive entries, ABI version unchanged):
+ *   data   uint8   [B, n_kv, cap, pitch]  contiguous, 16-byte aligned; pitch = mdg_kv8_pitch(r) = r rounded up to 16 (a caller may
+ *                                         pass a larger multiple of 16); elements are OCP e4m3 (torch.float8_e4m3fn); bytes
+ *                                         r .. pitch - 1 of every written row are zero
+ *   scale  float32 [B, n_kv, cap]         one power of two per (batch, kv head, token): for a row with finite amax > 0 the smallest
+ *                                         2^e with amax / 2^e <= 448, e clamped to the fp32 normal range [-126, 127]; 1 for amax == 0
+ * Element i of row t stands for e4m3(data[t][i]) * scale[t].  An e4m3 value has at most 4 significant bits and the scale is a
+ * power of two, so this value is exactly representable in bf16, and in f16 whenever it lies in f16's normal range: an f16 caller
+ * whose rows have a tiny amax (scale * 2^-9 under 2^-24) LOSES EXACTNESS there, the product rounds into f16's subnormals or to zero.
+ * A row that holds Inf or NaN gets whatever v_cvt_pk_fp8_f32 makes of its elements under the scale of its (then non-finite) amax;
+ * not specified further.  Rows at or beyond the tokens appended so far hold anything.
+ *   mdg_kv8_pitch    r rounded up to 16 (0 for r <= 0): a pure host function
+ *   mdg_kv8_append   quantises T new rows of a bf16 / f16 source, logical [B, n_kv, T, r] with its own batch, head and token strides
+ *                    in ELEMENTS and a unit last stride (K as mdg_rope_gather writes it; V as the transposed view of the projection
+ *                    output), into rows pos .. pos + T - 1: one pass, a group of 1 .. 16 lanes per row, amax by cross-lane
+ *                    reduction, the scale from amax's exponent bits, round-to-nearest-even conversion of x / scale (exact division),
+ *                    16-byte stores that include the zero padding, one scale store.  Refused: a dtype other than bf16 / f16, a
+ *                    negative extent, r outside 1..256, pitch < mdg_kv8_pitch(r) or no multiple of 16, pos < 0 or pos + T > cap,
+ *                    a NULL pointer, misaligned data (16) or scale (4), data or scale overlapping the source or each other.
+ *                    B, n_kv or T == 0 launches nothing and returns MDG_OK.
+ *   mdg_kv8_dequant  the inverse for rows 0 .. S - 1 into a contiguous bf16 / f16 out [B, n_kv, S, r]: exact for bf16.  The same
+ *                    refusals with S <= cap in place of the position check and out in place of the source.
+ *   mdg_attn_decode_kv8  mdg_attn_decode's product -- same domain T * G <= 32, column map, split rule (mdg_attn_decode_splits),
+ *                    workspace (mdg_attn_decode_ws_bytes), combine kernel, causal rule, out rows, determinism -- with K and V read
+ *                    from two caches of this layout that share B, n_kv and cap (k_pitch, v_pitch in bytes).  q is bf16 / f16 and is
+ *                    NOT quantised; both products run on the 32x32x16 bf16 / f16 MFMA on the exact dequantised values, so the bound
+ *                    of mdg_attn_decode holds against the softmax product of q with the DEQUANTISED K and V:
+ *                    |out - exact| <= 4 u max_j |v_deq[b, g, j, c]| over the admitted keys, with |scale * logit| <= 20.  What
+ *                    quantisation itself costs a model is not part of the bound.  mask: NULL, or mdg_attn_decode_masked's bool mask
+ *                    with its Hm and byte strides (then pass causal as that entry's caller would).  Refused: what mdg_attn_decode
+ *                    refuses, and S > cap, a pitch below mdg_kv8_pitch of its width or no multiple of 16, misaligned planes, a
+ *                    plane overlapping out or the workspace. */
+int64_t mdg_kv8_pitch(int r);
+int mdg_kv8_append(const void* src, int dtype, int64_t B, int n_kv, int64_t T, int r, int64_t src_batch_stride, int64_t src_head_stride,
+                   int64_t src_token_stride, void* data, void* scale, int64_t cap, int64_t pitch, int64_t pos, void* stream);
+int mdg_kv8_dequant(const void* data, const void* scale, int dtype, int64_t B, int n_kv, int64_t S, int r, int64_t cap, int64_t pitch,
+                    void* out, void* stream);
+int mdg_attn_decode_kv8(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale, int dtype,
+                        int64_t B, int64_t T, int64_t S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t cap, int64_t k_pitch,
+                        int64_t v_pitch, double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out,
+                        void* stream, const void* mask, int Hm, int64_t mask_batch_stride, int64_t mask_head_stride,
+                        int64_t mask_query_stride);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -42,18 +42,10 @@ namespace {
 
 using namespace attn;
 
-constexpr int THREADS = 256;
-constexpr int WAVES = 4;
-constexpr int COLS = 32;         // query columns of the tile
-constexpr int MAX_SPLITS = 256;  // also the combine kernel's workgroup size
-
-// Position in a Vs row of the first of the 4 consecutive keys 4 mq .. 4 mq + 3 of a 64-key tile (attn.hip's permutation): inside
-// k-step s of the second product element j of lane half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3) of the 32-key half, so key kappa
-// sits at 16 s + 8 h + 4 ((kappa >> 3) & 1) + (kappa & 3) and a lane's A fragment is one 16-byte read.
-__device__ __forceinline__ int v_quad_pos(int mq) {
-  const int kap = (4 * mq) & 31;
-  return ((4 * mq) & 32) + (kap & 16) + ((kap >> 2) & 1) * 8 + ((kap >> 3) & 1) * 4;
-}
+constexpr int THREADS = DECODE_THREADS;
+constexpr int WAVES = DECODE_WAVES;
+constexpr int COLS = DECODE_COLS;
+constexpr int MAX_SPLITS = DECODE_MAX_SPLITS;
 
 struct DecodeArgs {
   const void* q;
@@ -382,6 +374,19 @@ template <int DT> int launch_decode(const DecodeArgs& a, const MaskArgs* mk, dim
 int64_t ws_row_floats(int r_vo) { return (int64_t)((r_vo + 3) / 4 * 4 + 4); }
 
 }  // namespace
+
+int attn::decode_combine(int dtype, const float* ws, void* out, int64_t B, int64_t T, int n_heads, int r_vo, int splits, int64_t ld_out,
+                         hipStream_t st) {
+  DecodeArgs a{};  // what attn_combine_kernel reads
+  a.ws = const_cast<float*>(ws); a.out = out; a.T = T; a.ld_out = ld_out;
+  a.n_heads = n_heads; a.r_vo = r_vo; a.splits = splits; a.rp = (r_vo + 3) / 4 * 4;
+  const dim3 rows((unsigned)(B * n_heads * T));
+  if (dtype == MDG_BF16) hipLaunchKernelGGL((attn_combine_kernel<MDG_BF16>), rows, dim3(MAX_SPLITS), 0, st, a);
+  else hipLaunchKernelGGL((attn_combine_kernel<MDG_F16>), rows, dim3(MAX_SPLITS), 0, st, a);
+  MDG_LAUNCH_CHECK();
+  return MDG_OK;
+}
+
 }  // namespace mdg
 
 using namespace mdg;

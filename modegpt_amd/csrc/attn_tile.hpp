@@ -109,6 +109,27 @@ static inline void mask_span_of(const void* p, int64_t B, int64_t bs, int64_t H,
   hi = lo + (uintptr_t)((B - 1) * bs + (H - 1) * hs + (T - 1) * qs + S);
 }
 
+// ---------------------------------------------------------------- the device side the two decode kernels share (attn_decode.hip on
+// a bf16 / f16 cache, attn_decode_kv8.hip on an fp8 one): the kernels' constants, the second launch, and the place of a key in the
+// wave's transposed V tile.
+constexpr int DECODE_THREADS = 256;
+constexpr int DECODE_WAVES = 4;
+constexpr int DECODE_COLS = 32;         // query columns of the tile
+constexpr int DECODE_MAX_SPLITS = 256;  // also the combine kernel's workgroup size
+
+// The second launch of a decode call (attn_decode.hip's combine kernel, one workgroup per (batch, head, query)) over the partials
+// ws [B][n_heads][T][splits][RP + 4] a first kernel wrote on the same stream.
+int decode_combine(int dtype, const float* ws, void* out, int64_t B, int64_t T, int n_heads, int r_vo, int splits, int64_t ld_out,
+                   hipStream_t st);
+
+// Position in a Vs row of the first of the 4 consecutive keys 4 mq .. 4 mq + 3 of a 64-key tile (attn.hip's permutation): inside
+// k-step s of the second product element j of lane half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3) of the 32-key half, so key kappa
+// sits at 16 s + 8 h + 4 ((kappa >> 3) & 1) + (kappa & 3) and a lane's A fragment is one 16-byte read.
+__device__ __forceinline__ int v_quad_pos(int mq) {
+  const int kap = (4 * mq) & 31;
+  return ((4 * mq) & 32) + (kap & 16) + ((kap >> 2) & 1) * 8 + ((kap >> 3) & 1) * 4;
+}
+
 // ---------------------------------------------------------------- the host side of the four entries (attn.hip, attn_decode.hip)
 // What every entry receives, in the order of the C signatures, and what the masked entries receive besides.  The order of the checks
 // below is part of the interface: of two faults the caller is told the one checked first.

@@ -1493,6 +1493,116 @@ def attn_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
     return out
 
 
+def kv8_pitch(r: int) -> int:
+    """Bytes of a row of the fp8 KV cache that holds r elements (mdg_kv8_pitch): r rounded up to 16."""
+    return int(_lib.load().mdg_kv8_pitch(int(r)))
+
+
+def _kv8_planes(fn: str, data, scale, like=None):
+    """The checks of one cache (data uint8 [B, n_kv, cap, pitch], scale float32 [B, n_kv, cap], both contiguous on one GPU):
+    returns (B, n_kv, cap, pitch)."""
+    if (data.dtype != torch.uint8 or scale.dtype != torch.float32 or data.dim() != 4 or tuple(scale.shape) != tuple(data.shape[:3])
+            or not data.is_contiguous() or not scale.is_contiguous() or data.device != scale.device):
+        raise ValueError(f"{fn}: a cache is a contiguous uint8 data [B, n_kv, cap, pitch] with a contiguous float32 scale [B, n_kv, cap] "
+                         f"on one device, got {data.dtype} {tuple(data.shape)} / {scale.dtype} {tuple(scale.shape)}")
+    if like is not None and data.device != like.device:
+        raise ValueError(f"{fn}: cache on {data.device}, the other operand on {like.device}")
+    return tuple(data.shape)
+
+
+def kv8_append(src: torch.Tensor, data: torch.Tensor, scale: torch.Tensor, pos: int) -> None:
+    """Quantise the T rows of src [B, n_kv, T, r] (bf16 / f16, any batch / head / token strides, unit last stride: a transposed
+    projection output is taken as it is) into rows pos .. pos + T - 1 of an fp8 cache (mdg_kv8_append; the layout is in
+    include/modegpt_hip.h): OCP e4m3 with one power-of-two scale per row, padding bytes zero.  Nothing synchronises."""
+    _need_gpu(src, data, scale)
+    if src.dim() != 4 or src.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"kv8_append: src must be a 4-D bf16 or f16 tensor, got {src.dtype} {tuple(src.shape)}")
+    B, n_kv, cap, pitch = _kv8_planes("kv8_append", data, scale, src)
+    T, r = src.shape[2], src.shape[3]
+    if tuple(src.shape[:2]) != (B, n_kv) or pitch < kv8_pitch(r):
+        raise ValueError(f"kv8_append: src {tuple(src.shape)} does not fit a cache of data {tuple(data.shape)} (pitch >= {kv8_pitch(r)})")
+    if r > 1 and src.stride(3) != 1:
+        raise ValueError(f"kv8_append: src must have a contiguous last dimension, got strides {src.stride()}")
+    if not 0 <= int(pos) <= cap - T:
+        raise ValueError(f"kv8_append: rows {int(pos)} .. {int(pos) + T - 1} do not fit cap={cap}")
+    src = src.detach()
+    with torch.cuda.device(src.device):
+        check(_lib.load().mdg_kv8_append(src.data_ptr(), _DT[src.dtype], B, n_kv, T, r, src.stride(0), src.stride(1), src.stride(2),
+                                         data.data_ptr(), scale.data_ptr(), cap, pitch, int(pos), _stream(src)), "mdg_kv8_append")
+
+
+def kv8_dequant(data: torch.Tensor, scale: torch.Tensor, S: int, r: int, dtype=torch.bfloat16,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows 0 .. S - 1 of an fp8 cache as a contiguous [B, n_kv, S, r] tensor of `dtype` (mdg_kv8_dequant): e4m3 * scale, exact in
+    bf16.  `out`: a caller-owned contiguous tensor of that shape and dtype (it is returned)."""
+    _need_gpu(data, scale, out)
+    B, n_kv, cap, pitch = _kv8_planes("kv8_dequant", data, scale)
+    S, r = int(S), int(r)
+    if dtype not in (torch.bfloat16, torch.float16) or not 0 <= S <= cap or r < 1 or pitch < kv8_pitch(r):
+        raise ValueError(f"kv8_dequant: S={S}, r={r}, {dtype} do not fit a cache of data {tuple(data.shape)} (bf16 or f16)")
+    if out is None:
+        out = torch.empty(B, n_kv, S, r, dtype=dtype, device=data.device)
+    elif tuple(out.shape) != (B, n_kv, S, r) or out.dtype != dtype or out.device != data.device or not out.is_contiguous():
+        raise ValueError(f"kv8_dequant: out must be a contiguous {dtype} [{B}, {n_kv}, {S}, {r}] on {data.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(data.device):
+        check(_lib.load().mdg_kv8_dequant(data.data_ptr(), scale.data_ptr(), _DT[dtype], B, n_kv, S, r, cap, pitch, out.data_ptr(),
+                                          _stream(data)), "mdg_kv8_dequant")
+    return out
+
+
+def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor, v_data: torch.Tensor, v_scale: torch.Tensor, S: int,
+                    r_vo: int, scale: float, causal: bool = True, splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_decode's product with K and V read from fp8 caches (mdg_attn_decode_kv8): q [B, n_heads, T, r_qk] bf16 / f16 as it is, the
+    first S rows of (k_data, k_scale) holding r_qk elements and of (v_data, v_scale) holding r_vo, the two caches sharing B, n_kv
+    and cap -> [B, T, n_heads, r_vo].  Domain, `splits`, `out`, `mask` and the bound are attn_decode's, the bound against the
+    dequantised cache.  Nothing synchronises."""
+    _need_gpu(q, k_data, k_scale, v_data, v_scale, out)
+    fn = "attn_decode_kv8"
+    lib = _lib.load()
+    if q.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{fn}: q must be a 4-D bf16 or f16 tensor, got {q.dtype} {tuple(q.shape)}")
+    B, n_heads, T, r_qk = q.shape
+    Bk, n_kv, cap, k_pitch = _kv8_planes(fn, k_data, k_scale, q)
+    Bv, n_kv_v, cap_v, v_pitch = _kv8_planes(fn, v_data, v_scale, q)
+    S, r_vo = int(S), int(r_vo)
+    if (Bk, Bv, n_kv_v, cap_v) != (B, B, n_kv, cap) or not 0 <= S <= cap or k_pitch < kv8_pitch(r_qk) or r_vo < 1 or v_pitch < kv8_pitch(r_vo):
+        raise ValueError(f"{fn}: caches of data {tuple(k_data.shape)} / {tuple(v_data.shape)} do not hold S={S} rows of r_qk={r_qk} / "
+                         f"r_vo={r_vo} elements for q {tuple(q.shape)} (one B, n_kv and cap; pitch >= kv8_pitch of the width)")
+    if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
+        raise ValueError(f"{fn}: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit {ATTN_DECODE_COLUMNS} columns")
+    q = q.detach()
+    if not q.is_contiguous():
+        q = q.contiguous()
+    if out is None:
+        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
+    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
+          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
+          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"{fn}: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
+                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    if splits is None:
+        splits = attn_decode_splits(B, n_kv, S, q.device)
+    splits = int(splits)
+    if not 1 <= splits <= ATTN_DECODE_MAX_SPLITS:
+        raise ValueError(f"{fn}: splits={splits} must be within 1 .. {ATTN_DECODE_MAX_SPLITS}")
+    if B == 0 or T == 0:
+        return out
+    ws_bytes = int(lib.mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    masked = (None, 0, 0, 0, 0)
+    if mask is not None:
+        masked = (mask.data_ptr(), *_attn_mask(fn, mask, q, k_scale[:, :, :S, None]))
+    with torch.cuda.device(q.device):
+        check(lib.mdg_attn_decode_kv8(q.data_ptr(), k_data.data_ptr(), k_scale.data_ptr(), v_data.data_ptr(), v_scale.data_ptr(),
+                                      _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo, cap, k_pitch, v_pitch, float(scale),
+                                      1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(), ld_out, _stream(q), *masked),
+              "mdg_attn_decode_kv8")
+    return out
+
+
 def _qk_seq_accum(stem: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim) -> None:
     """The body qk_pair_accum and qk_causal_accum share (stem "qk_pair" / "qk_causal"): the argument checks, with messages under
     the caller's name, the two row matrices as [B*T, width] views, then mdg_<stem>_accum on a workspace of mdg_<stem>_ws_bytes."""

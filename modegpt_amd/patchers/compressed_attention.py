@@ -28,6 +28,11 @@ stock HF modules and gives their attention the compressed semantics, with the el
     batched evaluation, serving loops.  The kernels take the mask as it is (causal=False: the mask alone decides), nothing is
     inspected and nothing syncs; such calls are also counted in ATTN_MASKED.  Any other mask (additive float, another rank, strided
     keys) and modules with a sliding window stay on the interface.
+    With an Fp8KVCache (modegpt_amd/patchers/kv8_cache.py, engine-only: an fp8 KV cache that appends in place) as past_key_values,
+    update() returns views of the fp8 planes instead of tensors: a call the two decode switches would send to attn_decode runs
+    modegpt_amd.ops.attn_decode_kv8 (csrc/attn_decode_kv8.hip) straight from them, counted in ATTN_KERNELS["decode_kv8"]; a prefill
+    into an empty cache attends over the fresh k / v; every other call dequantises the cache (ops.kv8_dequant) and goes on as with
+    any cache.  Without such a cache nothing changes.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -57,7 +62,8 @@ import torch.nn as nn
 logger = logging.getLogger("MoDeGPT")
 PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_gather / by the torch expression
 ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
-ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1)
+ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1);
+#                                         a "decode_kv8" count appears with the first call mdg_attn_decode_kv8 serves (an Fp8KVCache)
 ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
 _DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
@@ -162,6 +168,9 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
     decided from dtype, shape and strides alone -- by the masked entries with causal=False; with MODEGPT_REQUIRE_HIP=1 any other
     mask raises with the reason."""
     B, T = q.shape[0], q.shape[2]
+    kv8 = getattr(k, "is_kv8", False)     # an Fp8KVCache's update returned views of its fp8 planes (they answer shape / stride)
+    if kv8 and k.S == T:                  # prefill into an empty cache: the fresh k / v, exactly as without the cache
+        k, v, kv8 = k.fresh, v.fresh, False
     if os.environ.get("MODEGPT_FUSED_ATTN", "0") == "1":
         mask = None
         why_mask = None
@@ -200,6 +209,15 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
                 decode = (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
                           and T * (n_h // n_kv) <= ops.ATTN_DECODE_COLUMNS)
                 kernel = "decode" if decode else "fwd"
+                if kv8 and decode:        # straight from the fp8 planes; the mask alone decides where there is one
+                    ATTN_KERNELS["decode_kv8"] = ATTN_KERNELS.get("decode_kv8", 0) + 1
+                    if mask is not None:
+                        ATTN_MASKED[kernel] += 1
+                    out = ops.attn_decode_kv8(q, k.data, k.scale, v.data, v.scale, k.S, v.r, float(scaling), causal=mask is None,
+                                              mask=mask, splits=_DECODE_SPLITS)
+                    return out.view(B, T, -1), None
+                if kv8:
+                    k, v, kv8 = k.dequant(), v.dequant(), False
                 ATTN_KERNELS[kernel] += 1
                 if mask is not None:
                     ATTN_MASKED[kernel] += 1
@@ -210,6 +228,8 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
             if os.environ.get("MODEGPT_REQUIRE_HIP", "0") == "1":
                 raise RuntimeError("compressed attention: MODEGPT_FUSED_ATTN=1 and MODEGPT_REQUIRE_HIP=1 but mdg_attn_fwd cannot "
                                    f"serve this call: {why}")
+    if kv8:
+        k, v = k.dequant(), v.dequant()
     ATTN_CALLS["interface"] += 1
     out, weights = _attention_interface(self)(self, q, k, v, attention_mask, dropout=0.0, scaling=scaling, **(extra or {}), **kwargs)
     return out.reshape(B, T, -1).contiguous(), weights
