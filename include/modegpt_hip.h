@@ -61,7 +61,8 @@ extern "C" {
                                 added under 10: mdg_attn_decode_ws_bytes, mdg_attn_decode_splits, mdg_attn_decode (the same product on a split-key decode schedule);
                                 added under 10: mdg_attn_mask_summary_bytes, mdg_attn_mask_summary, mdg_attn_fwd_masked, mdg_attn_decode_masked (both products under a bool mask);
                                 added under 10: mdg_kv8_pitch, mdg_kv8_append, mdg_kv8_dequant, mdg_attn_decode_kv8 (an fp8 KV cache for compressed heads:
-                                its layout, the append, the read-back and the split-key decode product straight from it) */
+                                its layout, the append, the read-back and the split-key decode product straight from it);
+                                added under 10: mdg_attn_fwd_kv8 (mdg_attn_fwd's product, any T, with or without a bool mask, straight from that cache) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -1074,7 +1075,8 @@ int mdg_attn_decode_masked(const void* q, const void* k, const void* v, int dtyp
                            int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream, const void* mask,
                            int Hm, int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride);
 
-/* ------------------------------------------------------------------ fp8 KV cache of compressed heads (csrc/kv8.hip, csrc/attn_decode_kv8.hip)
+/* ------------------------------------------------------------------ fp8 KV cache of compressed heads (csrc/kv8.hip, csrc/attn_decode_kv8.hip,
+ * csrc/attn_fwd_kv8.hip)
  * THE LAYOUT, for K and for V of one layer (additive entries, ABI version unchanged):
  *   data   uint8   [B, n_kv, cap, pitch]  contiguous, 16-byte aligned; pitch = mdg_kv8_pitch(r) = r rounded up to 16 (a caller may
  *                                         pass a larger multiple of 16); elements are OCP e4m3 (torch.float8_e4m3fn); bytes
@@ -1106,7 +1108,19 @@ int mdg_attn_decode_masked(const void* q, const void* k, const void* v, int dtyp
  *                    quantisation itself costs a model is not part of the bound.  mask: NULL, or mdg_attn_decode_masked's bool mask
  *                    with its Hm and byte strides (then pass causal as that entry's caller would).  Refused: what mdg_attn_decode
  *                    refuses, and S > cap, a pitch below mdg_kv8_pitch of its width or no multiple of 16, misaligned planes, a
- *                    plane overlapping out or the workspace. */
+ *                    plane overlapping out or the workspace.
+ *   mdg_attn_fwd_kv8 mdg_attn_fwd's product -- any T, the causal rule j <= i + S - T or every key, GQA, r_qk even and <= 256,
+ *                    r_vo <= 256, out rows of pitch ld_out, determinism -- with K and V read from two caches of this layout that
+ *                    share B, n_kv and cap, the arguments of mdg_attn_decode_kv8.  attn.hip's schedule (a wave per 32 queries of a
+ *                    head, 64-key tiles in LDS shared by 4 units of a kv head) behind a front end of aligned 16-byte loads; the raw
+ *                    bytes are converted with the row's scale on their way into LDS, so both products multiply the exact
+ *                    dequantised values and mdg_attn_fwd's bound holds against them: |out - exact| <= 4 u max_j |v_deq[b, g, j, c]|
+ *                    over the admitted keys, with |scale * logit| <= 20.  Rows at or beyond S are never read.  mask: NULL (then Hm,
+ *                    the strides, summary and summary_bytes are ignored), or mdg_attn_fwd_masked's bool mask with its Hm, byte
+ *                    strides and the tile summary mdg_attn_mask_summary wrote on the same stream (pass causal as that entry's caller
+ *                    would).  Refused, with a message before any device work: what mdg_attn_fwd and mdg_attn_fwd_masked refuse, and
+ *                    S > cap, a pitch below mdg_kv8_pitch of its width or no multiple of 16, misaligned planes, a plane overlapping
+ *                    out or the summary.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
 int64_t mdg_kv8_pitch(int r);
 int mdg_kv8_append(const void* src, int dtype, int64_t B, int n_kv, int64_t T, int r, int64_t src_batch_stride, int64_t src_head_stride,
                    int64_t src_token_stride, void* data, void* scale, int64_t cap, int64_t pitch, int64_t pos, void* stream);
@@ -1117,6 +1131,11 @@ int mdg_attn_decode_kv8(const void* q, const void* k_data, const void* k_scale, 
                         int64_t v_pitch, double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out,
                         void* stream, const void* mask, int Hm, int64_t mask_batch_stride, int64_t mask_head_stride,
                         int64_t mask_query_stride);
+int mdg_attn_fwd_kv8(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale, int dtype,
+                     int64_t B, int64_t T, int64_t S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t cap, int64_t k_pitch,
+                     int64_t v_pitch, double scale, int causal, void* out, int64_t ld_out, void* stream, const void* mask, int Hm,
+                     int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride, const void* summary,
+                     int64_t summary_bytes);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

@@ -1551,16 +1551,10 @@ def kv8_dequant(data: torch.Tensor, scale: torch.Tensor, S: int, r: int, dtype=t
     return out
 
 
-def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor, v_data: torch.Tensor, v_scale: torch.Tensor, S: int,
-                    r_vo: int, scale: float, causal: bool = True, splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
-                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """attn_decode's product with K and V read from fp8 caches (mdg_attn_decode_kv8): q [B, n_heads, T, r_qk] bf16 / f16 as it is, the
-    first S rows of (k_data, k_scale) holding r_qk elements and of (v_data, v_scale) holding r_vo, the two caches sharing B, n_kv
-    and cap -> [B, T, n_heads, r_vo].  Domain, `splits`, `out`, `mask` and the bound are attn_decode's, the bound against the
-    dequantised cache.  Nothing synchronises."""
-    _need_gpu(q, k_data, k_scale, v_data, v_scale, out)
-    fn = "attn_decode_kv8"
-    lib = _lib.load()
+def _kv8_attn_operands(fn: str, q, k_data, k_scale, v_data, v_scale, S, r_vo, out):
+    """The checks attn_decode_kv8 and attn_fwd_kv8 share: q 4-D bf16 / f16, the two caches (one B, n_kv and cap; S rows of r_qk / r_vo
+    elements fit), `out` allocated or held to attn_fwd's contract.  Returns (q contiguous, out, (B, T, S, n_heads, n_kv, r_qk, r_vo),
+    (cap, k_pitch, v_pitch), ld_out)."""
     if q.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"{fn}: q must be a 4-D bf16 or f16 tensor, got {q.dtype} {tuple(q.shape)}")
     B, n_heads, T, r_qk = q.shape
@@ -1570,8 +1564,6 @@ def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor
     if (Bk, Bv, n_kv_v, cap_v) != (B, B, n_kv, cap) or not 0 <= S <= cap or k_pitch < kv8_pitch(r_qk) or r_vo < 1 or v_pitch < kv8_pitch(r_vo):
         raise ValueError(f"{fn}: caches of data {tuple(k_data.shape)} / {tuple(v_data.shape)} do not hold S={S} rows of r_qk={r_qk} / "
                          f"r_vo={r_vo} elements for q {tuple(q.shape)} (one B, n_kv and cap; pitch >= kv8_pitch of the width)")
-    if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
-        raise ValueError(f"{fn}: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit {ATTN_DECODE_COLUMNS} columns")
     q = q.detach()
     if not q.is_contiguous():
         q = q.contiguous()
@@ -1583,6 +1575,23 @@ def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor
         raise ValueError(f"{fn}: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
                          f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
     ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    return q, out, (B, T, S, n_heads, n_kv, r_qk, r_vo), (cap, k_pitch, v_pitch), ld_out
+
+
+def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor, v_data: torch.Tensor, v_scale: torch.Tensor, S: int,
+                    r_vo: int, scale: float, causal: bool = True, splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_decode's product with K and V read from fp8 caches (mdg_attn_decode_kv8): q [B, n_heads, T, r_qk] bf16 / f16 as it is, the
+    first S rows of (k_data, k_scale) holding r_qk elements and of (v_data, v_scale) holding r_vo, the two caches sharing B, n_kv
+    and cap -> [B, T, n_heads, r_vo].  Domain, `splits`, `out`, `mask` and the bound are attn_decode's, the bound against the
+    dequantised cache.  Nothing synchronises."""
+    _need_gpu(q, k_data, k_scale, v_data, v_scale, out)
+    fn = "attn_decode_kv8"
+    lib = _lib.load()
+    q, out, dims, planes, ld_out = _kv8_attn_operands(fn, q, k_data, k_scale, v_data, v_scale, S, r_vo, out)
+    B, T, S, n_heads, n_kv, _, r_vo = dims
+    if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
+        raise ValueError(f"{fn}: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit {ATTN_DECODE_COLUMNS} columns")
     if splits is None:
         splits = attn_decode_splits(B, n_kv, S, q.device)
     splits = int(splits)
@@ -1597,9 +1606,32 @@ def attn_decode_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor
         masked = (mask.data_ptr(), *_attn_mask(fn, mask, q, k_scale[:, :, :S, None]))
     with torch.cuda.device(q.device):
         check(lib.mdg_attn_decode_kv8(q.data_ptr(), k_data.data_ptr(), k_scale.data_ptr(), v_data.data_ptr(), v_scale.data_ptr(),
-                                      _DT[q.dtype], B, T, S, n_heads, n_kv, r_qk, r_vo, cap, k_pitch, v_pitch, float(scale),
-                                      1 if causal else 0, splits, ws.data_ptr(), ws_bytes, out.data_ptr(), ld_out, _stream(q), *masked),
+                                      _DT[q.dtype], *dims, *planes, float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes,
+                                      out.data_ptr(), ld_out, _stream(q), *masked),
               "mdg_attn_decode_kv8")
+    return out
+
+
+def attn_fwd_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor, v_data: torch.Tensor, v_scale: torch.Tensor, S: int,
+                 r_vo: int, scale: float, causal: bool = True, mask: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_fwd's product with K and V read from fp8 caches (mdg_attn_fwd_kv8), any T: the operands of attn_decode_kv8 ->
+    [B, T, n_heads, r_vo].  `causal`, `out`, `mask` (its tile summary is built by a launch of its own on the same stream) and the
+    bound are attn_fwd's, the bound against the dequantised cache; nothing is dequantised into memory.  Nothing synchronises."""
+    _need_gpu(q, k_data, k_scale, v_data, v_scale, out)
+    fn = "attn_fwd_kv8"
+    q, out, dims, planes, ld_out = _kv8_attn_operands(fn, q, k_data, k_scale, v_data, v_scale, S, r_vo, out)
+    B, T, S = dims[:3]
+    masked = (None, 0, 0, 0, 0, None, 0)
+    if mask is not None:
+        Hm, *m_strides = _attn_mask(fn, mask, q, k_scale[:, :, :S, None])
+        summary, n_sum = _attn_mask_summary(mask, B, Hm, T, S, m_strides)
+        masked = (mask.data_ptr(), Hm, *m_strides, summary.data_ptr(), n_sum)
+    with torch.cuda.device(q.device):
+        check(_lib.load().mdg_attn_fwd_kv8(q.data_ptr(), k_data.data_ptr(), k_scale.data_ptr(), v_data.data_ptr(), v_scale.data_ptr(),
+                                           _DT[q.dtype], *dims, *planes, float(scale), 1 if causal else 0, out.data_ptr(), ld_out,
+                                           _stream(q), *masked),
+              "mdg_attn_fwd_kv8")
     return out
 
 

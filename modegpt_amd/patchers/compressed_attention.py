@@ -30,9 +30,11 @@ stock HF modules and gives their attention the compressed semantics, with the el
     keys) and modules with a sliding window stay on the interface.
     With an Fp8KVCache (modegpt_amd/patchers/kv8_cache.py, engine-only: an fp8 KV cache that appends in place) as past_key_values,
     update() returns views of the fp8 planes instead of tensors: a call the two decode switches would send to attn_decode runs
-    modegpt_amd.ops.attn_decode_kv8 (csrc/attn_decode_kv8.hip) straight from them, counted in ATTN_KERNELS["decode_kv8"]; a prefill
-    into an empty cache attends over the fresh k / v; every other call dequantises the cache (ops.kv8_dequant) and goes on as with
-    any cache.  Without such a cache nothing changes.
+    modegpt_amd.ops.attn_decode_kv8 (csrc/attn_decode_kv8.hip) straight from them, counted in ATTN_KERNELS["decode_kv8"]; every
+    other call the fused kernels serve against a non-empty cache (a chunked prefill, a later prompt, a wide verification step, any
+    cached call without the decode switch; masked ones too) runs modegpt_amd.ops.attn_fwd_kv8 (csrc/attn_fwd_kv8.hip) straight
+    from them as well, counted in ATTN_KERNELS["fwd_kv8"]; a prefill into an empty cache attends over the fresh k / v.  Only a call
+    that takes HF's interface dequantises the cache (ops.kv8_dequant).  Without such a cache nothing changes.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -63,7 +65,8 @@ logger = logging.getLogger("MoDeGPT")
 PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_gather / by the torch expression
 ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
 ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1);
-#                                         a "decode_kv8" count appears with the first call mdg_attn_decode_kv8 serves (an Fp8KVCache)
+#                                         a "decode_kv8" / "fwd_kv8" count appears with the first call mdg_attn_decode_kv8 /
+#                                         mdg_attn_fwd_kv8 serves (an Fp8KVCache)
 ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
 _DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
@@ -209,15 +212,13 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
                 decode = (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
                           and T * (n_h // n_kv) <= ops.ATTN_DECODE_COLUMNS)
                 kernel = "decode" if decode else "fwd"
-                if kv8 and decode:        # straight from the fp8 planes; the mask alone decides where there is one
-                    ATTN_KERNELS["decode_kv8"] = ATTN_KERNELS.get("decode_kv8", 0) + 1
+                if kv8:                   # straight from the fp8 planes; the mask alone decides where there is one
+                    ATTN_KERNELS[kernel + "_kv8"] = ATTN_KERNELS.get(kernel + "_kv8", 0) + 1
                     if mask is not None:
                         ATTN_MASKED[kernel] += 1
-                    out = ops.attn_decode_kv8(q, k.data, k.scale, v.data, v.scale, k.S, v.r, float(scaling), causal=mask is None,
-                                              mask=mask, splits=_DECODE_SPLITS)
+                    fn, own = (ops.attn_decode_kv8, {"splits": _DECODE_SPLITS}) if decode else (ops.attn_fwd_kv8, {})
+                    out = fn(q, k.data, k.scale, v.data, v.scale, k.S, v.r, float(scaling), causal=mask is None, mask=mask, **own)
                     return out.view(B, T, -1), None
-                if kv8:
-                    k, v, kv8 = k.dequant(), v.dequant(), False
                 ATTN_KERNELS[kernel] += 1
                 if mask is not None:
                     ATTN_MASKED[kernel] += 1

@@ -8,9 +8,11 @@ token) -- the layout of include/modegpt_hip.h -- and never copies itself on a de
 A layer takes its widths (r_qk, r_vo: they differ per layer in a compressed model), batch, kv heads, dtype and device from its first
 update, as transformers' DynamicLayer does.  update() appends the new rows with ops.kv8_append (csrc/kv8.hip) and returns two
 Fp8Rows -- (data, scale, S, r) views of the layer's K and V planes -- instead of tensors.  The forwards of
-patchers/compressed_attention.py recognise them: with MODEGPT_FUSED_ATTN=1 and MODEGPT_FUSED_ATTN_DECODE=1 a call in the decode
-kernel's domain runs ops.attn_decode_kv8 straight from the fp8 planes; a prefill into an empty cache attends over the fresh k / v it
-was given; every other call reads the cache back with ops.kv8_dequant and goes on as it would have with a DynamicCache.
+patchers/compressed_attention.py recognise them: with MODEGPT_FUSED_ATTN=1 every call the fused kernels serve reads the fp8 planes
+directly -- ops.attn_decode_kv8 for a call in the decode kernel's domain when MODEGPT_FUSED_ATTN_DECODE=1 is set as well,
+ops.attn_fwd_kv8 for every other one (chunked prefill, later prompts, wide verification steps) -- and a prefill into an empty cache
+attends over the fresh k / v it was given.  Only a call that takes HF's attention interface reads the cache back with
+ops.kv8_dequant and goes on as it would have with a DynamicCache.
 
 Engine-only: this module needs libmodegpt_hip.so and a GPU, and is not shipped next to a checkpoint.  Beam search
 (reorder_cache) is refused."""
