@@ -62,7 +62,9 @@ extern "C" {
                                 added under 10: mdg_attn_mask_summary_bytes, mdg_attn_mask_summary, mdg_attn_fwd_masked, mdg_attn_decode_masked (both products under a bool mask);
                                 added under 10: mdg_kv8_pitch, mdg_kv8_append, mdg_kv8_dequant, mdg_attn_decode_kv8 (an fp8 KV cache for compressed heads:
                                 its layout, the append, the read-back and the split-key decode product straight from it);
-                                added under 10: mdg_attn_fwd_kv8 (mdg_attn_fwd's product, any T, with or without a bool mask, straight from that cache) */
+                                added under 10: mdg_attn_fwd_kv8 (mdg_attn_fwd's product, any T, with or without a bool mask, straight from that cache);
+                                added under 10: mdg_kv8_paged_append, mdg_kv8_paged_dequant, mdg_attn_decode_paged8 (that cache in pages behind a block table,
+                                lengths and positions on the device) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -1136,6 +1138,58 @@ int mdg_attn_fwd_kv8(const void* q, const void* k_data, const void* k_scale, con
                      int64_t v_pitch, double scale, int causal, void* out, int64_t ld_out, void* stream, const void* mask, int Hm,
                      int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride, const void* summary,
                      int64_t summary_bytes);
+
+/* ------------------------------------------------------------------ paged fp8 KV cache (csrc/kv8_paged.hip, csrc/attn_decode_paged8.hip)
+ * THE PAGED LAYOUT, for K and for V of one layer (additive entries, ABI version unchanged).  Rows are exactly the rows of the layout
+ * above -- elements, zero padding bytes and scales; nothing about a row changes -- but memory is handed out in pages:
+ *   pool   data  uint8   [n_pages, n_kv, page, pitch]  contiguous, 16-byte aligned; pitch a multiple of 16, >= mdg_kv8_pitch(r)
+ *          scale float32 [n_pages, n_kv, page]         contiguous, 4-byte aligned
+ *                        page is a positive multiple of 64 (the key tile), so a 64-key tile never straddles two pages
+ *   block_table  int32 [B, table_len]  on the device: entry [b, p] is the page that holds keys p page .. p page + page - 1 of
+ *                        sequence b; the K pool and the V pool of a layer share it
+ *   seq_lens     int32 [B]             on the device: the number of keys S_b of each sequence, clamped on the device to
+ *                        0 .. table_len * page; S_b == 0 is an empty slot, its queries get zeros
+ * A call reads only table entries p < ceil(S_b / page) and only rows < S_b of their pages; every entry it may read must lie in
+ * [0, n_pages): the caller's contract (the kernels clamp an entry into that range, for memory safety only).  Nothing reads
+ * seq_lens, pos or the table on the host and nothing synchronises, so the arguments of a decode step do not change from step to step.
+ *   mdg_kv8_paged_append   ONE launch quantises T new rows of a K source (r_k wide) and of a V source (r_v wide), each bf16 / f16,
+ *                    logical [B, n_kv, T, r] with its own strides in ELEMENTS and a unit last stride as mdg_kv8_append takes them,
+ *                    into positions pos[b] .. pos[b] + T - 1 of sequence b (pos int32 [B] on the device): row pos[b] + t lands in page
+ *                    block_table[b][(pos[b] + t) / page] at offset (pos[b] + t) % page, crossing page boundaries as it goes.  The
+ *                    per-row work is mdg_kv8_append's and gives the same bytes and the same scale for the same row.  Positions
+ *                    outside 0 .. table_len * page - 1 are not written.  Refused: a dtype other than bf16 / f16, a negative extent,
+ *                    a width outside 1..256, a pitch below mdg_kv8_pitch of its width or no multiple of 16, page no positive
+ *                    multiple of 64, negative n_pages or table_len, products that overflow, a NULL pointer, a misaligned table or
+ *                    pos (4), data (16) or scale (4), a pool plane overlapping a source, the table, pos or another plane.
+ *                    B, n_kv or T == 0 launches nothing and returns MDG_OK.
+ *   mdg_kv8_paged_dequant  gathers rows 0 .. S - 1 (a host S, the same for every sequence, <= table_len * page) of one pool into
+ *                    a contiguous bf16 / f16 out [B, n_kv, S, r]; exact as mdg_kv8_dequant is.  The same refusals, with out in
+ *                    place of the sources.  B, n_kv or S == 0 launches nothing and returns MDG_OK.
+ *   mdg_attn_decode_paged8  mdg_attn_decode_kv8's product and domain -- T * G <= 32, r_qk even and <= 256, r_vo <= 256, column map,
+ *                    workspace (mdg_attn_decode_ws_bytes), combine kernel, optional bool mask, out rows -- from two pools.  Workgroup
+ *                    (b, kv head, split) reads S_b itself and cuts its chunk of L_b = 64 ceil(ceil(S_b / 64) / splits) keys, the split
+ *                    rule of mdg_attn_decode_kv8 per sequence; a chunk at or beyond S_b enters no tile.  causal: query i of sequence
+ *                    b sees keys j <= i + S_b - T (a query with no admitted key gets zeros).  For every sequence the result is
+ *                    BIT-IDENTICAL to mdg_attn_decode_kv8 on that sequence alone (B = 1, S = S_b, the same rows laid contiguously,
+ *                    the same splits), so that entry's bound holds per sequence.  max_S (0 .. table_len * page) is the mask's last
+ *                    extent and what a caller bases the split count on (mdg_attn_decode_splits); it bounds nothing else, and keys
+ *                    at or beyond it are not admitted under a mask.  Refused: what mdg_attn_decode_kv8 refuses (but causal with few
+ *                    keys: that is decided per sequence on the device), page no positive multiple of 64, negative n_pages or
+ *                    table_len, max_S outside 0 .. table_len * page, a NULL or misaligned (4) table or seq_lens, pools, table or
+ *                    seq_lens overlapping out or the workspace, products that overflow.  B == 0 or T == 0 launches nothing and
+ *                    returns MDG_OK. */
+int mdg_kv8_paged_append(const void* k_src, const void* v_src, int dtype, int64_t B, int n_kv, int64_t T, int r_k, int r_v,
+                         int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride,
+                         int64_t v_head_stride, int64_t v_token_stride, void* k_data, void* k_scale, void* v_data, void* v_scale,
+                         int64_t n_pages, int64_t page, int64_t k_pitch, int64_t v_pitch, const void* block_table, int64_t table_len,
+                         const void* pos, void* stream);
+int mdg_kv8_paged_dequant(const void* data, const void* scale, int dtype, int64_t B, int n_kv, int64_t S, int r, int64_t n_pages,
+                          int64_t page, int64_t pitch, const void* block_table, int64_t table_len, void* out, void* stream);
+int mdg_attn_decode_paged8(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale, int dtype,
+                           int64_t B, int64_t T, int64_t max_S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t n_pages, int64_t page,
+                           int64_t k_pitch, int64_t v_pitch, const void* block_table, int64_t table_len, const void* seq_lens,
+                           double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream,
+                           const void* mask, int Hm, int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

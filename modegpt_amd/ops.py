@@ -1635,6 +1635,144 @@ def attn_fwd_kv8(q: torch.Tensor, k_data: torch.Tensor, k_scale: torch.Tensor, v
     return out
 
 
+def _kv8_pool(fn: str, pool, like=None):
+    """The checks of one pool of the paged fp8 cache, a (data, scale) pair (data uint8 [n_pages, n_kv, page, pitch], scale float32
+    [n_pages, n_kv, page]; page a positive multiple of 64): returns (data, scale, n_pages, n_kv, page, pitch)."""
+    data, scale = pool
+    n_pages, n_kv, page, pitch = _kv8_planes(fn, data, scale, like)
+    if page <= 0 or page % 64:
+        raise ValueError(f"{fn}: page={page} of a pool {tuple(data.shape)} must be a positive multiple of 64")
+    return data, scale, n_pages, n_kv, page, pitch
+
+
+def _kv8_table(fn: str, block_table, vec, like, what):
+    """block_table int32 [B, table_len] and a per-sequence int32 [B] vector (seq_lens or pos), contiguous on `like`'s device:
+    returns (B, table_len)."""
+    for name, t, dim in (("block_table", block_table, 2), (what, vec, 1)):
+        if t.dtype != torch.int32 or t.dim() != dim or not t.is_contiguous() or t.device != like.device:
+            raise ValueError(f"{fn}: {name} must be a contiguous int32 {dim}-D tensor on {like.device}, got {t.dtype} {tuple(t.shape)} "
+                             f"on {t.device}")
+    if vec.shape[0] != block_table.shape[0]:
+        raise ValueError(f"{fn}: {what} {tuple(vec.shape)} does not fit block_table {tuple(block_table.shape)}")
+    return tuple(block_table.shape)
+
+
+def kv8_paged_append(k_src: torch.Tensor, v_src: torch.Tensor, k_pool, v_pool, block_table: torch.Tensor, pos: torch.Tensor) -> None:
+    """Quantise the T rows of k_src [B, n_kv, T, r_qk] and of v_src [B, n_kv, T, r_vo] (bf16 / f16, any batch / head / token strides,
+    unit last stride) into the paged fp8 cache in ONE launch (mdg_kv8_paged_append; layout in include/modegpt_hip.h): row t of
+    sequence b goes to position pos[b] + t, page block_table[b][(pos[b] + t) // page].  A pool is a (data, scale) pair; block_table
+    int32 [B, table_len] and pos int32 [B] live on the device and are not read on the host.  Nothing synchronises."""
+    fn = "kv8_paged_append"
+    _need_gpu(k_src, v_src, *k_pool, *v_pool, block_table, pos)
+    for name, src in (("k_src", k_src), ("v_src", v_src)):
+        if src.dim() != 4 or src.dtype not in (torch.bfloat16, torch.float16) or (src.shape[3] > 1 and src.stride(3) != 1):
+            raise ValueError(f"{fn}: {name} must be a 4-D bf16 or f16 tensor with a contiguous last dimension, got {src.dtype} "
+                             f"{tuple(src.shape)} strides {src.stride()}")
+    kd, ks, n_pages, n_kv, page, k_pitch = _kv8_pool(fn, k_pool, k_src)
+    vd, vs, n_pages_v, n_kv_v, page_v, v_pitch = _kv8_pool(fn, v_pool, k_src)
+    B, table_len = _kv8_table(fn, block_table, pos, k_src, "pos")
+    T, r_k, r_v = k_src.shape[2], k_src.shape[3], v_src.shape[3]
+    if (k_src.dtype != v_src.dtype or v_src.device != k_src.device or tuple(k_src.shape[:3]) != (B, n_kv, T)
+            or tuple(v_src.shape[:3]) != (B, n_kv, T) or (n_pages_v, n_kv_v, page_v) != (n_pages, n_kv, page)
+            or k_pitch < kv8_pitch(r_k) or v_pitch < kv8_pitch(r_v)):
+        raise ValueError(f"{fn}: k_src {tuple(k_src.shape)} / v_src {tuple(v_src.shape)} do not fit pools of data {tuple(kd.shape)} / "
+                         f"{tuple(vd.shape)} and a table {tuple(block_table.shape)} (one dtype, B, n_kv, T, n_pages and page; pitch >= "
+                         f"kv8_pitch of the width)")
+    k_src, v_src = k_src.detach(), v_src.detach()
+    with torch.cuda.device(k_src.device):
+        check(_lib.load().mdg_kv8_paged_append(k_src.data_ptr(), v_src.data_ptr(), _DT[k_src.dtype], B, n_kv, T, r_k, r_v,
+                                               k_src.stride(0), k_src.stride(1), k_src.stride(2), v_src.stride(0), v_src.stride(1),
+                                               v_src.stride(2), kd.data_ptr(), ks.data_ptr(), vd.data_ptr(), vs.data_ptr(), n_pages, page,
+                                               k_pitch, v_pitch, block_table.data_ptr(), table_len, pos.data_ptr(), _stream(k_src)),
+              "mdg_kv8_paged_append")
+
+
+def kv8_paged_dequant(pool, block_table: torch.Tensor, S: int, r: int, dtype=torch.bfloat16,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows 0 .. S - 1 of every sequence of one pool of the paged fp8 cache as a contiguous [B, n_kv, S, r] tensor of `dtype`
+    (mdg_kv8_paged_dequant): e4m3 * scale, exact in bf16.  `out`: a caller-owned contiguous tensor of that shape and dtype."""
+    fn = "kv8_paged_dequant"
+    _need_gpu(*pool, block_table, out)
+    data, scale, n_pages, n_kv, page, pitch = _kv8_pool(fn, pool)
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or not block_table.is_contiguous() or block_table.device != data.device:
+        raise ValueError(f"{fn}: block_table must be a contiguous int32 2-D tensor on {data.device}, got {block_table.dtype} "
+                         f"{tuple(block_table.shape)} on {block_table.device}")
+    B, table_len = block_table.shape
+    S, r = int(S), int(r)
+    if dtype not in (torch.bfloat16, torch.float16) or not 0 <= S <= table_len * page or r < 1 or pitch < kv8_pitch(r):
+        raise ValueError(f"{fn}: S={S}, r={r}, {dtype} do not fit a pool of data {tuple(data.shape)} behind a table "
+                         f"{tuple(block_table.shape)} (bf16 or f16)")
+    if out is None:
+        out = torch.empty(B, n_kv, S, r, dtype=dtype, device=data.device)
+    elif tuple(out.shape) != (B, n_kv, S, r) or out.dtype != dtype or out.device != data.device or not out.is_contiguous():
+        raise ValueError(f"{fn}: out must be a contiguous {dtype} [{B}, {n_kv}, {S}, {r}] on {data.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(data.device):
+        check(_lib.load().mdg_kv8_paged_dequant(data.data_ptr(), scale.data_ptr(), _DT[dtype], B, n_kv, S, r, n_pages, page, pitch,
+                                                block_table.data_ptr(), table_len, out.data_ptr(), _stream(data)),
+              "mdg_kv8_paged_dequant")
+    return out
+
+
+def attn_decode_paged8(q: torch.Tensor, k_pool, v_pool, block_table: torch.Tensor, seq_lens: torch.Tensor, r_vo: int, scale: float,
+                       causal: bool = True, max_S: Optional[int] = None, splits: Optional[int] = None,
+                       out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_decode_kv8's product from the paged fp8 cache (mdg_attn_decode_paged8): q [B, n_heads, T, r_qk] bf16 / f16, the two pools
+    ((data, scale) pairs sharing n_pages, n_kv and page), block_table int32 [B, table_len] and seq_lens int32 [B] on the device ->
+    [B, T, n_heads, r_vo].  Every sequence attends over its own seq_lens[b] keys (causal: query i sees j <= i + seq_lens[b] - T; an
+    empty sequence gets zeros) and gets the bits attn_decode_kv8 gives that sequence alone with the same `splits`.  `max_S`
+    (default table_len * page): the mask's last extent [B or 1, 1 or n_heads, T, max_S] and what `splits=None` asks
+    attn_decode_splits with.  Nothing is read on the host and nothing synchronises: a step's arguments do not change."""
+    fn = "attn_decode_paged8"
+    _need_gpu(q, *k_pool, *v_pool, block_table, seq_lens, out)
+    lib = _lib.load()
+    if q.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{fn}: q must be a 4-D bf16 or f16 tensor, got {q.dtype} {tuple(q.shape)}")
+    B, n_heads, T, r_qk = q.shape
+    kd, ks, n_pages, n_kv, page, k_pitch = _kv8_pool(fn, k_pool, q)
+    vd, vs, n_pages_v, n_kv_v, page_v, v_pitch = _kv8_pool(fn, v_pool, q)
+    Bt, table_len = _kv8_table(fn, block_table, seq_lens, q, "seq_lens")
+    r_vo = int(r_vo)
+    max_S = table_len * page if max_S is None else int(max_S)
+    if ((n_pages_v, n_kv_v, page_v) != (n_pages, n_kv, page) or Bt != B or not 0 <= max_S <= table_len * page
+            or k_pitch < kv8_pitch(r_qk) or r_vo < 1 or v_pitch < kv8_pitch(r_vo)):
+        raise ValueError(f"{fn}: pools of data {tuple(kd.shape)} / {tuple(vd.shape)} behind a table {tuple(block_table.shape)} do not "
+                         f"hold max_S={max_S} rows of r_qk={r_qk} / r_vo={r_vo} elements for q {tuple(q.shape)} (one n_pages, n_kv and "
+                         f"page; one B; pitch >= kv8_pitch of the width)")
+    if n_kv <= 0 or n_heads % n_kv or T * (n_heads // n_kv) > ATTN_DECODE_COLUMNS:
+        raise ValueError(f"{fn}: T={T} queries x a group of n_heads={n_heads} / n_kv={n_kv} heads must fit {ATTN_DECODE_COLUMNS} columns")
+    q = q.detach()
+    if not q.is_contiguous():
+        q = q.contiguous()
+    if out is None:
+        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
+    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
+          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
+          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"{fn}: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
+                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    if splits is None:
+        splits = attn_decode_splits(B, n_kv, max_S, q.device)
+    splits = int(splits)
+    if not 1 <= splits <= ATTN_DECODE_MAX_SPLITS:
+        raise ValueError(f"{fn}: splits={splits} must be within 1 .. {ATTN_DECODE_MAX_SPLITS}")
+    if B == 0 or T == 0:
+        return out
+    ws_bytes = int(lib.mdg_attn_decode_ws_bytes(B, T, n_heads, r_vo, splits))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device)
+    masked = (None, 0, 0, 0, 0)
+    if mask is not None:
+        masked = (mask.data_ptr(), *_attn_mask(fn, mask, q, torch.empty(B, n_kv, max_S, 0, device="meta")))   # its keys: max_S
+    with torch.cuda.device(q.device):
+        check(lib.mdg_attn_decode_paged8(q.data_ptr(), kd.data_ptr(), ks.data_ptr(), vd.data_ptr(), vs.data_ptr(), _DT[q.dtype], B, T, max_S,
+                                         n_heads, n_kv, r_qk, r_vo, n_pages, page, k_pitch, v_pitch, block_table.data_ptr(), table_len,
+                                         seq_lens.data_ptr(), float(scale), 1 if causal else 0, splits, ws.data_ptr(), ws_bytes,
+                                         out.data_ptr(), ld_out, _stream(q), *masked),
+              "mdg_attn_decode_paged8")
+    return out
+
+
 def _qk_seq_accum(stem: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim) -> None:
     """The body qk_pair_accum and qk_causal_accum share (stem "qk_pair" / "qk_causal"): the argument checks, with messages under
     the caller's name, the two row matrices as [B*T, width] views, then mdg_<stem>_accum on a workspace of mdg_<stem>_ws_bytes."""
