@@ -64,7 +64,8 @@ extern "C" {
                                 its layout, the append, the read-back and the split-key decode product straight from it);
                                 added under 10: mdg_attn_fwd_kv8 (mdg_attn_fwd's product, any T, with or without a bool mask, straight from that cache);
                                 added under 10: mdg_kv8_paged_append, mdg_kv8_paged_dequant, mdg_attn_decode_paged8 (that cache in pages behind a block table,
-                                lengths and positions on the device) */
+                                lengths and positions on the device);
+                                added under 10: mdg_attn_fwd_paged8 (mdg_attn_fwd_kv8's product, any T, with or without a bool mask, straight from the pages) */
 
 enum mdg_status {
   MDG_OK = 0,
@@ -1139,7 +1140,8 @@ int mdg_attn_fwd_kv8(const void* q, const void* k_data, const void* k_scale, con
                      int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride, const void* summary,
                      int64_t summary_bytes);
 
-/* ------------------------------------------------------------------ paged fp8 KV cache (csrc/kv8_paged.hip, csrc/attn_decode_paged8.hip)
+/* ------------------------------------------------------------------ paged fp8 KV cache (csrc/kv8_paged.hip, csrc/attn_decode_paged8.hip,
+ * csrc/attn_fwd_paged8.hip)
  * THE PAGED LAYOUT, for K and for V of one layer (additive entries, ABI version unchanged).  Rows are exactly the rows of the layout
  * above -- elements, zero padding bytes and scales; nothing about a row changes -- but memory is handed out in pages:
  *   pool   data  uint8   [n_pages, n_kv, page, pitch]  contiguous, 16-byte aligned; pitch a multiple of 16, >= mdg_kv8_pitch(r)
@@ -1177,7 +1179,23 @@ int mdg_attn_fwd_kv8(const void* q, const void* k_data, const void* k_scale, con
  *                    keys: that is decided per sequence on the device), page no positive multiple of 64, negative n_pages or
  *                    table_len, max_S outside 0 .. table_len * page, a NULL or misaligned (4) table or seq_lens, pools, table or
  *                    seq_lens overlapping out or the workspace, products that overflow.  B == 0 or T == 0 launches nothing and
- *                    returns MDG_OK. */
+ *                    returns MDG_OK.
+ *   mdg_attn_fwd_paged8  mdg_attn_fwd_kv8's product and domain -- any T, GQA, r_qk even and <= 256, r_vo <= 256, out rows of pitch
+ *                    ld_out, an optional bool mask with the tile summary mdg_attn_mask_summary wrote on the same stream, determinism
+ *                    -- from two pools, the arguments of mdg_attn_decode_paged8 without splits / ws, with summary / summary_bytes.
+ *                    The grid depends on B, n_kv and T only; every workgroup reads S_b itself.  causal: query i of sequence b sees
+ *                    keys j <= i + S_b - T; otherwise every key j < S_b.  A query with no admitted key, and every query of an
+ *                    empty slot, gets zeros.  Keys at or beyond S_b are never requested and table entries at or beyond
+ *                    ceil(S_b / page) never read; a window of 256 table entries is staged in LDS, so no row address waits on a
+ *                    table load from memory.  For every sequence the result is BIT-IDENTICAL to mdg_attn_fwd_kv8 on that sequence
+ *                    alone (B = 1, S = S_b, the same rows laid contiguously), so that entry's bound holds per sequence.  max_S
+ *                    (0 .. table_len * page) is the mask's last extent (mask [B or 1, Hm, T, max_S], summary over max_S keys) and
+ *                    bounds nothing else; under a mask keys at or beyond min(S_b, max_S) are not admitted (pass causal as
+ *                    mdg_attn_fwd_masked's caller would).  Refused, with a message before any device work: what mdg_attn_fwd_kv8
+ *                    refuses (but causal with few keys: that is decided per sequence on the device), page no positive multiple of
+ *                    64, negative n_pages or table_len, max_S outside 0 .. table_len * page, a NULL or misaligned (4) table or
+ *                    seq_lens, a short summary, pools, table, seq_lens or mask overlapping out or the summary, products that
+ *                    overflow.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
 int mdg_kv8_paged_append(const void* k_src, const void* v_src, int dtype, int64_t B, int n_kv, int64_t T, int r_k, int r_v,
                          int64_t k_batch_stride, int64_t k_head_stride, int64_t k_token_stride, int64_t v_batch_stride,
                          int64_t v_head_stride, int64_t v_token_stride, void* k_data, void* k_scale, void* v_data, void* v_scale,
@@ -1190,6 +1208,12 @@ int mdg_attn_decode_paged8(const void* q, const void* k_data, const void* k_scal
                            int64_t k_pitch, int64_t v_pitch, const void* block_table, int64_t table_len, const void* seq_lens,
                            double scale, int causal, int splits, void* ws, int64_t ws_bytes, void* out, int64_t ld_out, void* stream,
                            const void* mask, int Hm, int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride);
+int mdg_attn_fwd_paged8(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale, int dtype,
+                        int64_t B, int64_t T, int64_t max_S, int n_heads, int n_kv, int r_qk, int r_vo, int64_t n_pages, int64_t page,
+                        int64_t k_pitch, int64_t v_pitch, const void* block_table, int64_t table_len, const void* seq_lens,
+                        double scale, int causal, void* out, int64_t ld_out, void* stream, const void* mask, int Hm,
+                        int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride, const void* summary,
+                        int64_t summary_bytes);
 
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)

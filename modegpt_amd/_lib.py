@@ -142,6 +142,8 @@ SIGNATURES = {
     "mdg_kv8_paged_dequant": (_i32, [_ptr, _ptr, _i32, _i64, _i32, _i64, _i32, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr]),
     "mdg_attn_decode_paged8": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
                                        _ptr, _i64, _ptr, _f64, _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64]),
+    "mdg_attn_fwd_paged8": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
+                                    _ptr, _i64, _ptr, _f64, _i32, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64, _ptr, _i64]),
     "mdg_comm_unique_id": (_i32, [_ptr]),
     "mdg_comm_init": (_i32, [C.POINTER(_ptr), _i32, _i32, _ptr]),
     "mdg_allgather_layers": (_i32, [_ptr, _ptr, _sz, _ptr, _ptr]),

@@ -1773,6 +1773,55 @@ def attn_decode_paged8(q: torch.Tensor, k_pool, v_pool, block_table: torch.Tenso
     return out
 
 
+def attn_fwd_paged8(q: torch.Tensor, k_pool, v_pool, block_table: torch.Tensor, seq_lens: torch.Tensor, r_vo: int, scale: float,
+                    causal: bool = True, max_S: Optional[int] = None, mask: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_fwd_kv8's product from the paged fp8 cache (mdg_attn_fwd_paged8), any T: the operands of attn_decode_paged8 ->
+    [B, T, n_heads, r_vo].  Every sequence attends over its own seq_lens[b] keys (causal: query i sees j <= i + seq_lens[b] - T; a
+    query without a key and an empty sequence get zeros) and gets the bits attn_fwd_kv8 gives that sequence alone.  `max_S` (default
+    table_len * page): the last extent of `mask` [B or 1, 1 or n_heads, T, max_S], whose tile summary is built by a launch of its own
+    on the same stream; under a mask keys at or beyond it are not admitted.  Nothing is gathered or dequantised into memory, nothing
+    is read on the host and nothing synchronises."""
+    fn = "attn_fwd_paged8"
+    _need_gpu(q, *k_pool, *v_pool, block_table, seq_lens, out)
+    if q.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{fn}: q must be a 4-D bf16 or f16 tensor, got {q.dtype} {tuple(q.shape)}")
+    B, n_heads, T, r_qk = q.shape
+    kd, ks, n_pages, n_kv, page, k_pitch = _kv8_pool(fn, k_pool, q)
+    vd, vs, n_pages_v, n_kv_v, page_v, v_pitch = _kv8_pool(fn, v_pool, q)
+    Bt, table_len = _kv8_table(fn, block_table, seq_lens, q, "seq_lens")
+    r_vo = int(r_vo)
+    max_S = table_len * page if max_S is None else int(max_S)
+    if ((n_pages_v, n_kv_v, page_v) != (n_pages, n_kv, page) or Bt != B or not 0 <= max_S <= table_len * page
+            or k_pitch < kv8_pitch(r_qk) or r_vo < 1 or v_pitch < kv8_pitch(r_vo)):
+        raise ValueError(f"{fn}: pools of data {tuple(kd.shape)} / {tuple(vd.shape)} behind a table {tuple(block_table.shape)} do not "
+                         f"hold max_S={max_S} rows of r_qk={r_qk} / r_vo={r_vo} elements for q {tuple(q.shape)} (one n_pages, n_kv and "
+                         f"page; one B; pitch >= kv8_pitch of the width)")
+    q = q.detach()
+    if not q.is_contiguous():
+        q = q.contiguous()
+    if out is None:
+        out = torch.empty(B, T, n_heads, r_vo, dtype=q.dtype, device=q.device)
+    elif (tuple(out.shape) != (B, T, n_heads, r_vo) or out.dtype != q.dtype or out.device != q.device
+          or (r_vo > 1 and out.stride(3) != 1) or (n_heads > 1 and out.stride(2) != r_vo)
+          or (B > 1 and T > 1 and out.stride(0) != T * out.stride(1))):
+        raise ValueError(f"{fn}: out must be a {q.dtype} [{B}, {T}, {n_heads}, {r_vo}] on {q.device} with contiguous heads and rows "
+                         f"of one pitch, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    ld_out = out.stride(1) if T > 1 else out.stride(0) if B > 1 else n_heads * r_vo
+    masked = (None, 0, 0, 0, 0, None, 0)
+    if mask is not None:
+        Hm, *m_strides = _attn_mask(fn, mask, q, torch.empty(B, n_kv, max_S, 0, device="meta"))   # its keys: max_S
+        summary, n_sum = _attn_mask_summary(mask, B, Hm, T, max_S, m_strides)
+        masked = (mask.data_ptr(), Hm, *m_strides, summary.data_ptr(), n_sum)
+    with torch.cuda.device(q.device):
+        check(_lib.load().mdg_attn_fwd_paged8(q.data_ptr(), kd.data_ptr(), ks.data_ptr(), vd.data_ptr(), vs.data_ptr(), _DT[q.dtype], B, T,
+                                              max_S, n_heads, n_kv, r_qk, r_vo, n_pages, page, k_pitch, v_pitch, block_table.data_ptr(),
+                                              table_len, seq_lens.data_ptr(), float(scale), 1 if causal else 0, out.data_ptr(), ld_out,
+                                              _stream(q), *masked),
+              "mdg_attn_fwd_paged8")
+    return out
+
+
 def _qk_seq_accum(stem: str, pair, pair_raw, q_rows, k_rows, B, T, n_heads, n_kv, head_dim) -> None:
     """The body qk_pair_accum and qk_causal_accum share (stem "qk_pair" / "qk_causal"): the argument checks, with messages under
     the caller's name, the two row matrices as [B*T, width] views, then mdg_<stem>_accum on a workspace of mdg_<stem>_ws_bytes."""

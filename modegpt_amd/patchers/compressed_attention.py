@@ -37,8 +37,10 @@ stock HF modules and gives their attention the compressed semantics, with the el
     that takes HF's interface dequantises the cache (ops.kv8_dequant).  Without such a cache nothing changes.
     With a PagedFp8KVCache (modegpt_amd/patchers/kv8_paged_cache.py, engine-only: the same rows in pages behind a block table, the
     lengths on the device) a call the two decode switches would send to attn_decode_kv8 runs modegpt_amd.ops.attn_decode_paged8
-    (csrc/attn_decode_paged8.hip) straight from the pages, counted in ATTN_KERNELS["decode_paged8"]; a prefill into an empty cache
-    attends over the fresh k / v; every other cached call gathers the rows (ops.kv8_paged_dequant) and goes on as with tensors.
+    (csrc/attn_decode_paged8.hip) straight from the pages, counted in ATTN_KERNELS["decode_paged8"]; every other call the fused
+    kernels serve against a non-empty cache (masked ones too) runs modegpt_amd.ops.attn_fwd_paged8 (csrc/attn_fwd_paged8.hip)
+    straight from the pages as well, counted in ATTN_KERNELS["fwd_paged8"]; a prefill into an empty cache attends over the fresh
+    k / v.  Only a call that takes HF's interface gathers the rows (ops.kv8_paged_dequant).
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -70,8 +72,8 @@ PATH_CALLS = {"hip": 0, "torch": 0}     # rope/norm chains served by mdg_rope_ga
 ATTN_CALLS = {"hip": 0, "interface": 0}  # attention products served by the engine's kernels / by HF's attention interface
 ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_fwd / by mdg_attn_decode (MODEGPT_FUSED_ATTN_DECODE=1);
 #                                         a "decode_kv8" / "fwd_kv8" count appears with the first call mdg_attn_decode_kv8 /
-#                                         mdg_attn_fwd_kv8 serves (an Fp8KVCache), a "decode_paged8" count with the first call
-#                                         mdg_attn_decode_paged8 serves (a PagedFp8KVCache)
+#                                         mdg_attn_fwd_kv8 serves (an Fp8KVCache), a "decode_paged8" / "fwd_paged8" count with the
+#                                         first call mdg_attn_decode_paged8 / mdg_attn_fwd_paged8 serves (a PagedFp8KVCache)
 ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
 _DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
@@ -217,15 +219,14 @@ def _attend(self, q, k, v, attention_mask, scaling, kwargs, extra=None, want_wei
                 decode = (os.environ.get("MODEGPT_FUSED_ATTN_DECODE", "0") == "1" and n_h % n_kv == 0
                           and T * (n_h // n_kv) <= ops.ATTN_DECODE_COLUMNS)
                 kernel = "decode" if decode else "fwd"
-                if kv8 and getattr(k, "is_paged", False):
-                    if decode:            # straight from the pages; every sequence's own length is read on the device
-                        ATTN_KERNELS["decode_paged8"] = ATTN_KERNELS.get("decode_paged8", 0) + 1
-                        if mask is not None:
-                            ATTN_MASKED["decode"] += 1
-                        out = ops.attn_decode_paged8(q, k.pool, v.pool, k.block_table, k.seq_lens, v.r, float(scaling),
-                                                     causal=mask is None, max_S=k.S, splits=_DECODE_SPLITS, mask=mask)
-                        return out.view(B, T, -1), None
-                    k, v, kv8 = k.dequant(), v.dequant(), False     # every other cached call: gathered, then as with tensors
+                if kv8 and getattr(k, "is_paged", False):     # straight from the pages; every sequence's own length is read on the device
+                    ATTN_KERNELS[kernel + "_paged8"] = ATTN_KERNELS.get(kernel + "_paged8", 0) + 1
+                    if mask is not None:
+                        ATTN_MASKED[kernel] += 1
+                    fn, own = (ops.attn_decode_paged8, {"splits": _DECODE_SPLITS}) if decode else (ops.attn_fwd_paged8, {})
+                    out = fn(q, k.pool, v.pool, k.block_table, k.seq_lens, v.r, float(scaling), causal=mask is None, max_S=k.S,
+                             mask=mask, **own)
+                    return out.view(B, T, -1), None
                 if kv8:                   # straight from the fp8 planes; the mask alone decides where there is one
                     ATTN_KERNELS[kernel + "_kv8"] = ATTN_KERNELS.get(kernel + "_kv8", 0) + 1
                     if mask is not None:

@@ -11,8 +11,10 @@ A host free list hands a sequence a page when it crosses a page boundary -- the 
 all sequences of a batch together -- and the first layer's update of a step writes the new table entries, pos and seq_lens; every
 layer then appends its K and V rows with ONE ops.kv8_paged_append launch (csrc/kv8_paged.hip).  update() returns two PagedFp8Rows.
 The forwards of patchers/compressed_attention.py recognise them: a call the two decode switches would send to attn_decode_kv8 runs
-ops.attn_decode_paged8 (csrc/attn_decode_paged8.hip) straight from the pools, a prefill into an empty cache attends over the fresh
-k / v, and every other cached call gathers the rows with ops.kv8_paged_dequant and goes on as it would have with tensors.
+ops.attn_decode_paged8 (csrc/attn_decode_paged8.hip) straight from the pools, every other cached call the fused kernels serve (a
+chunked prefill, a later prompt, a wide verification step, masked or not) runs ops.attn_fwd_paged8 (csrc/attn_fwd_paged8.hip)
+straight from the pools as well, and a prefill into an empty cache attends over the fresh k / v.  Only a call that takes HF's
+attention interface gathers the rows with ops.kv8_paged_dequant.
 
 Engine-only, like kv8_cache.py.  An exhausted pool raises; reset() returns every page; beam search (reorder_cache) is refused."""
 from __future__ import annotations
