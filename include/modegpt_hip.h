@@ -1215,6 +1215,40 @@ int mdg_attn_fwd_paged8(const void* q, const void* k_data, const void* k_scale, 
                         int64_t mask_batch_stride, int64_t mask_head_stride, int64_t mask_query_stride, const void* summary,
                         int64_t summary_bytes);
 
+/* ------------------------------------------------------------------ fused rotary + append: from a layer's projections to the fp8 cache
+ * One launch (csrc/rope_kv8_step.hip) for what mdg_rope_gather (q) + mdg_rope_gather (k) + mdg_kv8_append x 2 / mdg_kv8_paged_append
+ * do in three or four.  The rotary half stands for src/patchers/LlamaRebuild.py:153-176 (cos / sin gathered by the layer's rotary
+ * mask, rotate_half over the kept columns) and src/patchers/DenseQwenRebuild.py:262-286 (the masked RMSNorm before it).
+ *   q [B*T, n_heads*r_qk] rows of pitch ld_q, k [B*T, n_kv*r_qk] rows of pitch ld_k, v [B, n_kv, T, r_vo] with batch / head / token
+ *   strides and a unit last stride (the transposed view of v_proj's output as it is), bf16 or f16; cos, sin, cs_batch_stride, mask
+ *   (int64 [n_kv, r_qk] or NULL when r_qk == hd), hd exactly as mdg_rope_gather takes them; q_norm_w, k_norm_w: each NULL or hd
+ *   elements (Qwen3's masked RMSNorm of that side) with eps.
+ *   q_out [B, n_heads, T, r_qk] contiguous; k_out [B, n_kv, T, r_qk] contiguous or NULL (a decode step needs no bf16 k; a prefill
+ *   into an empty cache attends over it).  The K and V rows of token t go to the cache:
+ *   mdg_rope_kv8_step        planes [B, n_kv, cap, pitch] + scales [B, n_kv, cap], rows pos .. pos + T - 1 (mdg_kv8_append's layout)
+ *   mdg_rope_kv8_paged_step  pools [n_pages, n_kv, page, pitch] + scales, row t of sequence b at position pos[b] + t through
+ *                            block_table [B, table_len], both int32 on the device (mdg_kv8_paged_append's layout and rule: a
+ *                            position outside 0 .. table_len * page - 1 is not written, table entries are clamped to the pool)
+ * Without a norm weight q_out and k_out are BIT-IDENTICAL to mdg_rope_gather's; with one the fp32 sum of squares has another order
+ * (as between mdg_rope_gather's own routes).  The K bytes and scales are what mdg_kv8_append / mdg_kv8_paged_append write when given
+ * this call's k_out, the V bytes and scales what they write for v; padding bytes of a pitch are zero.
+ * Refused, with a message before any device work: a dtype other than bf16 / f16; n_heads no multiple of n_kv; hd outside 2..256;
+ * r_qk odd, < 2 or > hd; r_vo outside 1..256; no mask with r_qk != hd; ld_q / ld_k below a row; a pitch below mdg_kv8_pitch(r) or
+ * no multiple of 16; pos + T beyond cap; page no positive multiple of 64, n_pages or table_len not positive; NULL or misaligned
+ * pointers (data 16, scales / table / pos 4, mask 8, elements 2 bytes); a cache, q_out or k_out overlapping an input or one another;
+ * products that overflow.  B == 0 or T == 0 launches nothing and returns MDG_OK. */
+int mdg_rope_kv8_step(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t v_batch_stride,
+                      int64_t v_head_stride, int64_t v_token_stride, int dtype, int64_t B, int64_t T, int n_heads, int n_kv, int r_qk,
+                      int r_vo, int hd, const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
+                      const void* q_norm_w, const void* k_norm_w, double eps, void* q_out, void* k_out, void* k_data, void* k_scale,
+                      void* v_data, void* v_scale, int64_t cap, int64_t k_pitch, int64_t v_pitch, int64_t pos, void* stream);
+int mdg_rope_kv8_paged_step(const void* q, int64_t ld_q, const void* k, int64_t ld_k, const void* v, int64_t v_batch_stride,
+                            int64_t v_head_stride, int64_t v_token_stride, int dtype, int64_t B, int64_t T, int n_heads, int n_kv,
+                            int r_qk, int r_vo, int hd, const void* cos, const void* sin, int64_t cs_batch_stride, const int64_t* mask,
+                            const void* q_norm_w, const void* k_norm_w, double eps, void* q_out, void* k_out, void* k_data,
+                            void* k_scale, void* v_data, void* v_scale, int64_t n_pages, int64_t page, int64_t k_pitch,
+                            int64_t v_pitch, const void* block_table, int64_t table_len, const void* pos, void* stream);
+
 /* ------------------------------------------------------------------ multi-GPU (the reference is single-process,
  * its unit of independent work is the layer loop of src/run_modegpt.py:107-156)
  * Layers shard over the GPUs of a node, one process per GPU, no data-path exchange until the end: ONE all-gather of the

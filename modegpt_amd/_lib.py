@@ -139,6 +139,11 @@ SIGNATURES = {
                                  _i32, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64, _ptr, _i64]),
     "mdg_kv8_paged_append": (_i32, [_ptr, _ptr, _i32, _i64, _i32, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr,
                                      _i64, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr]),
+    "mdg_rope_kv8_step": (_i32, [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _ptr, _ptr,
+                                  _i64, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
+    "mdg_rope_kv8_paged_step": (_i32, [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _ptr,
+                                        _ptr, _i64, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64,
+                                        _ptr, _i64, _ptr, _ptr]),
     "mdg_kv8_paged_dequant": (_i32, [_ptr, _ptr, _i32, _i64, _i32, _i64, _i32, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr]),
     "mdg_attn_decode_paged8": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
                                        _ptr, _i64, _ptr, _f64, _i32, _i32, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i32, _i64, _i64, _i64]),

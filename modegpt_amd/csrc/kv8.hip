@@ -51,19 +51,9 @@ template <int DT> __global__ __launch_bounds__(THREADS) void kv8_append_kernel(A
     amax = fmaxf(amax, fabsf(f[j]));
   }
   for (int d = (1 << a.lg_shift) >> 1; d; d >>= 1) amax = fmaxf(amax, __shfl_xor(amax, d));
-  const unsigned ab = __float_as_uint(amax);
-  int e = (int)(ab >> 23) - 127 - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = e < -126 ? -126 : e > 127 ? 127 : e;
-  const bool zero = amax == 0.f;
-  const float s = zero ? 1.f : __uint_as_float((unsigned)(e + 127) << 23);
-  const float inv = zero ? 1.f : __uint_as_float((unsigned)(127 - e) << 23);  // e <= 121 for any fp32 amax: a normal number
-  u32x4 p;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    int v = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w] * inv, f[4 * w + 1] * inv, 0, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w + 2] * inv, f[4 * w + 3] * inv, v, true);
-    p[w] = (unsigned)v;
-  }
+  float s, inv;
+  kv8::row_scale(amax, s, inv);
+  const u32x4 p = kv8::pack16(f, inv);
   if (!live) return;
   const int64_t slot = bh * a.cap + a.pos + t;
   unsigned char* drow = a.data + slot * a.pitch;

@@ -32,5 +32,28 @@ template <int DT> __device__ __forceinline__ u32x4 dequant8(unsigned w0, unsigne
                  Cvt<DT>::template pair<true>(w1, s)};
 }
 
+// The row quantiser of every kernel that writes the cache (kv8.hip, kv8_paged.hip, rope_kv8_step.hip), after the row's amax is known to
+// every lane.  row_scale: amax = m 2^k with 1 <= m < 2 gives e = k - 8 when m <= 1.75 (448 = 1.75 * 2^8) and k - 7 otherwise, clamped
+// to the fp32 normal range; the scale is 2^e and `inv` its exact reciprocal; an all-zero row gets scale 1.
+__device__ __forceinline__ void row_scale(float amax, float& s, float& inv) {
+  const unsigned ab = __float_as_uint(amax);
+  int e = (int)(ab >> 23) - 127 - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
+  e = e < -126 ? -126 : e > 127 ? 127 : e;
+  const bool zero = amax == 0.f;
+  s = zero ? 1.f : __uint_as_float((unsigned)(e + 127) << 23);
+  inv = zero ? 1.f : __uint_as_float((unsigned)(127 - e) << 23);  // e <= 121 for any fp32 amax: a normal number
+}
+// A lane's 16 elements as the 16 e4m3 bytes of its chunk: x * 2^-e is exact, so v_cvt_pk_fp8_f32 rounds x / scale once.
+__device__ __forceinline__ u32x4 pack16(const float (&f)[16], float inv) {
+  u32x4 p;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    int v = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w] * inv, f[4 * w + 1] * inv, 0, false);
+    v = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w + 2] * inv, f[4 * w + 3] * inv, v, true);
+    p[w] = (unsigned)v;
+  }
+  return p;
+}
+
 }  // namespace kv8
 }  // namespace mdg

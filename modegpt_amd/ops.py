@@ -1687,6 +1687,99 @@ def kv8_paged_append(k_src: torch.Tensor, v_src: torch.Tensor, k_pool, v_pool, b
               "mdg_kv8_paged_append")
 
 
+def _rope_kv8_operands(fn, q, k, v, cos, sin, mask, n_heads, n_kv, head_dim, q_norm_weight, k_norm_weight, k_out, q_out):
+    """The operands the two fused steps share: q [B, T, n_heads*r_qk], k [B, T, n_kv*r_qk], v [B, n_kv, T, r_vo] (any strides, unit last
+    one), cos / sin [B or 1, T, head_dim]; k_out None (not wanted), True (allocate) or a tensor.  Returns the C arguments up to k_out,
+    (q_out, k_out) and (B, T, r_qk, r_vo)."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 4 or q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"{fn}: q, k [B, T, width] and v [B, n_kv, T, r_vo] must be bf16 or f16 of one dtype, got {q.dtype} "
+                         f"{tuple(q.shape)}, {k.dtype} {tuple(k.shape)}, {v.dtype} {tuple(v.shape)}")
+    B, T, width = q.shape
+    r_qk, r_vo = width // n_heads, v.shape[3]
+    if r_qk * n_heads != width or tuple(k.shape) != (B, T, n_kv * r_qk) or tuple(v.shape[:3]) != (B, n_kv, T):
+        raise ValueError(f"{fn}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit {n_heads} / {n_kv} heads")
+    q, k, v = q.detach(), k.detach(), v.detach()
+    if q.stride(2) != 1 or q.stride(0) != T * q.stride(1):
+        q = q.contiguous()
+    if k.stride(2) != 1 or k.stride(0) != T * k.stride(1):
+        k = k.contiguous()
+    if r_vo > 1 and v.stride(3) != 1:
+        v = v.contiguous()
+    cos, sin = cos.to(q.dtype).contiguous(), sin.to(q.dtype).contiguous()
+    if cos.shape != sin.shape or cos.shape[-2:] != (T, head_dim) or cos.shape[0] not in (1, B):
+        raise ValueError(f"{fn}: cos/sin {tuple(cos.shape)} / {tuple(sin.shape)} do not fit [B or 1, {T}, {head_dim}]")
+    if mask is not None:
+        if mask.dtype != torch.int64 or tuple(mask.shape) != (n_kv, r_qk):
+            raise ValueError(f"{fn}: mask must be int64 [{n_kv}, {r_qk}], got {mask.dtype} {tuple(mask.shape)}")
+        mask = mask.contiguous()
+    qw, kw = (None if w is None else w.detach().to(q.dtype).contiguous() for w in (q_norm_weight, k_norm_weight))
+    outs = []
+    for name, out, heads in (("q_out", q_out, n_heads), ("k_out", k_out, n_kv)):
+        if out is True or (out is None and name == "q_out"):
+            out = torch.empty(B, heads, T, r_qk, dtype=q.dtype, device=q.device)
+        elif out is not None and (tuple(out.shape) != (B, heads, T, r_qk) or out.dtype != q.dtype or out.device != q.device
+                                  or not out.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous {q.dtype} [{B}, {heads}, {T}, {r_qk}] on {q.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} strides {out.stride()} on {out.device}")
+        outs.append(out)
+    keep = (q, k, v, cos, sin, mask, qw, kw)            # the tensors the pointers below borrow
+    args = (q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _DT[q.dtype], B, T,
+            n_heads, n_kv, r_qk, r_vo, head_dim, cos.data_ptr(), sin.data_ptr(), 0 if cos.shape[0] == 1 else T * head_dim, _p(mask),
+            _p(qw), _p(kw))
+    return keep, args, tuple(outs), (B, T, r_qk, r_vo)
+
+
+def rope_kv8_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor],
+                  n_heads: int, n_kv: int, head_dim: int, k_cache, v_cache, pos: int, q_norm_weight: Optional[torch.Tensor] = None,
+                  k_norm_weight: Optional[torch.Tensor] = None, eps: float = 1e-6, k_out=None, q_out: Optional[torch.Tensor] = None):
+    """A layer's projection outputs to rotated queries and the fp8 KV cache in ONE launch (mdg_rope_kv8_step): q [B, T, n_heads*r_qk],
+    k [B, T, n_kv*r_qk], v [B, n_kv, T, r_vo] (the transposed view of v_proj's output as it is), cos / sin / mask / head_dim / norm
+    weights as rope_gather takes them.  q is rotated into [B, n_heads, T, r_qk]; the rotated K rows and the V rows are quantised into
+    rows pos .. pos + T - 1 of the caches, each a (data, scale) pair as kv8_append takes them.  k_out: None -- the rotated k is not
+    written in bf16 at all -- True to allocate it, or a contiguous [B, n_kv, T, r_qk] tensor.  Returns (q_out, k_out or None).  Nothing
+    synchronises, nothing is read on the host."""
+    fn = "rope_kv8_step"
+    _need_gpu(q, k, v, cos, sin, *k_cache, *v_cache)
+    keep, args, (q_out, k_out), (B, T, r_qk, r_vo) = _rope_kv8_operands(fn, q, k, v, cos, sin, mask, n_heads, n_kv, head_dim, q_norm_weight,
+                                                                      k_norm_weight, k_out, q_out)
+    Bk, n_kv_k, cap, k_pitch = _kv8_planes(fn, *k_cache, q)
+    Bv, n_kv_v, cap_v, v_pitch = _kv8_planes(fn, *v_cache, q)
+    if ((Bk, n_kv_k, Bv, n_kv_v, cap_v) != (B, n_kv, B, n_kv, cap) or k_pitch < kv8_pitch(r_qk) or v_pitch < kv8_pitch(r_vo)
+            or not 0 <= int(pos) <= cap - T):
+        raise ValueError(f"{fn}: caches of data {tuple(k_cache[0].shape)} / {tuple(v_cache[0].shape)} do not hold rows {int(pos)} .. "
+                         f"{int(pos) + T - 1} of [{B}, {n_kv}, *, {r_qk} / {r_vo}] (one B, n_kv and cap; pitch >= kv8_pitch of the width)")
+    with torch.cuda.device(q.device):
+        check(_lib.load().mdg_rope_kv8_step(*args, float(eps), q_out.data_ptr(), _p(k_out), k_cache[0].data_ptr(), k_cache[1].data_ptr(),
+                                            v_cache[0].data_ptr(), v_cache[1].data_ptr(), cap, k_pitch, v_pitch, int(pos), _stream(q)),
+              "mdg_rope_kv8_step")
+    return q_out, k_out
+
+
+def rope_kv8_paged_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                        mask: Optional[torch.Tensor], n_heads: int, n_kv: int, head_dim: int, k_pool, v_pool, block_table: torch.Tensor,
+                        pos: torch.Tensor, q_norm_weight: Optional[torch.Tensor] = None, k_norm_weight: Optional[torch.Tensor] = None,
+                        eps: float = 1e-6, k_out=None, q_out: Optional[torch.Tensor] = None):
+    """rope_kv8_step into the paged fp8 cache (mdg_rope_kv8_paged_step): the pools, block_table int32 [B, table_len] and pos int32 [B]
+    of kv8_paged_append; row t of sequence b goes to position pos[b] + t.  Returns (q_out, k_out or None).  Nothing synchronises,
+    nothing is read on the host."""
+    fn = "rope_kv8_paged_step"
+    _need_gpu(q, k, v, cos, sin, *k_pool, *v_pool, block_table, pos)
+    keep, args, (q_out, k_out), (B, T, r_qk, r_vo) = _rope_kv8_operands(fn, q, k, v, cos, sin, mask, n_heads, n_kv, head_dim, q_norm_weight,
+                                                                      k_norm_weight, k_out, q_out)
+    kd, ks, n_pages, n_kv_k, page, k_pitch = _kv8_pool(fn, k_pool, q)
+    vd, vs, n_pages_v, n_kv_v, page_v, v_pitch = _kv8_pool(fn, v_pool, q)
+    Bt, table_len = _kv8_table(fn, block_table, pos, q, "pos")
+    if ((Bt, n_kv_k, n_pages_v, n_kv_v, page_v) != (B, n_kv, n_pages, n_kv, page) or k_pitch < kv8_pitch(r_qk)
+            or v_pitch < kv8_pitch(r_vo)):
+        raise ValueError(f"{fn}: pools of data {tuple(kd.shape)} / {tuple(vd.shape)} and a table {tuple(block_table.shape)} do not fit "
+                         f"[{B}, {n_kv}, *, {r_qk} / {r_vo}] (one B, n_kv, n_pages and page; pitch >= kv8_pitch of the width)")
+    with torch.cuda.device(q.device):
+        check(_lib.load().mdg_rope_kv8_paged_step(*args, float(eps), q_out.data_ptr(), _p(k_out), kd.data_ptr(), ks.data_ptr(),
+                                                  vd.data_ptr(), vs.data_ptr(), n_pages, page, k_pitch, v_pitch, block_table.data_ptr(),
+                                                  table_len, pos.data_ptr(), _stream(q)), "mdg_rope_kv8_paged_step")
+    return q_out, k_out
+
+
 def kv8_paged_dequant(pool, block_table: torch.Tensor, S: int, r: int, dtype=torch.bfloat16,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Rows 0 .. S - 1 of every sequence of one pool of the paged fp8 cache as a contiguous [B, n_kv, S, r] tensor of `dtype`

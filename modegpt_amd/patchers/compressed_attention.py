@@ -41,6 +41,13 @@ stock HF modules and gives their attention the compressed semantics, with the el
     kernels serve against a non-empty cache (masked ones too) runs modegpt_amd.ops.attn_fwd_paged8 (csrc/attn_fwd_paged8.hip)
     straight from the pages as well, counted in ATTN_KERNELS["fwd_paged8"]; a prefill into an empty cache attends over the fresh
     k / v.  Only a call that takes HF's interface gathers the rows (ops.kv8_paged_dequant).
+    MODEGPT_FUSED_KV_STEP=1 with either of these caches (any past_key_values with a `step` method), bf16 / f16 on a GPU: the two
+    rope_gather launches and the cache's append launch(es) of a layer become ONE, modegpt_amd.ops.rope_kv8_step /
+    rope_kv8_paged_step (csrc/rope_kv8_step.hip): q leaves rotated, K and V land quantised in the cache, and the rotated k is
+    written as a tensor only for a prefill into an empty cache.  Counted in KV_STEPS["fused"]; PATH_CALLS does not count these
+    calls.  Only calls of B * T <= KV_STEP_MAX_TOKENS (1024) tokens take it: decode steps and short chunks, where the call is
+    launch-bound and one launch takes 0.44-0.60 of the chain's time; a long prefill, where the fused kernel was measured 3-4 x
+    SLOWER than the chain, keeps the chain.  Off by default; the attention product and its routing are untouched.
 
 Two entry points share the forward functions:
   install_compressed_attention(adapter, rotary_masks)   live model right after ModelAdapter.convert_model
@@ -75,7 +82,10 @@ ATTN_KERNELS = {"fwd": 0, "decode": 0}  # of the "hip" ones: served by mdg_attn_
 #                                         mdg_attn_fwd_kv8 serves (an Fp8KVCache), a "decode_paged8" / "fwd_paged8" count with the
 #                                         first call mdg_attn_decode_paged8 / mdg_attn_fwd_paged8 serves (a PagedFp8KVCache)
 ATTN_MASKED = {"fwd": 0, "decode": 0}   # of those again: called with a bool mask (MODEGPT_FUSED_ATTN_MASK=1), per kernel
-_DECODE_SPLITS = None                   # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
+KV_STEPS = {"fused": 0}                 # layer calls whose rotation, norm and cache append ran as one launch (MODEGPT_FUSED_KV_STEP=1)
+KV_STEP_MAX_TOKENS = 1024               # B * T up to which the fused step was measured faster than the chain (0.44-0.60
+#                                         of its time up to 16 x 64 tokens, 1.6-2.0 x at 16 x 256): larger calls keep the chain
+_DECODE_SPLITS = None                  # an int overrides mdg_attn_decode_splits (tests and tuning; not an environment knob)
 _HIP_OPS = None
 _HIP_BROKEN = None                      # why the engine, although installed here, cannot serve (its library failed to load)
 
@@ -279,10 +289,16 @@ def _rope_forward(self, hidden_states, position_embeddings=None, attention_mask=
     if mask is not None:
         # the reference's gather index has batch extent 1 (LlamaRebuild.py:167-175): batch 0's table serves every batch
         cos, sin = cos[:1], sin[:1]
-    q = _rope_gather(q, cos, sin, mask, n_h, n_kv, hd, norm_weight=qw, eps=eps)         # [B, n_h,  T, r_qk]
-    k = _rope_gather(k, cos, sin, mask, n_kv, n_kv, hd, norm_weight=kw, eps=eps)        # [B, n_kv, T, r_qk]
-    if past_key_values is not None:
-        k, v = past_key_values.update(k, v, self.layer_idx)
+    if (os.environ.get("MODEGPT_FUSED_KV_STEP", "0") == "1" and hasattr(past_key_values, "step") and B * T <= KV_STEP_MAX_TOKENS
+            and q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and _hip_ops() is not None):
+        # rotation, norm and the cache append in one launch (an Fp8KVCache / PagedFp8KVCache: mdg_rope_kv8_step / _paged_step)
+        KV_STEPS["fused"] += 1
+        q, k, v = past_key_values.step(self.layer_idx, q, k, v, cos, sin, mask, n_h, hd, q_norm_weight=qw, k_norm_weight=kw, eps=eps)
+    else:
+        q = _rope_gather(q, cos, sin, mask, n_h, n_kv, hd, norm_weight=qw, eps=eps)         # [B, n_h,  T, r_qk]
+        k = _rope_gather(k, cos, sin, mask, n_kv, n_kv, hd, norm_weight=kw, eps=eps)        # [B, n_kv, T, r_qk]
+        if past_key_values is not None:
+            k, v = past_key_values.update(k, v, self.layer_idx)
     extra = {"sliding_window": self.sliding_window} if getattr(self, "sliding_window", None) is not None else {}
     out, weights = _attend(self, q, k, v, attention_mask, float(r_qk) ** -0.5, kwargs, extra)
     return self.o_proj(out), weights

@@ -12,7 +12,8 @@ patchers/compressed_attention.py recognise them: with MODEGPT_FUSED_ATTN=1 every
 directly -- ops.attn_decode_kv8 for a call in the decode kernel's domain when MODEGPT_FUSED_ATTN_DECODE=1 is set as well,
 ops.attn_fwd_kv8 for every other one (chunked prefill, later prompts, wide verification steps) -- and a prefill into an empty cache
 attends over the fresh k / v it was given.  Only a call that takes HF's attention interface reads the cache back with
-ops.kv8_dequant and goes on as it would have with a DynamicCache.
+ops.kv8_dequant and goes on as it would have with a DynamicCache.  step() is update() with the rotary stage of q and k in front, all in
+one launch (ops.rope_kv8_step, csrc/rope_kv8_step.hip); the forward calls it instead of update() under MODEGPT_FUSED_KV_STEP=1.
 
 Engine-only: this module needs libmodegpt_hip.so and a GPU, and is not shipped next to a checkpoint.  Beam search
 (reorder_cache) is refused."""
@@ -33,9 +34,10 @@ class Fp8Rows:
     is_kv8 = True
     requires_grad = False
 
-    def __init__(self, data, scale, S, r, fresh):
+    def __init__(self, data, scale, S, r, fresh, dtype=None):
+        # fresh is None for the K rows of a fused step (Fp8KVLayer.step) that wrote no bf16 k: then `dtype` is the layer's
         self.data, self.scale, self.S, self.r, self.fresh = data, scale, S, r, fresh
-        self.dtype, self.device = fresh.dtype, fresh.device
+        self.dtype, self.device = (dtype, data.device) if fresh is None else (fresh.dtype, fresh.device)
         self.shape = torch.Size((data.shape[0], data.shape[1], S, r))
 
     def stride(self, dim=None):
@@ -104,6 +106,26 @@ class Fp8KVLayer(CacheLayerMixin):
         return (Fp8Rows(self.keys, self.key_scale, self.length, self.r_qk, key_states),
                 Fp8Rows(self.values, self.value_scale, self.length, self.r_vo, value_states))
 
+    def step(self, q, k, v, cos, sin, mask, n_heads, head_dim, q_norm_weight=None, k_norm_weight=None, eps=1e-6):
+        """update() with the rotary stage in front, in one launch (ops.rope_kv8_step): q [B, T, n_heads*r_qk] and k [B, T, n_kv*r_qk]
+        as the projections wrote them, v [B, n_kv, T, r_vo] (a view).  Returns (q_rot [B, n_heads, T, r_qk], k_rows, v_rows); the rotated
+        k exists as a tensor (k_rows.fresh) only when the layer was empty, where the forward attends over it."""
+        B, T, n_kv = v.shape[0], v.shape[2], v.shape[1]
+        if k.dim() != 3 or k.shape[-1] % n_kv:
+            raise ValueError(f"Fp8KVCache.step: k {tuple(k.shape)} is not [B, T, {n_kv} * r_qk]")
+        if not self.is_initialized:
+            self.lazy_initialization(k.view(B, T, n_kv, -1).transpose(1, 2), v)
+        if (B, n_kv) != (self.batch, self.n_kv) or k.shape[-1] != n_kv * self.r_qk or v.shape[-1] != self.r_vo or k.shape[1] != T:
+            raise ValueError(f"Fp8KVCache layer of [{self.batch}, {self.n_kv}, *, {self.r_qk} / {self.r_vo}] was given k "
+                             f"{tuple(k.shape)}, v {tuple(v.shape)}")
+        self._reserve(self.length + T)
+        q_rot, fresh = ops.rope_kv8_step(q, k, v, cos, sin, mask, n_heads, n_kv, head_dim, (self.keys, self.key_scale),
+                                         (self.values, self.value_scale), self.length, q_norm_weight=q_norm_weight,
+                                         k_norm_weight=k_norm_weight, eps=eps, k_out=True if self.length == 0 else None)
+        self.length += T
+        return (q_rot, Fp8Rows(self.keys, self.key_scale, self.length, self.r_qk, fresh, self.dtype),
+                Fp8Rows(self.values, self.value_scale, self.length, self.r_vo, v))
+
     def get_seq_length(self) -> int:
         return self.length
 
@@ -125,3 +147,9 @@ class Fp8KVCache(Cache):
 
     def __init__(self, max_len: Optional[int] = None):
         super().__init__(layer_class_to_replicate=lambda: Fp8KVLayer(max_len))
+
+    def step(self, layer_idx: int, *args, **kwargs):
+        """Fp8KVLayer.step of layer `layer_idx` (created on first use, as update does): the fused rotary + append."""
+        while len(self.layers) <= layer_idx:
+            self.layers.append(self.layer_class_to_replicate())
+        return self.layers[layer_idx].step(*args, **kwargs)

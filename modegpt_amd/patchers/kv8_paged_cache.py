@@ -14,7 +14,8 @@ The forwards of patchers/compressed_attention.py recognise them: a call the two 
 ops.attn_decode_paged8 (csrc/attn_decode_paged8.hip) straight from the pools, every other cached call the fused kernels serve (a
 chunked prefill, a later prompt, a wide verification step, masked or not) runs ops.attn_fwd_paged8 (csrc/attn_fwd_paged8.hip)
 straight from the pools as well, and a prefill into an empty cache attends over the fresh k / v.  Only a call that takes HF's
-attention interface gathers the rows with ops.kv8_paged_dequant.
+attention interface gathers the rows with ops.kv8_paged_dequant.  step() is update() with the rotary stage of q and k in front, all in
+one launch (ops.rope_kv8_paged_step, csrc/rope_kv8_step.hip); the forward calls it instead of update() under MODEGPT_FUSED_KV_STEP=1.
 
 Engine-only, like kv8_cache.py.  An exhausted pool raises; reset() returns every page; beam search (reorder_cache) is refused."""
 from __future__ import annotations
@@ -33,10 +34,11 @@ class PagedFp8Rows:
     is_paged = True
     requires_grad = False
 
-    def __init__(self, pool, block_table, seq_lens, S, r, fresh):
+    def __init__(self, pool, block_table, seq_lens, S, r, fresh, dtype=None):
+        # fresh is None for the K rows of a fused step (PagedFp8KVLayer.step) that wrote no bf16 k: then `dtype` is the layer's
         self.pool, self.block_table, self.seq_lens, self.S, self.r, self.fresh = pool, block_table, seq_lens, S, r, fresh
-        self.dtype, self.device = fresh.dtype, fresh.device
-        self.shape = torch.Size((fresh.shape[0], fresh.shape[1], S, r))
+        self.dtype, self.device = (dtype, pool[0].device) if fresh is None else (fresh.dtype, fresh.device)
+        self.shape = torch.Size((block_table.shape[0], pool[0].shape[1], S, r))
 
     def stride(self, dim=None):
         st = (self.shape[1] * self.S * self.r, self.S * self.r, self.r, 1)     # of the gathered tensor
@@ -80,6 +82,26 @@ class PagedFp8KVLayer(CacheLayerMixin):
         return (PagedFp8Rows(self.keys, table, seq_lens, self.length, self.r_qk, key_states),
                 PagedFp8Rows(self.values, table, seq_lens, self.length, self.r_vo, value_states))
 
+    def step(self, q, k, v, cos, sin, mask, n_heads, head_dim, q_norm_weight=None, k_norm_weight=None, eps=1e-6):
+        """update() with the rotary stage in front, in one launch (ops.rope_kv8_paged_step): q [B, T, n_heads*r_qk] and
+        k [B, T, n_kv*r_qk] as the projections wrote them, v [B, n_kv, T, r_vo] (a view).  Returns (q_rot [B, n_heads, T, r_qk], k_rows,
+        v_rows); the rotated k exists as a tensor (k_rows.fresh) only when the layer was empty, where the forward attends over it."""
+        B, T, n_kv = v.shape[0], v.shape[2], v.shape[1]
+        if k.dim() != 3 or k.shape[-1] % n_kv:
+            raise ValueError(f"PagedFp8KVCache.step: k {tuple(k.shape)} is not [B, T, {n_kv} * r_qk]")
+        if not self.is_initialized:
+            self.lazy_initialization(k.view(B, T, n_kv, -1).transpose(1, 2), v)
+        if (B, n_kv) != (self.batch, self.n_kv) or k.shape[-1] != n_kv * self.r_qk or v.shape[-1] != self.r_vo or k.shape[1] != T:
+            raise ValueError(f"PagedFp8KVCache layer of [{self.batch}, {self.n_kv}, *, {self.r_qk} / {self.r_vo}] was given k "
+                             f"{tuple(k.shape)}, v {tuple(v.shape)}")
+        table, seq_lens, pos = self.owner.advance(self.batch, self.length, T, self.device)
+        q_rot, fresh = ops.rope_kv8_paged_step(q, k, v, cos, sin, mask, n_heads, n_kv, head_dim, self.keys, self.values, table, pos,
+                                               q_norm_weight=q_norm_weight, k_norm_weight=k_norm_weight, eps=eps,
+                                               k_out=True if self.length == 0 else None)
+        self.length += T
+        return (q_rot, PagedFp8Rows(self.keys, table, seq_lens, self.length, self.r_qk, fresh, self.dtype),
+                PagedFp8Rows(self.values, table, seq_lens, self.length, self.r_vo, v))
+
     def get_seq_length(self) -> int:
         return self.length
 
@@ -109,6 +131,12 @@ class PagedFp8KVCache(Cache):
         self.free = list(range(self.n_pages - 1, -1, -1))  # the host free list (pages are popped from its end: 0, 1, 2, ...)
         self.owned = None                                 # per sequence, the pages it was handed, in order
         self.block_table = self.seq_lens = self.pos = None
+
+    def step(self, layer_idx: int, *args, **kwargs):
+        """PagedFp8KVLayer.step of layer `layer_idx` (created on first use, as update does): the fused rotary + append."""
+        while len(self.layers) <= layer_idx:
+            self.layers.append(self.layer_class_to_replicate())
+        return self.layers[layer_idx].step(*args, **kwargs)
 
     @property
     def pages_in_use(self) -> int:
